@@ -20,12 +20,17 @@ N > 1 is one process per GPU.  Either the driver starts the ranks (torch.distrib
 LOCAL_RANK / WORLD_SIZE set) or `python bench.py --gpus N` does it itself: the parent starts N
 children BEFORE touching the GPU and relays rank 0's JSON line.
 
-Rank 0 prints ONE JSON line.  `value` = whole-job basin-ensemble-timesteps/s.  At N = 1 the line also
-carries `secondary` (configs 2-dyn, 3, 4 -- staged and under the reference's joint Newton policy --, one GPU's share of 5,
-config 5 at full size, the deltaMG minibatch shape, Hbv_2_hourly with gage routing, the sequence LSTM and one
-examples/train_dpl.py step; driver-timed in the same run, each with what limits it: `limited_by`) and
-`cpu_baseline` (the pure-torch eager restatement of the reference's path on the host cores -- `value` -- with the
-C/OpenMP oracle port beside it); every timed entry carries its per-step samples (`step_samples`: n, median, min, max).
+Rank 0 prints ONE JSON line.  `value` = whole-job basin-ensemble-timesteps/s; `ms_per_step` = the K timed steps'
+wall time / K (max over ranks).  At N = 1 the line also carries `secondary` (configs 2-dyn, 3, 4 -- staged and under the
+reference's joint Newton policy --, one GPU's share of 5, config 5 at full size, the deltaMG minibatch shape, Hbv_2_hourly
+with gage routing, the sequence LSTM and one examples/train_dpl.py step, driver-timed in the same run: name -> ms per
+step) and `cpu_baseline` (the pure-torch eager restatement of the reference's path on the host cores -- `value` -- with
+the C/OpenMP oracle port beside it).  The line stays a few KB: the whole record -- every secondary entry with what limits
+it (`limited_by`), its roofline and per-step samples (`step_samples`: n, median, min, max), the CPU baselines' passes --
+is printed to stderr as one `[bench] detail: {...}` line.
+
+--dump-outputs DIR writes what the last timed step computed (outputs, parameter gradients, loss) as DIR/<name>.npy, so
+that two builds can be compared output for output: the inputs depend on the arguments only.
 """
 from __future__ import annotations
 
@@ -262,6 +267,7 @@ class Workload:
             ps = torch.rand((B, (19 - self.n_dyn) * M), generator=g, device=dev).requires_grad_(True)
             pr = torch.rand((int(topo.sum()), 3), generator=g, device=dev).requires_grad_(True)
             self.params, self.leaves, self.shared = (pd, ps, pr), [pd, ps, pr], ps
+            self.leaf_names = ["p_dyn", "p_sta", "p_distr"]
             self.xd["ac_all"] = torch.rand(B, generator=g, device=dev) * 5000
             self.xd["elev_all"] = torch.rand(B, generator=g, device=dev) * 3000
             self.xd["outlet_topo"] = topo
@@ -275,14 +281,18 @@ class Workload:
             pd = torch.rand((T, B, self.n_dyn * M), generator=g, device=dev).requires_grad_(True)
             ps = torch.rand((B, (16 - self.n_dyn) * M), generator=g, device=dev).requires_grad_(True)
             self.params, self.leaves, self.shared = (pd, ps), [pd, ps], ps
+            self.leaf_names = ["p_dyn", "p_sta"]
             self.xd["ac_all"] = torch.rand(B, generator=g, device=dev) * 5000
             self.xd["elev_all"] = torch.rand(B, generator=g, device=dev) * 3000
         else:
             p = torch.randn((T, B, self.model.learnable_param_count), generator=g, device=dev).requires_grad_(True)
             self.params, self.leaves, self.shared = p, [p], p
+            self.leaf_names = ["parameters"]
         self.key = "flow_sim" if cls == "HbvAdj" else "streamflow"
         self.w = torch.randn((self.T_out, out_cols, 1), generator=g, device=dev)
         self.cls = cls
+        self.keep_outputs = False   # --dump-outputs: hold on to the last step's output dictionary
+        self.last_out = None
 
     @property
     def lane_steps(self):
@@ -291,11 +301,23 @@ class Workload:
     def step(self):
         for leaf in self.leaves:
             leaf.grad = None
+        self.last_out = None
         out = self.model(self.xd, self.params)
         loss = (out[self.key] * self.w).sum()
         loss.backward()
         self.last_loss = loss.detach()
+        if self.keep_outputs:
+            self.last_out = {k: v.detach() for k, v in out.items() if hasattr(v, "detach")}
         return loss
+
+    def outputs(self):
+        """What a caller of the step receives from the last one: the module's output dictionary and the gradient of
+        every raw parameter tensor (name -> tensor)."""
+        res = {f"out_{k}": v for k, v in (self.last_out or {}).items()}
+        for name, leaf in zip(self.leaf_names, self.leaves):
+            if leaf.grad is not None:
+                res[f"grad_{name}"] = leaf.grad
+        return res
 
     def shared_grad(self):
         """What a shared parameterisation network would receive from this shard, basin-summed:
@@ -824,6 +846,59 @@ def validate_collective(dev, world, rank):
 
 
 # --------------------------------------------------------------------------------------------
+# --dump-outputs and the result line
+# --------------------------------------------------------------------------------------------
+DUMP_BYTES = 64 * 10 ** 6     # --dump-outputs: at most this much in all, .npy headers included
+
+
+def dump_outputs(arrays, out_dir, suffix="", budget=DUMP_BYTES):
+    """Write every array of `arrays` (name -> tensor) as out_dir/<name><suffix>.npy in float32, `budget` bytes in all.
+
+    Arrays are taken smallest first; each gets an equal share of what is left.  An array larger than its share is written
+    as a fixed sample of its elements in row-major order: the flat indices are drawn from a generator seeded by the
+    array's name, so that two builds of the project write the same elements for the same arguments."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    left = (budget - 128 * len(items)) // 4      # float32 elements (an .npy header is 128 bytes)
+    written = []
+    for i, (name, t) in enumerate(items):
+        n = t.numel()
+        k = min(n, left // (len(items) - i))
+        if k == n:
+            a = t.detach().float().cpu().numpy()
+        else:
+            idx = np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, n, size=k))
+            where = tuple(torch.from_numpy(j).to(t.device) for j in np.unravel_index(idx, tuple(t.shape)))
+            a = t.detach()[where].float().cpu().numpy()
+        left -= a.size
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written.append(f"{name}{list(t.shape)}" + ("" if k == n else f" sample {a.size}"))
+    return written
+
+
+def compact_line(res):
+    """The result line: the headline and one summary of every other entry, a few KB at most.  The full record (every
+    secondary entry with its roofline, the CPU baselines' passes) goes to stderr."""
+    line = {k: v for k, v in res.items() if k not in ("roofline", "secondary", "cpu_baseline")}
+    rf = res.get("roofline")
+    if rf:
+        line["roofline"] = {k: rf[k] for k in ("bound", "kernel", "limited_by", "achieved", "peak", "unit", "frac",
+                                               "frac_8d", "frac_design", "traffic", "avg_ms") if k in rf}
+    if "secondary" in res:
+        line["secondary"] = {e["config"]: e["ms_per_step"] if "ms_per_step" in e else "error"
+                             for e in res["secondary"]}
+    cb = res.get("cpu_baseline")
+    if cb:
+        line["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "sample", "error") if k in cb}
+        for sub in ("port", "eager"):
+            if isinstance(cb.get(sub), dict):
+                line["cpu_baseline"][sub] = {k: cb[sub][k] for k in ("value", "cores", "kind", "error") if k in cb[sub]}
+    return line
+
+
 def main():
     if len(sys.argv) >= 5 and sys.argv[1] == "--eager-child":
         _eager_child(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), grad=(sys.argv[5:6] != ["nograd"]))
@@ -842,7 +917,16 @@ def main():
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu exists for the launcher's own test (tests/test_bench_launch.py swaps in a host "
                          "implementation of the ABI); the product library refuses host tensors")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- the module's output dictionary "
+                         "(out_<key>), the gradient of every raw parameter tensor (grad_<name>), the loss and the "
+                         "basin-summed shared gradient the step all-reduces -- as DIR/<name>.npy, float32, 64 MB in "
+                         "all (a fixed, seeded sample of an array that does not fit); ranks > 0 add .rank<r>")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -883,6 +967,7 @@ def main():
     else:
         B_rank = B_total
     wl = Workload(args.config, dev, seed=1000 + rank, B=B_rank, T=args.days or T0, M=args.nmul or M0)
+    wl.keep_outputs = args.dump_outputs is not None
 
     nshared = wl.shared.shape[-1]
     bucket = torch.zeros(nshared + 1, device=dev)
@@ -902,6 +987,15 @@ def main():
             sharding.all_reduce_sum_([bucket])
 
     dt, kavg = timed_steps(wl, args.steps, args.warmup, dev, world, after_step=exchange)
+    if args.dump_outputs is not None:
+        arrays = wl.outputs()
+        arrays["loss"] = bucket[nshared:]                   # summed over the ranks by the step's all-reduce
+        arrays["shared_grad"] = bucket[:nshared]
+        written = dump_outputs(arrays, args.dump_outputs, suffix=f".rank{rank}" if rank else "",
+                               budget=DUMP_BYTES // world)
+        wl.last_out = None
+        print(f"[bench] rank {rank}: wrote {len(written)} arrays to {args.dump_outputs}: {', '.join(written)}",
+              file=sys.stderr, flush=True)
     my_ms = 1e3 * dt / args.steps
     rank_ms = [my_ms]
     if world > 1:
@@ -1036,7 +1130,9 @@ def main():
             cb = dict(port, eager=cb)
         res["cpu_baseline"] = cb
     if rank == 0:
-        print(json.dumps(res))
+        # the whole record on stderr; stdout carries the one result line
+        print("[bench] detail: " + json.dumps(res), file=sys.stderr, flush=True)
+        print(json.dumps(compact_line(res)))
         sys.stdout.flush()
     if world > 1:
         dist.destroy_process_group()

@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures by running the REFERENCE (mhpi/hydrodl2).
 
-Runs only in the authoring container, where the reference checkout is mounted
-read-only at /root/reference.  Nothing of the reference travels: this script
+Runs only where a checkout of the reference is at hand; HYDRODL2_REFERENCE
+names its `src` directory.  Nothing of the reference travels: this script
 imports it, feeds it the bit-reproducible synthetic inputs of tests/synth.py
 and stores *outputs and gradients only* in tests/golden/<case>.npz.
 
-    python tests/golden/make_golden.py            # all cases
-    python tests/golden/make_golden.py hbv_ties   # one case
+    HYDRODL2_REFERENCE=<checkout>/src python tests/golden/make_golden.py            # all cases
+    HYDRODL2_REFERENCE=<checkout>/src python tests/golden/make_golden.py hbv_ties   # one case
+    HYDRODL2_REFERENCE=<checkout>/src python tests/golden/make_golden.py live       # live_draws.npz
+    HYDRODL2_REFERENCE=<checkout>/src python tests/golden/make_golden.py api        # reference_api.json
+
+`live`: the reference's outputs, final states and gradients on every drawn case of
+golden_cases.live_case (tests/test_live_reference.py).  `api`: the reference's public
+attribute surface, model discovery and refusals (tests/test_api_vs_reference.py).
 
 Import recipe: SURVEY.md §9.6 (the VCS-generated hydrodl2._version module is
 absent from the tree and is pre-seeded; the licence prompt skips itself because
@@ -23,7 +29,7 @@ import warnings
 import numpy as np
 import torch
 
-REF = "/root/reference/src"
+REF = os.environ.get("HYDRODL2_REFERENCE", "")
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
@@ -31,9 +37,8 @@ from tests import golden_cases as gc  # noqa: E402
 
 
 def _import_reference():
-    if not os.path.isdir(REF):
-        raise SystemExit("reference not present: fixtures can only be generated in the "
-                         "authoring container")
+    if not REF or not os.path.isdir(REF):
+        raise SystemExit("reference not present: set HYDRODL2_REFERENCE to the src directory of a checkout")
     sys.path.insert(0, REF)
     v = types.ModuleType("hydrodl2._version")
     v.__version__ = "1.2.0"
@@ -152,6 +157,70 @@ def _uh_fixture(hydrodl2) -> dict:
     return rec
 
 
+def _live_draws(hydrodl2) -> dict:
+    """Every drawn case of golden_cases.live_case, keys "<seed>:<record key>"."""
+    rec = {"torch_version": np.array(torch.__version__)}
+    for seed in gc.LIVE_SEEDS:
+        name = f"_live_{seed}"
+        gc.CASES[name] = gc.live_case(seed)
+        try:
+            for k, v in _run_case(hydrodl2, name).items():
+                if k != "torch_version":
+                    rec[f"{seed}:{k}"] = v
+        finally:
+            del gc.CASES[name]
+    return rec
+
+
+def _plain(v):
+    if isinstance(v, dict):
+        return {k: _plain(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_plain(x) for x in v]
+    if isinstance(v, (set, frozenset, type({}.keys()))):     # compared as a set
+        return sorted(_plain(x) for x in v)
+    if isinstance(v, (torch.device, torch.dtype)):
+        return str(v)
+    if torch.is_tensor(v):
+        return v.tolist()
+    return v
+
+
+def _raises(fn):
+    """Name of the exception `fn()` raises, or None."""
+    try:
+        fn()
+    except Exception as ex:  # noqa: BLE001
+        return type(ex).__name__
+    return None
+
+
+def _api_record(hydrodl2) -> dict:
+    """The reference's public surface as plain JSON (tests/test_api_vs_reference.py reads it)."""
+    from tests import golden_mts
+    from tests.test_api_vs_reference import ATTRS, BAD_STATES, CONFIGS
+    dev = torch.device("cpu")
+    rec = {"configs": [], "available_models": {k: list(v) for k, v in hydrodl2.available_models().items()}}
+    for family, cls, cfg in CONFIGS:
+        m = hydrodl2.load_model(family, cls)(None if cfg is None else dict(cfg), dev)
+        rec["configs"].append({"family": family, "cls": cls, "config": cfg,
+                               "attrs": {a: _plain(getattr(m, a)) for a in ATTRS if hasattr(m, a)},
+                               "order": {a: list(getattr(m, a)) for a in ("parameter_bounds", "flux_names", "state_names")}})
+    rec["load_unknown_family_raises"] = _raises(lambda: hydrodl2.load_model("no_such_family"))
+    rec["load_unknown_class_returns"] = hydrodl2.load_model("hbv", "Nope").__name__
+    rec["load_states_raises"] = [_raises(lambda: hydrodl2.load_model("hbv", "Hbv")(None, dev).load_states(bad))
+                                 for bad in BAD_STATES]
+    low, high = golden_mts.configs("mts_chunked")
+    cls = hydrodl2.load_model("hbv_2_mts", "Hbv_2_mts")
+    m = cls(dict(low), dict(high), dev)
+    rec["mts"] = {"no_config_raises": _raises(lambda: cls(None, None, dev)),
+                  "attrs": {a: ({"module": type(v).__name__} if isinstance(v, torch.nn.Module) else {"value": _plain(v)})
+                            for a, v in vars(m).items() if not a.startswith("_") and a != "training"},
+                  "sub": {sub: {a: _plain(getattr(getattr(m, sub), a)) for a in ATTRS if hasattr(getattr(m, sub), a)}
+                          for sub in ("low_freq_model", "high_freq_model")}}
+    return rec
+
+
 def main(argv):
     warnings.filterwarnings("ignore")
     torch.set_num_threads(4)
@@ -159,6 +228,19 @@ def main(argv):
     outdir = os.path.dirname(os.path.abspath(__file__))
     names = argv or (list(gc.CASES) + ["uh_routing"])
     for name in names:
+        if name == "api":
+            import json
+            path = os.path.join(outdir, "reference_api.json")
+            text = json.dumps(_api_record(hydrodl2), indent=1, sort_keys=True)
+            with open(path, "w") as f:
+                f.write(text + "\n")
+            print(f"{name:24s} {os.path.getsize(path) / 1024:8.1f} KiB")
+            continue
+        if name == "live":
+            path = os.path.join(outdir, "live_draws.npz")
+            np.savez_compressed(path, **_live_draws(hydrodl2))
+            print(f"{name:24s} {os.path.getsize(path) / 1024:8.1f} KiB")
+            continue
         rec = _uh_fixture(hydrodl2) if name == "uh_routing" else _run_case(hydrodl2, name)
         path = os.path.join(outdir, f"{name}.npz")
         np.savez_compressed(path, **rec)

@@ -152,6 +152,41 @@ CASES = {
 
 LONG_CASES = [n for n, c in CASES.items() if "_long_" in n]
 
+# Randomly drawn cases (tests/test_live_reference.py): a fixed seed list, each seed one configuration -- model class,
+# ensemble size, dynamic-parameter set, warm-up, dy_drop, routing, cold start, parameter spread.  The reference's
+# outputs for every draw are stored in tests/golden/live_draws.npz (make_golden.py live).
+LIVE_SEEDS = list(range(40))
+
+
+def live_case(seed: int) -> dict:
+    """Spec of draw `seed` (same form as a CASES entry)."""
+    import random
+    rng = random.Random(seed)
+    model = rng.choice(["Hbv", "Hbv", "Hbv_1_1p", "Hbv_2", "Hbv_2_hourly"])
+    names = list(PHY_NAMES[model]) + (["parBETAET"] if model == "Hbv" else [])
+    mode = rng.choice(["static", "few", "few", "all"])
+    dyn = [] if mode == "static" else (list(names) if mode == "all" else rng.sample(names, rng.randint(1, 3)))
+    if model == "Hbv" and "parBETAET" not in dyn and rng.random() < 0.5:
+        names.remove("parBETAET")
+    dyn = tuple(n for n in names if n in dyn)
+    kw = {}
+    if model in ("Hbv", "Hbv_1_1p") and rng.random() < 0.4:
+        kw["warm_up"] = rng.choice([5, 12])
+        kw["warm_up_states"] = rng.random() < 0.7
+    if dyn and rng.random() < 0.4:
+        kw["dy_drop"] = 0.3
+    if model in ("Hbv_2", "Hbv_2_hourly"):
+        kw["routing"] = rng.random() < 0.5       # (routing=False on Hbv / Hbv_1_1p crashes upstream: hbv.py:550-567)
+    spec = dict(model=model, config=_cfg(model, rng.choice([2, 3, 4, 16]), dyn, **kw),
+                T=rng.choice([24, 40, 64]), B=rng.choice([3, 5, 7]), seed=1000 + seed, loss="all",
+                torch_seed=seed, cold=rng.random() < 0.3, raw_scale=rng.choice([1.0, 1.0, 2.5]))
+    if model == "Hbv_2_hourly":
+        spec["G"] = rng.choice([2, 3])
+        # a day or two of hours from a cold start moves no water: every gradient is a 1e-12 rounding residue.  Not a case
+        spec["cold"] = False
+        spec["T"] = max(spec["T"], 64)
+    return spec
+
 FLUX_KEYS_BASE = [
     "streamflow", "srflow", "ssflow", "gwflow", "AET_hydro", "PET_hydro", "SWE",
     "streamflow_no_rout", "srflow_no_rout", "ssflow_no_rout", "gwflow_no_rout",

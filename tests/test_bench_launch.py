@@ -25,6 +25,7 @@ def _run(oracle_path, *extra, gpus=2):
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout
+    assert len(lines[0]) < 4096, len(lines[0])     # a line a driver can read; the full record is on stderr
     return json.loads(lines[0])
 
 
@@ -109,6 +110,7 @@ def test_bench_line_contract_on_gpu():
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout
+    assert len(lines[0]) < 4096, len(lines[0])
     r = json.loads(lines[0])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):

@@ -1,10 +1,10 @@
-"""CPU tier, authoring container only: the CPU oracle against the LIVE reference on freshly drawn cases.
+"""CPU tier: the CPU oracle against the reference on randomly drawn cases.
 
-The committed fixtures pin the oracle on 39 hand-picked configurations; this test draws more of them every run from a
-fixed seed list -- model class, ensemble size, dynamic-parameter set, warm-up, dy_drop, routing, cold start, parameter
-spread -- runs the reference itself (imported from /root/reference exactly as tests/golden/make_golden.py does) and this
-package through the oracle, and compares every output, the final states and every gradient at the stated tolerances
-(tests/helpers.py::compare).  Skipped where the reference is not present (the GPU box).
+The committed fixtures pin the oracle on 39 hand-picked configurations; this test draws 40 more from a fixed seed list
+(tests/golden_cases.py::live_case) -- model class, ensemble size, dynamic-parameter set, warm-up, dy_drop, routing, cold
+start, parameter spread -- runs this package through the oracle, and compares every output, the final states and every
+gradient at the stated tolerances (tests/helpers.py::compare) with what the reference itself computed on the same draw
+(tests/golden/live_draws.npz, written by tests/golden/make_golden.py's `live` target).
 
 One allowance the committed fixtures do not need: up to 0.5 % of a gradient tensor's elements (or four) may miss the per-GROUP
 tolerance as long as they meet BASELINE.md's original proposal, 2e-6 of the TENSOR's largest entry.  Measured: draw 2 (Hbv,
@@ -13,65 +13,39 @@ cancel to 1.3e-6, so float32 evaluations scatter around the float64 value 1.9462
 float32 evaluation of the same equations 1.8665e-4, the oracle 2.0047e-4; draw 138 (all 13 parameters dynamic, cold start)
 -- parK2's per-day gradients of the first days, 5e-5 in a tensor whose largest entry is 22.6: reference -0.44 %, oracle
 +0.34 %, second float32 evaluation +0.66 % from the float64 value.  (Seeds 0-299 under these rules: 297 agree; the other three are
-single small elements of the same kind.  The 40 seeds below are the committed, deterministic set.)
+single small elements of the same kind.  golden_cases.LIVE_SEEDS are the committed, deterministic set.)
 """
 import os
-import random
-import sys
 import warnings
 
+import numpy as np
 import pytest
 
 from . import golden_cases as gc
 from .helpers import compare, run_case
 
-REF = "/root/reference/src"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live_draws.npz")
 
 
 class _Rec(dict):
     files = property(lambda self: list(self.keys()))
 
 
-def _draw(seed: int) -> dict:
-    rng = random.Random(seed)
-    model = rng.choice(["Hbv", "Hbv", "Hbv_1_1p", "Hbv_2", "Hbv_2_hourly"])
-    names = list(gc.PHY_NAMES[model]) + (["parBETAET"] if model == "Hbv" else [])
-    mode = rng.choice(["static", "few", "few", "all"])
-    dyn = [] if mode == "static" else (list(names) if mode == "all" else rng.sample(names, rng.randint(1, 3)))
-    if model == "Hbv" and "parBETAET" not in dyn and rng.random() < 0.5:
-        names.remove("parBETAET")
-    dyn = tuple(n for n in names if n in dyn)
-    kw = {}
-    if model in ("Hbv", "Hbv_1_1p") and rng.random() < 0.4:
-        kw["warm_up"] = rng.choice([5, 12])
-        kw["warm_up_states"] = rng.random() < 0.7
-    if dyn and rng.random() < 0.4:
-        kw["dy_drop"] = 0.3
-    if model in ("Hbv_2", "Hbv_2_hourly"):
-        kw["routing"] = rng.random() < 0.5       # (routing=False on Hbv / Hbv_1_1p crashes upstream: hbv.py:550-567)
-    spec = dict(model=model, config=gc._cfg(model, rng.choice([2, 3, 4, 16]), dyn, **kw),
-                T=rng.choice([24, 40, 64]), B=rng.choice([3, 5, 7]), seed=1000 + seed, loss="all",
-                torch_seed=seed, cold=rng.random() < 0.3, raw_scale=rng.choice([1.0, 1.0, 2.5]))
-    if model == "Hbv_2_hourly":
-        spec["G"] = rng.choice([2, 3])
-        # a day or two of hours from a cold start moves no water: every gradient is a 1e-12 rounding residue.  Not a case
-        spec["cold"] = False
-        spec["T"] = max(spec["T"], 64)
-    return spec
+@pytest.fixture(scope="module")
+def live_draws():
+    with np.load(RECORD) as z:
+        return {k: z[k] for k in z.files}
 
 
-@pytest.mark.parametrize("seed", list(range(40)))
-def test_oracle_equals_the_live_reference_on_a_fresh_case(seed, oracle_backend):
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import make_golden
+@pytest.mark.parametrize("seed", gc.LIVE_SEEDS)
+def test_oracle_equals_the_live_reference_on_a_fresh_case(seed, live_draws, oracle_backend):
     name = f"_live_{seed}"
-    gc.CASES[name] = _draw(seed)
+    gc.CASES[name] = gc.live_case(seed)
     try:
+        ref = _Rec({k.split(":", 1)[1]: v for k, v in live_draws.items() if k.startswith(f"{seed}:")})
+        assert ref, f"draw {seed} is not in {RECORD}"
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            hydrodl2 = make_golden._import_reference()
-            ref = _Rec(make_golden._run_case(hydrodl2, name))
             res = run_case(name, "cpu")
         compare(name, res, ref, grad_outlier_frac=5e-3, grad_outlier_atol_rel=2e-6)
     finally:
