@@ -105,6 +105,10 @@ EXPORTS = ["hbvx_zero", "hbvx_zero_except", "hbvx_preferred_traj_layout", "hbvx_
            "hbvx_gage_route_forward", "hbvx_gage_route_backward",
            "hbvx_gage_route_workspace_bytes"]
 
+# Exports a library may lack (the CPU restatement under oracle/ has only the calls above); a call that needs one raises
+# HbvxError naming it.
+OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx"]
+
 
 class HbvxError(RuntimeError):
     pass
@@ -178,6 +182,15 @@ class Library:
                                          C.c_void_p]
         d.hbvx_lstm_check.restype = C.c_int
         d.hbvx_lstm_check.argtypes = [C.POINTER(LstmDesc), C.c_void_p, C.c_void_p]
+        self.missing = [name for name in OPTIONAL_EXPORTS if not hasattr(d, name)]
+        if "hbvx_lstm_forward_hx" not in self.missing:
+            d.hbvx_lstm_forward_hx.restype = C.c_int
+            d.hbvx_lstm_forward_hx.argtypes = [C.POINTER(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p,
+                                               C.c_uint64, C.c_void_p]
+        if "hbvx_lstm_backward_hx" not in self.missing:
+            d.hbvx_lstm_backward_hx.restype = C.c_int
+            d.hbvx_lstm_backward_hx.argtypes = [C.POINTER(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                                C.c_void_p, C.c_uint64, C.c_void_p]
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -267,6 +280,23 @@ class Library:
                       ws_bytes: int, stream: int):
         self._check(self.dll.hbvx_lstm_backward(C.byref(r), w_hh, gates, c_all, gh, gg, ws,
                                                 C.c_uint64(ws_bytes), C.c_void_p(stream)), "hbvx_lstm_backward")
+
+    def require(self, name: str):
+        """Raises HbvxError if this library lacks the optional export `name`."""
+        if name in self.missing:
+            raise HbvxError(f"{self.path}: missing export {name} (backend {self.backend!r})")
+
+    def lstm_forward_hx(self, r: LstmDesc, w_hh: int, gx: int, h0, c0, gates: int, c_all: int, h_all: int, ws,
+                        ws_bytes: int, stream: int):
+        self.require("hbvx_lstm_forward_hx")
+        self._check(self.dll.hbvx_lstm_forward_hx(C.byref(r), w_hh, gx, h0, c0, gates, c_all, h_all, ws,
+                                                  C.c_uint64(ws_bytes), C.c_void_p(stream)), "hbvx_lstm_forward_hx")
+
+    def lstm_backward_hx(self, r: LstmDesc, w_hh: int, gates: int, c0, c_all: int, gh: int, gc_last, gg: int, gc0,
+                         ws, ws_bytes: int, stream: int):
+        self.require("hbvx_lstm_backward_hx")
+        self._check(self.dll.hbvx_lstm_backward_hx(C.byref(r), w_hh, gates, c0, c_all, gh, gc_last, gg, gc0, ws,
+                                                   C.c_uint64(ws_bytes), C.c_void_p(stream)), "hbvx_lstm_backward_hx")
 
     def lstm_check(self, r: LstmDesc, ws, stream: int):
         self._check(self.dll.hbvx_lstm_check(C.byref(r), ws, C.c_void_p(stream)), "hbvx_lstm_check")

@@ -97,9 +97,9 @@ static hipError_t launch_lstm(K kern, LstmArgs a, int nwg, hipStream_t st)
     return hipGetLastError();
 }
 
-extern "C" int hbvx_lstm_forward(const hbvx_lstm_desc *d, const float *w_hh, const float *gx, float *gates,
-                                 float *c_all, float *h_all, void *workspace, uint64_t workspace_bytes,
-                                 void *stream)
+extern "C" int hbvx_lstm_forward_hx(const hbvx_lstm_desc *d, const float *w_hh, const float *gx, const float *h0,
+                                    const float *c0, float *gates, float *c_all, float *h_all, void *workspace,
+                                    uint64_t workspace_bytes, void *stream)
 {
     int rc = check_lstm(d);
     if (rc) return rc;
@@ -112,6 +112,7 @@ extern "C" int hbvx_lstm_forward(const hbvx_lstm_desc *d, const float *w_hh, con
     LstmArgs a{};
     a.T = d->T; a.B = d->B; a.ntile = (d->B + LSTM_ROWS - 1) / LSTM_ROWS;
     a.w_hh = w_hh; a.gx = gx; a.gates = gates; a.c_all = c_all; a.h_all = h_all;
+    a.h0 = h0; a.c0 = c0;
     a.cnt = (unsigned *)workspace;
     a.xch = (float *)((char *)workspace + lstm_counter_bytes(d));
     a.spin_limit = (unsigned)env_int("HBVX_LSTM_SPIN_LIMIT", (int)LSTM_SPIN_LIMIT);
@@ -129,9 +130,17 @@ extern "C" int hbvx_lstm_forward(const hbvx_lstm_desc *d, const float *w_hh, con
     return 0;
 }
 
-extern "C" int hbvx_lstm_backward(const hbvx_lstm_desc *d, const float *w_hh, const float *gates,
-                                  const float *c_all, const float *grad_h, float *grad_gates,
-                                  void *workspace, uint64_t workspace_bytes, void *stream)
+extern "C" int hbvx_lstm_forward(const hbvx_lstm_desc *d, const float *w_hh, const float *gx, float *gates,
+                                 float *c_all, float *h_all, void *workspace, uint64_t workspace_bytes,
+                                 void *stream)
+{
+    return hbvx_lstm_forward_hx(d, w_hh, gx, nullptr, nullptr, gates, c_all, h_all, workspace, workspace_bytes, stream);
+}
+
+extern "C" int hbvx_lstm_backward_hx(const hbvx_lstm_desc *d, const float *w_hh, const float *gates, const float *c0,
+                                     const float *c_all, const float *grad_h, const float *grad_c_last,
+                                     float *grad_gates, float *grad_c0, void *workspace, uint64_t workspace_bytes,
+                                     void *stream)
 {
     int rc = check_lstm(d);
     if (rc) return rc;
@@ -145,6 +154,7 @@ extern "C" int hbvx_lstm_backward(const hbvx_lstm_desc *d, const float *w_hh, co
     LstmArgs a{};
     a.T = d->T; a.B = d->B; a.ntile = (d->B + LSTM_ROWS - 1) / LSTM_ROWS;
     a.w_hh = w_hh; a.gx = gates; a.gates = grad_gates; a.c_in = c_all; a.dh = grad_h;
+    a.c0 = c0; a.dc_last = grad_c_last; a.dc0 = grad_c0;
     a.cnt = (unsigned *)workspace;
     a.xch = (float *)((char *)workspace + lstm_counter_bytes(d));
     a.spin_limit = (unsigned)env_int("HBVX_LSTM_SPIN_LIMIT", (int)LSTM_SPIN_LIMIT);
@@ -153,6 +163,14 @@ extern "C" int hbvx_lstm_backward(const hbvx_lstm_desc *d, const float *w_hh, co
       : d->H == 128 ? launch_lstm(k_lstm_bwd<128>, a, 8, st) : launch_lstm(k_lstm_bwd<256>, a, 16, st);
     if (e != hipSuccess) return hip_fail(e, "hbvx_lstm_backward launch");
     return 0;
+}
+
+extern "C" int hbvx_lstm_backward(const hbvx_lstm_desc *d, const float *w_hh, const float *gates,
+                                  const float *c_all, const float *grad_h, float *grad_gates,
+                                  void *workspace, uint64_t workspace_bytes, void *stream)
+{
+    return hbvx_lstm_backward_hx(d, w_hh, gates, nullptr, c_all, grad_h, nullptr, grad_gates, nullptr, workspace,
+                                 workspace_bytes, stream);
 }
 
 extern "C" int hbvx_lstm_check(const hbvx_lstm_desc *d, const void *workspace, void *stream)

@@ -6,6 +6,8 @@
 //
 //   gates_t = gx_t + h_{t-1} W_hh^T          (gx = x W_ih^T + b_ih + b_hh: one library GEMM, host side)
 //   i, f, o = sigmoid, g = tanh;  c_t = f c_{t-1} + i g;  h_t = o tanh(c_t)      (torch.nn.LSTM)
+//   (h_{-1}, c_{-1}) = (h0, c0), zeros when not given; backward: dc_{T-1} starts from grad_c_last, and
+//   grad_c0 = dc_0 f_0 after the last (t = 0) step
 //
 // Basins are independent, so the batch is cut into row tiles of 16 basins (the N of
 // v_mfma_f32_16x16x4_f32: exact f32 products, a k-ordered fmaf chain) and only the H/16 workgroups
@@ -53,6 +55,9 @@ struct LstmArgs {
     const float *c_in;               // backward: c_all
     const float *dh;                 // backward: grad_h [T,B,H]
     float *c_all, *h_all;            // forward outputs [T,B,H]
+    const float *h0, *c0;            // initial state [B,H] (forward: h0 and c0; backward: c0); NULL = zeros
+    const float *dc_last;            // backward: gradient w.r.t. c_{T-1} [B,H]; NULL = zeros
+    float *dc0;                      // backward: gradient w.r.t. c0 [B,H]; NULL = not wanted
     float *xch;                      // exchange slabs, one per time step and row tile, sentinel-filled by k_lstm_arm
     unsigned *cnt;                   // cnt[0] = error word (zeroed by k_lstm_arm)
     unsigned spin_limit;             // polls before a hand-off gives up (LSTM_SPIN_LIMIT; lowered by the fault-injection test)
@@ -143,14 +148,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     if (threadIdx.x == 0) timed_out = 0;
     __syncthreads();
     const bool publish = (int)blockIdx.x != a.drop_wg;
-    float c = 0.0f;
+    float c = a.c0 ? a.c0[(size_t)rowc * H + unit] : 0.0f;
     for (int t = 0; t < a.T; ++t) {
         const size_t e = ((size_t)t * a.B + rowc) * H + unit;
         lstm_f4 acc = {0, 0, 0, 0};
         if (fin) acc = *reinterpret_cast<const lstm_f4 *>(a.gx + e * 4);
-        if (t > 0) {
+        if (t > 0 || a.h0) {
+            // step 0 of a stateful call takes h0 through the same MFMA chain and LDS sum as every later step
+            // (its granules in the slab's [H/4][16 rows][4 units] order), so a run resumed from (h_{t-1}, c_{t-1})
+            // gives the bits of the uninterrupted one
             lstm_f4 hv[KQ];
-            if (!lstm_fetch<KQ>(a, a.xch + ((size_t)(t - 1) * a.ntile + tile) * slab, (int)(slab * 4), w * (H / 16), kq, n, hv))
+            if (t == 0) {
+#pragma unroll
+                for (int j = 0; j < KQ; ++j)
+                    hv[j] = *reinterpret_cast<const lstm_f4 *>(a.h0 + (size_t)rowc * H + 4 * (w * (H / 16) + 4 * j + kq));
+            } else if (!lstm_fetch<KQ>(a, a.xch + ((size_t)(t - 1) * a.ntile + tile) * slab, (int)(slab * 4), w * (H / 16), kq, n, hv))
                 timed_out = 1;                      // every lane of the wave stores the same word
             lstm_f4 p[UG];
 #pragma unroll
@@ -217,12 +229,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     if (threadIdx.x == 0) timed_out = 0;
     __syncthreads();
     const bool publish = (int)blockIdx.x != a.drop_wg;
-    float dc_carry = 0.0f;
+    float dc_carry = a.dc_last ? a.dc_last[(size_t)rowc * H + unit] : 0.0f;
     for (int t = a.T - 1; t >= 0; --t) {
         const size_t e = ((size_t)t * a.B + rowc) * H + unit;
         const lstm_f4 act = *reinterpret_cast<const lstm_f4 *>(a.gx + e * 4);
         const float ct = a.c_in[e];
-        const float cp = t > 0 ? a.c_in[e - (size_t)a.B * H] : 0.0f;
+        const float cp = t > 0 ? a.c_in[e - (size_t)a.B * H] : (a.c0 ? a.c0[e] : 0.0f);   // e = rowc H + unit at t = 0
         float dh = a.dh[e];
         if (t + 1 < a.T) {
             lstm_f4 gv[KB];
@@ -251,6 +263,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 if (live) {
                     const lstm_f4 bad = {__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
                     *reinterpret_cast<lstm_f4 *>(a.gates + e * 4) = bad;
+                    if (a.dc0) a.dc0[e - (size_t)t * a.B * H] = __builtin_nanf("");   // [rowc][unit]
                 }
                 return;
             }
@@ -266,6 +279,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         d[3] = dh * tc * og * (1.0f - og);
         dc_carry = dc * fg;
         if (live) *reinterpret_cast<lstm_f4 *>(a.gates + e * 4) = d;
+        if (t == 0 && live && a.dc0) a.dc0[e] = dc_carry;   // dc_0 f_0: the gradient w.r.t. c0
         if (t > 0 && publish) {
             // 16 lanes of one store instruction cover a unit's 256-byte block: whole lines
             // (d comes out of VALU instructions: an inline-asm store placed straight after MFMAs would read the

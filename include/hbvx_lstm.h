@@ -1,6 +1,7 @@
 /* hbvx_lstm.h -- C ABI of the sequence LSTM that feeds hbvx_forward (the
  * caller side of the hot path -- delta-MG's parameter network; it is not part of the reference
- * repository, the semantics are torch.nn.LSTM's: one layer, zero initial state, gate order i, f, g, o).
+ * repository, the semantics are torch.nn.LSTM's: one layer, gate order i, f, g, o; the initial state
+ * (h0, c0) is zero in the first two calls below and given in the *_hx calls).
  * Exported by the same shared library as include/hbvx.h (libhbvx.so on the GPU, the CPU restatement
  * under oracle/ for tests).  Plain pointers and sizes; device pointers for the HIP library.
  *
@@ -47,6 +48,28 @@ int hbvx_lstm_forward(const hbvx_lstm_desc *d, const float *w_hh, const float *g
 int hbvx_lstm_backward(const hbvx_lstm_desc *d, const float *w_hh, const float *gates,
                        const float *c_all, const float *grad_h, float *grad_gates,
                        void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* The same recurrence from an initial state (h0, c0) [B,H] (torch.nn.LSTM's hx for one layer), and its adjoint.
+ * Additive to ABI version 1: HBVX_LSTM_ABI_VERSION and the workspace size are those of the calls above, which
+ * are these calls with every state pointer NULL.  A NULL h0, c0 or grad_c_last stands for zeros.
+ *
+ * Forward: step 0 multiplies h0 by W_hh on the same path as every later step multiplies h_{t-1}, so a run
+ * resumed from (h_all[T1-1], c_all[T1-1]) on rows T1.. of the same gx gives the bits of the uninterrupted run.
+ * h0 must be 16-byte aligned like gx.
+ *
+ * Backward: grad_c_last [B,H] is the gradient w.r.t. c_{T-1} from outside the sequence (torch's c_n);
+ * grad_c0 [B,H] (NULL = not wanted) receives the gradient w.r.t. c0.  The gradient w.r.t. h0 is
+ * grad_gates[0] W_hh (gate rows in the (unit, gate) order of grad_gates), a GEMM on the caller's side like
+ * grad_x; so is the step-0 term grad_gates[0]^T h0 of grad_W_hh.  A time-out poisons grad_c0 with NaN as well. */
+int hbvx_lstm_forward_hx(const hbvx_lstm_desc *d, const float *w_hh, const float *gx,
+                         const float *h0, const float *c0,
+                         float *gates, float *c_all, float *h_all,
+                         void *workspace, uint64_t workspace_bytes, void *stream);
+int hbvx_lstm_backward_hx(const hbvx_lstm_desc *d, const float *w_hh, const float *gates,
+                          const float *c0, const float *c_all, const float *grad_h,
+                          const float *grad_c_last,
+                          float *grad_gates, float *grad_c0,
+                          void *workspace, uint64_t workspace_bytes, void *stream);
 
 /* Synchronises `stream` and reports whether the last call that used `workspace` completed: the
  * workgroups of a row tile wait for each other with bounded spins; a time-out (the partners were

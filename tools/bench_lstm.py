@@ -2,7 +2,10 @@
 """Sequence LSTM: hydrodl2_amd.lstm.SeqLSTM (include/hbvx_lstm.h) beside torch.nn.LSTM (MIOpen) on the
 same weights and input, forward and forward+backward, at the delta-MG shape by default.
 
-    python tools/bench_lstm.py [T B I H] [--steps 20]
+    python tools/bench_lstm.py [T B I H] [--state]
+
+--state: also SeqLSTM with a carried initial state (h0, c0 requiring grad, the loss on out, h_n and c_n), next
+to the zero-state call, on the same weights and input.
 """
 import json
 import os
@@ -55,6 +58,29 @@ def main():
     for name, m in (("fused", fused), ("torch", ref)):
         res[f"{name}_fwd_ms"] = round(timed(lambda: fwd(m), steps), 3)
         res[f"{name}_fwdbwd_ms"] = round(timed(lambda: fwdbwd(m), steps), 3)
+    if "--state" in sys.argv:
+        h0 = (0.5 * torch.randn(1, B, H, device=dev)).requires_grad_(True)
+        c0 = torch.randn(1, B, H, device=dev).requires_grad_(True)
+        g2, g3 = torch.randn(1, B, H, device=dev), torch.randn(1, B, H, device=dev)
+
+        def fwd_state():
+            with torch.no_grad():
+                return fused(x, (h0, c0))[0]
+
+        def fwdbwd_state():
+            for t in [x, h0, c0] + list(fused.parameters()):
+                t.grad = None
+            out, (hn, cn) = fused(x, (h0, c0))
+            ((out * gh).sum() + (hn * g2).sum() + (cn * g3).sum()).backward()
+
+        # alternated with the zero-state call, so that both see the same state of the box
+        for _ in range(2):
+            for key, fn in (("fused_fwd_ms", lambda: fwd(fused)), ("fused_state_fwd_ms", fwd_state),
+                            ("fused_fwdbwd_ms", lambda: fwdbwd(fused)), ("fused_state_fwdbwd_ms", fwdbwd_state)):
+                res.setdefault(key + "_runs", []).append(round(timed(fn, steps), 3))
+        for key in ("fused_fwd_ms", "fused_state_fwd_ms", "fused_fwdbwd_ms", "fused_state_fwdbwd_ms"):
+            res[key] = min(res[key + "_runs"])
+        res["state_fwdbwd_over_zero_state"] = round(res["fused_state_fwdbwd_ms"] / res["fused_fwdbwd_ms"], 4)
     ops.KERNEL_EVENTS = []
     for _ in range(steps):
         fwdbwd(fused)

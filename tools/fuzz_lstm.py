@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Randomised soak of the sequence LSTM (hydrodl2_amd.lstm.SeqLSTM on the GPU) against torch.nn.LSTM in
-fp64, with the tolerances of tests/test_lstm.py:  python tools/fuzz_lstm.py [n_cases] [seed]"""
+fp64, with the tolerances of tests/test_lstm.py:  python tools/fuzz_lstm.py [n_cases] [seed]
+A third of the cases start from a random initial state (tests/test_lstm_state.py: h0, c0 requiring grad, the
+loss on out, h_n and c_n), on one or two layers."""
 import os
 import random
 import sys
@@ -8,6 +10,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tests.test_lstm import _run  # noqa: E402
+from tests.test_lstm_state import _case, _check  # noqa: E402
 
 
 def main():
@@ -23,13 +26,18 @@ def main():
         for k in ("HBVX_LSTM_UNITS", "HBVX_LSTM_WGS_PER_CU"):
             os.environ.pop(k, None)
         os.environ.update(env)
+        state = rng.random() < 1 / 3
+        L = rng.choice([1, 2]) if state else 1
         try:
-            _run("cuda", T, B, I, H, seed=rng.randint(0, 10 ** 6))
+            if state:
+                _check(*_case(T, B, I, H, L=L, seed=rng.randint(0, 10 ** 6)), L=L)
+            else:
+                _run("cuda", T, B, I, H, seed=rng.randint(0, 10 ** 6))
             status = "ok"
         except AssertionError as e:
             bad += 1
             status = "MISMATCH " + str(e)[:200]
-        print(f"[{case:3d}] {status} T={T} B={B} I={I} H={H} {env}", flush=True)
+        print(f"[{case:3d}] {status} T={T} B={B} I={I} H={H} {env}" + (f" hx L={L}" if state else ""), flush=True)
     print(f"{n - bad}/{n} cases agree", flush=True)
     return 1 if bad else 0
 
