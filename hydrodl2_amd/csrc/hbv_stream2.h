@@ -1,6 +1,6 @@
 // hbv_stream2.h -- streaming forward / adjoint for large grids, second generation.
 //
-// Measured on MI355X (profiles/r02_*): the first streaming kernels (hbv_stream.h) were bound by the
+// Measured on MI355X (profiles/r02_*): the first streaming kernels (since retired) were bound by the
 // NUMBER of vector-memory instructions, stores above all -- a wave-store costs the CU ~20 cycles of
 // issue whatever its width (12 flux stores of 16 useful bytes cost as much as 7 trajectory stores of
 // 256 bytes: 0.85 ms each of a 2.2 ms forward at 3 waves per SIMD) -- and by dependent-instruction
@@ -12,9 +12,10 @@
 //     in the forward and 2 (3) loads in the adjoint instead of 5 + 5 (7 + 7), inside the same caller buffer;
 //   * one flux store per day: after the ensemble butterflies every lane of a basin holds every mean;
 //     member lane j keeps series j and the wave writes 12 series x 4 basins with ONE store;
-//   * the three forcings of a basin in one 12-byte load when their channels are adjacent;
+//   * the three forcings of a basin in one 12-byte load: the channels are a permutation of {0, 1, 2} and
+//     adjacent (launch_stream_plan.h; other layouts run the pipelined / tiled forward and their adjoints);
 //   * the dynamic-parameter set is a template constant (the sets users run: none, {BETA, BETAET},
-//     {BETA, K0, BETAET}); any other set of up to three stays on hbv_stream.h;
+//     {BETA, K0, BETAET}); any other set of up to six is a run-time slot list (SC 3 and 4 below);
 //   * the adjoint keeps one day of inputs in flight, accumulates the static-parameter gradients in
 //     place, and is compiled for three or more waves per SIMD.
 //
@@ -26,9 +27,66 @@
 #include "../../include/hbvx.h"
 #include "hbv_step.h"
 #include "hbv_tiled.h"
-#include "hbv_stream.h"
 
 namespace hbvx {
+
+// kernel arguments (by value): the descriptor, the outputs / gradient buffers, and the launch plan
+// (launch_stream_plan.h)
+struct StreamArgs {
+    hbvx_desc d;
+    hbvx_fwd_out o;
+    int lgMp;
+    int nd;
+    int dslot[6];      // run-time slot lists (SC >= 3): up to STREAM2_LIST_MAX
+    int per_xcd;       // basin groups per XCD (grid = 8 * per_xcd)
+};
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_(float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+
+// sums over the Mp lanes of a basin for NV values at once (every lane of the basin gets the sums);
+// the wave-uniform tests on lgMp are outside the loops over the values: 6 scalar branches per call
+// instead of 6 per value
+template <int NV>
+__device__ __forceinline__ void ens_sum_dpp(float *v, int lgMp)
+{
+    if (lgMp >= 1) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) v[k] += dpp_<0xB1>(v[k]);   // quad_perm [1,0,3,2]
+    }
+    if (lgMp >= 2) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) v[k] += dpp_<0x4E>(v[k]);   // quad_perm [2,3,0,1]
+    }
+    if (lgMp >= 3) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) v[k] += dpp_<0x141>(v[k]);  // row_half_mirror: the other quad of the 8
+    }
+    if (lgMp >= 4) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) v[k] += dpp_<0x140>(v[k]);  // row_mirror: the other half of the 16
+    }
+    if (lgMp >= 5) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) v[k] += __shfl_xor(v[k], 16, 64);
+    }
+    if (lgMp >= 6) {
+#pragma unroll
+        for (int k = 0; k < NV; k++) v[k] += __shfl_xor(v[k], 32, 64);
+    }
+}
+
+struct StreamBwdArgs {
+    hbvx_desc d;
+    hbvx_bwd_io io;
+    int lgMp;
+    int nd;
+    int dslot[6];      // run-time slot lists (SC >= 3): up to STREAM2_LIST_MAX
+    int per_xcd;
+};
 
 // compile-time dynamic-parameter sets (slot lists in parameter order)
 template <int SC> struct StreamDyn { static constexpr int nd = 0; };
@@ -38,7 +96,7 @@ template <> struct StreamDyn<2> { static constexpr int nd = 3; };
 // slots in parameter order).  The parameter vector stays in registers: it is only ever indexed by constants, a
 // run-time slot goes through a compare chain on a scalar (s2_put / s2_get: ~3 scalar + 1 vector instruction per
 // candidate slot).  What the compile-time sets save over this form is exactly those chains (~50 vector instructions
-// per day and parameter); what this form replaces is the first-generation kernel (hbv_stream.h): 5.1 ms where a
+// per day and parameter); the first-generation kernel this form replaced (since retired) ran 5.1 ms where a
 // compiled set runs 1.6 ms at 4 096 wavefronts.
 template <> struct StreamDyn<3> { static constexpr int nd = 3; };
 // SC == 4: the same for four to six parameters (more rows in flight and staged; above six the tiled forward and the

@@ -668,22 +668,6 @@ int hbvx_host::lg_members(int M)
     return lg;
 }
 
-template <typename Args, typename K0, typename K1, typename K2, typename K3, typename K4>
-static hipError_t launch_variant(const hbvx_desc *d, const Args &a, dim3 grid, hipStream_t st,
-                                 K0 k0, K1 k1, K2 k2, K3 k3, K4 k4)
-{
-    if (d->model == HBVX_MODEL_HOURLY) {
-        hipLaunchKernelGGL(k4, grid, dim3(64), 0, st, a);
-        return hipGetLastError();
-    }
-    if (d->model == HBVX_MODEL_HBV10 && d->n_param == 12) hipLaunchKernelGGL(k0, grid, dim3(64), 0, st, a);
-    else if (d->model == HBVX_MODEL_HBV10) hipLaunchKernelGGL(k1, grid, dim3(64), 0, st, a);
-    else if (d->model == HBVX_MODEL_HBV11P) hipLaunchKernelGGL(k2, grid, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k3, grid, dim3(64), 0, st, a);
-    return hipGetLastError();
-}
-
-
 int hbvx_host::env_int(const char *name, int dflt)
 {
     const char *v = getenv(name);
@@ -779,9 +763,11 @@ static int forward_dispatch(const hbvx_desc *d, const hbvx_fwd_out *out, void *s
             ca.lgMp = lg_members(d->M);
             const int bpw_c = 64 >> ca.lgMp;
             note_dispatch(0, "simple");
-            hipError_t ec = launch_variant(d, ca, dim3((d->B + bpw_c - 1) / bpw_c), (hipStream_t)stream,
-                                           k_fwd<MODEL_HBV10, false>, k_fwd<MODEL_HBV10, true>,
-                                           k_fwd<MODEL_HBV11P, true>, k_fwd<MODEL_HBV20, true>, k_fwd<MODEL_HOURLY, true>);
+            const dim3 grid_c((d->B + bpw_c - 1) / bpw_c);
+            hipError_t ec = with_model(d, [&](auto m, auto be) {
+                hipLaunchKernelGGL((k_fwd<m, be>), grid_c, dim3(64), 0, (hipStream_t)stream, ca);
+                return hipGetLastError();
+            });
             return ec == hipSuccess ? HBVX_OK : hip_fail(ec, "hbvx_forward (checkpoints) launch");
         }
         // packed trajectory: the streaming family only (hbvx_preferred_traj_layout said so)
@@ -802,9 +788,10 @@ static int forward_dispatch(const hbvx_desc *d, const hbvx_fwd_out *out, void *s
     const int bpw = 64 >> a.lgMp;
     dim3 grid((d->B + bpw - 1) / bpw);
     note_dispatch(0, "simple");
-    hipError_t e = launch_variant(d, a, grid, (hipStream_t)stream,
-                                  k_fwd<MODEL_HBV10, false>, k_fwd<MODEL_HBV10, true>,
-                                  k_fwd<MODEL_HBV11P, true>, k_fwd<MODEL_HBV20, true>, k_fwd<MODEL_HOURLY, true>);
+    hipError_t e = with_model(d, [&](auto m, auto be) {
+        hipLaunchKernelGGL((k_fwd<m, be>), grid, dim3(64), 0, (hipStream_t)stream, a);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return hip_fail(e, "hbvx_forward launch");
     return HBVX_OK;
 }
@@ -840,9 +827,10 @@ extern "C" int hbvx_backward(const hbvx_desc *d, const hbvx_bwd_io *io, void *st
     dim3 grid((d->B + bpw - 1) / bpw);
     store_gate(io, (hipStream_t)stream);
     note_dispatch(1, "simple");
-    hipError_t e = launch_variant(d, a, grid, (hipStream_t)stream,
-                                  k_bwd<MODEL_HBV10, false>, k_bwd<MODEL_HBV10, true>,
-                                  k_bwd<MODEL_HBV11P, true>, k_bwd<MODEL_HBV20, true>, k_bwd<MODEL_HOURLY, true>);
+    hipError_t e = with_model(d, [&](auto m, auto be) {
+        hipLaunchKernelGGL((k_bwd<m, be>), grid, dim3(64), 0, (hipStream_t)stream, a);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return hip_fail(e, "hbvx_backward launch");
     return HBVX_OK;
 }

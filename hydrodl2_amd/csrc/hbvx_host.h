@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/hbvx.h"
 #include "hbv_step.h"
@@ -38,6 +39,24 @@ inline bool aux_matches_traj(const hbvx_fwd_out *out) { return !hbvx::SAVE_POW |
 
 static const int LDS_BUDGET = 160 * 1024 - 512; // gfx950: 160 KiB per CU, one workgroup may take it all
 
+// The template instance of the descriptor's explicit model: f(model, BETAET) with the two as
+// std::integral_constant / std::bool_constant, constant expressions inside f (`k<model, betaet>`,
+// `if constexpr`); f's result is returned.  BETAET: HBV 1.0 has it with 13 parameters (not with 12), the
+// other models always.  The descriptor has passed check_desc; HBVADJ has launchers of its own.
+template <typename F>
+auto with_model(const hbvx_desc *d, F &&f)
+{
+    using namespace hbvx;
+    switch (d->model) {
+    case HBVX_MODEL_HBV10:
+        if (d->n_param == 13) return f(std::integral_constant<int, MODEL_HBV10>{}, std::true_type{});
+        return f(std::integral_constant<int, MODEL_HBV10>{}, std::false_type{});
+    case HBVX_MODEL_HBV11P: return f(std::integral_constant<int, MODEL_HBV11P>{}, std::true_type{});
+    case HBVX_MODEL_HOURLY: return f(std::integral_constant<int, MODEL_HOURLY>{}, std::true_type{});
+    default: return f(std::integral_constant<int, MODEL_HBV20>{}, std::true_type{});   // HBVX_MODEL_HBV20
+    }
+}
+
 // launch_pipe.hip
 bool try_fwd_pipe(const hbvx_desc *d, const hbvx_fwd_out *out, void *stream, int *rc);
 // launch_stream.hip
@@ -48,6 +67,15 @@ bool try_fwd_stream(const hbvx_desc *d, const hbvx_fwd_out *out, void *stream, i
 // models with different dynamic sets) would otherwise launch "big, small, big" with the attribute left at "small".
 // One process-wide table under a mutex (autograd's backward thread and the main thread share it); hbvx.hip defines it.
 hipError_t set_dynamic_lds(const void *kern, int lds);
+// one launch of a kernel with dynamic LDS (the attribute raised first when it needs to be)
+template <typename Args, typename K>
+hipError_t launch_tiled_one(K kern, const Args &a, dim3 grid, int threads, size_t lds, hipStream_t st)
+{
+    hipError_t e = set_dynamic_lds(reinterpret_cast<const void *>(kern), (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, a);
+    return hipGetLastError();
+}
 // hbvx_bwd_io.store_gate: make `st` wait for the caller's event before a kernel that stores gradients is launched
 inline void store_gate(const hbvx_bwd_io *io, hipStream_t st)
 {

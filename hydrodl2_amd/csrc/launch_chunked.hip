@@ -110,11 +110,7 @@ static hipError_t launch_chunked_t(const ChunkArgs &a, hipStream_t st)
 template <int DYN, bool GFULL>
 static hipError_t launch_chunked_v(const hbvx_desc *d, const ChunkArgs &a, hipStream_t st)
 {
-    if (d->model == HBVX_MODEL_HBV10 && d->n_param == 12) return launch_chunked_t<MODEL_HBV10, false, DYN, GFULL>(a, st);
-    if (d->model == HBVX_MODEL_HBV10) return launch_chunked_t<MODEL_HBV10, true, DYN, GFULL>(a, st);
-    if (d->model == HBVX_MODEL_HBV11P) return launch_chunked_t<MODEL_HBV11P, true, DYN, GFULL>(a, st);
-    if (d->model == HBVX_MODEL_HOURLY) return launch_chunked_t<MODEL_HOURLY, true, DYN, GFULL>(a, st);
-    return launch_chunked_t<MODEL_HBV20, true, DYN, GFULL>(a, st);
+    return with_model(d, [&](auto m, auto be) { return launch_chunked_t<m, be, DYN, GFULL>(a, st); });
 }
 
 static hipError_t launch_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, hipStream_t st)

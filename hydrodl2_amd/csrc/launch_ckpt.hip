@@ -79,9 +79,6 @@ Plan plan(const hbvx_desc *d, int K)
     return P;
 }
 
-template <typename K>
-void launch_remat(K kern, const RematArgs &a, dim3 grid, hipStream_t st) { hipLaunchKernelGGL(kern, grid, dim3(64), 0, st, a); }
-
 } // namespace
 
 // include/hbvx.h
@@ -103,7 +100,6 @@ bool hbvx_host::try_bwd_ckpt(const hbvx_desc *d, const hbvx_bwd_io *io, void *st
     const int lg = lg_members(d->M);
     const int bpw = 64 >> lg;
     const unsigned W = (unsigned)((d->B + bpw - 1) / bpw);
-    const int m = d->model;
     const Plan P = plan(d, K);
     if (io->workspace && io->workspace_bytes >= P.total && env_int("HBVX_CKPT_BLOCKWISE", 1) != 0) {
         char *w = (char *)io->workspace;
@@ -126,11 +122,7 @@ bool hbvx_host::try_bwd_ckpt(const hbvx_desc *d, const hbvx_bwd_io *io, void *st
             ra.aux = s_aux;
             ra.lgMp = lg; ra.K = K; ra.t0 = t0; ra.tb = tb;
             const dim3 grid(W, (unsigned)((tb + K - 1) / K));
-            if (m == HBVX_MODEL_HBV10 && d->n_param == 12) launch_remat(k_ckpt_remat<MODEL_HBV10, false>, ra, grid, st);
-            else if (m == HBVX_MODEL_HBV10) launch_remat(k_ckpt_remat<MODEL_HBV10, true>, ra, grid, st);
-            else if (m == HBVX_MODEL_HBV11P) launch_remat(k_ckpt_remat<MODEL_HBV11P, true>, ra, grid, st);
-            else if (m == HBVX_MODEL_HOURLY) launch_remat(k_ckpt_remat<MODEL_HOURLY, true>, ra, grid, st);
-            else launch_remat(k_ckpt_remat<MODEL_HBV20, true>, ra, grid, st);
+            with_model(d, [&](auto m, auto be) { hipLaunchKernelGGL((k_ckpt_remat<m, be>), grid, dim3(64), 0, st, ra); });
             hipError_t e = hipGetLastError();
             // the block's window of the gradient series, compacted to [series, tb, B]
             if (e == hipSuccess && io->grad_flux) e = copy_window(io->grad_flux, s_gf, nf, tb, T, B, t0, st);
@@ -188,11 +180,7 @@ bool hbvx_host::try_bwd_ckpt(const hbvx_desc *d, const hbvx_bwd_io *io, void *st
     const dim3 grid(W);
     const size_t lds = (size_t)K * 7 * 64 * sizeof(float);
     store_gate(io, st);   // the one kernel of this path stores the dynamic-parameter / forcing gradients
-    if (m == HBVX_MODEL_HBV10 && d->n_param == 12) hipLaunchKernelGGL((k_bwd_ckpt<MODEL_HBV10, false>), grid, dim3(64), lds, st, a);
-    else if (m == HBVX_MODEL_HBV10) hipLaunchKernelGGL((k_bwd_ckpt<MODEL_HBV10, true>), grid, dim3(64), lds, st, a);
-    else if (m == HBVX_MODEL_HBV11P) hipLaunchKernelGGL((k_bwd_ckpt<MODEL_HBV11P, true>), grid, dim3(64), lds, st, a);
-    else if (m == HBVX_MODEL_HOURLY) hipLaunchKernelGGL((k_bwd_ckpt<MODEL_HOURLY, true>), grid, dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((k_bwd_ckpt<MODEL_HBV20, true>), grid, dim3(64), lds, st, a);
+    with_model(d, [&](auto m, auto be) { hipLaunchKernelGGL((k_bwd_ckpt<m, be>), grid, dim3(64), lds, st, a); });
     hipError_t e = hipGetLastError();
     note_dispatch(1, "ckpt-lds");
     *rc = e != hipSuccess ? hip_fail(e, "hbvx_backward (checkpoints) launch") : HBVX_OK;

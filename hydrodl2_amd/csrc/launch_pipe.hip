@@ -5,16 +5,6 @@
 using namespace hbvx;
 using namespace hbvx_host;
 
-template <typename Args, typename K>
-static hipError_t launch_tiled_one(K kern, const Args &a, dim3 grid, int threads, size_t lds,
-                                   hipStream_t st)
-{
-    hipError_t e = set_dynamic_lds(reinterpret_cast<const void *>(kern), (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, a);
-    return hipGetLastError();
-}
-
 bool hbvx_host::try_fwd_pipe(const hbvx_desc *d, const hbvx_fwd_out *out, void *stream, int *rc)
 {
         // HBV 1.0 / 1.1p / 2.0, at most PIPE_MAXDYN dynamic parameters, flux requested: pipelined
@@ -89,44 +79,42 @@ bool hbvx_host::try_fwd_pipe(const hbvx_desc *d, const hbvx_fwd_out *out, void *
             const int dflag = env_int("HBVX_PIPE_DIRECT", -1);
             const bool direct = !SAVE_POW && (dflag >= 0 ? dflag != 0 : bpw_p >= 8);
             hipStream_t st = (hipStream_t)stream;
-            hipError_t e;
             // compile-time dynamic sets (hbv_pipe.h, SC): {BETA, BETAET} and {BETA, K0, BETAET}
             unsigned dmask = 0;
             for (int i = 0; i < d->n_param; i++) dmask |= d->p[i].dyn ? (1u << i) : 0u;
             const int sc = dmask == ((1u << P_BETA) | (1u << P_BETAET)) ? 1
                          : dmask == ((1u << P_BETA) | (1u << P_K0) | (1u << P_BETAET)) ? 2 : 0;
-#define PIPE_GO(MODEL, BE, TR, DY, MANY, SC) e = launch_tiled_one(k_fwd_pipe<MODEL, BE, TR, DY, MANY, SC>, pa, grid_p, pthreads, lds, st)
-#define PIPE_GO3(MODEL, BE, TR, S1, S2)                                                            \
-    do {                                                                                           \
-        if (many) PIPE_GO(MODEL, BE, TR, true, true, 0);                                           \
-        else if (dy && sc == 1 && S1) PIPE_GO(MODEL, BE, TR, true, false, (S1 ? 1 : 0));           \
-        else if (dy && sc == 2 && S2) PIPE_GO(MODEL, BE, TR, true, false, (S2 ? 2 : 0));           \
-        else if (dy) PIPE_GO(MODEL, BE, TR, true, false, 0);                                       \
-        else PIPE_GO(MODEL, BE, TR, false, false, 0);                                              \
-    } while (0)
-#define PIPE_GO4(MODEL, BE, S1, S2)                                                                \
-    do {                                                                                           \
-        if (tr && direct) PIPE_GO3(MODEL, BE, 2, S1, S2);                                          \
-        else if (tr) PIPE_GO3(MODEL, BE, 1, S1, S2);                                               \
-        else PIPE_GO3(MODEL, BE, 0, S1, S2);                                                       \
-    } while (0)
-            if (adj) {   // at most PIPE_FEWDYN dynamic parameters (pmodel), descriptor flags
-#define PIPE_GO_ADJ(BE)                                                                            \
-    do {                                                                                           \
-        if (tr) { if (dy) PIPE_GO(MODEL_HBVADJ, BE, 1, true, false, 0); else PIPE_GO(MODEL_HBVADJ, BE, 1, false, false, 0); } \
-        else { if (dy) PIPE_GO(MODEL_HBVADJ, BE, 0, true, false, 0); else PIPE_GO(MODEL_HBVADJ, BE, 0, false, false, 0); } \
-    } while (0)
-                if (be) PIPE_GO_ADJ(true);
-                else PIPE_GO_ADJ(false);
-#undef PIPE_GO_ADJ
-            } else if (d->model == HBVX_MODEL_HBV11P) PIPE_GO4(MODEL_HBV11P, true, true, false);
-            else if (d->model == HBVX_MODEL_HBV20) PIPE_GO4(MODEL_HBV20, true, false, true);
-            else if (d->model == HBVX_MODEL_HOURLY) PIPE_GO4(MODEL_HOURLY, true, false, true);
-            else if (be) PIPE_GO4(MODEL_HBV10, true, true, true);
-            else PIPE_GO4(MODEL_HBV10, false, false, false);
-#undef PIPE_GO4
-#undef PIPE_GO3
-#undef PIPE_GO
+            // the instance for one (model, BETAET, trajectory mode), all three as std::integral_constant
+            auto go = [&](auto m, auto be_c, auto trm) -> hipError_t {
+                constexpr int MODEL = decltype(m)::value, TR = decltype(trm)::value;
+                constexpr bool BE = decltype(be_c)::value;
+                // the compiled sets: {BETA, BETAET} for HBV 1.0 with BETAET and 1.1p, {BETA, K0, BETAET} for HBV 1.0
+                // with BETAET, 2.0 and hourly
+                constexpr bool S1 = BE && (MODEL == MODEL_HBV10 || MODEL == MODEL_HBV11P);
+                constexpr bool S2 = BE && (MODEL == MODEL_HBV10 || MODEL == MODEL_HBV20 || MODEL == MODEL_HOURLY);
+                auto launch = [&](auto kern) { return launch_tiled_one(kern, pa, grid_p, pthreads, lds, st); };
+                if constexpr (MODEL != MODEL_HBVADJ)    // (HBVADJ: at most PIPE_FEWDYN dynamic parameters, pmodel)
+                    if (many) return launch(k_fwd_pipe<MODEL, BE, TR, true, true, 0>);
+                if constexpr (S1)
+                    if (dy && sc == 1) return launch(k_fwd_pipe<MODEL, BE, TR, true, false, 1>);
+                if constexpr (S2)
+                    if (dy && sc == 2) return launch(k_fwd_pipe<MODEL, BE, TR, true, false, 2>);
+                if (dy) return launch(k_fwd_pipe<MODEL, BE, TR, true, false, 0>);
+                return launch(k_fwd_pipe<MODEL, BE, TR, false, false, 0>);
+            };
+            constexpr std::integral_constant<int, 0> tr0{};
+            constexpr std::integral_constant<int, 1> tr1{};
+            constexpr std::integral_constant<int, 2> tr2{};
+            hipError_t e;
+            if (adj) {   // HBVADJ's own instances (descriptor flags): the drained row trajectory or none
+                constexpr std::integral_constant<int, MODEL_HBVADJ> ma{};
+                if (be) e = tr ? go(ma, std::true_type{}, tr1) : go(ma, std::true_type{}, tr0);
+                else e = tr ? go(ma, std::false_type{}, tr1) : go(ma, std::false_type{}, tr0);
+            } else {
+                e = with_model(d, [&](auto m, auto be_c) {
+                    return tr && direct ? go(m, be_c, tr2) : (tr ? go(m, be_c, tr1) : go(m, be_c, tr0));
+                });
+            }
             note_dispatch(0, "pipe");
             *rc = e != hipSuccess ? hip_fail(e, "hbvx_forward (pipelined) launch") : HBVX_OK;
             return true;

@@ -1,5 +1,5 @@
-// launch_stream_bwd.hip -- host dispatch of the streaming adjoints for large grids (hbv_stream2.h, hbv_stream2_ckpt.h;
-// hbv_stream.h for forcing layouts the second generation does not take).  The forwards: launch_stream.hip.
+// launch_stream_bwd.hip -- host dispatch of the streaming adjoints for large grids (hbv_stream2.h, hbv_stream2_ckpt.h).
+// The forwards: launch_stream.hip.
 #include "launch_stream_plan.h"
 #include "hbv_stream2_ckpt.h"
 
@@ -9,18 +9,10 @@ using namespace hbvx_host::stream_plan;
 
 namespace {
 
+// true when four waves per SIMD hold the grid in fewer rounds than three (hbv_stream2.h, W4)
 bool four_waves_pay(int64_t wgs)
 {
-    static int n_cu_of[64] = {0};
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-        if (n_cu_of[dev] == 0) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-            n_cu_of[dev] = v;
-        }
-        n_cu = n_cu_of[dev];
-    }
+    const int n_cu = device_cu_count();
     const int64_t s3 = (int64_t)n_cu * 4 * 3, s4 = (int64_t)n_cu * 4 * 4;
     return (wgs + s4 - 1) / s4 < (wgs + s3 - 1) / s3;
 }
@@ -64,8 +56,6 @@ void go_bwd2c(bool gfull, int K, const StreamBwdArgs &sa, dim3 grid, hipStream_t
     }
 }
 
-// second-generation kernels exist for these (model, BETAET, dynamic set) combinations
-
 } // namespace
 
 bool hbvx_host::try_bwd_stream(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc)
@@ -77,14 +67,13 @@ bool hbvx_host::try_bwd_stream(const hbvx_desc *d, const hbvx_bwd_io *io, void *
     bool ok = P.ok && (io->grad_flux || io->grad_flux4) && (packed || P.rows_ok);
     for (int i = 0; i < d->n_param && ok; i++)
         if (d->p[i].dyn && io->g[i].dyn)
-            ok = io->g[i].dyn_t_stride >= 0 && (int64_t)d->B * io->g[i].dyn_b_stride * 4 < lim &&
-                 (P.sc >= 0 || ((int64_t)d->T * io->g[i].dyn_t_stride + (int64_t)d->B * io->g[i].dyn_b_stride) * 4 < lim);
+            ok = io->g[i].dyn_t_stride >= 0 && (int64_t)d->B * io->g[i].dyn_b_stride * 4 < lim;
     if (packed) {
-        if (!(ok && P.sc >= 0 && P.packed_ok)) {
+        if (!(ok && P.packed_ok)) {
             *rc = fail(HBVX_E_UNSUPPORTED, "packed trajectory: no adjoint kernel for this call");
             return true;
         }
-    } else if (!(ok && !adjoint_pinned_elsewhere() && P.wgs >= stream_min(P, true, true))) {
+    } else if (!(ok && !adjoint_pinned_elsewhere() && P.wgs >= stream_min(true))) {
         return false;
     }
     StreamBwdArgs sa;
@@ -92,33 +81,16 @@ bool hbvx_host::try_bwd_stream(const hbvx_desc *d, const hbvx_bwd_io *io, void *
     sa.io = *io;
     sa.lgMp = P.lg;
     sa.nd = P.nd;
-    sa.per_xcd = 0;
     for (int k = 0; k < 6; k++) sa.dslot[k] = k < P.nd ? P.dslot[k] : 0;
-    const bool few = P.nd > 0, gfull = io->grad_flux != nullptr;
-    dim3 grid_s((unsigned)P.wgs);
+    sa.per_xcd = (int)((P.wgs + 7) / 8);
+    const dim3 grid2((unsigned)(8 * sa.per_xcd));
+    const bool gfull = io->grad_flux != nullptr;
+    const int trj = packed ? 2 : 1;
     hipStream_t st = (hipStream_t)stream;
     store_gate(io, st);          // single pass: the one kernel stores
-    if (P.sc >= 0) {
-        sa.per_xcd = (int)((P.wgs + 7) / 8);
-        const dim3 grid2((unsigned)(8 * sa.per_xcd));
-        STREAM2_DISPATCH(go_bwd2, d, P.sc, packed ? 2 : 1, gfull, sa, grid2, st);
-    } else {
-#define STREAM_GO(MODEL, BE)                                                                              \
-    do {                                                                                                  \
-        if (few) { if (gfull) hipLaunchKernelGGL((k_bwd_stream<MODEL, BE, true, true>), grid_s, dim3(64), 0, st, sa);    \
-                   else hipLaunchKernelGGL((k_bwd_stream<MODEL, BE, true, false>), grid_s, dim3(64), 0, st, sa); }      \
-        else { if (gfull) hipLaunchKernelGGL((k_bwd_stream<MODEL, BE, false, true>), grid_s, dim3(64), 0, st, sa);       \
-               else hipLaunchKernelGGL((k_bwd_stream<MODEL, BE, false, false>), grid_s, dim3(64), 0, st, sa); }         \
-    } while (0)
-        if (d->model == HBVX_MODEL_HBV10 && d->n_param == 12) STREAM_GO(MODEL_HBV10, false);
-        else if (d->model == HBVX_MODEL_HBV10) STREAM_GO(MODEL_HBV10, true);
-        else if (d->model == HBVX_MODEL_HBV11P) STREAM_GO(MODEL_HBV11P, true);
-        else if (d->model == HBVX_MODEL_HOURLY) STREAM_GO(MODEL_HOURLY, true);
-        else STREAM_GO(MODEL_HBV20, true);
-#undef STREAM_GO
-    }
+    with_stream2(d, P.sc, [&](auto m, auto be, auto sc) { go_bwd2<m, be, sc>(trj, gfull, sa, grid2, st); });
     hipError_t e = hipGetLastError();
-    note_dispatch(1, P.sc >= 0 ? "stream2" : "stream");
+    note_dispatch(1, "stream2");
     *rc = e != hipSuccess ? hip_fail(e, "hbvx_backward (stream) launch") : HBVX_OK;
     return true;
 }
@@ -135,9 +107,9 @@ bool hbvx_host::stream_ckpt_applicable(const hbvx_desc *d, int K)
     const int want = env_int("HBVX_CKPT_ONCHIP", -1);
     if (want == 0) return false;
     const StreamPlan P = plan_stream(d);
-    if (!(P.ok && P.sc >= 0 && P.sc != 4 && P.packed_ok)) return false;
+    if (!(P.ok && P.sc != 4 && P.packed_ok)) return false;
     if (want == 1) return true;
-    return !adjoint_pinned_elsewhere() && P.wgs >= stream_min(P, true, true);
+    return !adjoint_pinned_elsewhere() && P.wgs >= stream_min(true);
 }
 
 bool hbvx_host::try_bwd_stream_ckpt(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc)
@@ -162,7 +134,7 @@ bool hbvx_host::try_bwd_stream_ckpt(const hbvx_desc *d, const hbvx_bwd_io *io, v
     store_gate(io, st);          // single pass: the one kernel stores
     hipError_t e = hipSuccess;
     const bool gfull = io->grad_flux != nullptr;
-    STREAM2_DISPATCH(go_bwd2c, d, P.sc, gfull, K, sa, grid2, st, &e);
+    with_stream2(d, P.sc, [&](auto m, auto be, auto sc) { go_bwd2c<m, be, sc>(gfull, K, sa, grid2, st, &e); });
     if (e == hipSuccess) e = hipGetLastError();
     note_dispatch(1, "ckpt-stream2");
     *rc = e != hipSuccess ? hip_fail(e, "hbvx_backward (on-chip checkpoints) launch") : HBVX_OK;

@@ -65,31 +65,15 @@ static bool geom_bwd(const hbvx_desc *d, const hbvx_bwd_io *io, TileGeom &g)
     return false;
 }
 
-template <typename Args, typename K>
-static hipError_t launch_tiled_one(K kern, const Args &a, dim3 grid, int threads, size_t lds,
-                                   hipStream_t st)
+// threads of a tiled launch: one stepper wave and nh helper waves (HBVX_NH); limit256: the kernel's HBV 2.0 / hourly
+// instances are compiled for 256 threads (hbv_tiled.h, bwd_tiled_threads)
+static int tiled_threads(const hbvx_desc *d, dim3 grid, bool limit256)
 {
-    hipError_t e = set_dynamic_lds(reinterpret_cast<const void *>(kern), (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, st, a);
-    return hipGetLastError();
+    int nh = env_int("HBVX_NH", grid.x >= 1024 ? 3 : 7);
+    nh = nh < 1 ? 1 : (nh > 7 ? 7 : nh);
+    if (limit256 && (d->model == HBVX_MODEL_HBV20 || d->model == HBVX_MODEL_HOURLY)) nh = nh > 3 ? 3 : nh;
+    return 64 * (1 + nh);
 }
-
-// LIMIT256: the kernel's HBV 2.0 / hourly instances are compiled for 256 threads (hbv_tiled.h, bwd_tiled_threads)
-#define LAUNCH_TILED_V(K, d, a, grid, lds, st, ...)                                                \
-    ([&]() -> hipError_t {                                                                        \
-        int nh = env_int("HBVX_NH", (grid).x >= 1024 ? 3 : 7);                                    \
-        nh = nh < 1 ? 1 : (nh > 7 ? 7 : nh);                                                      \
-        if (LIMIT256 && ((d)->model == HBVX_MODEL_HBV20 || (d)->model == HBVX_MODEL_HOURLY)) nh = nh > 3 ? 3 : nh; \
-        const int threads = 64 * (1 + nh);                                                        \
-        const int m = (d)->model;                                                                 \
-        const bool be = (d)->n_param == 13;                                                       \
-        if (m == HBVX_MODEL_HBV10 && !be) return launch_tiled_one(K<MODEL_HBV10, false, __VA_ARGS__>, a, grid, threads, lds, st); \
-        if (m == HBVX_MODEL_HBV10) return launch_tiled_one(K<MODEL_HBV10, true, __VA_ARGS__>, a, grid, threads, lds, st);         \
-        if (m == HBVX_MODEL_HBV11P) return launch_tiled_one(K<MODEL_HBV11P, true, __VA_ARGS__>, a, grid, threads, lds, st);       \
-        if (m == HBVX_MODEL_HOURLY) return launch_tiled_one(K<MODEL_HOURLY, true, __VA_ARGS__>, a, grid, threads, lds, st);       \
-        return launch_tiled_one(K<MODEL_HBV20, true, __VA_ARGS__>, a, grid, threads, lds, st);    \
-    })()
 
 bool hbvx_host::try_fwd_tiled(const hbvx_desc *d, const hbvx_fwd_out *out, void *stream, int *rc)
 {
@@ -101,9 +85,12 @@ bool hbvx_host::try_fwd_tiled(const hbvx_desc *d, const hbvx_fwd_out *out, void 
             dim3 grid_t((d->B + bpw_t - 1) / bpw_t);
             const size_t lds = (size_t)2 * (ta.g.in_sz + ta.g.out_sz) * 4;
             const bool dyn = ta.g.NDm > 0;
-            constexpr bool LIMIT256 = false;
-            hipError_t e = dyn ? LAUNCH_TILED_V(k_fwd_tiled, d, ta, grid_t, lds, (hipStream_t)stream, true)
-                               : LAUNCH_TILED_V(k_fwd_tiled, d, ta, grid_t, lds, (hipStream_t)stream, false);
+            const int threads = tiled_threads(d, grid_t, false);
+            hipStream_t st = (hipStream_t)stream;
+            hipError_t e = with_model(d, [&](auto m, auto be) {
+                return dyn ? launch_tiled_one(k_fwd_tiled<m, be, true>, ta, grid_t, threads, lds, st)
+                           : launch_tiled_one(k_fwd_tiled<m, be, false>, ta, grid_t, threads, lds, st);
+            });
             note_dispatch(0, "tiled");
             *rc = e != hipSuccess ? hip_fail(e, "hbvx_forward (tiled) launch") : HBVX_OK;
             return true;
@@ -121,19 +108,16 @@ bool hbvx_host::try_bwd_tiled(const hbvx_desc *d, const hbvx_bwd_io *io, void *s
             dim3 grid_t((d->B + bpw_t - 1) / bpw_t);
             const size_t lds = (size_t)2 * (ta.g.in_sz + ta.g.out_sz) * 4;
             const bool dyn = ta.g.NDm > 0, gfull = io->grad_flux != nullptr;
-            hipStream_t st_ = (hipStream_t)stream;
-            store_gate(io, st_);
-            hipError_t e =
-                [&]() -> hipError_t {
-                    if (dyn) {
-                        constexpr bool LIMIT256 = true;
-                        return gfull ? LAUNCH_TILED_V(k_bwd_tiled, d, ta, grid_t, lds, st_, true, true)
-                                     : LAUNCH_TILED_V(k_bwd_tiled, d, ta, grid_t, lds, st_, true, false);
-                    }
-                    constexpr bool LIMIT256 = false;
-                    return gfull ? LAUNCH_TILED_V(k_bwd_tiled, d, ta, grid_t, lds, st_, false, true)
-                                 : LAUNCH_TILED_V(k_bwd_tiled, d, ta, grid_t, lds, st_, false, false);
-                }();
+            const int threads = tiled_threads(d, grid_t, dyn);
+            hipStream_t st = (hipStream_t)stream;
+            store_gate(io, st);
+            hipError_t e = with_model(d, [&](auto m, auto be) {
+                if (dyn)
+                    return gfull ? launch_tiled_one(k_bwd_tiled<m, be, true, true>, ta, grid_t, threads, lds, st)
+                                 : launch_tiled_one(k_bwd_tiled<m, be, true, false>, ta, grid_t, threads, lds, st);
+                return gfull ? launch_tiled_one(k_bwd_tiled<m, be, false, true>, ta, grid_t, threads, lds, st)
+                             : launch_tiled_one(k_bwd_tiled<m, be, false, false>, ta, grid_t, threads, lds, st);
+            });
             note_dispatch(1, "tiled");
             *rc = e != hipSuccess ? hip_fail(e, "hbvx_backward (tiled) launch") : HBVX_OK;
             return true;

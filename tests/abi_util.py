@@ -39,10 +39,11 @@ def make_problem(model="Hbv", T=40, B=5, M=4, dyn=(), betaet=False, drop_frac=0.
     if model == "Hbv_2_hourly":  # per-step depths of an hourly record
         prob["x"] = prob["x"] * np.array([1.0 / 8.0, 1.0, 1.0 / 24.0], np.float32)
         prob["routing"] = routing = False  # its 72-tap routing is not the library's 15-tap one
-    # `channels`: where (prcp, tmean, pet) sit in the last axis of x (config key `variables` of the modules)
+    # `channels`: where (prcp, tmean, pet) sit in the last axis of x (config key `variables` of the modules); an index
+    # above 2 widens that axis (a C-ABI caller's forcing tensor), the channels no index names holding a decoy value
     prob["channels"] = tuple(channels)
     if tuple(channels) != (0, 1, 2):
-        xp = np.empty_like(prob["x"])
+        xp = np.full((T, B, max(3, max(channels) + 1)), 7.5, np.float32)
         for std, pos in enumerate(channels):
             xp[:, :, pos] = prob["x"][:, :, std]
         prob["x"] = xp

@@ -171,12 +171,13 @@ def test_pipelined_forward_equals_tiled_forward(M, B, T, model, dyn, betaet, dro
     ("Hbv", (), 1, 131200), ("Hbv_2", (), 2, 65600), ("Hbv", ("parK1",), 64, 2050)])
 def test_stream_forward_equals_tiled_forward(model, dyn, M, B, hip_backend, monkeypatch):
     """Large grids (>= 2048 wavefronts of state here, so that both directions take it) run the
-    streaming one-wave kernels (hbv_stream.h).  The forward is bit-identical to the tiled /
-    pipelined kernels (same step arithmetic, same ensemble add tree), with and without the saved
-    trajectory; the single-pass adjoint is bit-identical to the serial tiled adjoint (T < 128)."""
+    streaming kernels (hbv_stream2.h).  The forward is bit-identical to the tiled / pipelined
+    kernels (same step arithmetic, same ensemble add tree), with and without the saved trajectory;
+    the single-pass adjoint matches the serial tiled adjoint (T < 128) up to the rounding noted below."""
     T = 37
     prob = make_problem(model=model, T=T, B=B, M=M, dyn=dyn, drop_frac=0.3 if dyn else 0.0, seed=33)
     a = run_problem(prob, None, device="cuda:0", backward=True)
+    assert (hip_backend.last_dispatch(0), hip_backend.last_dispatch(1)) == ("stream2", "stream2")
     a2 = run_problem(prob, None, device="cuda:0", backward=False)
     monkeypatch.setenv("HBVX_STREAM", "0")
     b = run_problem(prob, None, device="cuda:0", backward=True)
@@ -186,6 +187,20 @@ def test_stream_forward_equals_tiled_forward(model, dyn, M, B, hip_backend, monk
     # the streaming adjoint applies a static parameter's range factor once, after the sum over days
     # (the tiled one per day): same terms, rounding differs in the last bits
     assert_grad_close("g_params", a["g_params"], b["g_params"], column_groups(prob["ny"], M), rtol=2e-5, atol_rel=1e-6)
+
+
+def test_other_forcing_layout_runs_pipelined_and_time_parallel(hip_backend, oracle_path, monkeypatch):
+    """Forcing channels outside {0, 1, 2} (a caller's wider forcing tensor) are not a layout the streaming kernels
+    read (launch_stream_plan.h::plan_stream): with the streaming threshold at one wavefront the pipelined forward and
+    the time-parallel adjoint still run, and match the oracle, forcing gradient included."""
+    monkeypatch.setenv("HBVX_STREAM_MIN", "1")
+    prob = make_problem(model="Hbv", T=140, B=9, M=16, dyn=("parBETA", "parBETAET"), drop_frac=0.3, seed=21,
+                        channels=(3, 0, 2))
+    got = run_problem(prob, None, device="cuda:0", x_grad=True)
+    fwd, bwd = hip_backend.last_dispatch(0), hip_backend.last_dispatch(1)
+    want = run_problem(prob, oracle_path, device="cpu", x_grad=True)
+    compare_runs(prob, got, want)
+    assert fwd in ("pipe", "tiled") and bwd in ("chunked", "tiled"), (fwd, bwd)
 
 
 STREAM2_CASES = [
@@ -344,11 +359,11 @@ def test_long_golden_case_under_every_adjoint(name, env_id, hip_backend, monkeyp
     compare(name, res, ref)
     model = gc.CASES[name]["model"]
     dyn = tuple(gc.CASES[name]["config"]["dynamic_params"][model])
-    # hbv_stream2.h holds every set of at most three dynamic parameters (two compiled sets, the rest as a run-time slot
-    # list: launch_stream.hip::plan_stream); more than three stay on the first generation / the time-parallel adjoint
+    # hbv_stream2.h holds every set of at most six dynamic parameters (two compiled sets, the rest as a run-time slot
+    # list: launch_stream_plan.h::plan_stream); more than six stay on the time-parallel adjoint
     has_stream2 = len(dyn) <= 6
     if want_bwd == {"stream2"} and not has_stream2:
-        want_bwd = {"chunked", "stream"}     # no second-generation instance for this dynamic set
+        want_bwd = {"chunked"}               # no streaming instance for this dynamic set
     if want_bwd == {"ckpt-stream2"} and len(dyn) > 3:
         want_bwd = {"ckpt-block:chunked"}    # the on-chip checkpoint kernel holds the three-slot lists (launch_stream_bwd.hip)
     if gc.CASES[name].get("muwts"):
