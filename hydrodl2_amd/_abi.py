@@ -72,6 +72,18 @@ class BwdIO(C.Structure):
                 ("workspace", _fp), ("workspace_bytes", C.c_uint64), ("store_gate", _fp)]
 
 
+class ParamTan(C.Structure):
+    _fields_ = [("dyn", _fp), ("sta", _fp),
+                ("dyn_t_stride", C.c_int64), ("dyn_b_stride", C.c_int64),
+                ("sta_b_stride", C.c_int64)]
+
+
+class TanIO(C.Structure):
+    """hbvx_tan_io: the tangents of one forward-mode call (include/hbvx.h)."""
+    _fields_ = [("x", _fp), ("muwts", _fp), ("state_in", _fp), ("p", ParamTan * MAX_PARAM),
+                ("tan_flux", _fp), ("tan_state_out", _fp), ("n_flux", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class RouteDesc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("T", C.c_int32), ("B", C.c_int32),
                 ("S", C.c_int32), ("L", C.c_int32), ("raw_sigmoid", C.c_int32),
@@ -107,7 +119,8 @@ EXPORTS = ["hbvx_zero", "hbvx_zero_except", "hbvx_preferred_traj_layout", "hbvx_
 
 # Exports a library may lack (the CPU restatement under oracle/ has only the calls above); a call that needs one raises
 # HbvxError naming it.
-OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx"]
+OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forward_tangent", "hbvx_route_tangent",
+                    "hbvx_bfi_tangent"]
 
 
 class HbvxError(RuntimeError):
@@ -191,6 +204,17 @@ class Library:
             d.hbvx_lstm_backward_hx.restype = C.c_int
             d.hbvx_lstm_backward_hx.argtypes = [C.POINTER(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
                                                 C.c_void_p, C.c_uint64, C.c_void_p]
+        if "hbvx_forward_tangent" not in self.missing:
+            d.hbvx_forward_tangent.restype = C.c_int
+            d.hbvx_forward_tangent.argtypes = [C.POINTER(Desc), C.POINTER(TanIO), C.c_void_p]
+            if d.hbvx_sizeof(7) != C.sizeof(TanIO):
+                raise HbvxError(f"{path}: layout mismatch for TanIO: {d.hbvx_sizeof(7)} != {C.sizeof(TanIO)}")
+        if "hbvx_route_tangent" not in self.missing:
+            d.hbvx_route_tangent.restype = C.c_int
+            d.hbvx_route_tangent.argtypes = [C.POINTER(RouteDesc), _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
+        if "hbvx_bfi_tangent" not in self.missing:
+            d.hbvx_bfi_tangent.restype = C.c_int
+            d.hbvx_bfi_tangent.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_float, _fp, C.c_void_p]
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -297,6 +321,20 @@ class Library:
         self.require("hbvx_lstm_backward_hx")
         self._check(self.dll.hbvx_lstm_backward_hx(C.byref(r), w_hh, gates, c0, c_all, gh, gc_last, gg, gc0, ws,
                                                    C.c_uint64(ws_bytes), C.c_void_p(stream)), "hbvx_lstm_backward_hx")
+
+    def forward_tangent(self, desc: Desc, io: TanIO, stream: int):
+        self.require("hbvx_forward_tangent")
+        self._check(self.dll.hbvx_forward_tangent(C.byref(desc), C.byref(io), C.c_void_p(stream)), "hbvx_forward_tangent")
+
+    def route_tangent(self, r: RouteDesc, q: int, uh: int, q_dot, ra_dot, rb_dot, q_rout_dot: int, stream: int):
+        self.require("hbvx_route_tangent")
+        self._check(self.dll.hbvx_route_tangent(C.byref(r), q, uh, q_dot, ra_dot, rb_dot, q_rout_dot,
+                                                C.c_void_p(stream)), "hbvx_route_tangent")
+
+    def bfi_tangent(self, T: int, B: int, qs: int, q2: int, qs_dot, q2_dot, nearzero: float, out: int, stream: int):
+        self.require("hbvx_bfi_tangent")
+        self._check(self.dll.hbvx_bfi_tangent(T, B, qs, q2, qs_dot, q2_dot, C.c_float(nearzero), out,
+                                              C.c_void_p(stream)), "hbvx_bfi_tangent")
 
     def lstm_check(self, r: LstmDesc, ws, stream: int):
         self._check(self.dll.hbvx_lstm_check(C.byref(r), ws, C.c_void_p(stream)), "hbvx_lstm_check")

@@ -18,7 +18,7 @@ import os
 import torch
 
 from .. import _abi
-from ..ops import Bfi, ParamSource, RouteSource, StepConfig, hbv_path
+from ..ops import Bfi, ParamSource, RouteSource, StepConfig, has_tangent, hbv_path
 
 
 class HbvModule(torch.nn.Module):
@@ -271,9 +271,16 @@ class HbvModule(torch.nn.Module):
                 ) -> Union[tuple, dict[str, torch.Tensor]]:
         """Reference: hbv.py:284-361 (orchestration) + :363-596 (`_PBM`)."""
         if self.graph and x_dict['x_phy'].is_cuda:
+            self._refuse_dual_graph(x_dict, parameters)
             from hydrodl2_amd.graphed import graphed_forward
             return graphed_forward(self, x_dict, parameters)
         return self._forward_eager(x_dict, parameters)
+
+    def _refuse_dual_graph(self, x_dict, parameters) -> None:
+        """A captured HIP graph replays the primal launches only: forward-mode AD runs eagerly."""
+        if has_tangent(tuple(x_dict.values()), parameters):
+            raise ValueError(f"{type(self).__name__}(graph=True) does not support forward-mode AD (dual inputs); "
+                             "use graph=False")
 
     def _forward_eager(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor
                        ) -> Union[tuple, dict[str, torch.Tensor]]:
@@ -313,10 +320,13 @@ class HbvModule(torch.nn.Module):
                     raise ValueError(f"{name} holds non-finite values (check_finite is set)")
         cfg_w, cfg = self._step_configs(T_total, ngrid, ny, warm_up, x.device)
 
-        # hbv.py:327-346: state warm-up, all parameters static from row warm_up-1, no grad
+        # hbv.py:327-346: state warm-up, all parameters static from row warm_up-1, no grad.  no_grad does not stop
+        # forward-mode AD: under a forward-AD level the reference's tangent flows through the warm-up, so the dual is
+        # kept there (and only there; detach() would drop the tangent)
         if cfg_w is not None:
+            pw = parameters if has_tangent(parameters) else parameters.detach()
             with torch.no_grad():
-                state_in = hbv_path(cfg_w, x, state_in, None, None, None, parameters.detach()).state_out
+                state_in = hbv_path(cfg_w, x, state_in, None, None, None, pw).state_out
 
         # hbv.py:349-353.  The dy_drop masks are drawn per call (hbv.py:240-246), also when nothing can drop
         T = T_total - warm_up

@@ -356,6 +356,11 @@ struct FluxGrad {
     float gQ, gQ0, gQ1, gQ2, gET, gSWE, grech, gexc, gef, gtosoil, gPERC, gcap;
 };
 
+// Tangents of the per-day series of one lane (forward-mode derivative of what FluxGrad weights).
+struct FluxTan {
+    float Q, Q0, Q1, Q2, ET, SWE, rech, exc, ef, tosoil, PERC, cap;
+};
+
 // All intermediates of one step.  The compiler keeps what is live in VGPRs.
 template <int MODEL, bool BETAET>
 struct Step {
@@ -664,6 +669,102 @@ struct Step {
         gp[P_TT] += aTTe * mlo;
 
         a[0] = aSP; a[1] = aMW; a[2] = aSM; a[3] = aSUZ; a[4] = aSLZ;
+    }
+
+    // Tangent (forward-mode derivative) of fwd(), the transpose of bwd() line for line: the same predicates, tie
+    // weights and power derivatives (torch's forward formulas: minimum ties 1/2 each, clamp inclusive, d(x**y) = 0
+    // at x == 0).  Reads the intermediates fwd() left -- with CHAIN = false, the reference's form of the evaporation
+    // quotient, as the adjoint's recomputation.  ds[5]: tangents of the storages entering the day in, leaving it out.
+    // dp[]: tangents of the day's physical parameters; dx[3]: of (P, T, PET).  f: tangents of the day's series.
+    HBVX_HDM void tan(const float *p, float nz, const float *dp, const float *dx, float *ds, FluxTan &f) const
+    {
+        HBVX_ADJ_FMA
+        const float BETA = p[P_BETA], FC = p[P_FC], K0 = p[P_K0], K1 = p[P_K1], K2 = p[P_K2], LP = p[P_LP],
+                    CFMAX = p[P_CFMAX], CFR = p[P_CFR], CWH = p[P_CWH];
+        float wa, wb;
+        // snow
+        const float dTTe = dp[P_TT] * mlo;
+        const float dRAIN = dx[0] * m_rain;
+        const float dSP1 = ds[0] + dx[0] * m_snow;
+        const float ddT = dx[1] - dTTe;
+        const float dmp = dp[P_CFMAX] * dT + CFMAX * ddT;
+        const float dmpc = (mp >= 0.0f) ? dmp : 0.0f;
+        minw_(mpc, SP1, wa, wb);
+        const float dmelt = dmpc * wa + dSP1 * wb;
+        const float dMW1 = ds[1] + dmelt;
+        const float dSP2 = dSP1 - dmelt;
+        const float dcc = dp[P_CFR] * CFMAX + CFR * dp[P_CFMAX];
+        const float drp = dcc * dT2 + cc * (dTTe - dx[1]);
+        const float drpc = (rp >= 0.0f) ? drp : 0.0f;
+        minw_(rpc, MW1, wa, wb);
+        const float drefr = drpc * wa + dMW1 * wb;
+        const float dSP3 = dSP2 + drefr;
+        const float dMW2 = dMW1 - drefr;
+        const float dts0 = dMW2 - (dp[P_CWH] * SP3 + CWH * dSP3);
+        const float dtosoil = (ts0 >= 0.0f) ? dts0 : 0.0f;
+        const float dMW3 = dMW2 - dtosoil;
+        // soil
+        const float dr = div_approx_(ds[2] - r * dp[P_FC], FC);
+        const float kr = (r > 0.0f) ? BETA * div_approx_(sw0, r) : 0.0f;
+        const float kb = (r > 0.0f) ? sw0 * log_fast_(r) : 0.0f;
+        const float dsw0 = kr * dr + kb * dp[P_BETA];
+        const float dsw = (sw0 >= 0.0f && sw0 <= 1.0f) ? dsw0 : 0.0f;
+        const float drt = dRAIN + dtosoil;
+        const float drech = drt * sw + rt * dsw;
+        const float dSM1 = ((ds[2] + dRAIN) + dtosoil) - drech;
+        const float dexc = (e0 >= 0.0f) ? dSM1 - dp[P_FC] : 0.0f;
+        const float dSM2 = dSM1 - dexc;
+        const float dlpfc = dp[P_LP] * FC + LP * dp[P_FC];
+        const float dq = div_approx_(dSM2 - q * dlpfc, lpfc);
+        float def0 = dq;
+        if (BETAET) {
+            const float BE = p[P_BETAET];
+            const float kq = (q > 0.0f) ? BE * div_approx_(ef0, q) : 0.0f;
+            const float ke = (q > 0.0f) ? ef0 * log_fast_(q) : 0.0f;
+            def0 = kq * dq + ke * dp[P_BETAET];
+        }
+        const float def = (ef0 >= 0.0f && ef0 <= 1.0f) ? def0 : 0.0f;
+        const float dpe = dx[2] * ef + PET * def;
+        minw_(SM2, pe, wa, wb);
+        const float dET = dSM2 * wa + dpe * wb;
+        const float dSM3 = (dd >= nz) ? dSM2 - dET : 0.0f;
+        // capillary rise
+        float dcap = 0.0f, dSM4 = dSM3, dSLZ0 = ds[4];
+        if (MODEL != MODEL_HBV10) {
+            const float C = p[P_C];
+            const float dx1 = div_approx_(dSM3 - x1 * dp[P_FC], FC);
+            const float drc = (x1 <= 1.0f) ? dx1 : 0.0f;
+            const float dcs = dp[P_C] * SLZ + C * ds[4];
+            const float dcapp = dcs * om - cs * drc;
+            minw_(SLZ, capp, wa, wb);
+            dcap = ds[4] * wa + dcapp * wb;
+            dSM4 = (smc >= nz) ? dSM3 + dcap : 0.0f;
+            dSLZ0 = (slc >= nz) ? ds[4] - dcap : 0.0f;
+        }
+        // groundwater
+        const float dSUZ1 = (ds[3] + drech) + dexc;
+        minw_(SUZ1, p[P_PERC], wa, wb);
+        const float dPERC = dSUZ1 * wa + dp[P_PERC] * wb;
+        const float dSUZ2 = dSUZ1 - dPERC;
+        const float du0c = (u0 >= 0.0f) ? dSUZ2 - dp[P_UZL] : 0.0f;
+        const float dQ0 = dp[P_K0] * u0c + K0 * du0c;
+        const float dSUZ3 = dSUZ2 - dQ0;
+        const float dQ1 = dp[P_K1] * SUZ3 + K1 * dSUZ3;
+        const float dSUZ4 = dSUZ3 - dQ1;
+        const float dSLZ1 = dSLZ0 + dPERC;
+        float dSLZ1p = dSLZ1;
+        if (MODEL == MODEL_HBV20) {
+            const float RT = p[P_RT];
+            const float da1 = (a0 >= -1.0f && a0 <= 1.0f) ? -(dp[P_AC] * 0.001f) : 0.0f;
+            const float dLF = (da1 * RT + a1 * dp[P_RT]) * m1 + (ee * dp[P_RT]) * m2;
+            dSLZ1p = (sl >= 0.0f) ? dSLZ1 + dLF : 0.0f;
+        }
+        const float dQ2 = dp[P_K2] * SLZ1p + K2 * dSLZ1p;
+        const float dSLZ2 = dSLZ1p - dQ2;
+
+        f.Q = (dQ0 + dQ1) + dQ2; f.Q0 = dQ0; f.Q1 = dQ1; f.Q2 = dQ2; f.ET = dET; f.SWE = dSP3; f.rech = drech;
+        f.exc = dexc; f.ef = def; f.tosoil = dtosoil; f.PERC = dPERC; f.cap = dcap;
+        ds[0] = dSP3; ds[1] = dMW3; ds[2] = dSM4; ds[3] = dSUZ4; ds[4] = dSLZ2;
     }
 
     // ---- transposed state Jacobian of one day, HBV 1.0 only --------------------------------

@@ -64,6 +64,7 @@ extern "C" uint64_t hbvx_sizeof(int which)
     case 6: return sizeof(hbvx_gage_desc);
     case 4: return sizeof(hbvx_param_src);
     case 5: return sizeof(hbvx_param_grad);
+    case 7: return sizeof(hbvx_tan_io);
     default: return 0;
     }
 }
@@ -240,6 +241,132 @@ __global__ void __launch_bounds__(64) k_fwd(const FwdArgs A)
             o.state_out[k * N + L.n] = st[k];
             if (o.traj && !ckpt_k) o.traj[((int64_t)k * (T + 1) + T) * N + L.n] = st[k];
         }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// tangent-linear recurrence (forward-mode AD of the same lines): the primal day recomputed as the adjoint does
+// (CHAIN off: the reference's evaporation quotient, so every predicate is the adjoint's) and five state tangents
+// carried beside it.  Parameter tangents: d/dr descale(sigmoid(r)) = s (1 - s) (hi - lo), s from the primal's own
+// sigmoid (sigmoid_ for static values, sigmoid_dyn_ for dynamic rows, as k_fwd).  Only the rows the primal reads
+// are read: every row of a dynamic parameter, one of a static one.
+// ---------------------------------------------------------------------------
+struct TanArgs {
+    hbvx_desc d;
+    hbvx_tan_io io;
+    int lgMp;
+};
+
+template <int MODEL, bool BETAET>
+__global__ void __launch_bounds__(64) k_fwd_tan(const TanArgs A)
+{
+    constexpr int NP = NParam<MODEL, BETAET>::value;
+    const hbvx_desc &d = A.d;
+    const hbvx_tan_io &io = A.io;
+    const int lgMp = A.lgMp;
+    const LaneId L = lane_id(d, lgMp);
+    const int T = d.T;
+    const int64_t N = (int64_t)d.B * d.M;
+    const bool raw = d.raw_sigmoid != 0;
+    const float nz = d.nearzero;
+    const float ac = MODEL == MODEL_HBV20 ? d.ac[L.b] : 0.0f;
+    const float elev = MODEL == MODEL_HBV20 ? d.elev[L.b] : 0.0f;
+
+    float p[NPARAM_MAX], dp[NPARAM_MAX], psta[NP], dpsta[NP];
+    const float *dynp[NP];
+    const float *dynt[NP];
+    bool use_dyn[NP];
+    unsigned dmask = 0;
+#pragma unroll
+    for (int i = 0; i < NP; i++) {
+        const hbvx_param_src &s = d.p[i];
+        const hbvx_param_tan &ts = io.p[i];
+        const float v = s.sta[(int64_t)L.b * s.sta_b_stride + L.j];
+        const float u = raw ? sigmoid_(v) : v;
+        const float tv = ts.sta ? ts.sta[(int64_t)L.b * ts.sta_b_stride + L.j] : 0.0f;
+        psta[i] = descale_(u, s.lo, s.hi);
+        dpsta[i] = (raw ? tv * (u * (1.0f - u)) : tv) * (s.hi - s.lo);
+        dynp[i] = s.dyn ? s.dyn + (int64_t)L.b * s.dyn_b_stride + L.j : s.sta;
+        dynt[i] = ts.dyn ? ts.dyn + (int64_t)L.b * ts.dyn_b_stride + L.j : nullptr;
+        use_dyn[i] = s.dyn && !(s.drop && s.drop[L.b]);
+        if (s.dyn) dmask |= 1u << i;
+        p[i] = psta[i];
+        dp[i] = dpsta[i];
+    }
+#pragma unroll
+    for (int i = NP; i < NPARAM_MAX; i++) p[i] = dp[i] = 0.0f;
+
+    float st[5], ds[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        st[k] = d.state_in ? d.state_in[k * N + L.n] : 0.001f;
+        ds[k] = io.state_in ? io.state_in[k * N + L.n] : 0.0f;
+    }
+    const float *xb = d.x + (int64_t)L.b * d.x_b_stride;
+    const float *xtb = io.x ? io.x + (int64_t)L.b * d.x_b_stride : nullptr;
+    const float *mu = d.muwts ? d.muwts + (int64_t)L.b * d.mu_b_stride + L.j : nullptr;
+    const float *mut = (mu && io.muwts) ? io.muwts + (int64_t)L.b * d.mu_b_stride + L.j : nullptr;
+    const float invM = 1.0f / (float)d.M;
+    const int nf = io.n_flux;
+
+    for (int t = 0; t < T; t++) {
+        Step<MODEL, BETAET> s;
+        const float *xr = xb + (int64_t)t * d.x_t_stride;
+        s.P = xr[d.ch_prcp]; s.Tf = xr[d.ch_tmean]; s.PET = xr[d.ch_pet];
+        float dx[3] = {0.0f, 0.0f, 0.0f};
+        if (xtb) {
+            const float *xt = xtb + (int64_t)t * d.x_t_stride;
+            dx[0] = xt[d.ch_prcp]; dx[1] = xt[d.ch_tmean]; dx[2] = xt[d.ch_pet];
+        }
+#pragma unroll
+        for (int i = 0; i < NP; i++)
+            if (((dmask >> i) & 1) && use_dyn[i]) {
+                const float v = dynp[i][(int64_t)t * d.p[i].dyn_t_stride];
+                const float u = raw ? sigmoid_dyn_(v) : v;
+                const float tv = dynt[i] ? dynt[i][(int64_t)t * io.p[i].dyn_t_stride] : 0.0f;
+                p[i] = descale_(u, d.p[i].lo, d.p[i].hi);
+                dp[i] = (raw ? tv * (u * (1.0f - u)) : tv) * (d.p[i].hi - d.p[i].lo);
+            }
+        s.SP = st[0]; s.MW = st[1]; s.SM = st[2]; s.SUZ = st[3]; s.SLZ = st[4];
+        s.template fwd<false>(p, nz, ac, elev, 0.f, 0.f);
+        FluxTan f;
+        s.tan(p, nz, dp, dx, ds, f);
+        st[0] = s.SP3; st[1] = s.MW3; st[2] = s.SM4; st[3] = s.SUZ4; st[4] = s.SLZ2;
+
+        if (io.tan_flux) {
+            const float act = L.active ? 1.0f : 0.0f;
+            float tq = f.Q;
+            if (mu) {
+                const float wq = mu[(int64_t)t * d.mu_t_stride];
+                const float dwq = mut ? mut[(int64_t)t * d.mu_t_stride] : 0.0f;
+                tq = f.Q * wq + s.Q * dwq;
+            }
+            float g[HBVX_MAX_FLUX];
+            g[HBVX_F_QSIM] = tq * act;
+            g[HBVX_F_Q0] = f.Q0 * act;
+            g[HBVX_F_Q1] = f.Q1 * act;
+            g[HBVX_F_Q2] = f.Q2 * act;
+            g[HBVX_F_AET] = f.ET * act;
+            g[HBVX_F_SWE] = f.SWE * act;
+            g[HBVX_F_RECHARGE] = f.rech * act;
+            g[HBVX_F_EXCS] = f.exc * act;
+            g[HBVX_F_EVAPFACTOR] = f.ef * act;
+            g[HBVX_F_TOSOIL] = f.tosoil * act;
+            g[HBVX_F_PERC] = f.PERC * act;
+            g[HBVX_F_CAPILLARY] = f.cap * act;
+#pragma unroll
+            for (int k = 0; k < HBVX_MAX_FLUX; k++) {
+                if (k < nf) {
+                    float v = ens_sum(g[k], lgMp);
+                    if (!(k == HBVX_F_QSIM && mu)) v = v * invM;
+                    if (L.leader) io.tan_flux[((int64_t)k * T + t) * d.B + L.b] = v;
+                }
+            }
+        }
+    }
+    if (L.active) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) io.tan_state_out[k * N + L.n] = ds[k];
     }
 }
 
@@ -548,6 +675,71 @@ __global__ void __launch_bounds__(256) k_route_bwd(int T, int B, int S, int L,
 #pragma unroll
         for (int k = 0; k < HBVX_UH_MAXLEN; k++)
             if (k < L) ws[((int64_t)chunk * L + k) * B + b] = gw[k];
+    }
+}
+
+// Tangent of the routing: y_dot[s,t,b] = sum_k UH[b,k] q_dot[s,t-k,b] + UH_dot[b,k] q[s,t-k,b], with
+//   UH_dot_k = w_k ((ln t_k - sum_j w_j ln t_j) aa_dot + (t_k - sum_j w_j t_j) / theta^2 theta_dot)
+// (the derivatives k_route_bwd_params applies; the means in double, where their sum cancels).  The thread layout
+// of k_route_fwd; every thread forms its basin's UH_dot itself (15 taps: cheaper than a second launch).
+__global__ void __launch_bounds__(256) k_route_tan(const hbvx_route_desc r, const float *__restrict__ q,
+                                                   const float *__restrict__ uh, const float *__restrict__ qd,
+                                                   const float *__restrict__ rad, const float *__restrict__ rbd,
+                                                   float *__restrict__ yd)
+{
+    const int T = r.T, B = r.B, L = r.L;
+    const int b = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int chunk = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int t0 = chunk * ROUTE_CHUNK;
+    if (b >= B || t0 >= T) return;
+    const int t1 = min(T, t0 + ROUTE_CHUNK);
+    const int s = blockIdx.z;
+    float ua, ub, a, bb;
+    route_ab(r, b, ua, ub, a, bb);
+    const float theta = fmaxf(bb, 0.0f) + 0.5f;
+    float dua = rad ? rad[(int64_t)b * r.r_stride] : 0.0f, dub = rbd ? rbd[(int64_t)b * r.r_stride] : 0.0f;
+    if (r.raw_sigmoid) {
+        dua *= ua * (1.0f - ua);
+        dub *= ub * (1.0f - ub);
+    }
+    const double daa = (a > 0.0f) ? (double)(dua * (r.a_hi - r.a_lo)) : 0.0;      // relu (uh_routing.py:11-14)
+    const double dth = (bb > 0.0f) ? (double)(dub * (r.b_hi - r.b_lo)) : 0.0;
+    float w[HBVX_UH_MAXLEN], dw[HBVX_UH_MAXLEN];
+    load_uh(uh, b, L, w);
+    double mlt = 0.0, mt = 0.0;
+#pragma unroll
+    for (int k = 0; k < HBVX_UH_MAXLEN; k++) {
+        const double tk = (double)k + 0.5;
+        mlt += (double)w[k] * log(tk);
+        mt += (double)w[k] * tk;
+    }
+    const double th2 = (double)theta * (double)theta;
+#pragma unroll
+    for (int k = 0; k < HBVX_UH_MAXLEN; k++) {
+        const double tk = (double)k + 0.5;
+        dw[k] = (float)((double)w[k] * ((log(tk) - mlt) * daa + ((tk - mt) / th2) * dth));
+    }
+    const float *qs = q + (int64_t)s * T * B + b;
+    const float *qds = qd ? qd + (int64_t)s * T * B + b : nullptr;
+    float *ys = yd + (int64_t)s * T * B + b;
+    float win[HBVX_UH_MAXLEN], dwin[HBVX_UH_MAXLEN];
+#pragma unroll
+    for (int k = 1; k < HBVX_UH_MAXLEN; k++) {
+        win[k] = (t0 - k >= 0) ? qs[(int64_t)(t0 - k) * B] : 0.0f;
+        dwin[k] = (qds && t0 - k >= 0) ? qds[(int64_t)(t0 - k) * B] : 0.0f;
+    }
+    for (int t = t0; t < t1; t++) {
+        win[0] = qs[(int64_t)t * B];
+        dwin[0] = qds ? qds[(int64_t)t * B] : 0.0f;
+        float acc = 0.0f;
+#pragma unroll
+        for (int k = 0; k < HBVX_UH_MAXLEN; k++) acc += w[k] * dwin[k] + dw[k] * win[k];
+        ys[(int64_t)t * B] = acc;
+#pragma unroll
+        for (int k = HBVX_UH_MAXLEN - 1; k > 0; k--) {
+            win[k] = win[k - 1];
+            dwin[k] = dwin[k - 1];
+        }
     }
 }
 
@@ -975,6 +1167,100 @@ extern "C" int hbvx_bfi(int32_t T, int32_t B, const float *qs, const float *q2, 
                        nearzero, bfi);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "hbvx_bfi launch");
+    return HBVX_OK;
+}
+
+// Tangent of the baseflow index (quotient rule), the block layout and summation order of k_bfi.
+__global__ void __launch_bounds__(1024) k_bfi_tan(int T, int B, const float *__restrict__ qs,
+                                                  const float *__restrict__ q2, const float *__restrict__ qsd,
+                                                  const float *__restrict__ q2d, float nz, float *__restrict__ bfid)
+{
+    __shared__ float r0[64][16], r2[64][16], d0[64][16], d2[64][16];
+    const int bl = threadIdx.x & 15, sl = threadIdx.x >> 4;
+    const int b = blockIdx.x * 16 + bl;
+    float a0 = 0.0f, a2 = 0.0f, e0 = 0.0f, e2 = 0.0f;
+    if (b < B) {
+        for (int t = sl; t < T; t += 64) {
+            a0 += qs[(int64_t)t * B + b];
+            a2 += q2[(int64_t)t * B + b];
+            e0 += qsd ? qsd[(int64_t)t * B + b] : 0.0f;
+            e2 += q2d ? q2d[(int64_t)t * B + b] : 0.0f;
+        }
+    }
+    r0[sl][bl] = a0;
+    r2[sl][bl] = a2;
+    d0[sl][bl] = e0;
+    d2[sl][bl] = e2;
+    __syncthreads();
+    if (sl == 0 && b < B) {
+        float s0 = 0.0f, s2 = 0.0f, t0 = 0.0f, t2 = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 64; k++) {
+            s0 += r0[k][bl];
+            s2 += r2[k][bl];
+            t0 += d0[k][bl];
+            t2 += d2[k][bl];
+        }
+        const float den = s0 + nz;
+        bfid[b] = 100.0f * ((t2 - s2 * (t0 / den)) / den);
+    }
+}
+
+extern "C" int hbvx_bfi_tangent(int32_t T, int32_t B, const float *qs, const float *q2, const float *qs_dot,
+                                const float *q2_dot, float nearzero, float *bfi_dot, void *stream)
+{
+    if (!qs || !q2 || !bfi_dot || T <= 0 || B <= 0) return fail(HBVX_E_NULL, "hbvx_bfi_tangent: bad arguments");
+    hipLaunchKernelGGL(k_bfi_tan, dim3((B + 15) / 16), dim3(1024), 0, (hipStream_t)stream, T, B, qs, q2, qs_dot,
+                       q2_dot, nearzero, bfi_dot);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "hbvx_bfi_tangent launch");
+    return HBVX_OK;
+}
+
+extern "C" int hbvx_forward_tangent(const hbvx_desc *d, const hbvx_tan_io *io, void *stream)
+{
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (d->model != HBVX_MODEL_HBV10 && d->model != HBVX_MODEL_HBV11P && d->model != HBVX_MODEL_HBV20)
+        return fail(HBVX_E_UNSUPPORTED, "hbvx_forward_tangent: HBV 1.0 / 1.1p / 2.0 only");
+    if (!io || !io->tan_state_out) return fail(HBVX_E_NULL, "tan_state_out is NULL");
+    const int want_nf = (d->model == HBVX_MODEL_HBV10) ? 11 : 12;
+    if (io->tan_flux && io->n_flux != want_nf) return fail(HBVX_E_SHAPE, "n_flux does not match model");
+    for (int i = d->n_param; i < HBVX_MAX_PARAM; i++)
+        if (io->p[i].dyn || io->p[i].sta) return fail(HBVX_E_SHAPE, "tangent for a parameter slot the model lacks");
+    for (int i = 0; i < d->n_param; i++)
+        if (io->p[i].dyn && !d->p[i].dyn) return fail(HBVX_E_SHAPE, "dynamic tangent for a static parameter");
+    TanArgs a;
+    a.d = *d;
+    a.io = *io;
+    a.lgMp = lg_members(d->M);
+    const int bpw = 64 >> a.lgMp;
+    const dim3 grid((d->B + bpw - 1) / bpw);
+    hipStream_t st = (hipStream_t)stream;
+    switch (d->model) {
+    case HBVX_MODEL_HBV10:
+        if (d->n_param == 13) hipLaunchKernelGGL((k_fwd_tan<MODEL_HBV10, true>), grid, dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((k_fwd_tan<MODEL_HBV10, false>), grid, dim3(64), 0, st, a);
+        break;
+    case HBVX_MODEL_HBV11P: hipLaunchKernelGGL((k_fwd_tan<MODEL_HBV11P, true>), grid, dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL((k_fwd_tan<MODEL_HBV20, true>), grid, dim3(64), 0, st, a); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "hbvx_forward_tangent launch");
+    return HBVX_OK;
+}
+
+extern "C" int hbvx_route_tangent(const hbvx_route_desc *r, const float *q, const float *uh, const float *q_dot,
+                                  const float *ra_dot, const float *rb_dot, float *q_rout_dot, void *stream)
+{
+    int rc = check_route(r);
+    if (rc) return rc;
+    if (!q || !uh || !q_rout_dot) return fail(HBVX_E_NULL, "route buffer is NULL");
+    const int nchunk = (r->T + ROUTE_CHUNK - 1) / ROUTE_CHUNK;
+    hipLaunchKernelGGL(k_route_tan, dim3((r->B + 63) / 64, (nchunk + 3) / 4, r->S), dim3(256), 0, (hipStream_t)stream,
+                       *r, q, uh, q_dot, ra_dot, rb_dot, q_rout_dot);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "hbvx_route_tangent launch");
     return HBVX_OK;
 }
 

@@ -65,6 +65,7 @@ class Hbv_2(HbvModule):
     def forward(self, x_dict: dict[str, torch.Tensor], parameters):
         """Reference: hbv_2.py:324-390.  `graph=True`: the call's launches replayed as HIP graphs (graphed.py)."""
         if self.graph and x_dict['x_phy'].is_cuda:
+            self._refuse_dual_graph(x_dict, parameters)
             from hydrodl2_amd.graphed import graphed_forward
             return graphed_forward(self, x_dict, parameters)
         return self._forward_eager(x_dict, parameters)

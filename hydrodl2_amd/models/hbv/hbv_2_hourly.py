@@ -18,7 +18,7 @@ import torch
 
 from hydrodl2_amd import _abi
 from hydrodl2_amd.core.hbv_module import HbvModule
-from hydrodl2_amd.ops import GageRoute, GageTopology, ParamSource, StepConfig, hbv_path, state_series
+from hydrodl2_amd.ops import GageRoute, GageTopology, ParamSource, StepConfig, hbv_path, state_series, has_tangent
 
 
 class Hbv_2_hourly(HbvModule):
@@ -101,6 +101,9 @@ class Hbv_2_hourly(HbvModule):
 
     def forward(self, x_dict: dict[str, torch.Tensor], parameters):
         """Reference: hbv_2_hourly.py:376-449.  `graph=True`: HIP-graph replay (graphed.py)."""
+        if has_tangent(tuple(x_dict.values()), parameters):
+            raise NotImplementedError("forward-mode AD (dual inputs) is not implemented for Hbv_2_hourly: "
+                                      "Hbv, Hbv_1_1p and Hbv_2 support it")
         if self.graph and x_dict['x_phy'].is_cuda:
             from hydrodl2_amd.graphed import graphed_forward
             return graphed_forward(self, x_dict, parameters)

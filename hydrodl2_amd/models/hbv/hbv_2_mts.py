@@ -26,7 +26,7 @@ from tqdm import tqdm
 from hydrodl2_amd import _abi
 from hydrodl2_amd.models.hbv.hbv_2 import Hbv_2
 from hydrodl2_amd.models.hbv.hbv_2_hourly import Hbv_2_hourly
-from hydrodl2_amd.ops import ParamSource
+from hydrodl2_amd.ops import ParamSource, has_tangent
 
 
 class Hbv_2_mts(torch.nn.Module):
@@ -200,6 +200,9 @@ class Hbv_2_mts(torch.nn.Module):
         in one piece.  Otherwise the unit runoff is produced block by block (inputs may live on
         the host; a block is moved to the device when its turn comes) without gage routing, and
         the gage routing then runs over the assembled runoff in temporal windows."""
+        if has_tangent(tuple(x_dict.values()), parameters):
+            raise NotImplementedError("forward-mode AD (dual inputs) is not implemented for Hbv_2_mts: "
+                                      "Hbv, Hbv_1_1p and Hbv_2 support it")
         hourly = self.high_freq_model
         n_units = x_dict['areas'].shape[0]
         hourly.use_distr_routing = False

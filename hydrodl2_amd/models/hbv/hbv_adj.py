@@ -24,7 +24,7 @@ from typing import Any, Optional
 import torch
 
 from hydrodl2_amd import _abi
-from hydrodl2_amd.ops import HbvAdjPath, ParamSource, RouteSource, StepConfig
+from hydrodl2_amd.ops import HbvAdjPath, ParamSource, RouteSource, StepConfig, has_tangent
 
 
 class HbvAdj(torch.nn.Module):
@@ -150,6 +150,9 @@ class HbvAdj(torch.nn.Module):
 
     def forward(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor):
         """hbv_adj.py:227-330.  `graph=True`: HIP-graph replay of the call (graphed.py)."""
+        if has_tangent(tuple(x_dict.values()), parameters):
+            raise NotImplementedError("forward-mode AD (dual inputs) is not implemented for HbvAdj: "
+                                      "Hbv, Hbv_1_1p and Hbv_2 support it")
         if self.graph and x_dict['x_phy'].is_cuda:
             from hydrodl2_amd.graphed import graphed_forward
             return graphed_forward(self, x_dict, parameters)

@@ -20,6 +20,7 @@ import struct
 from typing import List, NamedTuple, Optional, Sequence
 
 import torch
+import torch.autograd.forward_ad as _fwAD
 
 from . import _abi
 from ._lib import get_library
@@ -358,6 +359,20 @@ def _check_tensor(lib, t: torch.Tensor, name: str):
         raise RuntimeError(f"{name}: test library expects host tensors")
 
 
+def has_tangent(*ts) -> bool:
+    """Whether any of `ts` (tensors, tuples / lists of tensors, or anything else, which is ignored) carries a
+    forward-mode tangent at the current torch.autograd.forward_ad level.  False at once when no level is active."""
+    if _fwAD._current_level < 0:
+        return False
+    for t in ts:
+        if isinstance(t, (tuple, list)):
+            if has_tangent(*t):
+                return True
+        elif torch.is_tensor(t) and _fwAD.unpack_dual(t).tangent is not None:
+            return True
+    return False
+
+
 def _mu_t0(cfg: StepConfig) -> int:
     return cfg.t0 if cfg.mu_t0 is None else cfg.mu_t0
 
@@ -566,10 +581,17 @@ def _hbv_forward(ctx, cfg: StepConfig, x, state_in, muwts, ac, elev, ptensors):
     ctx.set_materialize_grads(False)
     if needs_grad:
         ctx.save_for_backward(x, state_in, muwts, ac, elev, traj, aux, flux, uh, routed, *ptensors)
-    nondiff = [state_out]
+    # Under a forward-AD level the final storages carry a tangent (HbvPath.jvp): a state warm-up hands it to the
+    # main call.  Otherwise they are a non-differentiable output, as always.
+    fwd_ad = _fwAD._current_level >= 0 and not isinstance(ctx, _NoCtx)
+    if fwd_ad:
+        ctx.save_for_forward(x, state_in, muwts, ac, elev, flux, uh, routed, *ptensors)
+    ctx.state_tangent = fwd_ad
+    nondiff = [] if fwd_ad else [state_out]
     if traj is not None:
         nondiff.append(traj)
-    ctx.mark_non_differentiable(*nondiff)
+    if nondiff:
+        ctx.mark_non_differentiable(*nondiff)
     # every series leaves as its own [T,B,1] view (the shape the flux dictionary holds): one autograd
     # output each, no select / unsqueeze nodes on the caller's side (16 of them cost the host 0.1 ms
     # per call, a fifth of a deltaMG-sized step)
@@ -738,6 +760,73 @@ class HbvPath(torch.autograd.Function):
 
         return (None, gx, None, gmu, None, None, *gp)
 
+    @staticmethod
+    @_device_guard
+    def jvp(ctx, _cfg_t, x_t, s_t, mu_t, ac_t, elev_t, *p_t):
+        """Forward mode (torch.autograd.forward_ad): tangents of every output along the inputs' tangents."""
+        return _hbv_tangent(ctx, x_t, s_t, mu_t, ac_t, elev_t, p_t)
+
+
+def _hbv_tangent(ctx, x_t, s_t, mu_t, ac_t, elev_t, p_t):
+    """Forward-mode derivative of _hbv_forward along one direction: hbvx_forward_tangent (the recurrence),
+    hbvx_route_tangent (the unit hydrograph) and hbvx_bfi_tangent, on the tensors the forward saved."""
+    if ac_t is not None or elev_t is not None:
+        raise ValueError("forward-mode AD: tangents of ac_all / elev_all are not supported")
+    lib = get_library()
+    cfg: StepConfig = ctx.cfg
+    x, state_in, muwts, ac, elev, flux, uh, routed, *ptensors = ctx.saved_tensors
+    dev = x.device
+    T, B, M = cfg.T, cfg.B, cfg.M
+    stream = _stream_of(lib, x)
+    io = _abi.TanIO()
+    keep = []                   # the tangent buffers the launch reads: alive until it is enqueued
+    if x_t is not None:
+        xt = x_t
+        if xt.stride() != x.stride():
+            xt = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=dev).copy_(x_t)
+        keep.append(xt)
+        io.x = _ptr(xt, cfg.t0 * x.stride(0))
+    if mu_t is not None and muwts is not None:
+        mt = mu_t.contiguous()
+        keep.append(mt)
+        io.muwts = _ptr(mt, _mu_t0(cfg) * B * M)
+    if s_t is not None and state_in is not None:
+        stt = s_t.contiguous()
+        keep.append(stt)
+        io.state_in = _ptr(stt)
+    pts = [None if t is None else t.contiguous() for t in p_t]
+    for ps in cfg.params:
+        g = io.p[ps.slot]
+        if pts[ps.tensor_idx] is not None:
+            g.sta, g.sta_b_stride = _ptr(pts[ps.tensor_idx], ps.sta_off), ps.sta_bs
+        if ps.dyn_off >= 0 and pts[ps.dyn_tensor_idx] is not None:
+            g.dyn = _ptr(pts[ps.dyn_tensor_idx], ps.dyn_off)
+            g.dyn_t_stride, g.dyn_b_stride = ps.dyn_ts, ps.dyn_bs
+    tflux = _out((cfg.n_flux, T, B), dev) if cfg.want_flux else None
+    tstate = _out((5, B, M), dev)
+    io.tan_flux, io.tan_state_out, io.n_flux = _ptr(tflux), _ptr(tstate), cfg.n_flux
+    desc = _fill_desc(cfg, x, state_in, muwts, ac, elev, ptensors)
+    _call(lib, 'hbvx_forward_tangent', lib.forward_tangent, desc, io, stream)
+
+    troute = None
+    if routed is not None:
+        r = _route_desc(cfg, ptensors)
+        rs = cfg.route
+        rt = pts[rs.tensor_idx]
+        troute = _out((4, T, B), dev)
+        _call(lib, 'hbvx_route_tangent', lib.route_tangent, r, _ptr(flux), _ptr(uh), _ptr(tflux),
+              _ptr(rt, rs.a_off), _ptr(rt, rs.b_off), _ptr(troute), stream)
+    tbfi = None
+    if ctx.has_bfi:
+        src, tsrc = (routed, troute) if routed is not None else (flux, tflux)
+        k2 = 3 if routed is not None else _abi.F_Q2
+        tbfi = _out((B,), dev)
+        _call(lib, 'hbvx_bfi_tangent', lib.bfi_tangent, T, B, _ptr(src), _ptr(src, k2 * T * B), _ptr(tsrc),
+              _ptr(tsrc, k2 * T * B), float(cfg.nearzero), _ptr(tbfi), stream)
+    rrows = tuple(troute.unsqueeze(-1).unbind(0)) if troute is not None else ()
+    rows = tuple(tflux.unsqueeze(-1).unbind(0)) if tflux is not None else ()
+    return (tstate if ctx.state_tangent else None, None, None, tbfi) + rrows + rows
+
 
 class PathOut(NamedTuple):
     """What one call of the path returns.  `flux`: tuple of the n_flux series [T,B,1] (index it with the hbvx_flux
@@ -754,9 +843,12 @@ class PathOut(NamedTuple):
 def hbv_path(cfg: StepConfig, x, state_in, muwts, ac, elev, *ptensors) -> PathOut:
     """Run the path.  A call that cannot need a gradient (grad mode off, or no input requires one) runs the
     forward as a plain function; otherwise through the autograd node `HbvPath`."""
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in ptensors)
-                                    or (muwts is not None and muwts.requires_grad)
-                                    or (state_in is not None and state_in.requires_grad)):
+    dual = has_tangent(x, state_in, muwts, ac, elev, ptensors)
+    if dual and has_tangent(ac, elev):
+        raise ValueError("forward-mode AD: tangents of ac_all / elev_all are not supported")
+    if dual or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in ptensors)
+                                             or (muwts is not None and muwts.requires_grad)
+                                             or (state_in is not None and state_in.requires_grad))):
         outs = HbvPath.apply(cfg, x, state_in, muwts, ac, elev, *ptensors)
     elif x.is_cuda and torch.cuda.current_device() != x.device.index:
         with torch.cuda.device(x.device):
@@ -924,7 +1016,23 @@ class Bfi(torch.autograd.Function):
         _call(lib, 'hbvx_bfi', lib.bfi, T, B, _ptr(qs_c), _ptr(q2_c), float(nearzero), _ptr(out),
               _stream_of(lib, qs_c))
         ctx.save_for_backward(qs_c, q2_c)
+        if _fwAD._current_level >= 0:
+            ctx.save_for_forward(qs_c, q2_c)
         ctx.nearzero = float(nearzero)
+        return out
+
+    @staticmethod
+    @_device_guard
+    def jvp(ctx, qs_t, q2_t, _nz_t):
+        """Forward mode: the quotient rule in the library (hbvx_bfi_tangent)."""
+        lib = get_library()
+        qs, q2 = ctx.saved_tensors
+        T, B = qs.shape
+        tqs = qs_t.contiguous().view(T, B) if qs_t is not None else None
+        tq2 = q2_t.contiguous().view(T, B) if q2_t is not None else None
+        out = _out((B,), qs.device)
+        _call(lib, 'hbvx_bfi_tangent', lib.bfi_tangent, T, B, _ptr(qs), _ptr(q2), _ptr(tqs), _ptr(tq2),
+              ctx.nearzero, _ptr(out), _stream_of(lib, qs))
         return out
 
     @staticmethod

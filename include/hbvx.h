@@ -17,6 +17,9 @@
  *   hbvx_route_forward   replaces uh_gamma + uh_conv on the ensemble means:
  *                        core/calc/uh_routing.py:5-57, called at hbv.py:523-538.
  *   hbvx_route_backward  replaces conv1d/lgamma/pow autograd of those lines.
+ *   hbvx_forward_tangent, hbvx_route_tangent, hbvx_bfi_tangent
+ *                        replace torch.autograd.forward_ad over the same lines
+ *                        (forward mode: one tangent direction per call).
  *
  * Ownership: the caller allocates and owns every buffer; the library keeps no
  * state between calls and allocates nothing persistent.  All device work is
@@ -234,7 +237,7 @@ int hbvx_version(void);                 /* HBVX_ABI_VERSION */
 const char *hbvx_last_error(void);
 const char *hbvx_backend(void);         /* "hip:gfx950" or "cpu-oracle" */
 uint64_t hbvx_sizeof(int which);        /* 0 desc, 1 fwd_out, 2 bwd_io, 3 route_desc,
-                                           4 param_src, 5 param_grad, 6 gage_desc: layout check */
+                                           4 param_src, 5 param_grad, 6 gage_desc, 7 tan_io: layout check */
 /* Diagnostic: the kernel family that took the process's last hbvx_forward (direction 0) / hbvx_backward (1) call --
  * "pipe", "stream2", "stream", "tiled", "simple", "chunked", "ckpt-block:<family>", "ckpt-lds"; "oracle" in the CPU
  * restatement.  The parity tests assert that the family they mean to pin against the reference is the one that ran. */
@@ -326,6 +329,44 @@ int hbvx_gage_route_backward(const hbvx_gage_desc *r, const float *qs, const flo
  * (dG/dx)^T lambda = dL/dx, dL/dtheta = -lambda^T dG/dtheta, dL/dx_t = lambda/dt. */
 int hbvx_adj_forward(const hbvx_desc *d, const hbvx_fwd_out *out, void *stream);
 int hbvx_adj_backward(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream);
+
+/* Forward-mode derivative (tangent-linear model) of hbvx_forward, HBV 1.0 / 1.1p / 2.0 only.  One direction per call:
+ * given the tangents of the raw inputs, the tangents of the flux series and of the final storages.  The call re-runs
+ * the primal day by day beside the five state tangents (one lane per (basin, member)); the primal outputs themselves
+ * come from hbvx_forward.  Conventions are torch's forward formulas (binary minimum: 1/2 each at a tie; clamps
+ * inclusive; d(x**y) = 0 at x == 0), the transpose of hbvx_backward's.  dy_drop masks (hbvx_param_src.drop) blend
+ * the tangents as they blend the values.  Tangents of `ac` / `elev` are not supported.
+ * Tangent of a raw parameter tensor: same addressing as hbvx_param_src (dyn rows for every (t,b,j) of the call
+ * when the parameter is dynamic, sta for the static value); NULL = zero tangent. */
+typedef struct hbvx_param_tan {
+    const float *dyn;
+    const float *sta;
+    int64_t dyn_t_stride;
+    int64_t dyn_b_stride;
+    int64_t sta_b_stride;
+} hbvx_param_tan;
+
+typedef struct hbvx_tan_io {
+    const float *x;          /* tangent of desc->x, addressed like it (same strides), or NULL */
+    const float *muwts;      /* tangent of desc->muwts, addressed like it, or NULL */
+    const float *state_in;   /* [5,B,M] tangent of desc->state_in, or NULL (= 0) */
+    hbvx_param_tan p[HBVX_MAX_PARAM];
+    float *tan_flux;         /* [n_flux,T,B] (overwritten) or NULL (no series: a state warm-up) */
+    float *tan_state_out;    /* [5,B,M] (overwritten), required */
+    int32_t n_flux;          /* 11 (HBV 1.0) or 12 */
+    int32_t reserved0;
+} hbvx_tan_io;
+
+int hbvx_forward_tangent(const hbvx_desc *d, const hbvx_tan_io *io, void *stream);
+/* Tangent of hbvx_route_forward: q [S,T,B] and uh [B,L] from that call, q_dot [S,T,B] (or NULL = 0) the tangent of
+ * q, ra_dot / rb_dot the tangents of the routing inputs at ra_dot[b*r->r_stride] (or NULL = 0):
+ * q_rout_dot = conv(q_dot, uh) + conv(q, d uh / d(a, b) . (a_dot, b_dot))  [S,T,B] (overwritten). */
+int hbvx_route_tangent(const hbvx_route_desc *r, const float *q, const float *uh, const float *q_dot,
+                       const float *ra_dot, const float *rb_dot, float *q_rout_dot, void *stream);
+/* Tangent of hbvx_bfi: bfi_dot[b] = 100 (sum_t q2_dot / (S0 + nearzero) - sum_t q2 * sum_t qs_dot / (S0 + nearzero)^2),
+ * S0 = sum_t qs; fixed-order sums. */
+int hbvx_bfi_tangent(int32_t T, int32_t B, const float *qs, const float *q2, const float *qs_dot, const float *q2_dot,
+                     float nearzero, float *bfi_dot, void *stream);
 
 /* Zero `bytes` bytes at `ptr` (streaming non-temporal stores).  The autograd contract of the plug-in wants
  * gradient tensors shaped like the raw parameter tensor [T,B,ny] (hbv.py:211-246: static parameters read
