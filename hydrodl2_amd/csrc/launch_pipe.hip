@@ -27,6 +27,15 @@ bool hbvx_host::try_fwd_pipe(const hbvx_desc *d, const hbvx_fwd_out *out, void *
                                      (int64_t)1 << 31;
         if (mu) off32 = off32 && ((int64_t)d->B * d->mu_b_stride + (int64_t)Kt * d->mu_t_stride) * 4 < (int64_t)1 << 31 &&
                         d->mu_t_stride >= 0;
+        // the kernel's buffer descriptors span `rows` day strides from a tile's first day (hbv_pipe.h, rsrc_of), and a
+        // load outside that range returns 0: every basin's values must lie within its day's stride -- the day the
+        // outer dimension of x and of each staged row.  A [B,T,3] buffer viewed as [T,B,3] is not: the tiled forward
+        const int chmax = std::max(d->ch_prcp, std::max(d->ch_tmean, d->ch_pet));
+        bool day_outer = (int64_t)(d->B - 1) * d->x_b_stride + chmax + 1 <= d->x_t_stride;
+        for (int i = 0; i < d->n_param; i++)
+            if (d->p[i].dyn)
+                day_outer = day_outer && (int64_t)(d->B - 1) * d->p[i].dyn_b_stride + d->M <= d->p[i].dyn_t_stride;
+        if (mu) day_outer = day_outer && (int64_t)(d->B - 1) * d->mu_b_stride + d->M <= d->mu_t_stride;
         const int64_t wgs_p = ((int64_t)d->B + (64 >> lg_members(d->M)) - 1) / (64 >> lg_members(d->M));
         const bool pmodel = d->model == HBVX_MODEL_HBV10 || d->model == HBVX_MODEL_HBV11P ||
                             d->model == HBVX_MODEL_HBV20 || d->model == HBVX_MODEL_HOURLY ||
@@ -36,7 +45,7 @@ bool hbvx_host::try_fwd_pipe(const hbvx_desc *d, const hbvx_fwd_out *out, void *
         const int ckpt_k = (out->traj && HBVX_TRAJ_KIND(out->traj_layout) == HBVX_TRAJ_CKPT)
                                ? HBVX_TRAJ_CKPT_DAYS(out->traj_layout) : 0;
         const bool ckpt_fits = !ckpt_k || ((int64_t)((d->T + ckpt_k - 1) / ckpt_k) * 5 * d->B * d->M * 4 < (int64_t)1 << 32);
-        if (ckpt_fits && use_tiled(d) && !(fv && !strcmp(fv, "tiled")) && pmodel && off32 &&
+        if (ckpt_fits && use_tiled(d) && !(fv && !strcmp(fv, "tiled")) && pmodel && off32 && day_outer &&
             nd <= PIPE_MAXDYN && (int)lds <= LDS_BUDGET && wgs_p < 4096 && !(adj && d->muwts) && (out->flux || adj) && d->T >= 4 * Kt &&
             (adj ? !ckpt_k : (ckpt_k ? true : aux_matches_traj(out))) &&
             (int64_t)d->B * d->M * 4 * Kt < (int64_t)1 << 31 &&

@@ -1,0 +1,129 @@
+"""Golden cases through oracle/hbv_restate64.py, the float64 restatement of Hbv, Hbv_1_1p and Hbv_2
+(tests/test_restate64.py pins it to the reference's fixtures; tests/test_jvp_f64_gpu.py measures the HIP tangents
+against it)."""
+from __future__ import annotations
+
+import importlib.util
+import os
+
+import numpy as np
+import torch
+import torch.autograd.forward_ad as fwAD
+
+from . import golden_cases as gc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_MOD = None
+
+
+def restate():
+    """The module oracle/hbv_restate64.py (loaded once)."""
+    global _MOD
+    if _MOD is None:
+        spec = importlib.util.spec_from_file_location("hbv_restate64", os.path.join(ROOT, "oracle", "hbv_restate64.py"))
+        _MOD = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(_MOD)
+    return _MOD
+
+
+def config_kwargs(model: str, cfg) -> dict:
+    """Keyword arguments of hbv_restate64.run for a module config (None = the module defaults)."""
+    cfg = cfg or {}
+    kw = dict(nmul=cfg.get("nmul", 1), dynamic=tuple((cfg.get("dynamic_params") or {}).get(model, ())),
+              warm_up=cfg.get("warm_up", 0), warm_up_states=cfg.get("warm_up_states", True),
+              variables=tuple(cfg.get("variables", ("prcp", "tmean", "pet"))), comprout=cfg.get("comprout", False),
+              nearzero=cfg.get("nearzero", 1e-5))
+    if "routing" in cfg:
+        kw["routing"] = cfg["routing"]
+    return kw
+
+
+def masks_for(model: str, cfg, B: int, torch_seed=None) -> dict:
+    """The dy_drop masks one module call draws (after torch.manual_seed(torch_seed) when given)."""
+    kw = config_kwargs(model, cfg)
+    if torch_seed is not None:
+        torch.manual_seed(torch_seed)
+    m = restate().drop_masks(model, kw["dynamic"], B, float((cfg or {}).get("dy_drop", 0.0)))
+    return m if (cfg or {}).get("dy_drop", 0.0) > 0 else {}
+
+
+def run_inputs(model: str, cfg, inp: dict, masks: dict, dtype=torch.float64, device="cpu", dirs=None,
+               grad_leaves=(), states=None, aux=None):
+    """hbv_restate64.run on the numpy inputs `inp` (golden_cases.build_inputs form) cast to `dtype`.  `dirs`: input
+    name -> tangent (those inputs become duals of the caller's forward-AD level); `grad_leaves`: input names that
+    require grad.  Returns (outputs, states, leaves by name)."""
+    def arg(k):
+        t = torch.as_tensor(np.asarray(inp[k])).to(device=device, dtype=dtype)
+        if k in grad_leaves:
+            t.requires_grad_(True)
+        leaves[k] = t
+        if dirs is not None and k in dirs:
+            return fwAD.make_dual(t, torch.as_tensor(np.asarray(dirs[k])).to(device=device, dtype=dtype))
+        return t
+    leaves = {}
+    kw = config_kwargs(model, cfg)
+    extra = {}
+    if model == "Hbv_2":
+        params = (arg("p_dyn"), arg("p_sta"))
+        extra = dict(ac_all=arg("ac_all"), elev_all=arg("elev_all"))
+    else:
+        params = arg("parameters")
+    mu = arg("muwts") if "muwts" in inp else None
+    out, st = restate().run(model, arg("x_phy"), params, masks=masks, muwts=mu, states=states, aux=aux,
+                                 **kw, **extra)
+    return out, st, leaves
+
+
+def case_reverse(name: str, dtype=torch.float64) -> dict:
+    """Outputs, storages and (for a case with a loss) the loss gradients of golden case `name`, keyed as the fixture
+    tests/golden/<name>.npz is."""
+    spec = gc.CASES[name]
+    model, cfg = spec["model"], spec["config"]
+    inp = gc.build_inputs(name)
+    res = {}
+    if spec.get("two_call"):          # cache_states: the second call starts from the storages the first one left
+        T, h = spec["T"], spec["T"] // 2
+        with torch.no_grad():
+            i1 = dict(inp, x_phy=inp["x_phy"][:h], parameters=np.concatenate([inp["parameters"][:h - 1],
+                                                                              inp["parameters"][-1:]], 0))
+            out1, st1, _ = run_inputs(model, cfg, i1, {}, dtype)
+            i2 = dict(inp, x_phy=inp["x_phy"][h:], parameters=inp["parameters"][h:])
+            out2, st2, _ = run_inputs(model, cfg, i2, {}, dtype, states=st1)
+        for tag, out, st in (("1", out1, st1), ("2", out2, st2)):
+            res.update({f"out{tag}/{k}": v.numpy() for k, v in out.items()})
+            res[f"states{tag}"] = torch.stack(st).numpy()
+        return res
+    masks = masks_for(model, cfg, spec["B"], spec.get("torch_seed"))
+    leaves = ["p_dyn", "p_sta"] if model == "Hbv_2" else ["parameters"]
+    if spec.get("x_grad"):
+        leaves.append("x_phy")
+    keys = gc.loss_keys(name)
+    out, st, lv = run_inputs(model, cfg, inp, masks, dtype, grad_leaves=leaves if keys else ())
+    res.update({f"out/{k}": v.detach().numpy() for k, v in out.items()})
+    res["states"] = torch.stack([s.detach() for s in st]).numpy()
+    if keys:
+        loss = sum((torch.from_numpy(gc.loss_weight(name, k, out[k].shape)).to(dtype) * out[k]).sum() for k in keys)
+        loss.backward()
+        for k in leaves:
+            g = lv[k].grad
+            res[f"grad/{k}"] = (torch.zeros_like(lv[k]) if g is None else g).numpy()
+    return res
+
+
+def bfi_term_scale(aux: dict) -> np.ndarray:
+    """Per basin, the size of the two terms whose difference is BFI's tangent, 100 (|dS2| + S2 |dS0'|/S0') / S0'
+    (S2 = sum of the routed Q2, S0' = sum of the routed Qs + nearzero, d = their tangents), from run(aux=...)
+    under forward AD: where they cancel, float32 rounds each of them, not their small difference."""
+    (s2, ds2), (s0, ds0) = (fwAD.unpack_dual(v) for v in aux["bfi_sums"])
+    ds2 = torch.zeros_like(s2) if ds2 is None else ds2
+    ds0 = torch.zeros_like(s0) if ds0 is None else ds0
+    return (100 * (ds2.abs() + s2.abs() * ds0.abs() / s0.abs()) / s0.abs()).detach().cpu().double().numpy()
+
+
+def tangents(out: dict, keys) -> dict:
+    """Output tangents (float64 numpy, zeros where none flows) of `keys` from duals of the current level."""
+    res = {}
+    for k in keys:
+        p, t = fwAD.unpack_dual(out[k])
+        res[k] = (torch.zeros_like(p) if t is None else t).detach().cpu().double().numpy()
+    return res

@@ -1,0 +1,85 @@
+"""CPU tier: oracle/hbv_restate64.py, the float64 restatement of Hbv, Hbv_1_1p and Hbv_2, against the fixtures the
+reference itself produced -- outputs, storages and reverse-mode gradients of every golden case of those models
+(tests/golden/<case>.npz, at helpers.compare's committed tolerances) and the output tangents of the 22 forward-mode
+fixtures (tests/golden/jvp_<case>.npz, at the tolerances of tests/test_jvp_gpu.py (a)).  Once pinned here, the
+restatement is the float64 yardstick of tests/test_jvp_f64_gpu.py."""
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.autograd.forward_ad as fwAD
+
+from . import golden_cases as gc
+from . import golden_jvp as gj
+from . import restate_util as ru
+from .helpers import GOLDEN_DIR, compare, load_golden
+from .test_jvp_gpu import BFI_ATOL_REL, TAN_FLOOR, _assert_tangent_close
+
+# every golden case of the three daily models (hbv_cache_states included: two calls, storages carried across)
+CASES = [n for n, s in gc.CASES.items() if s["model"] in ("Hbv", "Hbv_1_1p", "Hbv_2")]
+
+
+def test_scope():
+    """The restatement's scope is every Hbv / Hbv_1_1p / Hbv_2 fixture, and every forward-mode fixture."""
+    assert len(CASES) == 33 and set(gj.JVP_CASES) <= set(CASES)
+
+
+# Elements where the float64 restatement and the reference's float32 run part for a reason of precision alone, each
+# with its float64 evidence.  They are left out of the float64 comparison, bounded below, and these cases are also
+# compared whole in float32, where the restatement reproduces the reference within the committed tolerances.
+#  * hbv11p_long_dyn_all, member 4 of basin 4: on day 157 PERC = min(SUZ, parPERC) ties.  float64: SUZ 8.23424176,
+#    parPERC 8.23424182 (SUZ below by 6e-8, so PERC = SUZ); the reference's float32 SUZ is 8.2342758, 3.4e-5 above its
+#    parPERC after 157 days of rounding, so PERC = parPERC.  The gradient then follows the other one-sided slope through
+#    SUZ: the 14 parameter columns of that member on days 53-157 differ (up to 14.3 against 5.9); nothing else does.
+#  * Hbv_2's SNOWPACK series on the day a snowpack melts out: SP = SP + snow - melt leaves 0.17-0.78 of a 15-43 mm
+#    pack, so the float32 rounding of the pack (5e-6 of it after 180 days of increments) becomes 2.5e-4 of the result.
+#    float64 against the fixture: hbv2_long_routing (day 180) 0.171422 vs 0.171379 (pack 42.79), hbv2_long_dyn3
+#    (day 187) 0.460176 vs 0.460056 (pack 21.69), hbv2_long_static_cold (day 184) 0.783688 vs 0.783583 (pack 15.51);
+#    the next day both are 0.  Bound: 1e-5 x the member's largest SNOWPACK.
+PRECISION_ONLY = {
+    "hbv11p_long_dyn_all": ("grad/parameters", (slice(None), 4, slice(4, 14 * 16, 16)), None),
+    "hbv2_long_routing": ("states", (0, 180, 5, 2), 1e-5),
+    "hbv2_long_dyn3": ("states", (0, 187, 5, 10), 1e-5),
+    "hbv2_long_static_cold": ("states", (0, 184, 3, 5), 1e-5),
+}
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_restatement_matches_reference(name):
+    res = ru.case_reverse(name)
+    ref = load_golden(name)
+    missing = [k for k in ref.files if k not in ("torch_version", "loss") and k not in res]
+    assert not missing, missing
+    if name in PRECISION_ONLY:
+        key, idx, bound = PRECISION_ONLY[name]
+        got, want = res[key][idx], ref[key][idx]
+        if bound is not None:          # a snowpack element: within `bound` x the member's largest SNOWPACK
+            scale = float(np.abs(ref[key][(0, slice(None)) + tuple(idx[2:])]).max())
+            assert abs(float(got) - float(want)) <= bound * scale, (name, got, want, scale)
+        res = dict(res)
+        res[key] = res[key].copy()
+        res[key][idx] = want           # the rest of the tensor is compared as usual
+        compare(name, ru.case_reverse(name, torch.float32), ref)
+    compare(name, res, ref)
+
+
+@pytest.mark.parametrize("name", gj.JVP_CASES)
+def test_restatement_tangents_match_reference(name):
+    spec = gc.CASES[name]
+    ref = np.load(os.path.join(GOLDEN_DIR, f"jvp_{name}.npz"))
+    inp = gc.build_inputs(name)
+    dirs = gj.directions(name, inp)
+    masks = ru.masks_for(spec["model"], spec["config"], spec["B"], spec.get("torch_seed"))
+    keys = gj.output_keys(name)
+    with fwAD.dual_level():
+        out, _, _ = ru.run_inputs(spec["model"], spec["config"], inp, masks, torch.float64, dirs=dirs)
+        tan = ru.tangents(out, keys)
+    top = max(float(np.abs(ref[f"tan/{k}"]).max()) for k in keys if k != "BFI")
+    for k in keys:
+        b = ref[f"tan/{k}"]
+        if k == "BFI":
+            _assert_tangent_close(f"restate-jvp:{name}:{k}", tan[k], b, atol_rel=BFI_ATOL_REL)
+        else:
+            m = float(np.abs(b).max())
+            _assert_tangent_close(f"restate-jvp:{name}:{k}", tan[k], b, scale=m if m >= TAN_FLOOR * top else top)
