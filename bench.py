@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's configs.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg5]
+    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg5] [--full]
 
 A "step" is one forward + backward pass of the HBV hot path over one batch of synthetic
 CAMELS-shaped input through the drop-in module (`hydrodl2_amd.load_model`): raw NN output ->
@@ -21,13 +21,17 @@ LOCAL_RANK / WORLD_SIZE set) or `python bench.py --gpus N` does it itself: the p
 children BEFORE touching the GPU and relays rank 0's JSON line.
 
 Rank 0 prints ONE JSON line.  `value` = whole-job basin-ensemble-timesteps/s; `ms_per_step` = the K timed steps'
-wall time / K (max over ranks).  At N = 1 the line also carries `secondary` (configs 2-dyn, 3, 4 -- staged and under the
-reference's joint Newton policy --, one GPU's share of 5, config 5 at full size, the deltaMG minibatch shape, Hbv_2_hourly
-with gage routing, the sequence LSTM and one examples/train_dpl.py step, driver-timed in the same run: name -> ms per
-step) and `cpu_baseline` (the pure-torch eager restatement of the reference's path on the host cores -- `value` -- with
-the C/OpenMP oracle port beside it).  The line stays a few KB: the whole record -- every secondary entry with what limits
-it (`limited_by`), its roofline and per-step samples (`step_samples`: n, median, min, max), the CPU baselines' passes --
-is printed to stderr as one `[bench] detail: {...}` line.
+wall time / K (max over ranks).  A plain run does only what that line needs: set-up, W warm-up and K timed steps, the
+roofline of the headline priced on the timed steps' own kernel events, --dump-outputs if given, the line.
+
+--full (N = 1) adds, after the headline, everything that takes runs of its own: `secondary` (configs 2-dyn, 3, 4 --
+staged and under the reference's joint Newton policy --, one GPU's share of 5, config 5 at full size, the deltaMG
+minibatch shape, Hbv_2_hourly with gage routing, the sequence LSTM and one examples/train_dpl.py step, driver-timed in
+the same run: name -> ms per step) and `cpu_baseline` (the pure-torch eager restatement of the reference's path on the
+host cores -- `value` -- with the C/OpenMP oracle port beside it); --no-secondary / --no-cpu-baseline leave one of the two
+out.  The line stays a few KB: the whole record -- every secondary entry with what limits it (`limited_by`), its roofline
+and per-step samples (`step_samples`: n, median, min, max), the CPU baselines' passes -- is printed to stderr as one
+`[bench] detail: {...}` line.
 
 --dump-outputs DIR writes what the last timed step computed (outputs, parameter gradients, loss) as DIR/<name>.npy, so
 that two builds can be compared output for output: the inputs depend on the arguments only.
@@ -911,8 +915,11 @@ def main():
     ap.add_argument("--basins", type=int, default=None)
     ap.add_argument("--nmul", type=int, default=None)
     ap.add_argument("--days", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also time the secondary configurations and the CPU baselines (one GPU); "
+                         "a plain run reports the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary configurations")
     ap.add_argument("--cpu-sample-days", type=int, default=1825)
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu exists for the launcher's own test (tests/test_bench_launch.py swaps in a host "
@@ -1073,7 +1080,7 @@ def main():
     if dev.type == "cuda":
         torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and dev.type == "cuda" and not args.no_secondary:
+    if rank == 0 and world == 1 and dev.type == "cuda" and args.full and not args.no_secondary:
         # the other BASELINE configs under the same clock: 5 timed steps each, same event timing
         sec = []
         print(f"[bench] headline done: {ms_per_step:.3f} ms/step; secondary configs ...", file=sys.stderr, flush=True)
@@ -1113,7 +1120,7 @@ def main():
             torch.cuda.empty_cache()
         res["secondary"] = sec
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         print("[bench] cpu baselines ...", file=sys.stderr, flush=True)
         # `value` = the reference-equivalent CPU path (PyTorch eager, one ATen call per operator per day + the autograd
         # tape: kind "restatement"); the C / OpenMP oracle port -- a far better CPU program than the

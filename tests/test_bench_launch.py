@@ -69,6 +69,25 @@ def test_self_launch_eight_ranks_strong_cfg5_uneven(oracle_path):
     assert r["value"] == pytest.approx(100003 * 1 * 6 / (r["ms_per_step"] * 1e-3), rel=1e-6)
 
 
+def test_plain_run_reports_the_headline_alone(oracle_path):
+    """One rank without --full: set-up, warm-up, timed steps and the line -- no CPU baselines (which would run here, on the
+    host, under --full) and no secondary configurations."""
+    env = dict(os.environ, HBVX_TEST_ABI_LIBRARY=oracle_path, HBVX_TEST_ROOT=ROOT, OMP_NUM_THREADS="1",
+               WORLD_SIZE="1", RANK="0",
+               PYTHONPATH=os.path.join(ROOT, "tests", "cpu_seam") + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--device", "cpu", "--steps", "2",
+           "--warmup", "1", "--basins", "4", "--days", "20", "--nmul", "2"]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    r = json.loads(lines[0])
+    assert r["n_gpus"] == 1 and r["steps"] == 2 and r["warmup"] == 1
+    assert r["value"] == pytest.approx(4 * 2 * 20 / (r["ms_per_step"] * 1e-3), rel=1e-6)
+    assert "secondary" not in r and "cpu_baseline" not in r
+    assert "cpu baselines" not in out.stderr and "secondary configs" not in out.stderr
+
+
 def test_world_size_mismatch_is_refused():
     env = dict(os.environ, WORLD_SIZE="3", RANK="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "cpu"], env=env,
@@ -98,13 +117,13 @@ def test_a_rank_that_dies_before_the_rendezvous_ends_the_job_quickly(oracle_path
 
 @pytest.mark.gpu
 def test_bench_line_contract_on_gpu():
-    """`python bench.py` on one GPU (child process): ONE JSON line with every field the driver reads, the
+    """`python bench.py --full` on one GPU (child process): ONE JSON line with every field the driver reads, the
     roofline object priced on live HIP-event kernel times, the CPU baselines with their core count, and
     throughput consistent with the step time.  Small shape, the full code path."""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-secondary",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-secondary",
            "--basins", "64", "--days", "730", "--cpu-sample-days", "64"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -136,3 +155,23 @@ def test_bench_line_contract_on_gpu():
         assert cb["port"]["kind"] == "port" and cb["port"]["value"] > 0
     smp = r["step_samples"]
     assert smp["n"] == 3 and smp["ms_min"] <= smp["ms_median"] <= smp["ms_max"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_on_gpu():
+    """`python bench.py` without --full on one GPU: the headline and its roofline, nothing that takes runs of its own."""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--basins", "64",
+           "--days", "730"]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    r = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "step_samples"):
+        assert key in r, key
+    assert r["value"] == pytest.approx(64 * 16 * 730 / (r["ms_per_step"] * 1e-3), rel=1e-6)
+    assert r["roofline"]["bound"] == "hbm" and 0.0 < r["roofline"]["avg_ms"] <= r["ms_per_step"] * 1.5
+    assert "secondary" not in r and "cpu_baseline" not in r

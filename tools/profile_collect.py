@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Turn the raw rocprofv3 output of tools/profile_round.sh into the committed summaries:
 
-    python tools/profile_collect.py <tag>
+    python tools/profile_collect.py <tag> [<raw output directory of profile_round.sh>, default profile_out/]
 
     profiles/<tag>_kernel_stats.csv      per-kernel time (rocprofv3 --kernel-trace --stats)
     profiles/<tag>_pmc_fetch_size.csv    per-kernel FETCH_SIZE (KiB) of the hbvx kernels, averaged
@@ -86,25 +86,25 @@ def sq_counters(tag, out):
                             f"(a pure fma loop at four waves per SIMD: 0.70, profiles/r03_issue_rate.txt)\n")
 
 
-def main(tag):
+def main(tag, raw_root):
     """(see the module docstring)"""
-    raw = os.path.join(ROOT, "gpurun_out", f"prof_{tag}")
+    raw = os.path.join(raw_root, f"prof_{tag}")
     out = os.path.join(ROOT, "profiles")
     stats = glob.glob(os.path.join(raw, "kt", "**", "*kernel_stats.csv"), recursive=True)
     shutil.copy(stats[0], os.path.join(out, f"{tag}_kernel_stats.csv"))
-    with open(os.path.join(ROOT, "gpurun_out", f"prof_{tag}.bench.json")) as f:
+    with open(os.path.join(raw_root, f"prof_{tag}.bench.json")) as f:
         line = [l for l in f if l.startswith("{")][-1]
     with open(os.path.join(out, f"{tag}_bench.json"), "w") as f:
         f.write(line)
     st = glob.glob(os.path.join(raw, "cfgs", "**", "*kernel_stats.csv"), recursive=True)
     if st:
         shutil.copy(st[0], os.path.join(out, f"{tag}_configs_kernel_stats.csv"))
-        js = os.path.join(ROOT, "gpurun_out", f"prof_{tag}.cfgs.jsonl")
+        js = os.path.join(raw_root, f"prof_{tag}.cfgs.jsonl")
         if os.path.exists(js):
             shutil.copy(js, os.path.join(out, f"{tag}_bench_configs.jsonl"))
     for extra in ("lstm", "dpl"):
         st = glob.glob(os.path.join(raw, extra, "**", "*kernel_stats.csv"), recursive=True)
-        js = os.path.join(ROOT, "gpurun_out", f"prof_{tag}.{extra}.json")
+        js = os.path.join(raw_root, f"prof_{tag}.{extra}.json")
         if st and os.path.exists(js):
             shutil.copy(st[0], os.path.join(out, f"{tag}_{extra}_kernel_stats.csv"))
             with open(js) as f:
@@ -157,4 +157,4 @@ def main(tag):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "r02")
+    main(sys.argv[1] if len(sys.argv) > 1 else "r02", os.path.abspath(sys.argv[2] if len(sys.argv) > 2 else "profile_out"))
