@@ -120,7 +120,7 @@ EXPORTS = ["hbvx_zero", "hbvx_zero_except", "hbvx_preferred_traj_layout", "hbvx_
 # Exports a library may lack (the CPU restatement under oracle/ has only the calls above); a call that needs one raises
 # HbvxError naming it.
 OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forward_tangent", "hbvx_route_tangent",
-                    "hbvx_bfi_tangent"]
+                    "hbvx_bfi_tangent", "hbvx_lstm_tangent"]
 
 
 class HbvxError(RuntimeError):
@@ -204,6 +204,10 @@ class Library:
             d.hbvx_lstm_backward_hx.restype = C.c_int
             d.hbvx_lstm_backward_hx.argtypes = [C.POINTER(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
                                                 C.c_void_p, C.c_uint64, C.c_void_p]
+        if "hbvx_lstm_tangent" not in self.missing:
+            d.hbvx_lstm_tangent.restype = C.c_int
+            d.hbvx_lstm_tangent.argtypes = [C.POINTER(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                            C.c_void_p, C.c_uint64, C.c_void_p]
         if "hbvx_forward_tangent" not in self.missing:
             d.hbvx_forward_tangent.restype = C.c_int
             d.hbvx_forward_tangent.argtypes = [C.POINTER(Desc), C.POINTER(TanIO), C.c_void_p]
@@ -321,6 +325,12 @@ class Library:
         self.require("hbvx_lstm_backward_hx")
         self._check(self.dll.hbvx_lstm_backward_hx(C.byref(r), w_hh, gates, c0, c_all, gh, gc_last, gg, gc0, ws,
                                                    C.c_uint64(ws_bytes), C.c_void_p(stream)), "hbvx_lstm_backward_hx")
+
+    def lstm_tangent(self, r: LstmDesc, w_hh: int, gates: int, c0, c_all: int, gx_t: int, h0_t, c0_t, h_t: int,
+                     c_t_last, ws, ws_bytes: int, stream: int):
+        self.require("hbvx_lstm_tangent")
+        self._check(self.dll.hbvx_lstm_tangent(C.byref(r), w_hh, gates, c0, c_all, gx_t, h0_t, c0_t, h_t, c_t_last, ws,
+                                               C.c_uint64(ws_bytes), C.c_void_p(stream)), "hbvx_lstm_tangent")
 
     def forward_tangent(self, desc: Desc, io: TanIO, stream: int):
         self.require("hbvx_forward_tangent")

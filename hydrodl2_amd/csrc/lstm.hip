@@ -67,8 +67,8 @@ static int lstm_cu_count()
     return n_cu[dev];
 }
 
-template <typename K>
-static hipError_t launch_lstm(K kern, LstmArgs a, int nwg, hipStream_t st)
+template <typename K, typename A>
+static hipError_t launch_lstm(K kern, A a, int nwg, hipStream_t st)
 {
     const int n_cu = lstm_cu_count();
     // Residency: a launch never holds more workgroups than fit on the chip at once, so every partner
@@ -97,6 +97,13 @@ static hipError_t launch_lstm(K kern, LstmArgs a, int nwg, hipStream_t st)
     return hipGetLastError();
 }
 
+// The forward's (and the tangent's) workgroup form: 8 units per workgroup while twice the workgroups still fit one
+// launch at one per CU, else 16
+static bool lstm_eight_units(const hbvx_lstm_desc *d, int ntile)
+{
+    return env_int("HBVX_LSTM_UNITS", ntile * (d->H / 8) <= lstm_cu_count() ? 8 : 16) == 8;
+}
+
 extern "C" int hbvx_lstm_forward_hx(const hbvx_lstm_desc *d, const float *w_hh, const float *gx, const float *h0,
                                     const float *c0, float *gates, float *c_all, float *h_all, void *workspace,
                                     uint64_t workspace_bytes, void *stream)
@@ -117,10 +124,7 @@ extern "C" int hbvx_lstm_forward_hx(const hbvx_lstm_desc *d, const float *w_hh, 
     a.xch = (float *)((char *)workspace + lstm_counter_bytes(d));
     a.spin_limit = (unsigned)env_int("HBVX_LSTM_SPIN_LIMIT", (int)LSTM_SPIN_LIMIT);
     a.drop_wg = env_int("HBVX_LSTM_DEBUG_DROP_WG", -1);
-    // 8 units per workgroup while twice the workgroups still fit one launch at one per CU, else 16
-    const int n_cu = lstm_cu_count();
-    const bool small = env_int("HBVX_LSTM_UNITS", a.ntile * (d->H / 8) <= n_cu ? 8 : 16) == 8;
-    if (small)
+    if (lstm_eight_units(d, a.ntile))
         e = d->H == 64 ? launch_lstm(k_lstm_fwd<64, 2>, a, 8, st)
           : d->H == 128 ? launch_lstm(k_lstm_fwd<128, 2>, a, 16, st) : launch_lstm(k_lstm_fwd<256, 2>, a, 32, st);
     else
@@ -171,6 +175,36 @@ extern "C" int hbvx_lstm_backward(const hbvx_lstm_desc *d, const float *w_hh, co
 {
     return hbvx_lstm_backward_hx(d, w_hh, gates, nullptr, c_all, grad_h, nullptr, grad_gates, nullptr, workspace,
                                  workspace_bytes, stream);
+}
+
+extern "C" int hbvx_lstm_tangent(const hbvx_lstm_desc *d, const float *w_hh, const float *gates, const float *c0,
+                                 const float *c_all, const float *gx_t, const float *h0_t, const float *c0_t,
+                                 float *h_t, float *c_t_last, void *workspace, uint64_t workspace_bytes, void *stream)
+{
+    int rc = check_lstm(d);
+    if (rc) return rc;
+    if (!w_hh || !gates || !c_all || !gx_t || !h_t) return fail(HBVX_E_NULL, "lstm buffer is NULL");
+    if (!workspace || workspace_bytes < hbvx_lstm_workspace_bytes(d))
+        return fail(HBVX_E_NULL, "lstm workspace missing or too small");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = lstm_prepare(d, workspace, false, st);
+    if (e != hipSuccess) return hip_fail(e, "hbvx_lstm_tangent arm");
+    LstmTanArgs a{};
+    a.T = d->T; a.B = d->B; a.ntile = (d->B + LSTM_ROWS - 1) / LSTM_ROWS;
+    a.w_hh = w_hh; a.gx_t = gx_t; a.gates = gates; a.c_all = c_all; a.c0 = c0;
+    a.h0_t = h0_t; a.c0_t = c0_t; a.h_t = h_t; a.c_t_last = c_t_last;
+    a.cnt = (unsigned *)workspace;
+    a.xch = (float *)((char *)workspace + lstm_counter_bytes(d));
+    a.spin_limit = (unsigned)env_int("HBVX_LSTM_SPIN_LIMIT", (int)LSTM_SPIN_LIMIT);
+    a.drop_wg = env_int("HBVX_LSTM_DEBUG_DROP_WG", -1);
+    if (lstm_eight_units(d, a.ntile))
+        e = d->H == 64 ? launch_lstm(k_lstm_tan<64, 2>, a, 8, st)
+          : d->H == 128 ? launch_lstm(k_lstm_tan<128, 2>, a, 16, st) : launch_lstm(k_lstm_tan<256, 2>, a, 32, st);
+    else
+        e = d->H == 64 ? launch_lstm(k_lstm_tan<64, 4>, a, 4, st)
+          : d->H == 128 ? launch_lstm(k_lstm_tan<128, 4>, a, 8, st) : launch_lstm(k_lstm_tan<256, 4>, a, 16, st);
+    if (e != hipSuccess) return hip_fail(e, "hbvx_lstm_tangent launch");
+    return 0;
 }
 
 extern "C" int hbvx_lstm_check(const hbvx_lstm_desc *d, const void *workspace, void *stream)

@@ -11,12 +11,17 @@ persistent HIP kernel per direction; `hbvx_lstm_forward_hx` / `hbvx_lstm_backwar
 given or c_n has a gradient); the time-parallel parts -- input projection, weight, input and h0
 gradients -- are plain library GEMMs here.  Like the rest of the package there is no CPU path: on a
 host tensor, or without the HIP library, the call raises.
+
+Forward mode: under torch.autograd.forward_ad, `LstmSeq.jvp` carries one tangent direction (on x, the weights
+and biases, h0 and c0) to h and c_n through `hbvx_lstm_tangent`, a third persistent kernel; a library without
+that export raises HbvxError naming it.  torch.func.jvp / jacfwd are not supported.
 """
 from __future__ import annotations
 
 import math
 
 import torch
+import torch.autograd.forward_ad as _fwAD
 
 from . import _abi
 from ._lib import get_library
@@ -106,7 +111,10 @@ class LstmSeq(torch.autograd.Function):
         if check:
             lib.lstm_check(r, ops._ptr(ws), st)
         ctx.save_for_backward(x_c, w_ih_p, w_hh_c, gx, c_all, h_all, perm, h0, c0)
+        if _fwAD._current_level >= 0:        # forward mode (jvp) reads the same tensors
+            ctx.save_for_forward(x_c, w_ih_p, w_hh_c, gx, c_all, h_all, perm, h0, c0)
         ctx.check = check
+        ctx.cn = cn
         ctx.mark_non_differentiable(c_all)
         ctx.set_materialize_grads(False)     # an unused output's gradient stays None: no zeros, no c_n term
         if cn:
@@ -154,6 +162,63 @@ class LstmSeq(torch.autograd.Function):
             gb[perm] = dg.sum(0)
         gh0 = dg[:B] @ w_hh.index_select(0, perm) if h0 is not None and need[6] else None   # dgates_0 W_hh
         return (gx.view(T, B, I) if gx is not None else None), gw_ih, gw_hh, gb, gb, None, gh0, gc0, None
+
+    @staticmethod
+    @ops._device_guard
+    def jvp(ctx, x_t, w_ih_t, w_hh_t, b_ih_t, b_hh_t, _check_t, h0_t, c0_t, _cn_t):
+        """Forward mode (torch.autograd.forward_ad): tangents of h and c_n along the inputs' tangents.  The time-parallel
+        terms of the tangent are library GEMMs here, gx' = x' W_ih^T + x W_ih'^T + b_ih' + b_hh' + [h0; h_0..h_{T-2}]
+        W_hh'^T (rows in the (unit, gate) order of gx; a term whose tangent is None is left out); the recurrence
+        z'_t = gx'_t + h'_{t-1} W_hh^T and the cell's tangent are hbvx_lstm_tangent, on the primal the forward saved."""
+        lib = get_library()
+        lib.require("hbvx_lstm_tangent")
+        x, w_ih_p, w_hh, gates, c_all, h_all, perm, h0, c0 = ctx.saved_tensors
+        T, B, I = x.shape
+        H = w_hh.shape[1]
+        gt = None                                                               # gx' [T*B, 4H]
+        if x_t is not None:
+            gt = x_t.reshape(T * B, I) @ w_ih_p.t()
+        if w_ih_t is not None:
+            term = x.reshape(T * B, I) @ w_ih_t.index_select(0, perm).t()
+            gt = term if gt is None else gt.add_(term)
+        if b_ih_t is not None or b_hh_t is not None:
+            bt = b_ih_t if b_hh_t is None else (b_hh_t if b_ih_t is None else b_ih_t + b_hh_t)
+            bt = bt.index_select(0, perm)
+            gt = bt.expand(T * B, 4 * H).clone() if gt is None else gt.add_(bt)
+        if w_hh_t is not None:
+            w_hh_tp = w_hh_t.index_select(0, perm).t()
+            if gt is None:
+                gt = torch.zeros(T * B, 4 * H, dtype=torch.float32, device=x.device)
+            if T > 1:                                                           # h_{t-1} W_hh'^T, t >= 1
+                gt[B:].addmm_(h_all[:-1].reshape((T - 1) * B, H), w_hh_tp)
+            if h0 is not None:                                                  # the step-0 term: h_{-1} = h0
+                gt[:B].addmm_(h0, w_hh_tp)
+        if gt is None:
+            gt = torch.zeros(T * B, 4 * H, dtype=torch.float32, device=x.device)
+        gt = gt.contiguous()
+        state_t = []
+        for t, name in ((h0_t, 'h0'), (c0_t, 'c0')):
+            if t is not None:
+                ops._check_tensor(lib, t, f"tangent of {name}")
+                t = t.contiguous()
+                if t.data_ptr() % 16:                                           # h0' is read in 16-byte granules
+                    t = t.clone()
+            state_t.append(t)
+        h0_t, c0_t = state_t
+        r = _abi.LstmDesc(abi_version=_abi.LSTM_ABI_VERSION, T=T, B=B, H=H)
+        ws_bytes = lib.lstm_workspace_bytes(r)
+        ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=x.device)
+        h_t = ops._out((T, B, H), x.device)
+        cn_t = ops._out((B, H), x.device) if ctx.cn else None
+        st = ops._stream_of(lib, x)
+        ops._call(lib, 'hbvx_lstm_tangent', lib.lstm_tangent, r, ops._ptr(w_hh), ops._ptr(gates), ops._ptr(c0),
+                  ops._ptr(c_all), ops._ptr(gt), ops._ptr(h0_t), ops._ptr(c0_t), ops._ptr(h_t), ops._ptr(cn_t),
+                  ops._ptr(ws), ws_bytes, st)
+        if ctx.check:
+            lib.lstm_check(r, ops._ptr(ws), st)
+        if ctx.cn:
+            return h_t, None, cn_t
+        return h_t, None
 
 
 def lstm_seq(x, w_ih, w_hh, b_ih, b_hh, check: bool = False):

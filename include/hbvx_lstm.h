@@ -31,9 +31,9 @@ typedef struct hbvx_lstm_desc {
     int32_t T, B, H;     /* steps, basins (batch), hidden units; the HIP library needs H in {64, 128, 256} */
 } hbvx_lstm_desc;
 
-/* Scratch for either call below (bytes; caller-owned, contents undefined afterwards): the per-step
- * exchange slabs through which the workgroups of a 16-basin row tile hand h_t (forward) or the gate
- * gradients (backward) to each other, and the arrival counters. */
+/* Scratch for any call below (bytes; caller-owned, contents undefined afterwards): the per-step
+ * exchange slabs through which the workgroups of a 16-basin row tile hand h_t (forward), h'_t (tangent) or
+ * the gate gradients (backward) to each other, and the arrival counters. */
 uint64_t hbvx_lstm_workspace_bytes(const hbvx_lstm_desc *d);
 
 /* w_hh [4H,H] (torch.nn.LSTM.weight_hh_l0), gx [T,B,H,4] = x W_ih^T + b_ih + b_hh in (unit, gate)
@@ -70,6 +70,23 @@ int hbvx_lstm_backward_hx(const hbvx_lstm_desc *d, const float *w_hh, const floa
                           const float *grad_c_last,
                           float *grad_gates, float *grad_c0,
                           void *workspace, uint64_t workspace_bytes, void *stream);
+
+/* Forward-mode derivative of hbvx_lstm_forward_hx along one direction (tangents written with a prime), on the
+ * primal that call produced: gates [T,B,H,4] (activated, (unit, gate) layout) and c_all [T,B,H], from the same w_hh
+ * and c0.  Additive to ABI version 1 like the *_hx calls: the same descriptor, validation and workspace size.
+ *
+ *   z'_t = gx'_t + h'_{t-1} W_hh^T        gx_t [T,B,H,4], (unit, gate) layout: every time-parallel term of the
+ *                                         tangent, formed by the caller -- x' W_ih^T + x W_ih'^T + b_ih' + b_hh'
+ *                                         + [h0; h_0 .. h_{T-2}] W_hh'^T
+ *   di = i(1-i) z'_i, df = f(1-f) z'_f, dg = (1-g^2) z'_g, do = o(1-o) z'_o
+ *   c'_t = df c_{t-1} + f c'_{t-1} + di g + i dg;   h'_t = do tanh(c_t) + o (1 - tanh(c_t)^2) c'_t
+ *   (h'_{-1}, c'_{-1}) = (h0_t, c0_t); c_{-1} = c0
+ *
+ * -> h_t [T,B,H] (h'), c_t_last [B,H] (c'_{T-1}; NULL = not wanted).  A NULL c0, h0_t or c0_t stands for zeros.
+ * h0_t must be 16-byte aligned like gx_t.  A time-out poisons h_t[T-1] and c_t_last with NaN (hbvx_lstm_check). */
+int hbvx_lstm_tangent(const hbvx_lstm_desc *d, const float *w_hh, const float *gates, const float *c0,
+                      const float *c_all, const float *gx_t, const float *h0_t, const float *c0_t,
+                      float *h_t, float *c_t_last, void *workspace, uint64_t workspace_bytes, void *stream);
 
 /* Synchronises `stream` and reports whether the last call that used `workspace` completed: the
  * workgroups of a row tile wait for each other with bounded spins; a time-out (the partners were

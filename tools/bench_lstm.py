@@ -2,10 +2,12 @@
 """Sequence LSTM: hydrodl2_amd.lstm.SeqLSTM (include/hbvx_lstm.h) beside torch.nn.LSTM (MIOpen) on the
 same weights and input, forward and forward+backward, at the delta-MG shape by default.
 
-    python tools/bench_lstm.py [T B I H] [--state]
+    python tools/bench_lstm.py [T B I H] [--state] [--jvp]
 
 --state: also SeqLSTM with a carried initial state (h0, c0 requiring grad, the loss on out, h_n and c_n), next
 to the zero-state call, on the same weights and input.
+--jvp: forward + JVP (torch.autograd.forward_ad, one direction on x: hbvx_lstm_tangent behind the forward) against
+the forward alone, at B and at 5 B, and the tangent kernel's own time.
 """
 import json
 import os
@@ -81,6 +83,34 @@ def main():
         for key in ("fused_fwd_ms", "fused_state_fwd_ms", "fused_fwdbwd_ms", "fused_state_fwdbwd_ms"):
             res[key] = min(res[key + "_runs"])
         res["state_fwdbwd_over_zero_state"] = round(res["fused_state_fwdbwd_ms"] / res["fused_fwdbwd_ms"], 4)
+    if "--jvp" in sys.argv:
+        import torch.autograd.forward_ad as fwAD
+        for Bj in (B, 5 * B):
+            xj = torch.randn(T, Bj, I, device=dev)
+            tj = torch.randn_like(xj)
+
+            def fwd_only():
+                with torch.no_grad():
+                    return fused(xj)[0]
+
+            def fwd_jvp():
+                with torch.no_grad(), fwAD.dual_level():
+                    return fwAD.unpack_dual(fused(fwAD.make_dual(xj, tj))[0]).tangent
+
+            runs = {"fwd": [], "fwd_jvp": []}
+            for _ in range(2):          # alternated, so that both see the same state of the box
+                runs["fwd"].append(round(timed(fwd_only, steps), 3))
+                runs["fwd_jvp"].append(round(timed(fwd_jvp, steps), 3))
+            ops.KERNEL_EVENTS = []
+            for _ in range(steps):
+                fwd_jvp()
+            torch.cuda.synchronize()
+            ev, ops.KERNEL_EVENTS = ops.KERNEL_EVENTS, None
+            r = {"B": Bj, "fwd_ms": min(runs["fwd"]), "fwd_jvp_ms": min(runs["fwd_jvp"]), "runs": runs}
+            for n in ("hbvx_lstm_forward", "hbvx_lstm_tangent"):
+                r[n + "_ms"] = round(sum(a.elapsed_time(b) for k, a, b in ev if k == n) / steps, 3)
+            r["fwd_jvp_over_fwd"] = round(r["fwd_jvp_ms"] / r["fwd_ms"], 4)
+            res.setdefault("jvp", []).append(r)
     ops.KERNEL_EVENTS = []
     for _ in range(steps):
         fwdbwd(fused)
