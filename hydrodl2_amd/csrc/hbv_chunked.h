@@ -39,7 +39,8 @@ struct ChunkArgs {
     int nchunk;
     float *phi;   // [nchunk][30][N]  Phi (5 propagated unit adjoints x 5) then phi (5)
     float *abnd;  // [nchunk][5][N]   adjoint entering each chunk from the future
-    float *gpart; // [nchunk][NP][N]  per-chunk static-parameter gradient (unit space)
+    float *gpart; // [nchunk][NP][N]  per-chunk static-parameter gradient (unit space); the one-pass form's
+                  // [nchunk][onepass_rows(NP)][N] G_c and g0_c rows (k_bwd_chunk_onepass)
     int nd;       // DYN == 1: number of dynamic parameters (<= CHUNK_FEW) and their slots
     int dslot[3];
     int per_xcd;  // basin groups per XCD of the block map below (host: chunk_per_xcd)
@@ -459,6 +460,106 @@ __global__ void __launch_bounds__(64) k_bwd_chunk_phi(const ChunkArgs A)
     }
 }
 
+// ---- B1+B3 in one pass: HBV 1.0, static parameters only ------------------------------------------
+// With every parameter static and no forcing gradient the sweep (B3) is there only to turn the chunk's incoming
+// adjoint a_c into parameter gradients, and that map is linear:
+//     g_c = sum_t Jθ_t^T a_{t+1} = G_c a_c + g0_c,   G_c = sum_t Jθ_t^T M_{t+1},   g0_c = sum_t Jθ_t^T m_{t+1}
+// where M_{t+1} (the propagated unit adjoints, Phi) and m_{t+1} (the offset, phi, with the day's flux sources) are
+// exactly what B1 carries backwards through the chunk.  So this kernel is B1 plus, per vector, the gp[] lines of
+// bwd() (Step::jt_gp), and the trajectory is read once.  The sparsity of the unit vectors carries over: Phi[0..1]
+// stay in the snow block (4 parameters), Phi[2] reaches snow and soil (7 / 8), Phi[3..4] and the offset all NP.
+// Workspace rows of a chunk (ChunkArgs::gpart, [nchunk][onepass_rows(NP)][N]): per parameter i, the rows of G_c for
+// k = onepass_kmin(i) .. 4, then g0_c[i].  k_bwd_chunk_fold + k_bwd_chunk_reduce finish sum_c (G_c a_c + g0_c).
+__host__ __device__ constexpr int onepass_kmin(int i)
+{
+    return (i == P_TT || i == P_CFMAX || i == P_CFR || i == P_CWH) ? 0
+         : ((i == P_BETA || i == P_FC || i == P_LP || i == P_BETAET) ? 2 : 3);
+}
+__host__ __device__ constexpr int onepass_row(int i)
+{
+    int r = 0;
+    for (int j = 0; j < i; j++) r += 6 - onepass_kmin(j);
+    return r;
+}
+__host__ __device__ constexpr int onepass_rows(int NP) { return onepass_row(NP); }
+
+// Registers: 156 / 161 VGPRs (three waves per SIMD) with the runoff-only loss, 179 / 187 (two) with GFULL's full adjoint
+// step on the offset.  Forced to 128 (four waves) the compiler spills 19-33 values (runoff-only) and 84-98 (GFULL).
+template <bool BETAET, bool GFULL>
+__global__ void __launch_bounds__(64) k_bwd_chunk_onepass(const ChunkArgs A)
+{
+    constexpr int MODEL = MODEL_HBV10, DYN = 0;
+    constexpr int NP = ChunkNP<MODEL, BETAET>::value;
+    typedef Step<MODEL, BETAET> S;
+    const int ds_[3] = {0, 0, 0};
+    const hbvx_desc &d = A.d;
+    const hbvx_bwd_io &io = A.io;
+    ChunkBlock blk;
+    if (!chunk_block(d, A.lgMp, A.per_xcd, blk)) return;
+    const ChunkLane L = chunk_lane(d, A.lgMp, blk.bx);
+    const int chunk = blk.chunk;
+    const int t0 = chunk * A.C, t1 = min(d.T, t0 + A.C);
+    const int64_t N = (int64_t)d.B * d.M;
+    const bool raw = d.raw_sigmoid != 0;
+    const float nz = d.nearzero, invM = 1.0f / (float)d.M;
+    float usta[NP], psta[NP];
+    bool use_dyn[NP];
+    chunk_static<NP, DYN>(d, L, raw, usta, psta, use_dyn, 0, ds_);
+
+    float Phi[5][5], phi[5];
+    float G[6][NPARAM_MAX];   // G[k]: Jθ^T sums of the unit vector Phi[k]; G[5]: of the offset (entries never touched fold away)
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        phi[k] = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 5; i++) Phi[k][i] = (i == k) ? 1.0f : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+#pragma unroll
+        for (int i = 0; i < NPARAM_MAX; i++) G[k][i] = 0.0f;
+    ChunkRaw<NP> Rn;
+    chunk_issue<NP, DYN, GFULL>(d, io, L, t1 - 1, io.n_flux, Rn, 0, ds_);
+    for (int t = t1 - 1; t >= t0; t--) {
+        ChunkRaw<NP> Rc = Rn;
+        if (t > t0) chunk_issue<NP, DYN, GFULL>(d, io, L, t - 1, io.n_flux, Rn, 0, ds_);   // next day's loads in flight
+        ChunkDay<MODEL, BETAET, NP> D;
+        chunk_finish<MODEL, BETAET, NP, DYN, GFULL>(d, Rc, raw, nz, 0.0f, 0.0f, usta, psta, use_dyn, io.n_flux, invM,
+                                                    D, 0, ds_, io.grad_flux4 != nullptr);
+        const typename S::JT c = D.s.jt_coef(D.p, nz);
+        const typename S::JG k = D.s.jg_coef(D.p, nz);
+        S::template jt_gp<0>(c, k, Phi[0], G[0]);
+        S::template jt_gp<0>(c, k, Phi[1], G[1]);
+        S::template jt_gp<1>(c, k, Phi[2], G[2]);
+        S::template jt_gp<2>(c, k, Phi[3], G[3]);
+        S::template jt_gp<2>(c, k, Phi[4], G[4]);
+        if constexpr (!GFULL) {
+            S::template jt_gp<2, true>(c, k, phi, G[5], D.g.gQ0 + D.g.gQ, D.g.gQ1 + D.g.gQ, D.g.gQ2 + D.g.gQ);
+        } else {
+            float gx[3];
+            D.s.bwd(D.p, nz, D.g, phi, G[5], gx);   // its gp output is g0_c
+        }
+    }
+    if (L.active) {
+        float *dst = A.phi + ((int64_t)chunk * 30) * N + L.n;
+#pragma unroll
+        for (int k = 0; k < 5; k++)
+#pragma unroll
+            for (int i = 0; i < 5; i++) dst[(int64_t)(k * 5 + i) * N] = Phi[k][i];
+#pragma unroll
+        for (int i = 0; i < 5; i++) dst[(int64_t)(25 + i) * N] = phi[i];
+        float *gdst = A.gpart + ((int64_t)chunk * onepass_rows(NP)) * N + L.n;
+#pragma unroll
+        for (int i = 0; i < NP; i++) {
+            const int r0 = onepass_row(i), k0 = onepass_kmin(i);
+#pragma unroll
+            for (int kk = 0; kk < 5; kk++)
+                if (kk >= k0) gdst[(int64_t)(r0 + kk - k0) * N] = G[kk][i];
+            gdst[(int64_t)(r0 + 5 - k0) * N] = G[5][i];
+        }
+    }
+}
+
 #ifndef HBVX_CHUNK_NO_SHARED_KERNELS   // non-template kernels: defined in launch_chunked.hip only
 // ---- B2 -------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) k_bwd_chunk_scan(const ChunkArgs A)
@@ -690,6 +791,52 @@ __global__ void __launch_bounds__(256) k_bwd_chunk_reduce(const ChunkArgs A, int
     }
     float *dst = io.g[i].sta + (int64_t)b * io.g[i].sta_b_stride + j;
     *dst += gsum;
+}
+
+// ---- B4 of the one-pass form --------------------------------------------------------------------
+// Two fixed-order stages (deterministic).  k_bwd_chunk_fold: per (lane, group of ONEPASS_GROUP chunks), every
+// parameter at once: sum over the group's chunks of G_c a_c + g0_c, times (hi - lo) -- each G_c row and boundary
+// adjoint is read once, by ~4 900 waves at config 2 (a first version with one thread per (parameter, lane) walking
+// all 115 chunks read the boundary adjoints 39 times over on 2 000 waves: 0.26 ms).  The group partials go to the
+// maps' rows ([ngroup][NP][N]: free once the scan has run), and k_bwd_chunk_reduce finishes them as in the two-pass
+// form (sigmoid' chain, accumulate into the static-row gradient).
+// The fold works in float64: G_c a_c + g0_c is where the unit vectors' contributions meet and cancel (parPERC's
+// aPERC = SLZ share - SUZ share), which the two-pass sweep does day by day on the true adjoint instead.  In float32
+// the one-pass parPERC gradient missed float64 by 2.3 x the two-pass error at 32 x 16 x 730
+// (tests/test_chunk_onepass_f64_gpu.py); the fold is memory-bound, the float64 arithmetic is free.
+#define ONEPASS_GROUP 4
+template <int NP>
+__global__ void __launch_bounds__(256) k_bwd_chunk_fold(const ChunkArgs A)
+{
+    constexpr int NR = onepass_rows(NP);
+    const hbvx_desc &d = A.d;
+    const int64_t N = (int64_t)d.B * d.M;
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const int grp = blockIdx.y;
+    const int c0 = grp * ONEPASS_GROUP, c1 = min(A.nchunk, c0 + ONEPASS_GROUP);
+    double acc[NP];
+#pragma unroll
+    for (int i = 0; i < NP; i++) acc[i] = 0.0;
+    for (int c = c0; c < c1; c++) {
+        const float *g = A.gpart + (int64_t)c * NR * N + n;
+        const float *ab = A.abnd + (int64_t)c * 5 * N + n;
+        double a[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) a[k] = ab[(int64_t)k * N];
+#pragma unroll
+        for (int i = 0; i < NP; i++) {
+            const int k0 = onepass_kmin(i), r0 = onepass_row(i);
+            double v = g[(int64_t)(r0 + 5 - k0) * N];
+#pragma unroll
+            for (int k = 0; k < 5; k++)
+                if (k >= k0) v += (double)g[(int64_t)(r0 + k - k0) * N] * a[k];
+            acc[i] += v;
+        }
+    }
+    float *dst = A.phi + (int64_t)grp * NP * N + n;
+#pragma unroll
+    for (int i = 0; i < NP; i++) dst[(int64_t)i * N] = (float)acc[i] * (d.p[i].hi - d.p[i].lo);
 }
 
 #endif

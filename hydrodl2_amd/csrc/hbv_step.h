@@ -966,6 +966,135 @@ struct Step {
         a[1] = mw1;
         a[0] = sp2 + (mw1 - sp2) * c.wm;
     }
+
+    // ---- parameter Jacobian of one day, HBV 1.0 only ----------------------------------------
+    // The one-pass static adjoint (hbv_chunked.h, k_bwd_chunk_onepass) sums, beside every vector v it propagates
+    // through a chunk (the five unit adjoints and the offset), what bwd() adds to gp[] for v: Jθ^T v.  JG holds the
+    // day's coefficients -- bwd()'s predicates, tie weights and power derivatives, with masks and tie weights folded
+    // in only where the product is exact (0/1 masks, weights 0 / 1/2 / 1) -- and jt_gp<LEVEL, AFF>() is jt_unit<LEVEL>
+    // (AFF: jt_affine with its three runoff sources) line for line plus gp[] += for the parameters that vector
+    // reaches: LEVEL 0 (snow block) TT CFMAX CFR CWH;  LEVEL 1 + BETA FC LP (BETAET);  LEVEL 2 / AFF every one.
+    // The products and sums of bwd()'s gp lines keep their order, so a unit vector's gp equals bwd()'s for it up
+    // to the rounding of the a-propagation itself (tests/test_step_jg_host.py).
+    struct JG {
+        float SLZ1p, SUZ3, u0c, wPb;                        // groundwater (wPb: parPERC's tie weight)
+        float cE, dq, db, qlp, FC, LP, crt, dr, dbr, rFC;   // soil
+        float SP3, kr, dT2, CFMAX, CFR, cc, km, dT;         // snow
+    };
+
+    HBVX_HDM JG jg_coef(const float *p, float nz) const
+    {
+        static_assert(MODEL == MODEL_HBV10, "jg_coef: HBV 1.0 only");
+        JG c;
+        float wa, wb;
+        c.SLZ1p = SLZ1p; c.SUZ3 = SUZ3; c.u0c = u0c;
+        minw_(SUZ1, p[P_PERC], wa, wb);
+        c.wPb = wb;
+        // soil: aef0 = mef (PET (wb (-(md a2))))  -- every factor but PET is 0, 1/2 or 1
+        minw_(SM2, pe, wa, wb);
+        const float mef = (ef0 >= 0.0f && ef0 <= 1.0f) ? 1.0f : 0.0f;
+        const float md = (dd >= nz) ? 1.0f : 0.0f;
+        c.cE = -((md * wb) * mef) * PET;
+        c.dq = 1.0f; c.db = 0.0f;
+        if (BETAET) {
+            const float BE = p[P_BETAET];
+            c.dq = (q > 0.0f) ? BE * div_approx_(ef0, q) : 0.0f;
+            c.db = (q > 0.0f) ? ef0 * log_fast_(q) : 0.0f;
+        }
+        c.qlp = div_approx_(q, lpfc);
+        c.FC = p[P_FC]; c.LP = p[P_LP];
+        const float msw = (sw0 >= 0.0f && sw0 <= 1.0f) ? 1.0f : 0.0f;
+        c.crt = rt * msw;
+        c.dr = (r > 0.0f) ? p[P_BETA] * div_approx_(sw0, r) : 0.0f;
+        c.dbr = (r > 0.0f) ? sw0 * log_fast_(r) : 0.0f;
+        c.rFC = div_approx_(r, p[P_FC]);
+        // snow
+        c.SP3 = SP3; c.dT2 = dT2; c.CFMAX = p[P_CFMAX]; c.CFR = p[P_CFR]; c.cc = cc; c.dT = dT;
+        minw_(rpc, MW1, wa, wb);
+        c.kr = (rp >= 0.0f) ? wa : 0.0f;
+        minw_(mpc, SP1, wa, wb);
+        c.km = (mp >= 0.0f) ? wa : 0.0f;
+        return c;
+    }
+
+    template <int LEVEL, bool AFF = false>
+    static HBVX_HDM void jt_gp(const JT &c, const JG &k, float *a, float *gp, float s0 = 0.0f, float s1 = 0.0f,
+                               float s2 = 0.0f)
+    {
+        HBVX_ADJ_FMA
+        static_assert(!AFF || LEVEL == 2, "jt_gp: the affine form is a full vector");
+        float ats = 0.0f;
+        if (LEVEL >= 1) {
+            float U = 0.0f;
+            if (LEVEL >= 2) {
+                const float a3 = a[3], a4 = a[4];
+                float sl;
+                if (AFF) {
+                    sl = c.cS * a4 + c.K2 * s2;
+                    const float z3 = c.k1c * a3 + c.K1 * s1;
+                    const float z2 = z3 * c.k0c + c.k0m * s0;
+                    U = z2 * c.wac + c.wP * sl;
+                } else {
+                    sl = c.cS * a4;
+                    U = c.cU * a3 + c.wP * sl;
+                }
+                // bwd()'s groundwater gp lines on the same vector
+                const float aQ2 = s2 - a4;
+                gp[P_K2] += aQ2 * k.SLZ1p;
+                const float aQ1 = s1 - a3;
+                gp[P_K1] += aQ1 * k.SUZ3;
+                const float aSUZ3 = a3 + aQ1 * c.K1;
+                const float aQ0 = s0 - aSUZ3;
+                gp[P_K0] += aQ0 * k.u0c;
+                const float au0 = aQ0 * c.k0m;
+                gp[P_UZL] -= au0;
+                const float aPERC = sl - (aSUZ3 + au0);
+                gp[P_PERC] += aPERC * k.wPb;
+                a[3] = U;
+                a[4] = sl;
+            }
+            const float a2 = a[2];
+            const float s2_ = c.kap * a2;
+            const float ae0 = c.me * (U - s2_);
+            const float s1_ = s2_ + ae0;
+            const float w = U - s1_;
+            a[2] = s1_ + c.rho * w;
+            ats = s1_ + c.sw * w;
+            // soil gp lines
+            const float aef0 = a2 * k.cE;
+            float aq = aef0;
+            if (BETAET) {
+                aq = aef0 * k.dq;
+                gp[P_BETAET] += aef0 * k.db;
+            }
+            const float alpfc = -aq * k.qlp;
+            gp[P_LP] += alpfc * k.FC;
+            gp[P_FC] += alpfc * k.LP;
+            gp[P_FC] -= ae0;
+            const float asw0 = w * k.crt;
+            gp[P_BETA] += asw0 * k.dbr;
+            const float ar = asw0 * k.dr;
+            gp[P_FC] += -ar * k.rFC;
+        }
+        const float t = c.mts * (ats - a[1]);
+        gp[P_CWH] -= t * k.SP3;
+        const float mw2 = a[1] + t;
+        const float sp2 = a[0] - t * c.cwh;
+        const float x = sp2 - mw2;                    // arefr
+        const float mw1 = mw2 + x * c.wr;
+        const float arp = x * k.kr;
+        const float acc = arp * k.dT2;
+        gp[P_CFR] += acc * k.CFMAX;
+        gp[P_CFMAX] += acc * k.CFR;
+        float aTTe = arp * k.cc;
+        const float y = mw1 - sp2;                    // amelt
+        const float amp = y * k.km;
+        gp[P_CFMAX] += amp * k.dT;
+        aTTe -= amp * k.CFMAX;
+        gp[P_TT] += aTTe;                             // (HBV 1.0: TTe = TT)
+        a[1] = mw1;
+        a[0] = sp2 + y * c.wm;
+    }
 };
 
 } // namespace hbvx

@@ -2,6 +2,9 @@
 #include "hbvx_host.h"
 #include "hbv_chunked.h"
 
+#include <algorithm>
+#include <atomic>
+
 using namespace hbvx;
 using namespace hbvx_host;
 
@@ -29,22 +32,60 @@ bool hbvx_host::chunked_applicable(const hbvx_desc *d)
 
 static int np_of(const hbvx_desc *d) { return d->n_param; }
 
+// Whether the descriptor admits the one-pass static adjoint (hbv_chunked.h, k_bwd_chunk_onepass): HBV 1.0 with every
+// parameter static.  (The call must also have no learned ensemble weights and no forcing gradient; the workspace is
+// sized on the descriptor's model and parameters alone, so that its size does not depend on those or on the knob.)
+static bool onepass_admitted(const hbvx_desc *d)
+{
+    return d->model == HBVX_MODEL_HBV10 && (d->n_param == 12 || d->n_param == 13) && count_dyn(d) == 0;
+}
+
+// per-chunk rows of static-gradient partials: the two-pass sweep's NP, or the one-pass form's G_c and g0_c
+static int gpart_rows(const hbvx_desc *d)
+{
+    const int np = np_of(d);
+    return onepass_admitted(d) ? std::max(np, onepass_rows(np)) : np;
+}
+
 extern "C" uint64_t hbvx_backward_workspace_bytes(const hbvx_desc *d)
 {
     if (!d || d->T <= 0 || d->B <= 0 || d->M <= 0 || !chunked_applicable(d)) return 0;
     const int C = chunk_days();
     const uint64_t nchunk = (uint64_t)(d->T + C - 1) / C;
-    return nchunk * (uint64_t)d->B * (uint64_t)d->M * (uint64_t)(35 + np_of(d)) * sizeof(float);
+    return nchunk * (uint64_t)d->B * (uint64_t)d->M * (uint64_t)(35 + gpart_rows(d)) * sizeof(float);
 }
 
+// Which form of the time-parallel adjoint the last chunked call ran: 1 one-pass, 2 two-pass (0: none yet).
+// hbvx_last_dispatch(1) says "chunked" for both.
+static std::atomic<int> g_chunk_form{0};
+extern "C" int hbvx_chunk_form(void) { return g_chunk_form.load(); }
+
 template <int MODEL, bool BETAET, int DYN, bool GFULL>
-static hipError_t launch_chunked_t(const ChunkArgs &a, hipStream_t st)
+static hipError_t launch_chunked_t(const ChunkArgs &a, hipStream_t st, bool onepass)
 {
     const hbvx_desc &d = a.d;
     const int bpw = 64 >> a.lgMp;
     const int64_t N = (int64_t)d.B * d.M;
     (void)bpw;
     dim3 g2((unsigned)(8 * a.per_xcd * a.nchunk));      // XCD-aware 1-D block map (hbv_chunked.h::chunk_block)
+    if constexpr (MODEL == MODEL_HBV10 && DYN == 0) {
+        if (onepass) {   // static parameters only: the trajectory is read once (hbv_chunked.h, k_bwd_chunk_onepass)
+            g_chunk_form = 1;
+            hipLaunchKernelGGL((k_bwd_chunk_onepass<BETAET, GFULL>), g2, dim3(64), 0, st, a);
+            hipLaunchKernelGGL(k_bwd_chunk_scan, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, a);
+            store_gate(&a.io, st);
+            const int ngroup = (a.nchunk + ONEPASS_GROUP - 1) / ONEPASS_GROUP;
+            hipLaunchKernelGGL((k_bwd_chunk_fold<ChunkNP<MODEL, BETAET>::value>),
+                               dim3((unsigned)((N + 255) / 256), (unsigned)ngroup), dim3(256), 0, st, a);
+            ChunkArgs r = a;            // the group partials, in the maps' rows (hbv_chunked.h, B4 of the one-pass form)
+            r.gpart = a.phi;
+            r.nchunk = ngroup;
+            hipLaunchKernelGGL(k_bwd_chunk_reduce, dim3((unsigned)((N + 255) / 256), d.n_param), dim3(256), 0, st,
+                               r, d.n_param);
+            return hipGetLastError();
+        }
+    }
+    g_chunk_form = 2;
     // the two slot lists users actually run get compile-time slots (hbv_chunked.h::SlotCombo)
     int sc = 0;
     const bool mu = d.muwts != nullptr;     // (the compiled slot combos have no MU instance: the slot-list form below)
@@ -108,9 +149,9 @@ static hipError_t launch_chunked_t(const ChunkArgs &a, hipStream_t st)
 }
 
 template <int DYN, bool GFULL>
-static hipError_t launch_chunked_v(const hbvx_desc *d, const ChunkArgs &a, hipStream_t st)
+static hipError_t launch_chunked_v(const hbvx_desc *d, const ChunkArgs &a, hipStream_t st, bool onepass = false)
 {
-    return with_model(d, [&](auto m, auto be) { return launch_chunked_t<m, be, DYN, GFULL>(a, st); });
+    return with_model(d, [&](auto m, auto be) { return launch_chunked_t<m, be, DYN, GFULL>(a, st, onepass); });
 }
 
 static hipError_t launch_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, hipStream_t st)
@@ -143,7 +184,9 @@ static hipError_t launch_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, hipS
                  d->p[i].dyn_t_stride == d->p[0].dyn_t_stride && d->p[i].dyn_b_stride == d->p[0].dyn_b_stride;
     if (alldyn) return gfull ? launch_chunked_v<3, true>(d, a, st) : launch_chunked_v<3, false>(d, a, st);
     if (ndyn > 0) return gfull ? launch_chunked_v<2, true>(d, a, st) : launch_chunked_v<2, false>(d, a, st);
-    return gfull ? launch_chunked_v<0, true>(d, a, st) : launch_chunked_v<0, false>(d, a, st);
+    // HBVX_CHUNK_ONEPASS=0 (test / tool knob): the two-pass form where the one-pass one would run
+    const bool onepass = onepass_admitted(d) && !d->muwts && !io->grad_x && env_int("HBVX_CHUNK_ONEPASS", 1) != 0;
+    return gfull ? launch_chunked_v<0, true>(d, a, st, onepass) : launch_chunked_v<0, false>(d, a, st, onepass);
 }
 
 bool hbvx_host::try_bwd_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc)
