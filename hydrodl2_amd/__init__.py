@@ -6,7 +6,9 @@ routing, forward and adjoint, as hand-written HIP kernels for gfx950 behind the
 C ABI of include/hbvx.h.  See DESIGN.md.
 """
 from hydrodl2_amd.api import available_models, available_modules, load_model, load_module
+from hydrodl2_amd.sensitivity import jvp_batch, parameter_jacobian
 
 __version__ = "0.1.0"
 
-__all__ = ["__version__", "available_models", "available_modules", "load_model", "load_module"]
+__all__ = ["__version__", "available_models", "available_modules", "load_model", "load_module", "jvp_batch",
+           "parameter_jacobian"]

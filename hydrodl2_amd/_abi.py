@@ -84,6 +84,15 @@ class TanIO(C.Structure):
                 ("tan_flux", _fp), ("tan_state_out", _fp), ("n_flux", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class TanBatch(C.Structure):
+    """hbvx_tan_batch: the tangents of a forward-mode call over n_dir directions (include/hbvx.h)."""
+    _fields_ = [("n_dir", C.c_int32), ("n_flux", C.c_int32), ("flux_mask", C.c_uint32), ("dyn_t0", C.c_int32),
+                ("x", _fp), ("x_d_stride", C.c_int64), ("muwts", _fp), ("mu_d_stride", C.c_int64),
+                ("state_in", _fp), ("state_d_stride", C.c_int64), ("p", ParamTan * MAX_PARAM),
+                ("dyn_d_stride", C.c_int64 * MAX_PARAM), ("sta_d_stride", C.c_int64 * MAX_PARAM),
+                ("tan_flux", _fp), ("tan_state_out", _fp)]
+
+
 class RouteDesc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("T", C.c_int32), ("B", C.c_int32),
                 ("S", C.c_int32), ("L", C.c_int32), ("raw_sigmoid", C.c_int32),
@@ -120,7 +129,8 @@ EXPORTS = ["hbvx_zero", "hbvx_zero_except", "hbvx_preferred_traj_layout", "hbvx_
 # Exports a library may lack (the CPU restatement under oracle/ has only the calls above); a call that needs one raises
 # HbvxError naming it.
 OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forward_tangent", "hbvx_route_tangent",
-                    "hbvx_bfi_tangent", "hbvx_lstm_tangent"]
+                    "hbvx_bfi_tangent", "hbvx_lstm_tangent", "hbvx_forward_tangent_batch", "hbvx_route_tangent_batch",
+                    "hbvx_bfi_tangent_batch"]
 
 
 class HbvxError(RuntimeError):
@@ -219,6 +229,19 @@ class Library:
         if "hbvx_bfi_tangent" not in self.missing:
             d.hbvx_bfi_tangent.restype = C.c_int
             d.hbvx_bfi_tangent.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_float, _fp, C.c_void_p]
+        if "hbvx_forward_tangent_batch" not in self.missing:
+            d.hbvx_forward_tangent_batch.restype = C.c_int
+            d.hbvx_forward_tangent_batch.argtypes = [C.POINTER(Desc), C.POINTER(TanBatch), C.c_void_p]
+            if d.hbvx_sizeof(8) != C.sizeof(TanBatch):
+                raise HbvxError(f"{path}: layout mismatch for TanBatch: {d.hbvx_sizeof(8)} != {C.sizeof(TanBatch)}")
+        if "hbvx_route_tangent_batch" not in self.missing:
+            d.hbvx_route_tangent_batch.restype = C.c_int
+            d.hbvx_route_tangent_batch.argtypes = [C.POINTER(RouteDesc), C.c_int32, _fp, _fp, _fp, C.c_int64, _fp, _fp,
+                                                   C.c_int64, _fp, C.c_void_p]
+        if "hbvx_bfi_tangent_batch" not in self.missing:
+            d.hbvx_bfi_tangent_batch.restype = C.c_int
+            d.hbvx_bfi_tangent_batch.argtypes = [C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_int64,
+                                                 C.c_float, _fp, C.c_void_p]
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -345,6 +368,23 @@ class Library:
         self.require("hbvx_bfi_tangent")
         self._check(self.dll.hbvx_bfi_tangent(T, B, qs, q2, qs_dot, q2_dot, C.c_float(nearzero), out,
                                               C.c_void_p(stream)), "hbvx_bfi_tangent")
+
+    def forward_tangent_batch(self, desc: Desc, tb: TanBatch, stream: int):
+        self.require("hbvx_forward_tangent_batch")
+        self._check(self.dll.hbvx_forward_tangent_batch(C.byref(desc), C.byref(tb), C.c_void_p(stream)),
+                    "hbvx_forward_tangent_batch")
+
+    def route_tangent_batch(self, r: RouteDesc, n_dir: int, q: int, uh: int, q_dot, q_dot_ds: int, ra_dot, rb_dot,
+                            r_ds: int, q_rout_dot: int, stream: int):
+        self.require("hbvx_route_tangent_batch")
+        self._check(self.dll.hbvx_route_tangent_batch(C.byref(r), n_dir, q, uh, q_dot, q_dot_ds, ra_dot, rb_dot, r_ds,
+                                                      q_rout_dot, C.c_void_p(stream)), "hbvx_route_tangent_batch")
+
+    def bfi_tangent_batch(self, T: int, B: int, n_dir: int, qs: int, q2: int, qs_dot, q2_dot, dot_ds: int,
+                          nearzero: float, out: int, stream: int):
+        self.require("hbvx_bfi_tangent_batch")
+        self._check(self.dll.hbvx_bfi_tangent_batch(T, B, n_dir, qs, q2, qs_dot, q2_dot, dot_ds, C.c_float(nearzero),
+                                                    out, C.c_void_p(stream)), "hbvx_bfi_tangent_batch")
 
     def lstm_check(self, r: LstmDesc, ws, stream: int):
         self._check(self.dll.hbvx_lstm_check(C.byref(r), ws, C.c_void_p(stream)), "hbvx_lstm_check")

@@ -12,11 +12,13 @@ only; every arithmetic step of the path runs in the HIP library.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as _C
 from dataclasses import dataclass, field
 import functools
 import os
 import struct
+import threading
 from typing import List, NamedTuple, Optional, Sequence
 
 import torch
@@ -511,6 +513,38 @@ class _NoCtx:
         pass
 
 
+class PathRecord(NamedTuple):
+    """What one call of the path worked on and produced: the inputs hbv_tangent_batch differentiates along."""
+    cfg: StepConfig
+    x: torch.Tensor
+    state_in: Optional[torch.Tensor]
+    muwts: Optional[torch.Tensor]
+    ac: Optional[torch.Tensor]
+    elev: Optional[torch.Tensor]
+    ptensors: tuple
+    flux: Optional[torch.Tensor]
+    uh: Optional[torch.Tensor]
+    routed: Optional[torch.Tensor]
+    state_out: torch.Tensor
+
+
+# sensitivity.jvp_batch runs the primal through the module's own forward (warm-up pass, dy_drop draws, caches and
+# all) and then needs what each call of the path worked on: inside `record_paths()` every _hbv_forward of THIS thread
+# appends its PathRecord to the list the context manager hands out (other threads' calls are not seen).
+_TAP = threading.local()
+
+
+@contextlib.contextmanager
+def record_paths():
+    """with record_paths() as records: ... -- the PathRecords of the path calls this thread makes inside the block."""
+    outer = getattr(_TAP, "records", None)
+    _TAP.records = records = []
+    try:
+        yield records
+    finally:
+        _TAP.records = outer
+
+
 def _hbv_forward(ctx, cfg: StepConfig, x, state_in, muwts, ac, elev, ptensors):
     lib = get_library()
     _check_tensor(lib, x, "x_phy")
@@ -598,6 +632,9 @@ def _hbv_forward(ctx, cfg: StepConfig, x, state_in, muwts, ac, elev, ptensors):
     rrows = tuple(routed.unsqueeze(-1).unbind(0)) if routed is not None else ()
     rows = tuple(flux.unsqueeze(-1).unbind(0)) if flux is not None else ()
     ctx.n_routed = len(rrows)
+    tap = getattr(_TAP, "records", None)
+    if tap is not None:
+        tap.append(PathRecord(cfg, x, state_in, muwts, ac, elev, tuple(ptensors), flux, uh, routed, state_out))
     return (state_out, traj, layout, bfi) + rrows + rows
 
 
@@ -826,6 +863,131 @@ def _hbv_tangent(ctx, x_t, s_t, mu_t, ac_t, elev_t, p_t):
     rrows = tuple(troute.unsqueeze(-1).unbind(0)) if troute is not None else ()
     rows = tuple(tflux.unsqueeze(-1).unbind(0)) if tflux is not None else ()
     return (tstate if ctx.state_tangent else None, None, None, tbfi) + rrows + rows
+
+
+class BatchOut(NamedTuple):
+    """Tangents of one call of the path along D directions.  `flux` [D,n_sel,T,B]: the series of `flux_mask` in
+    ascending order; `routed` [D,S,T,B]; `bfi` [D,B]; `state_out` [D,5,B,M] (None: all zero, nothing was launched)."""
+    flux: Optional[torch.Tensor]
+    routed: Optional[torch.Tensor]
+    bfi: Optional[torch.Tensor]
+    state_out: Optional[torch.Tensor]
+
+
+def _batch_source(p: torch.Tensor, t: torch.Tensor, off: int):
+    """Where element `off` of parameter tensor `p` lies in its batched tangent `t`: (element offset, per-direction
+    stride) or None when the tangent holds nothing for it.  `t` is full ([D, *p.shape]) or, for a [T,B,W] tensor,
+    compact ([D,B,W]: the full tangent that is zero everywhere but in row T-1)."""
+    if tuple(t.shape[1:]) == tuple(p.shape):
+        return off, p.numel()
+    row = p[0].numel()
+    r, rem = divmod(off, row)
+    return (rem, row) if r == p.shape[0] - 1 else None
+
+
+def hbv_tangent_batch(rec: PathRecord, D: int, x_t=None, mu_t=None, s_t=None, p_t=(), flux_mask: int = 0,
+                      n_routed: int = 0, want_bfi: bool = False) -> BatchOut:
+    """Forward-mode derivative of one call of the path along D directions at once: hbvx_forward_tangent_batch,
+    hbvx_route_tangent_batch and hbvx_bfi_tangent_batch on what the forward worked on (`rec`).
+
+    x_t [D, *x.shape], mu_t [D, *muwts.shape], s_t [D,5,B,M], p_t: one tangent per parameter tensor, full or compact
+    (_batch_source); None: zero.  Only the flux series of `flux_mask` (bits: enum hbvx_flux) are computed and stored,
+    the leading `n_routed` of the four runoff series are routed (their bits must be set), `want_bfi` needs all four
+    routed or, without routing, Qsim and Q2."""
+    lib = get_library()
+    cfg = rec.cfg
+    x, ptensors = rec.x, rec.ptensors
+    dev = x.device
+    T, B, M = cfg.T, cfg.B, cfg.M
+    stream = _stream_of(lib, x)
+    tb = _abi.TanBatch()
+    tb.n_dir, tb.n_flux, tb.flux_mask = D, cfg.n_flux, flux_mask
+    keep = []                   # the tangent buffers the launch reads: alive until it is enqueued
+    if x_t is not None:
+        xt = x_t
+        if tuple(xt.stride()[1:]) != tuple(x.stride()):
+            span = sum((n - 1) * st for n, st in zip(x.shape, x.stride())) + 1
+            xt = torch.empty(D * span, dtype=x.dtype, device=dev).as_strided((D,) + tuple(x.shape),
+                                                                              (span,) + tuple(x.stride()))
+            xt.copy_(x_t)
+        keep.append(xt)
+        tb.x, tb.x_d_stride = _ptr(xt, cfg.t0 * x.stride(0)), xt.stride(0)
+    if mu_t is not None and rec.muwts is not None:
+        mt = mu_t.contiguous()
+        keep.append(mt)
+        tb.muwts, tb.mu_d_stride = _ptr(mt, _mu_t0(cfg) * B * M), mt.stride(0)
+    if s_t is not None and rec.state_in is not None:
+        stt = s_t.contiguous()
+        keep.append(stt)
+        tb.state_in, tb.state_d_stride = _ptr(stt), 5 * B * M
+    pts = [None if t is None else t.contiguous() for t in p_t]
+    pts += [None] * (len(ptensors) - len(pts))
+    keep += pts
+    dyn_t0 = None
+    for ps in cfg.params:
+        g = tb.p[ps.slot]
+        t = pts[ps.tensor_idx]
+        src = None if t is None else _batch_source(ptensors[ps.tensor_idx], t, ps.sta_off)
+        if src is not None:
+            g.sta, g.sta_b_stride, tb.sta_d_stride[ps.slot] = _ptr(t, src[0]), ps.sta_bs, src[1]
+        t = pts[ps.dyn_tensor_idx] if ps.dyn_off >= 0 else None
+        if t is None:
+            continue
+        p = ptensors[ps.dyn_tensor_idx]
+        if tuple(t.shape[1:]) == tuple(p.shape):
+            off, ds, t0 = ps.dyn_off, p.numel(), 0
+        else:
+            # compact: its one row is the tensor's last, day (T_total - 1 - first row of the call) of this call
+            row = p[0].numel()
+            first, col = divmod(ps.dyn_off, row)
+            t0 = p.shape[0] - 1 - first
+            if t0 != T - 1:
+                raise ValueError("compact parameter tangents need a call that ends at the tensor's last row")
+            off, ds = col, row
+        if dyn_t0 is not None and dyn_t0 != t0:
+            raise ValueError("full and compact tangents cannot be mixed over dynamic parameter tensors")
+        dyn_t0 = t0
+        g.dyn, tb.dyn_d_stride[ps.slot] = _ptr(t, off), ds
+        g.dyn_t_stride, g.dyn_b_stride = ps.dyn_ts, ps.dyn_bs
+    tb.dyn_t0 = dyn_t0 or 0
+    have_any = bool(tb.x or tb.muwts or tb.state_in or any(tb.p[ps.slot].sta or tb.p[ps.slot].dyn for ps in cfg.params))
+    rs = cfg.route if n_routed else None
+    rt = pts[rs.tensor_idx] if rs is not None else None
+    if not flux_mask and not have_any:
+        return BatchOut(None, None, None, None)     # a warm-up nothing moves: its state tangent is zero
+    nsel = bin(flux_mask).count("1")
+    tflux = _out((D, nsel, T, B), dev) if flux_mask else None
+    tstate = _out((D, 5, B, M), dev)
+    tb.tan_flux, tb.tan_state_out = _ptr(tflux), _ptr(tstate)
+    desc = _fill_desc(cfg, x, rec.state_in, rec.muwts, rec.ac, rec.elev, ptensors)
+    _call(lib, 'hbvx_forward_tangent_batch', lib.forward_tangent_batch, desc, tb, stream)
+
+    troute = None
+    if rs is not None:
+        if flux_mask & ((1 << n_routed) - 1) != (1 << n_routed) - 1:
+            raise ValueError("routing needs the leading runoff series in flux_mask")
+        r = _route_desc(cfg, ptensors, S=n_routed)
+        a = b = None
+        if rt is not None:
+            a = _batch_source(ptensors[rs.tensor_idx], rt, rs.a_off)
+            b = _batch_source(ptensors[rs.tensor_idx], rt, rs.b_off)
+        troute = _out((D, n_routed, T, B), dev)
+        _call(lib, 'hbvx_route_tangent_batch', lib.route_tangent_batch, r, D, _ptr(rec.flux), _ptr(rec.uh), _ptr(tflux),
+              nsel * T * B, _ptr(rt, a[0]) if a else None, _ptr(rt, b[0]) if b else None, a[1] if a else 0,
+              _ptr(troute), stream)
+    tbfi = None
+    if want_bfi:
+        if troute is not None:
+            src, tsrc, k2, tk2, ds = rec.routed, troute, 3, 3, n_routed * T * B
+        else:
+            src, tsrc, k2, ds = rec.flux, tflux, _abi.F_Q2, nsel * T * B
+            tk2 = bin(flux_mask & ((1 << k2) - 1)).count("1")
+        if tsrc is None or (troute is not None and n_routed != 4) or (troute is None and flux_mask & 9 != 9):
+            raise ValueError("BFI needs the streamflow and groundwater series")
+        tbfi = _out((D, B), dev)
+        _call(lib, 'hbvx_bfi_tangent_batch', lib.bfi_tangent_batch, T, B, D, _ptr(src), _ptr(src, k2 * T * B), _ptr(tsrc),
+              _ptr(tsrc, tk2 * T * B), ds, float(cfg.nearzero), _ptr(tbfi), stream)
+    return BatchOut(tflux, troute, tbfi, tstate)
 
 
 class PathOut(NamedTuple):

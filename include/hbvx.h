@@ -20,6 +20,9 @@
  *   hbvx_forward_tangent, hbvx_route_tangent, hbvx_bfi_tangent
  *                        replace torch.autograd.forward_ad over the same lines
  *                        (forward mode: one tangent direction per call).
+ *   hbvx_forward_tangent_batch, hbvx_route_tangent_batch, hbvx_bfi_tangent_batch
+ *                        the same over a leading direction axis: many directions on one
+ *                        primal (sensitivity series, per-basin Jacobians).
  *
  * Ownership: the caller allocates and owns every buffer; the library keeps no
  * state between calls and allocates nothing persistent.  All device work is
@@ -237,7 +240,8 @@ int hbvx_version(void);                 /* HBVX_ABI_VERSION */
 const char *hbvx_last_error(void);
 const char *hbvx_backend(void);         /* "hip:gfx950" or "cpu-oracle" */
 uint64_t hbvx_sizeof(int which);        /* 0 desc, 1 fwd_out, 2 bwd_io, 3 route_desc,
-                                           4 param_src, 5 param_grad, 6 gage_desc, 7 tan_io: layout check */
+                                           4 param_src, 5 param_grad, 6 gage_desc, 7 tan_io, 8 tan_batch:
+                                           layout check */
 /* Diagnostic: the kernel family that took the process's last hbvx_forward (direction 0) / hbvx_backward (1) call --
  * "pipe", "stream2", "stream", "tiled", "simple", "chunked", "ckpt-block:<family>", "ckpt-lds"; "oracle" in the CPU
  * restatement.  The parity tests assert that the family they mean to pin against the reference is the one that ran. */
@@ -367,6 +371,50 @@ int hbvx_route_tangent(const hbvx_route_desc *r, const float *q, const float *uh
  * S0 = sum_t qs; fixed-order sums. */
 int hbvx_bfi_tangent(int32_t T, int32_t B, const float *qs, const float *q2, const float *qs_dot, const float *q2_dot,
                      float nearzero, float *bfi_dot, void *stream);
+
+/* Several directions per call (optional exports; a library may lack them).  The same tangent-linear model as
+ * hbvx_forward_tangent, hbvx_route_tangent and hbvx_bfi_tangent over a leading direction axis of n_dir: one launch, the
+ * directions run as further workgroups beside each other on the SIMDs one direction leaves idle.  Direction d's
+ * arithmetic is the one-direction call's, operation for operation.
+ * Every input tangent is a base pointer plus a per-direction stride in elements (direction d at ptr + d * stride,
+ * addressed within a direction like the one-direction struct); a NULL pointer or a stride of 0 means a zero tangent.
+ * The static part of a parameter tangent may therefore point into a compact [n_dir,B,ny] array (sta_d_stride = B*ny,
+ * sta_b_stride = ny).  The dyn rows of the parameter tangents cover days dyn_t0 .. T-1 of the call (day t at row
+ * t - dyn_t0); on earlier days the dynamic tangents are zero.  dyn_t0 = 0 is a full [n_dir,T,B,ny] tensor; dyn_t0 = T-1
+ * with dyn pointing into the compact array is "only the last row moves".
+ * Outputs: only the series whose bit is set in flux_mask (bit k = enum hbvx_flux k, below n_flux) are computed and
+ * written, in ascending order of k: tan_flux [n_dir, n_sel, T, B], n_sel = popcount(flux_mask); all twelve series of
+ * 671 basins x 7300 days are 235 MB per direction, a streamflow Jacobian needs one.  tan_flux may be NULL when
+ * flux_mask is 0 (a state warm-up).  tan_state_out [n_dir,5,B,M] is required. */
+typedef struct hbvx_tan_batch {
+    int32_t n_dir;           /* >= 1 */
+    int32_t n_flux;          /* 11 (HBV 1.0) or 12: what flux_mask is checked against */
+    uint32_t flux_mask;
+    int32_t dyn_t0;          /* 0 .. T-1 */
+    const float *x;          /* tangent of desc->x, addressed like it within a direction, or NULL */
+    int64_t x_d_stride;
+    const float *muwts;      /* tangent of desc->muwts, addressed like it within a direction, or NULL */
+    int64_t mu_d_stride;
+    const float *state_in;   /* [n_dir,5,B,M] at state_d_stride per direction, or NULL */
+    int64_t state_d_stride;
+    hbvx_param_tan p[HBVX_MAX_PARAM];
+    int64_t dyn_d_stride[HBVX_MAX_PARAM];
+    int64_t sta_d_stride[HBVX_MAX_PARAM];
+    float *tan_flux;
+    float *tan_state_out;
+} hbvx_tan_batch;            /* hbvx_sizeof(8) */
+
+int hbvx_forward_tangent_batch(const hbvx_desc *d, const hbvx_tan_batch *tb, void *stream);
+/* hbvx_route_tangent over n_dir directions: q_dot direction d at q_dot + d * q_dot_d_stride ([S,T,B] within it; the
+ * leading S series of a tan_flux row), ra_dot / rb_dot of direction d at ra_dot + d * r_d_stride + b * r->r_stride;
+ * q_rout_dot [n_dir,S,T,B] (overwritten).  NULL or stride 0: zero tangent.  n_dir * S <= 65535. */
+int hbvx_route_tangent_batch(const hbvx_route_desc *r, int32_t n_dir, const float *q, const float *uh,
+                             const float *q_dot, int64_t q_dot_d_stride, const float *ra_dot, const float *rb_dot,
+                             int64_t r_d_stride, float *q_rout_dot, void *stream);
+/* hbvx_bfi_tangent over n_dir directions: qs_dot / q2_dot of direction d at ptr + d * dot_d_stride ([T,B] each);
+ * bfi_dot [n_dir,B] (overwritten).  n_dir <= 65535. */
+int hbvx_bfi_tangent_batch(int32_t T, int32_t B, int32_t n_dir, const float *qs, const float *q2, const float *qs_dot,
+                           const float *q2_dot, int64_t dot_d_stride, float nearzero, float *bfi_dot, void *stream);
 
 /* Zero `bytes` bytes at `ptr` (streaming non-temporal stores).  The autograd contract of the plug-in wants
  * gradient tensors shaped like the raw parameter tensor [T,B,ny] (hbv.py:211-246: static parameters read

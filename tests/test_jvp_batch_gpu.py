@@ -1,0 +1,382 @@
+"""GPU tier: many forward-mode directions per call (hydrodl2_amd.sensitivity.jvp_batch / parameter_jacobian on
+hbvx_forward_tangent_batch, hbvx_route_tangent_batch, hbvx_bfi_tangent_batch).  The fixtures, directions and
+tolerances are those of tests/test_jvp_gpu.py: the same quantity against the same references.
+
+(a) every JVP case with the three directions [v, 0, 2 v]: [0] against the reference's tangents
+    (tests/golden/jvp_<case>.npz), [1] exactly zero, [2] twice [0] (a tangent-linear chain scaled by two is exact in
+    binary floating point short of underflow);
+(b) D in {1, 5, 37} directions against D one-direction forward_ad calls (a tail group and several direction groups);
+    whether the two are bit-identical is recorded in the parity report, not asserted (two kernels, two schedules);
+(c) the primal outputs are bit-identical to a plain call and the generator advances as in one plain call;
+(d) parameter_jacobian contracted with the loss weights against row T-1 of the module's own backward gradient, at
+    twice the gradient tolerance of tests/abi_util.py (both sides are float32 kernels, each with its own error of that
+    size against the exact value), and the sum over all elements within test_dot_product_against_backward's bound;
+(e) eight one-hot columns at 256 basins x 16 x 730 days against float64 forward AD of oracle/hbv_torch_eager.py;
+(f) keys=('streamflow',) returns that key alone and allocates no [D,12,T,B] buffer; the compact and the full form of
+    the parameter tangent give equal tangents;
+(g) what is refused;
+(h) x_phy as a [T,B,3] view of a [B,T,3] buffer, with a tangent on it, gives the tangents of a contiguous x_phy;
+(i) a tangent on the cached states a run starts from against one-direction calls with dual states;
+(j) parameter_jacobian on a module that starts from cached states: the same Jacobian in one piece and in many, and
+    the module left where one plain call leaves it.
+"""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.autograd.forward_ad as fwAD
+
+from hydrodl2_amd.sensitivity import jvp_batch, one_hot_directions, parameter_jacobian
+
+from . import golden_cases as gc
+from . import golden_jvp as gj
+from . import synth
+from .abi_util import GRAD_ATOL_REL, GRAD_RTOL, REPORT, assert_grad_close, column_groups
+from .helpers import GOLDEN_DIR
+from .test_jvp_gpu import BFI_ATOL_REL, ROOT, TAN_FLOOR, _assert_tangent_close, _inputs, _model, _run_jvp
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+
+def _stack(dirs_list):
+    """[{name: array}, ...] -> {name: [D, ...] tensor on the GPU}"""
+    return {k: torch.from_numpy(np.stack([np.asarray(d[k], np.float32) for d in dirs_list])).to(DEV)
+            for k in dirs_list[0]}
+
+
+def _run_batch(name, tangents, keys=None, model=None):
+    """(primal outputs, {key: [D, ...] float64 numpy}) of jvp_batch on golden case `name`."""
+    spec = gc.CASES[name]
+    model = model or _model(name, torch.device(DEV))
+    if "torch_seed" in spec:
+        torch.manual_seed(spec["torch_seed"])
+    _, x_dict, params = _inputs(name, DEV)
+    out, tan = jvp_batch(model, x_dict, params, tangents, keys=keys)
+    return out, {k: v.detach().double().cpu().numpy() for k, v in tan.items()}
+
+
+def _compare_keys(label, name, got, want):
+    """test_jvp_gpu.test_jvp_matches_reference's comparison: got[k] against want[k] over the case's output keys."""
+    top = max(float(np.abs(want[k]).max()) for k in gj.output_keys(name) if k != "BFI")
+    for k in gj.output_keys(name):
+        b = np.asarray(want[k], np.float64)
+        if k == "BFI":
+            _assert_tangent_close(f"{label}:{k}", got[k], b, atol_rel=BFI_ATOL_REL)
+        else:
+            m = float(np.abs(b).max())
+            _assert_tangent_close(f"{label}:{k}", got[k], b, scale=m if m >= TAN_FLOOR * top else top)
+
+
+# (a) -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", gj.JVP_CASES)
+def test_three_directions_against_the_reference(name):
+    ref = np.load(os.path.join(GOLDEN_DIR, f"jvp_{name}.npz"))
+    v = gj.directions(name, gc.build_inputs(name))
+    tangents = _stack([v, {k: np.zeros_like(a) for k, a in v.items()}, {k: 2.0 * a for k, a in v.items()}])
+    _, tan = _run_batch(name, tangents)
+    assert set(tan) == set(gj.output_keys(name))
+    _compare_keys(f"jvpb:{name}", name, {k: t[0] for k, t in tan.items()}, {k: ref[f"tan/{k}"] for k in tan})
+    for k, t in tan.items():
+        assert t.shape[0] == 3 and t.shape[1:] == ref[f"tan/{k}"].shape, (k, t.shape)
+        assert not t[1].any(), f"{name}:{k}: zero direction gave {np.abs(t[1]).max():.3g}"
+        np.testing.assert_allclose(t[2], 2.0 * t[0], rtol=1e-6, atol=1e-35, err_msg=f"{name}:{k}")
+
+
+# (b) -----------------------------------------------------------------------------------------------------------------
+_SINGLE = {}
+
+
+def _direction(name, d):
+    """Direction d of case `name`: the fixture's streams on another seed."""
+    inp = gc.build_inputs(name)
+    spec = gc.CASES[name]
+    return {k: synth.normalish(inp[k].shape, spec["seed"] + 1000 + d, gj.JVP_STREAMS[k])
+            for k in gj.directions(name, inp)}
+
+
+def _single(name, d):
+    if (name, d) not in _SINGLE:
+        _SINGLE[name, d] = _run_jvp(name, _direction(name, d))[1]
+    return _SINGLE[name, d]
+
+
+@pytest.mark.parametrize("D", [1, 5, 37])
+@pytest.mark.parametrize("name", ["hbv_dyn2_drop", "hbv_muwts_warmup", "hbv_m3_xgrad", "hbv2_dyn3_routing",
+                                  "hbv11p_dyn_all"])
+def test_batch_against_one_direction_calls(name, D):
+    _, tan = _run_batch(name, _stack([_direction(name, d) for d in range(D)]))
+    n_diff = size = 0
+    worst = 0.0
+    for d in range(D):
+        want = _single(name, d)
+        _compare_keys(f"jvpb-1dir:{name}:D{D}:d{d}", name, {k: t[d] for k, t in tan.items()}, want)
+        for k in want:
+            diff = np.abs(tan[k][d] - want[k])
+            n_diff += int((diff != 0).sum())
+            size += diff.size
+            worst = max(worst, float(diff.max()))
+    REPORT.append((f"jvpb-bit-identical:{name}:D{D}:{'yes' if n_diff == 0 else 'no'}", worst, 0.0, n_diff, size))
+
+
+# (c) -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["hbv_warmup_states", "hbv_dyn2_drop", "hbv_muwts", "hbv2_dyn3_routing"])
+def test_primal_is_a_plain_call(name):
+    spec = gc.CASES[name]
+    v = gj.directions(name, gc.build_inputs(name))
+    out, _ = _run_batch(name, _stack([v, v]))
+    after_batch = torch.get_rng_state()
+    model = _model(name, torch.device(DEV))
+    if "torch_seed" in spec:
+        torch.manual_seed(spec["torch_seed"])
+    _, x_dict, params = _inputs(name, DEV)
+    with torch.no_grad():
+        plain = model(x_dict, params)
+    assert set(out) == set(plain)
+    for k in plain:
+        np.testing.assert_array_equal(out[k].detach().cpu().numpy(), plain[k].cpu().numpy(), err_msg=f"{name}:{k}")
+    if "torch_seed" in spec:
+        assert torch.equal(after_batch, torch.get_rng_state()), f"{name}: generator not advanced as by one plain call"
+
+
+# (d) -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["hbv_long_static", "hbv2_long_static_cold", "hbv_static_m16"])
+def test_jacobian_against_backward(name):
+    spec = gc.CASES[name]
+    dev = torch.device(DEV)
+    model = _model(name, dev)
+    _, x_dict, params = _inputs(name, DEV)
+    J = parameter_jacobian(model, x_dict, params, max_directions=48)
+    cols = J["columns"]
+    Js = J["streamflow"].double().cpu().numpy()
+    assert Js.shape == (spec["T"], spec["B"], len(cols))
+    w = gc.loss_weight(name, "streamflow", Js.shape[:2] + (1,)).astype(np.float64)[..., 0]
+    got = np.einsum("tb,tbc->bc", w, Js)
+
+    model = _model(name, dev)
+    _, x_dict, params = _inputs(name, DEV, requires_grad=True)
+    out = model(x_dict, params)
+    (torch.from_numpy(w.astype(np.float32)).to(dev).unsqueeze(-1) * out["streamflow"]).sum().backward()
+    if isinstance(params, tuple):
+        row = params[1].grad.double().cpu().numpy()
+    else:
+        row = params.grad.double().cpu().numpy()[-1]
+    want = row[:, cols]
+    groups = column_groups(row.shape[-1], spec["config"]["nmul"])[cols]
+    # twice the gradient tolerance (module docstring): rtol and the per-group absolute part both doubled; the routing
+    # groups keep their ratio to the others inside assert_grad_close (1e-4 -> 2e-4)
+    assert_grad_close(f"jacobian:{name}", got, want, groups=groups, rtol=2 * GRAD_RTOL, atol_rel=2 * GRAD_ATOL_REL)
+    lhs, rhs = float(got.sum()), float(want.sum())
+    bound = 1e-4 * np.sqrt(float((w ** 2).sum())) * np.sqrt(float((Js ** 2).sum()))
+    REPORT.append((f"jacobian-sum:{name}", abs(lhs - rhs), abs(lhs - rhs) / bound, 0, 1))
+    assert abs(lhs - rhs) <= bound, (lhs, rhs, bound)
+
+
+# (e) -----------------------------------------------------------------------------------------------------------------
+def test_one_hot_columns_at_many_wavefronts_against_float64_eager():
+    spec = importlib.util.spec_from_file_location("hbv_torch_eager", os.path.join(ROOT, "oracle", "hbv_torch_eager.py"))
+    eager = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(eager)
+    import hydrodl2_amd
+    T, B, M, seed = 730, 256, 16, 61
+    ny = 12 * M + 2
+    x = torch.from_numpy(synth.forcing(T, B, seed)).cuda()
+    p = torch.from_numpy(synth.raw_parameters(T, B, ny, seed)).cuda()
+    cols = sorted(np.random.default_rng(20261).choice(ny, size=8, replace=False).tolist())
+    model = hydrodl2_amd.load_model("hbv", "Hbv")({"nmul": M, "dynamic_params": {"Hbv": []}}, torch.device("cuda"))
+    keys = [k for k in model.flux_names if k != "PET_hydro"]
+    _, tan = jvp_batch(model, {"x_phy": x}, p, {"parameters": one_hot_directions(cols, B, ny, x.device)}, keys=keys)
+    got = {k: v.double().cpu().numpy() for k, v in tan.items()}
+    old_dtype, old_dev = torch.get_default_dtype(), torch.get_default_device()
+    torch.set_default_dtype(torch.float64)
+    torch.set_default_device("cuda")
+    try:
+        for c, col in enumerate(cols):
+            d = torch.zeros((T, B, ny), dtype=torch.float64)
+            d[T - 1, :, col] = 1.0
+            with fwAD.dual_level():
+                ref = eager.hbv_eager(x.double(), fwAD.make_dual(p.double(), d), M, dynamic=())
+                want = {k: fwAD.unpack_dual(v).tangent.cpu().numpy() for k, v in ref.items() if k in got}
+            assert set(want) == set(got)
+            for k in got:
+                _assert_tangent_close(f"jvpb-f64:col{col}:{k}", got[k][c], want[k])
+    finally:
+        torch.set_default_dtype(old_dtype)
+        torch.set_default_device(old_dev)
+
+
+# (f) -----------------------------------------------------------------------------------------------------------------
+def test_one_key_costs_one_series_and_compact_equals_full():
+    name = "hbv_long_static"
+    spec = gc.CASES[name]
+    T, B = spec["T"], spec["B"]
+    D = 24
+    inp = gc.build_inputs(name)
+    ny = inp["parameters"].shape[-1]
+    compact = synth.normalish((D, B, ny), spec["seed"], gj.JVP_STREAMS["parameters"])
+    full = np.zeros((D,) + inp["parameters"].shape, np.float32)
+    full[:, T - 1] = compact
+    model = _model(name, torch.device(DEV))
+    tc = torch.from_numpy(compact).to(DEV)
+    tf = torch.from_numpy(full).to(DEV)
+    _, x_dict, params = _inputs(name, DEV)
+    jvp_batch(model, x_dict, params, {"parameters": tc}, keys=("streamflow",))         # warm the allocator's pools
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    out, tan = jvp_batch(model, x_dict, params, {"parameters": tc}, keys=("streamflow",))
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - base
+    assert list(tan) == ["streamflow"] and tan["streamflow"].shape == (D, T, B, 1)
+    all_series = D * 11 * T * B * 4                  # what the [D,n_flux,T,B] buffer of a full-key call takes alone
+    REPORT.append((f"jvpb-memory:{name}:peak-bytes-of-{all_series}", float(peak), peak / all_series, 0, 1))
+    # needed: one raw and one routed series per direction and the primal call's own buffers, a fifth of that
+    assert peak < all_series, (peak, all_series)
+    _, t_all = jvp_batch(model, x_dict, params, {"parameters": tc})
+    assert set(t_all) == set(gj.output_keys(name))
+    assert torch.equal(t_all["streamflow"], tan["streamflow"])
+    _, t_full = jvp_batch(model, x_dict, params, {"parameters": tf})
+    for k in t_all:
+        assert torch.equal(t_all[k], t_full[k]), k
+
+
+def test_compact_form_with_dynamic_parameters_and_warm_up():
+    """The compact form IS the full tensor that is zero but in row T-1: with dynamic parameters (their last-row tangent
+    only) and with a state warm-up (which reads row warm_up - 1: no parameter tangent)."""
+    for name in ("hbv_dyn2_drop", "hbv_warmup_states", "hbv2_dyn3_routing"):
+        spec = gc.CASES[name]
+        inp = gc.build_inputs(name)
+        two = spec["model"] == "Hbv_2"
+        key = "p_dyn" if two else "parameters"
+        T = inp[key].shape[0]
+        D = 3
+        compact = synth.normalish((D,) + inp[key].shape[1:], spec["seed"], gj.JVP_STREAMS[key])
+        full = np.zeros((D,) + inp[key].shape, np.float32)
+        full[:, T - 1] = compact
+        _, a = _run_batch(name, {key: torch.from_numpy(compact).to(DEV)})
+        _, b = _run_batch(name, {key: torch.from_numpy(full).to(DEV)})
+        for k in a:
+            np.testing.assert_array_equal(a[k], b[k], err_msg=f"{name}:{k}")
+        assert np.abs(a["streamflow"]).max() > 0, name
+
+
+# (g) -----------------------------------------------------------------------------------------------------------------
+def test_refusals():
+    import hydrodl2_amd
+    from . import golden_mts as gm
+    dev = torch.device(DEV)
+    name = "hbv_static_m16"
+    v = gj.directions(name, gc.build_inputs(name))
+    _, x_dict, params = _inputs(name, DEV)
+    with pytest.raises(ValueError, match="forward-mode AD"):
+        jvp_batch(_model(name, dev, graph=True), x_dict, params, _stack([v]))
+    _, x2, p2 = _inputs("hbv2_static", DEV)
+    with pytest.raises(ValueError, match="ac_all"):
+        jvp_batch(_model("hbv2_static", dev), x2, p2, {"ac_all": torch.ones_like(x2["ac_all"]).unsqueeze(0)})
+    with pytest.raises(ValueError, match="elev_all"):
+        jvp_batch(_model("hbv2_static", dev), x2, p2, {"elev_all": torch.ones_like(x2["elev_all"]).unsqueeze(0)})
+    xd = {"x_phy": torch.zeros(8, 3, 3, device=dev)}
+    xt = {"x_phy": torch.ones(1, 8, 3, 3, device=dev)}
+    for cls in (hydrodl2_amd.load_model("hbv_adj", "HbvAdj"), hydrodl2_amd.load_model("hbv_2_hourly", "Hbv_2_hourly")):
+        with pytest.raises(NotImplementedError, match="forward-mode AD"):
+            jvp_batch(cls(None, dev), xd, torch.zeros(8, 3, 40, device=dev), xt)
+    low, high = gm.configs(next(iter(gm.CASES)))
+    mts = hydrodl2_amd.load_model("hbv_2_mts", "Hbv_2_mts")(low, high, dev)
+    with pytest.raises(NotImplementedError, match="forward-mode AD"):
+        jvp_batch(mts, xd, torch.zeros(8, 3, 40, device=dev), xt)
+    with pytest.raises(NotImplementedError, match="forward-mode AD"):
+        parameter_jacobian(mts, xd, torch.zeros(8, 3, 40, device=dev))
+    with pytest.raises(ValueError, match="dynamic parameter"):
+        _, xq, pq = _inputs("hbv_dyn2", DEV)
+        parameter_jacobian(_model("hbv_dyn2", dev), xq, pq, names=["parBETA"])
+
+
+# (h) -----------------------------------------------------------------------------------------------------------------
+def test_strided_forcings_with_a_forcing_tangent():
+    name = "hbv_m3_xgrad"
+    dirs = _stack([_direction(name, d) for d in range(3)])
+    model = _model(name, torch.device(DEV))
+    _, x_dict, params = _inputs(name, DEV)
+    _, want = jvp_batch(model, x_dict, params, dirs)
+    x = x_dict["x_phy"]
+    view = x.transpose(0, 1).contiguous().transpose(0, 1)
+    assert not view.is_contiguous() and torch.equal(view, x)
+    _, got = jvp_batch(model, dict(x_dict, x_phy=view), params, dirs)
+    for k in want:
+        assert torch.equal(got[k], want[k]), k
+
+
+# (i) -----------------------------------------------------------------------------------------------------------------
+def test_tangent_on_cached_states():
+    name = "hbv_static_m16"
+    spec = gc.CASES[name]
+    B, M, D = spec["B"], spec["config"]["nmul"], 3
+    dev = torch.device(DEV)
+    _, x_dict, params = _inputs(name, DEV)
+    first = _model(name, dev, cache_states=True)
+    first(x_dict, params)
+    states = tuple(s.clone() for s in first.states)          # where the next run starts
+    s_dirs = torch.from_numpy(synth.normalish((D, 5, B, M), spec["seed"], 75)).to(DEV)
+
+    model = _model(name, dev, cache_states=True)
+    model.load_states(states)
+    _, tan = jvp_batch(model, x_dict, params, {"states": s_dirs})
+    assert float(tan["streamflow"].abs().max()) > 0
+    for d in range(D):
+        one = _model(name, dev, cache_states=True)
+        with fwAD.dual_level():
+            one.states = tuple(fwAD.make_dual(states[k], s_dirs[d, k]) for k in range(5))
+            out = one(x_dict, params)
+            want = {}
+            for k in gj.output_keys(name):
+                prim, t = fwAD.unpack_dual(out[k])           # (PET_hydro carries none: the forcings have no tangent)
+                want[k] = (torch.zeros_like(prim) if t is None else t).double().cpu().numpy()
+        _compare_keys(f"jvpb-states:{name}:d{d}", name, {k: tan[k][d].double().cpu().numpy() for k in want}, want)
+    with pytest.raises(ValueError, match="states"):
+        jvp_batch(model, x_dict, params, {"states": s_dirs[:, :4]})
+
+
+# (j) -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["hbv_static_m16", "hbv2_static"])
+def test_jacobian_in_pieces_on_cached_states(name):
+    """Every call of a module with cache_states=True starts from the storages the call before left: a Jacobian built
+    piece by piece must differentiate ONE run, not a run per piece."""
+    dev = torch.device(DEV)
+    _, x_dict, params = _inputs(name, DEV)
+    first = _model(name, dev, cache_states=True)
+    first(x_dict, params)
+    states = tuple(s.clone() for s in first.states)
+
+    def module():
+        m = _model(name, dev, cache_states=True)
+        m.load_states(states)
+        return m
+    plain = module()
+    with torch.no_grad():
+        want_out = plain(x_dict, params)
+    whole_m, pieces_m = module(), module()
+    whole = parameter_jacobian(whole_m, x_dict, params, keys=("streamflow", "BFI"), max_directions=4096)
+    pieces = parameter_jacobian(pieces_m, x_dict, params, keys=("streamflow", "BFI"), max_directions=7)
+    C = len(whole["columns"])
+    assert C > 3 * 7 and pieces["columns"] == whole["columns"]
+    assert whole["BFI"].shape == (gc.CASES[name]["B"], C)
+    for k in ("streamflow", "BFI"):
+        assert torch.equal(pieces[k], whole[k]), k
+    assert float(whole["streamflow"][..., 8:].abs().max()) > 0
+    for m in (whole_m, pieces_m):
+        for a, b in zip(m.states, plain.states):
+            assert torch.equal(a, b)
+    # and it is the Jacobian of the run that starts from `states`: column 0 against a one-direction call
+    one = module()
+    d = torch.zeros_like(params[1] if isinstance(params, tuple) else params)
+    (d if isinstance(params, tuple) else d[-1])[:, whole["columns"][0]] = 1.0
+    with fwAD.dual_level():
+        dual = (params[0], fwAD.make_dual(params[1], d)) if isinstance(params, tuple) else fwAD.make_dual(params, d)
+        out = one(x_dict, dual)
+        t = fwAD.unpack_dual(out["streamflow"]).tangent
+        assert torch.equal(fwAD.unpack_dual(out["streamflow"]).primal, want_out["streamflow"])
+    _assert_tangent_close(f"jacobian-cached:{name}", whole["streamflow"][..., 0].double().cpu().numpy(),
+                          t[..., 0].double().cpu().numpy())
