@@ -130,7 +130,7 @@ EXPORTS = ["hbvx_zero", "hbvx_zero_except", "hbvx_preferred_traj_layout", "hbvx_
 # HbvxError naming it.
 OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forward_tangent", "hbvx_route_tangent",
                     "hbvx_bfi_tangent", "hbvx_lstm_tangent", "hbvx_forward_tangent_batch", "hbvx_route_tangent_batch",
-                    "hbvx_bfi_tangent_batch"]
+                    "hbvx_bfi_tangent_batch", "hbvx_lstm_tangent_batch", "hbvx_lstm_tangent_batch_workspace_bytes"]
 
 
 class HbvxError(RuntimeError):
@@ -218,6 +218,13 @@ class Library:
             d.hbvx_lstm_tangent.restype = C.c_int
             d.hbvx_lstm_tangent.argtypes = [C.POINTER(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
                                             C.c_void_p, C.c_uint64, C.c_void_p]
+        if "hbvx_lstm_tangent_batch" not in self.missing:
+            d.hbvx_lstm_tangent_batch.restype = C.c_int
+            d.hbvx_lstm_tangent_batch.argtypes = [C.POINTER(LstmDesc), C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                                  _fp, _fp, C.c_void_p, C.c_uint64, C.c_void_p]
+        if "hbvx_lstm_tangent_batch_workspace_bytes" not in self.missing:
+            d.hbvx_lstm_tangent_batch_workspace_bytes.restype = C.c_uint64
+            d.hbvx_lstm_tangent_batch_workspace_bytes.argtypes = [C.POINTER(LstmDesc), C.c_int32]
         if "hbvx_forward_tangent" not in self.missing:
             d.hbvx_forward_tangent.restype = C.c_int
             d.hbvx_forward_tangent.argtypes = [C.POINTER(Desc), C.POINTER(TanIO), C.c_void_p]
@@ -354,6 +361,17 @@ class Library:
         self.require("hbvx_lstm_tangent")
         self._check(self.dll.hbvx_lstm_tangent(C.byref(r), w_hh, gates, c0, c_all, gx_t, h0_t, c0_t, h_t, c_t_last, ws,
                                                C.c_uint64(ws_bytes), C.c_void_p(stream)), "hbvx_lstm_tangent")
+
+    def lstm_tangent_batch_workspace_bytes(self, r: LstmDesc, n_dir: int) -> int:
+        self.require("hbvx_lstm_tangent_batch_workspace_bytes")
+        return int(self.dll.hbvx_lstm_tangent_batch_workspace_bytes(C.byref(r), n_dir))
+
+    def lstm_tangent_batch(self, r: LstmDesc, n_dir: int, w_hh: int, gates: int, c0, c_all: int, gx_t: int, h0_t,
+                           c0_t, h_t: int, c_t_last, ws, ws_bytes: int, stream: int):
+        self.require("hbvx_lstm_tangent_batch")
+        self._check(self.dll.hbvx_lstm_tangent_batch(C.byref(r), n_dir, w_hh, gates, c0, c_all, gx_t, h0_t, c0_t, h_t,
+                                                     c_t_last, ws, C.c_uint64(ws_bytes), C.c_void_p(stream)),
+                    "hbvx_lstm_tangent_batch")
 
     def forward_tangent(self, desc: Desc, io: TanIO, stream: int):
         self.require("hbvx_forward_tangent")

@@ -38,9 +38,9 @@ __global__ void __launch_bounds__(256) k_lstm_arm(lstm_u4 *__restrict__ p, uint6
     }
 }
 
-static hipError_t lstm_prepare(const hbvx_lstm_desc *d, void *workspace, bool backward, hipStream_t st)
+static hipError_t lstm_prepare(const hbvx_lstm_desc *d, void *workspace, bool backward, hipStream_t st, int n_dir = 1)
 {
-    const uint64_t n16 = (lstm_counter_bytes(d) + lstm_slab_bytes(d, backward)) / 16;   // both multiples of 16
+    const uint64_t n16 = (lstm_counter_bytes(d) + n_dir * lstm_slab_bytes(d, backward)) / 16;   // both multiples of 16
     const uint64_t want = (n16 + 255) / 256;
     const unsigned grid = (unsigned)(want < 8192 ? (want ? want : 1) : 8192);
     hipLaunchKernelGGL(k_lstm_arm, dim3(grid), dim3(256), 0, st, (lstm_u4 *)workspace, n16, lstm_counter_bytes(d) / 16);
@@ -67,8 +67,10 @@ static int lstm_cu_count()
     return n_cu[dev];
 }
 
+// `nitem` units of work (row tiles; hbvx_lstm_tangent_batch: (direction, row tile) pairs) of `nwg` workgroups each;
+// a launch covers items a.tile0 ..
 template <typename K, typename A>
-static hipError_t launch_lstm(K kern, A a, int nwg, hipStream_t st)
+static hipError_t launch_lstm(K kern, A a, int nwg, hipStream_t st, int nitem)
 {
     const int n_cu = lstm_cu_count();
     // Residency: a launch never holds more workgroups than fit on the chip at once, so every partner
@@ -76,7 +78,7 @@ static hipError_t launch_lstm(K kern, A a, int nwg, hipStream_t st)
     // to three workgroups share a CU; the LDS request is sized so that exactly `wpc` fit: a batch that
     // fits one launch at one workgroup per CU gets a CU per workgroup, larger batches interleave two or
     // three row tiles per SIMD, which hides one tile's hand-off latency behind the others' MFMAs.
-    const int need = a.ntile * nwg;
+    const int need = nitem * nwg;
     int wpc = env_int("HBVX_LSTM_WGS_PER_CU", (need + n_cu - 1) / n_cu);
     wpc = wpc < 1 ? 1 : (wpc > 3 ? 3 : wpc);
     hipFuncAttributes fa;
@@ -86,19 +88,26 @@ static hipError_t launch_lstm(K kern, A a, int nwg, hipStream_t st)
     const int lds = total > (int)fa.sharedSizeBytes ? total - (int)fa.sharedSizeBytes : 0;
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
-    const int cap = n_cu * wpc / nwg > 0 ? n_cu * wpc / nwg : 1;       // row tiles one launch can hold
-    const int launches = (a.ntile + cap - 1) / cap;
-    const int per_launch = (a.ntile + launches - 1) / launches;        // balanced
-    for (int t0 = 0; t0 < a.ntile; t0 += per_launch) {
+    const int cap = n_cu * wpc / nwg > 0 ? n_cu * wpc / nwg : 1;       // items one launch can hold
+    const int launches = (nitem + cap - 1) / cap;
+    const int per_launch = (nitem + launches - 1) / launches;          // balanced
+    for (int t0 = 0; t0 < nitem; t0 += per_launch) {
         a.tile0 = t0;
-        const int nt = a.ntile - t0 < per_launch ? a.ntile - t0 : per_launch;
+        const int nt = nitem - t0 < per_launch ? nitem - t0 : per_launch;
         hipLaunchKernelGGL(kern, dim3(nt * nwg), dim3(256), lds, st, a);
     }
     return hipGetLastError();
 }
 
+template <typename K, typename A>
+static hipError_t launch_lstm(K kern, A a, int nwg, hipStream_t st)
+{
+    return launch_lstm(kern, a, nwg, st, a.ntile);
+}
+
 // The forward's (and the tangent's) workgroup form: 8 units per workgroup while twice the workgroups still fit one
 // launch at one per CU, else 16
+// (ntile: the units of work of the call -- (direction, row tile) pairs in hbvx_lstm_tangent_batch)
 static bool lstm_eight_units(const hbvx_lstm_desc *d, int ntile)
 {
     return env_int("HBVX_LSTM_UNITS", ntile * (d->H / 8) <= lstm_cu_count() ? 8 : 16) == 8;
@@ -204,6 +213,48 @@ extern "C" int hbvx_lstm_tangent(const hbvx_lstm_desc *d, const float *w_hh, con
         e = d->H == 64 ? launch_lstm(k_lstm_tan<64, 4>, a, 4, st)
           : d->H == 128 ? launch_lstm(k_lstm_tan<128, 4>, a, 8, st) : launch_lstm(k_lstm_tan<256, 4>, a, 16, st);
     if (e != hipSuccess) return hip_fail(e, "hbvx_lstm_tangent launch");
+    return 0;
+}
+
+extern "C" uint64_t hbvx_lstm_tangent_batch_workspace_bytes(const hbvx_lstm_desc *d, int32_t n_dir)
+{
+    if (!d || d->T <= 0 || d->B <= 0 || d->H <= 0 || n_dir < 1) return 0;
+    return lstm_counter_bytes(d) + (uint64_t)n_dir * lstm_slab_bytes(d, false);
+}
+
+extern "C" int hbvx_lstm_tangent_batch(const hbvx_lstm_desc *d, int32_t n_dir, const float *w_hh, const float *gates,
+                                       const float *c0, const float *c_all, const float *gx_t, const float *h0_t,
+                                       const float *c0_t, float *h_t, float *c_t_last, void *workspace,
+                                       uint64_t workspace_bytes, void *stream)
+{
+    int rc = check_lstm(d);
+    if (rc) return rc;
+    if (n_dir < 1) return fail(HBVX_E_SHAPE, "lstm n_dir must be at least 1");
+    if (!w_hh || !gates || !c_all || !gx_t || !h_t) return fail(HBVX_E_NULL, "lstm buffer is NULL");
+    const int64_t npair = (int64_t)n_dir * ((d->B + LSTM_ROWS - 1) / LSTM_ROWS);
+    // a launch's grid is pairs x H/8 workgroups at the most, counted in int
+    if (npair > INT32_MAX / 32) return fail(HBVX_E_SHAPE, "lstm n_dir x row tiles out of range");
+    if (!workspace || workspace_bytes < hbvx_lstm_tangent_batch_workspace_bytes(d, n_dir))
+        return fail(HBVX_E_NULL, "lstm workspace missing or too small");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = lstm_prepare(d, workspace, false, st, n_dir);
+    if (e != hipSuccess) return hip_fail(e, "hbvx_lstm_tangent_batch arm");
+    LstmTanArgs a{};
+    a.T = d->T; a.B = d->B; a.ntile = (d->B + LSTM_ROWS - 1) / LSTM_ROWS;
+    a.w_hh = w_hh; a.gx_t = gx_t; a.gates = gates; a.c_all = c_all; a.c0 = c0;
+    a.h0_t = h0_t; a.c0_t = c0_t; a.h_t = h_t; a.c_t_last = c_t_last;
+    a.cnt = (unsigned *)workspace;
+    a.xch = (float *)((char *)workspace + lstm_counter_bytes(d));
+    a.spin_limit = (unsigned)env_int("HBVX_LSTM_SPIN_LIMIT", (int)LSTM_SPIN_LIMIT);
+    a.drop_wg = env_int("HBVX_LSTM_DEBUG_DROP_WG", -1);
+    const int np = (int)npair;
+    if (lstm_eight_units(d, np))
+        e = d->H == 64 ? launch_lstm(k_lstm_dirs<64, 2>, a, 8, st, np)
+          : d->H == 128 ? launch_lstm(k_lstm_dirs<128, 2>, a, 16, st, np) : launch_lstm(k_lstm_dirs<256, 2>, a, 32, st, np);
+    else
+        e = d->H == 64 ? launch_lstm(k_lstm_dirs<64, 4>, a, 4, st, np)
+          : d->H == 128 ? launch_lstm(k_lstm_dirs<128, 4>, a, 8, st, np) : launch_lstm(k_lstm_dirs<256, 4>, a, 16, st, np);
+    if (e != hipSuccess) return hip_fail(e, "hbvx_lstm_tangent_batch launch");
     return 0;
 }
 

@@ -6,8 +6,11 @@ Marquardt calibration or the columns of an assimilation step want tens to hundre
 here they share one primal run and one launch of each tangent kernel (hbvx_forward_tangent_batch,
 hbvx_route_tangent_batch, hbvx_bfi_tangent_batch in include/hbvx.h).
 
-Out of scope: `torch.func.jvp` / `jacfwd` / vmap over `make_dual`, batched tangents through `SeqLSTM`, and the hourly,
-implicit and multi-timescale models.
+Directions that start upstream of the model -- on the inputs or weights of the parameter network -- come through
+`SeqLSTM.jvp_batch` (hydrodl2_amd/lstm.py), whose `[D,T,B,ny]` output is a full-form 'parameters' tangent here
+(examples/input_sensitivity.py).
+
+Out of scope: `torch.func.jvp` / `jacfwd` / vmap over `make_dual`, and the hourly, implicit and multi-timescale models.
 """
 from __future__ import annotations
 

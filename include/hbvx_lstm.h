@@ -88,6 +88,22 @@ int hbvx_lstm_tangent(const hbvx_lstm_desc *d, const float *w_hh, const float *g
                       const float *c_all, const float *gx_t, const float *h0_t, const float *c0_t,
                       float *h_t, float *c_t_last, void *workspace, uint64_t workspace_bytes, void *stream);
 
+/* hbvx_lstm_tangent along n_dir directions in one call, on one primal (w_hh, gates, c0, c_all are shared):
+ * gx_t [D,T,B,H,4], h0_t and c0_t [D,B,H] (NULL = zeros for every direction) -> h_t [D,T,B,H], c_t_last [D,B,H]
+ * (NULL = not wanted), D = n_dir, each dense.  Slice d of the outputs holds the bits hbvx_lstm_tangent gives for
+ * slice d of gx_t, h0_t, c0_t under the same HBVX_LSTM_UNITS: the unit of work is the pair (direction, row tile)
+ * instead of the row tile, with the arithmetic of a pair unchanged, so directions fill the SIMDs that one
+ * direction's row tiles leave idle.  Pairs are cut into launches by the residency rule above.
+ * Additive to ABI version 1.  The exchange slabs grow with n_dir, so the workspace has a size query of its own
+ * (0 for a descriptor without a size or n_dir < 1); hbvx_lstm_check reads this workspace like any other.  Refused
+ * before any device work: n_dir < 1, n_dir x ceil(B/16) above 2^26 - 1, and everything hbvx_lstm_tangent refuses.
+ * A time-out poisons h_t[d][T-1] and c_t_last[d] of the pairs that saw it. */
+uint64_t hbvx_lstm_tangent_batch_workspace_bytes(const hbvx_lstm_desc *d, int32_t n_dir);
+int hbvx_lstm_tangent_batch(const hbvx_lstm_desc *d, int32_t n_dir, const float *w_hh, const float *gates,
+                            const float *c0, const float *c_all, const float *gx_t, const float *h0_t,
+                            const float *c0_t, float *h_t, float *c_t_last, void *workspace,
+                            uint64_t workspace_bytes, void *stream);
+
 /* Synchronises `stream` and reports whether the last call that used `workspace` completed: the
  * workgroups of a row tile wait for each other with bounded spins; a time-out (the partners were
  * not resident, e.g. the GPU was shared) poisons the outputs with NaN and is reported here. */
