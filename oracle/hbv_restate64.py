@@ -1,5 +1,6 @@
-"""Dtype-agnostic pure-torch restatement of the reference's daily HBV models Hbv, Hbv_1_1p and Hbv_2 with their
-module-level orchestration.  TEST INFRASTRUCTURE ONLY (tests/ and tools/ import it; the product never does).
+"""Dtype-agnostic pure-torch restatement of the reference's daily HBV models Hbv, Hbv_1_1p and Hbv_2 and of the hourly
+model Hbv_2_hourly (second half of this file: `run_hourly`, `pbm_hourly`, `gage_route`) with their module-level
+orchestration.  TEST INFRASTRUCTURE ONLY (tests/ and tools/ import it; the product never does).
 
 Why it exists: the reference hard-codes float32, so no float64 run of it can be made.  This file restates the same
 equations in whatever dtype its inputs carry; run in float64 under torch.autograd.forward_ad (or reverse mode) it is
@@ -73,8 +74,8 @@ def table(model: str, dynamic=()) -> list:
 
 def drop_order(model: str, dynamic) -> list:
     """Names of the dynamic parameters in the order the reference draws their drop masks: table order for Hbv /
-    Hbv_1_1p (hbv.py:236-246), config-list order for Hbv_2 (hbv_2.py:254-258)."""
-    if model == "Hbv_2":
+    Hbv_1_1p (hbv.py:236-246), config-list order for Hbv_2 and Hbv_2_hourly (hbv_2.py:254-258)."""
+    if model in ("Hbv_2", "Hbv_2_hourly"):                              # (hbv_2_hourly.py:283-288: the same loop)
         return list(dynamic)
     return [n for n, _, _ in table(model, dynamic) if n in dynamic]
 
@@ -267,3 +268,212 @@ def run(model: str, x_phy, parameters, *, nmul: int = 1, dynamic=(), warm_up: in
     if cutoff:
         out = {k: (v if k == "BFI" else v[cutoff:]) for k, v in out.items()}
     return out, (st_ser if model == "Hbv_2" else st_out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Hbv_2_hourly (models/hbv/hbv_2_hourly.py): HBV 2.0 in rate form with dt = 1/24 day.
+#   * parameter table   19 parameters (hbv_2_hourly.py:91-115); parF0's bounds are (5/dt, 120/dt) = (120, 2880) mm/d.
+#                       Tuple parameters (p_dyn, p_sta, p_distr) without sigmoid; dynamic ones in the ORDER OF THE
+#                       CONFIG LIST, one drop mask each drawn in that order (:277-295); static ones in table order,
+#                       the two per-unit routing columns after them (:229-256).
+#   * recurrence        :527-675 -- guard rails at the top of every step (:529-533), P and PET divided by dt first
+#                       (:485-487), every `/ dt` and `* dt` where the reference has it, Hortonian infiltration excess
+#                       (:575-595), Qsim = Q0 + Q1 + Q2 + IE (:652).
+#   * ensemble          mean, or the muwts-weighted sum of Qsim (:678-681).
+#   * per-unit routing  optional, 72 taps (:684-700, lenF :45); `Qs * dt` (:741); pred_cutoff (:761-764).
+#   * gage routing      lagged-UH, area-weighted, per (gage, unit) pair (:800-897): `gage_route`.
+#   * states            the five [T,B,M] series (:670-675,725); initial storages as an argument (the storages a
+#                       cache_states caller carries in, :424-427), default 0.001 (:152-160).
+HOURLY = BASE + EXTRA["Hbv_2"] + [("parF0", 5.0 * 24, 120.0 * 24), ("parFMIN", 0.0, 1.0), ("parALPHA", 0.5, 5.0)]
+HOURLY_ROUTE = [("route_a", 0, 5.0), ("route_b", 0, 12.0)]                      # :116-119
+HOURLY_DISTR = [("route_a", 0, 5.0), ("route_b", 0, 12.0), ("route_tau", 0, 48.0)]   # :120-124
+HOURLY_LENF = 72                                                                 # :45
+HOURLY_SERIES = ["Qsim", "Q0", "Q1", "Q2", "AET", "SWE", "recharge", "excs", "evapfactor", "tosoil", "PERC", "capillary"]
+
+
+def pbm_hourly(P, Tm, PET, par, states, nearzero, ac, elev, events=None):
+    """The hourly recurrence (hbv_2_hourly.py:527-675).  P / Tm / PET: [T,B] forcing as given (depth per step);
+    par: name -> [T,B,M] or [B,M] (static); states: the five storages [B,M] entering hour 0; ac / elev [B].
+    Returns (series name -> [T,B,M] in HOURLY_SERIES order -- rates per day, as the loop stores them --, the five state
+    series [T,B,M]).  `events` (a dict, optional) receives name -> [T,B,M] bool tensors of the branches taken."""
+    dt = 1.0 / 24                                                        # :58
+    SP, MW, SM, SUZ, SLZ = states
+    T = P.shape[0]
+    Pr, PETr = P / dt, PET / dt                                          # :485-487
+    Ac, El = ac.unsqueeze(-1), elev.unsqueeze(-1)
+    hi = (El >= 2000).to(P.dtype)
+    lo = (El < 2000).to(P.dtype)
+    rows = {k: [] for k in HOURLY_SERIES}
+    ser = [[] for _ in range(5)]
+    ev = {} if events is not None else None
+
+    def mark(k, v):
+        if ev is not None:
+            ev.setdefault(k, []).append(v.detach() if torch.is_tensor(v) else v)
+
+    for t in range(T):
+        p = {k: (v[t] if v.dim() == 3 else v) for k, v in par.items()}
+        if ev is not None:
+            mark("rail", (SP < 0) | (MW < 0) | (SM < nearzero) | (SUZ < nearzero) | (SLZ < nearzero))
+        SP = torch.clamp(SP, min=0.0)                                    # :529-533
+        MW = torch.clamp(MW, min=0.0)
+        SM = torch.clamp(SM, min=nearzero)
+        SUZ = torch.clamp(SUZ, min=nearzero)
+        SLZ = torch.clamp(SLZ, min=nearzero)
+        Pt, Tt, Et = Pr[t].unsqueeze(-1), Tm[t].unsqueeze(-1), PETr[t].unsqueeze(-1)
+        tt = hi * 4.0 + lo * p["parTT"]                                  # :544-546
+        rain = Pt * (Tt >= tt).to(Pt.dtype)
+        snow = Pt * (Tt < tt).to(Pt.dtype)
+        # snow (:551-572)
+        SP = SP + snow * dt
+        SP_before = SP
+        melt = torch.clamp(p["parCFMAX"] * (Tt - tt), min=0.0)
+        melt = torch.min(melt * dt, SP)
+        MW = MW + melt
+        SP = SP - melt
+        refr = torch.clamp(p["parCFR"] * p["parCFMAX"] * (tt - Tt), min=0.0)
+        refr = torch.min(refr * dt, MW)
+        SP = SP + refr
+        MW = MW - refr
+        tosoil = torch.clamp((MW - p["parCWH"] * SP) / dt, min=0.0)
+        MW = MW - tosoil * dt
+        # Hortonian infiltration excess (:577-595)
+        W = rain + tosoil
+        r = SM / p["parFC"]
+        s = torch.clamp(r, 0.0, 1.0 - 0.01)
+        fmin = p["parFMIN"] * p["parF0"]
+        fcap = fmin + (p["parF0"] - fmin) * torch.pow(1.0 - s, p["parALPHA"])
+        infil = torch.minimum(W, fcap)
+        IE = torch.clamp(W - fcap, min=0.0)
+        wet = torch.clamp(r ** p["parBETA"], 0.0, 1.0)
+        rech = infil * wet
+        SM = SM + (infil - rech) * dt
+        # excess, evaporation (:603-613)
+        exc = torch.clamp((SM - p["parFC"]) / dt, min=0.0)
+        SM = SM - exc * dt
+        ef0 = (SM / (p["parLP"] * p["parFC"])) ** p["parBETAET"]
+        ef = torch.clamp(ef0, min=0.0, max=1.0)
+        pet_dt = Et * ef * dt
+        et = torch.min(SM, pet_dt) / dt
+        if ev is not None:
+            mark("IE", IE > 0); mark("excess", exc > 0); mark("s_clamped", r > 1.0 - 0.01)
+            mark("ef_clamped", ef0 > 1.0); mark("et_sm_limited", (SM < pet_dt) & (Et > 0))
+            mark("et_pet_limited", (SM >= pet_dt) & (Et > 0)); mark("refreeze", refr > 0)
+            mark("SP_before", SP_before); mark("SP_after", SP)
+        SM = torch.clamp(SM - et * dt, min=nearzero)
+        # capillary rise (:616-628)
+        capp = p["parC"] * SLZ * (1.0 - torch.clamp(SM / p["parFC"], max=1.0)) * dt
+        cap = torch.min(SLZ, capp) / dt
+        if ev is not None:
+            mark("cap_slz_limited", SLZ < capp); mark("cap_unlimited", (SLZ >= capp) & (capp > 0))
+        SM = torch.clamp(SM + cap * dt, min=nearzero)
+        SLZ = torch.clamp(SLZ - cap * dt, min=nearzero)
+        # groundwater boxes (:631-648)
+        SUZ = SUZ + (rech + exc) * dt
+        perc = torch.min(SUZ, p["parPERC"] * dt) / dt
+        SUZ = SUZ - perc * dt
+        q0 = p["parK0"] * torch.clamp(SUZ - p["parUZL"], min=0.0)
+        SUZ = SUZ - q0 * dt
+        q1 = p["parK1"] * SUZ
+        SUZ = SUZ - q1 * dt
+        SLZ = SLZ + perc * dt
+        lf = (torch.clamp((Ac - p["parAC"]) / 1000, min=-1, max=1) * p["parRT"] * (Ac < 2500)
+              + torch.exp(torch.clamp(-(Ac - 2500) / 50, min=-10.0, max=0.0)) * p["parRT"] * (Ac >= 2500))
+        SLZ = torch.clamp(SLZ + lf * dt, min=0.0)
+        q2 = p["parK2"] * SLZ
+        SLZ = SLZ - q2 * dt
+        if ev is not None:
+            mark("Q0", q0 > 0)
+        for k, v in zip(HOURLY_SERIES, (q0 + q1 + q2 + IE, q0, q1, q2, et, SP, rech, exc, ef, tosoil, perc, cap)):
+            rows[k].append(v)
+        for i, v in enumerate((SP, MW, SM, SUZ, SLZ)):
+            ser[i].append(v)
+    if events is not None:
+        events.update({k: torch.stack(v) for k, v in ev.items()})
+    return {k: torch.stack(v) for k, v in rows.items()}, tuple(torch.stack(v) for v in ser)
+
+
+def hourly_uh(a, b, length, tau=None):
+    """uh_gamma (core/calc/uh_routing.py:5-22) of `length` taps for a / b [n], then, with `tau` [n], the fractional
+    shift _frac_shift1d (hbv_2_hourly.py:857-897).  Returns [length, n]."""
+    dt = a.dtype
+    aa, theta = torch.relu(a) + 0.1, torch.relu(b) + 0.5
+    t = torch.arange(0.5, length * 1.0, dtype=dt, device=a.device).unsqueeze(1)
+    w = 1 / (aa.lgamma().exp() * theta ** aa) * t ** (aa - 1) * torch.exp(-t / theta)
+    w = w / w.sum(0)
+    if tau is not None:
+        L = length
+        k = torch.floor(tau).unsqueeze(0)
+        f = tau.unsqueeze(0) - k
+        tt = torch.arange(L, dtype=dt, device=a.device).unsqueeze(1)
+        i0, i1 = tt - k, tt - (k + 1)
+        w0 = torch.gather(w, 0, i0.clamp(0, L - 1).long()) * ((i0 >= 0) & (i0 <= L - 1)).to(dt)
+        w1 = torch.gather(w, 0, i1.clamp(0, L - 1).long()) * ((i1 >= 0) & (i1 <= L - 1)).to(dt)
+        w = (1.0 - f) * w0 + f * w1
+    return w
+
+
+def gage_route(qs, dp, topo, areas, lag_uh=True, bounds=None):
+    """distr_routing (hbv_2_hourly.py:800-855): unit runoff qs [T,U] -> gage streamflow [T,G].  dp [n_pairs,3] in
+    [0,1] (route_a, route_b, route_tau), pairs in the row-major order of `topo == 1` [G,U]; areas [U]."""
+    bounds = bounds or [(lo, hi) for _, lo, hi in HOURLY_DISTR]
+    T = qs.shape[0]
+    L = min(T, HOURLY_LENF)
+    a, b, tau = (_rescale(dp[:, i], bounds[i][0], bounds[i][1]) for i in range(3))
+    w = hourly_uh(a, b, L, tau if lag_uh else None)
+    pairs = (topo == 1).nonzero()
+    rows, cols = pairs[:, 0], pairs[:, 1]
+    y = route((qs * areas[None, :])[:, cols], w)
+    acc = torch.zeros((T, topo.shape[0]), dtype=qs.dtype, device=qs.device).index_add(1, rows, y)
+    return acc / (topo * areas[None, :]).sum(1).clamp(min=1e-6)[None, :]
+
+
+def run_hourly(x_phy, parameters, *, nmul: int = 1, dynamic=(), masks=None, variables=("prcp", "tmean", "pet"),
+               routing: bool = False, nearzero: float = 1e-5, muwts=None, ac_all=None, elev_all=None,
+               outlet_topo=None, areas=None, states=None, pred_cutoff: int = 0, warm_up_states: bool = True,
+               cache_states: bool = False, events=None) -> tuple:
+    """One forward call of Hbv_2_hourly as the reference module runs it (hbv_2_hourly.py:376-798; `cache_states`: the
+    first such call after load_states(`states`)).  parameters: (p_dyn [T,B,n_dy*M], p_sta
+    [B,n_st*M(+2)], p_distr [n_pairs,3]) in [0,1].  Returns ({"Qs": [T,B,1], "streamflow": [T,G,1]}, the five
+    [T,B,M] state series).  `pred_cutoff` is the module attribute of that name (0: no config key sets it, :39)."""
+    M = nmul
+    dynamic = tuple(dynamic)
+    masks = masks or {}
+    T, B = x_phy.shape[0], x_phy.shape[1]
+    dt_, dev = x_phy.dtype, x_phy.device
+    p_dyn, p_sta, p_distr = parameters
+    stat = [nm for nm, _, _ in HOURLY if nm not in dynamic]
+    dview = p_dyn.reshape(T, B, len(dynamic), M)
+    par = {}
+    for nm, lo, hi in HOURLY:
+        if nm in dynamic:
+            i = dynamic.index(nm)
+            dyn, sta = dview[:, :, i, :], dview[-1, :, i, :]
+            m = masks.get(nm)
+            if m is not None:
+                m = m.to(dt_).view(1, -1, 1)
+                dyn = dyn * (1 - m) + sta.unsqueeze(0) * m                # :285-290
+            par[nm] = _rescale(dyn, lo, hi)
+        else:
+            i = stat.index(nm)
+            par[nm] = _rescale(p_sta[:, i * M:(i + 1) * M], lo, hi)
+    if states is None:
+        states = tuple(torch.full((B, M), 0.001, dtype=dt_, device=dev) for _ in range(5))
+    ch = [list(variables).index(v) for v in ("prcp", "tmean", "pet")]
+    s, ser = pbm_hourly(x_phy[:, :, ch[0]], x_phy[:, :, ch[1]], x_phy[:, :, ch[2]], par, states, nearzero,
+                        ac_all, elev_all, events)
+    qsim = s["Qsim"].mean(-1) if muwts is None else (s["Qsim"] * muwts).sum(-1)  # :678-681
+    if routing:                                                                   # :684-700
+        ab = p_sta[:, len(stat) * M:len(stat) * M + 2]
+        uh = hourly_uh(_rescale(ab[:, 0], *HOURLY_ROUTE[0][1:]), _rescale(ab[:, 1], *HOURLY_ROUTE[1][1:]),
+                       min(T, HOURLY_LENF))
+        qsim = route(qsim, uh)
+    qs = qsim * (1.0 / 24)                                                        # :741
+    out = {"Qs": qs.unsqueeze(-1)}
+    if not warm_up_states:                                                        # :761-764 (pred_cutoff)
+        out["Qs"] = out["Qs"][pred_cutoff:]
+    # :766-796 -- a cache_states call routes its DETACHED history (here: this call alone, the first one after
+    # load_states) and returns the last row only
+    routed = gage_route(qs.detach() if cache_states else qs, p_distr, outlet_topo, areas).unsqueeze(-1)
+    out["streamflow"] = routed[-1:] if cache_states else routed
+    return out, ser

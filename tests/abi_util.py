@@ -26,8 +26,11 @@ MODEL_ID = {"Hbv": _abi.MODEL_HBV10, "Hbv_1_1p": _abi.MODEL_HBV11P, "Hbv_2": _ab
 
 
 def make_problem(model="Hbv", T=40, B=5, M=4, dyn=(), betaet=False, drop_frac=0.0, seed=1,
-                 routing=True, muwts=False, cold=False, raw_scale=1.0, channels=(0, 1, 2)):
-    """numpy inputs + a builder of (cfg, tensors) for a raw [T,B,ny] parameter tensor."""
+                 routing=True, muwts=False, cold=False, raw_scale=1.0, channels=(0, 1, 2), forcing="daily", storm=4.0,
+                 day0=0.0, wet=False):
+    """numpy inputs + a builder of (cfg, tensors) for a raw [T,B,ny] parameter tensor.  forcing="hourly": the hourly
+    model on synth.forcing_hourly(storm, day0) instead of the daily series scaled to hourly depths; wet: carried-in
+    storages synth.wet_states (run_problem hands them to the library as state_in) instead of the default 0.001."""
     names = list(PHY_NAMES[model])
     if model == "Hbv" and (betaet or "parBETAET" in dyn):
         names.append("parBETAET")
@@ -35,10 +38,16 @@ def make_problem(model="Hbv", T=40, B=5, M=4, dyn=(), betaet=False, drop_frac=0.
     ny = n * M + 2
     prob = dict(model=model, T=T, B=B, M=M, names=names, n=n, ny=ny, dyn=list(dyn),
                 routing=routing)
-    prob["x"] = synth.forcing(T, B, seed, cold=cold)
+    if forcing == "hourly":
+        prob["x"] = synth.forcing_hourly(T, B, seed, storm=storm, day0=day0)
+    else:
+        prob["x"] = synth.forcing(T, B, seed, cold=cold)
     if model == "Hbv_2_hourly":  # per-step depths of an hourly record
-        prob["x"] = prob["x"] * np.array([1.0 / 8.0, 1.0, 1.0 / 24.0], np.float32)
+        if forcing != "hourly":
+            prob["x"] = prob["x"] * np.array([1.0 / 8.0, 1.0, 1.0 / 24.0], np.float32)
         prob["routing"] = routing = False  # its 72-tap routing is not the library's 15-tap one
+    if wet:
+        prob["state_in"] = synth.wet_states(B, M, seed)
     # `channels`: where (prcp, tmean, pet) sit in the last axis of x (config key `variables` of the modules); an index
     # above 2 widens that axis (a C-ABI caller's forcing tensor), the channels no index names holding a decoy value
     prob["channels"] = tuple(channels)
@@ -95,7 +104,8 @@ def run_problem(prob, lib_path, device="cpu", x_grad=False, backward=True, t0=0,
         if prob["routing"]:
             off = (T - 1) * B * ny + n * M
             cfg.route = RouteSource(0, off, off + 1, ny, [0, 2.9], [0, 6.5])
-        po = hbv_path(cfg, x, None, mu, ac, elev, p)
+        st_in = torch.from_numpy(prob["state_in"]).to(dev).contiguous() if "state_in" in prob else None
+        po = hbv_path(cfg, x, st_in, mu, ac, elev, p)
         rows, routed, state_out, traj = po.flux, po.routed, po.state_out, po.traj
         flux = torch.stack([r[..., 0] for r in rows])
         if routed is not None:

@@ -83,6 +83,8 @@ def _run_case(hydrodl2, name: str) -> dict:
     if spec.get("x_grad"):
         leaves.append(("x_phy", x))
 
+    if "states0" in inp:          # storages carried in: cache_states + load_states (hbv_2_hourly.py:172-192,424-427)
+        model.load_states(tuple(torch.from_numpy(s.copy()) for s in inp["states0"]))
     if "torch_seed" in spec:
         torch.manual_seed(spec["torch_seed"])
 

@@ -148,6 +148,22 @@ CASES = {
     "hourly_long_routing": dict(model="Hbv_2_hourly",
                                 config=_cfg("Hbv_2_hourly", 16, ("parBETA", "parF0"), routing=True, dy_drop=0.3),
                                 T=256, B=6, G=2, seed=48, loss="all", torch_seed=9),
+    # --- the hourly model's wet regime: storages carried in wet (synth.wet_states, through load_states + cache_states,
+    # hbv_2_hourly.py:424-427; `streamflow` is then the last row only, :792-794), hourly storm forcing
+    # (synth.forcing_hourly), unit parameters spread towards the ends of their ranges, and the forcing gradient.  On
+    # these the Hortonian excess (IE > 0), the soil excess and the fast-runoff box (Q0 > 0) are active in the
+    # reference's own tape (tests/test_hourly_f64.py counts them).
+    "hourly_wet_routing": dict(model="Hbv_2_hourly", config=_cfg("Hbv_2_hourly", 2, routing=True, cache_states=True),
+                               T=240, B=8, G=3, seed=61, loss="all", x_grad=True, forcing="hourly", storm=6.0,
+                               day0=100.25, wet_start=True, unit_spread=True),
+    "hourly_wet_dyn3_drop": dict(model="Hbv_2_hourly",
+                                 config=_cfg("Hbv_2_hourly", 16, ("parF0", "parBETA", "parK0"), dy_drop=0.3,
+                                             cache_states=True),
+                                 T=200, B=5, G=2, seed=62, loss="all", x_grad=True, torch_seed=21, forcing="hourly",
+                                 storm=6.0, day0=130.25, wet_start=True, unit_spread=True),
+    "hourly_wet_muwts": dict(model="Hbv_2_hourly", config=_cfg("Hbv_2_hourly", 4, ("parALPHA",), cache_states=True),
+                             T=300, B=6, G=2, seed=63, loss="all", x_grad=True, muwts=True, forcing="hourly", storm=5.0,
+                             day0=75.25, wet_start=True, unit_spread=True),
 }
 
 LONG_CASES = [n for n, c in CASES.items() if "_long_" in n]
@@ -221,7 +237,10 @@ def build_inputs(name: str) -> dict:
     T, B, seed = spec["T"], spec["B"], spec["seed"]
     nmul = cfg.get("nmul", 1)
     out = {}
-    x = synth.forcing(T, B, seed, cold=spec.get("cold", False))
+    if spec.get("forcing") == "hourly":       # hourly depths already
+        x = synth.forcing_hourly(T, B, seed, storm=spec.get("storm", 4.0), day0=spec.get("day0", 0.0))
+    else:
+        x = synth.forcing(T, B, seed, cold=spec.get("cold", False))
     variables = cfg.get("variables", ["prcp", "tmean", "pet"])
     order = [["prcp", "tmean", "pet"].index(v) for v in variables]
     out["x_phy"] = np.ascontiguousarray(x[:, :, order])
@@ -242,7 +261,14 @@ def build_inputs(name: str) -> dict:
             out["outlet_topo"] = topo
             out["areas"] = (synth.uniform((B,), seed, 14) * np.float32(90.0) + np.float32(5.0)).astype(np.float32)
             out["p_distr"] = synth.unit_parameters((int(topo.sum()), 3), seed, 15)
-            out["x_phy"] = out["x_phy"] * np.array([1.0 / 8.0, 1.0, 1.0 / 24.0], np.float32)[order]
+            if spec.get("forcing") != "hourly":
+                out["x_phy"] = out["x_phy"] * np.array([1.0 / 8.0, 1.0, 1.0 / 24.0], np.float32)[order]
+        if spec.get("unit_spread"):           # unit parameters pushed towards the ends of (0,1): u -> smoothstep(u)
+            for k in ("p_dyn", "p_sta"):
+                u = out[k].astype(np.float64)
+                out[k] = (u * u * (3.0 - 2.0 * u)).astype(np.float32)
+        if spec.get("wet_start"):             # storages carried into the call, [5,B,nmul]
+            out["states0"] = synth.wet_states(B, nmul, seed)
     else:
         ny = n * nmul + 2
         out["parameters"] = synth.raw_parameters(T, B, ny, seed, spec.get("raw_scale", 1.0))

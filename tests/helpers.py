@@ -57,6 +57,8 @@ def run_case(name: str, device: str):
         leaves = [("parameters", p)]
     if spec.get("x_grad"):
         leaves.append(("x_phy", x))
+    if "states0" in inp:          # storages carried in (the case's config sets cache_states)
+        model.load_states(tuple(torch.from_numpy(s.copy()).to(dev) for s in inp["states0"]))
     if "torch_seed" in spec:
         torch.manual_seed(spec["torch_seed"])
 

@@ -79,6 +79,8 @@ def case_reverse(name: str, dtype=torch.float64) -> dict:
     tests/golden/<name>.npz is."""
     spec = gc.CASES[name]
     model, cfg = spec["model"], spec["config"]
+    if model == "Hbv_2_hourly":
+        return hourly_case_reverse(name, dtype)
     inp = gc.build_inputs(name)
     res = {}
     if spec.get("two_call"):          # cache_states: the second call starts from the storages the first one left
@@ -107,6 +109,86 @@ def case_reverse(name: str, dtype=torch.float64) -> dict:
         for k in leaves:
             g = lv[k].grad
             res[f"grad/{k}"] = (torch.zeros_like(lv[k]) if g is None else g).numpy()
+    return res
+
+
+def hourly_case_reverse(name: str, dtype=torch.float64, events=None) -> dict:
+    """case_reverse for a golden case of Hbv_2_hourly: Qs, streamflow, the five state series and the loss gradients of
+    p_dyn, p_sta, p_distr (and x_phy where the case asks), keyed as the fixture is.  A case with `states0` is one
+    cache_states call from loaded storages: its gage routing reads the detached history and returns the last row
+    (hbv_2_hourly.py:770-794)."""
+    spec = gc.CASES[name]
+    cfg = spec["config"]
+    inp = gc.build_inputs(name)
+    kw = config_kwargs("Hbv_2_hourly", cfg)
+    masks = masks_for("Hbv_2_hourly", cfg, spec["B"], spec.get("torch_seed"))
+    t = {k: torch.as_tensor(np.asarray(v)).to(dtype) for k, v in inp.items()}
+    leaves = ["p_dyn", "p_sta", "p_distr"] + (["x_phy"] if spec.get("x_grad") else [])
+    for k in leaves:
+        t[k].requires_grad_(True)
+    states = tuple(t["states0"]) if "states0" in t else None
+    out, ser = restate().run_hourly(
+        t["x_phy"], (t["p_dyn"], t["p_sta"], t["p_distr"]), nmul=kw["nmul"], dynamic=kw["dynamic"], masks=masks,
+        variables=kw["variables"], routing=kw.get("routing", False), nearzero=kw["nearzero"], muwts=t.get("muwts"),
+        ac_all=t["ac_all"], elev_all=t["elev_all"], outlet_topo=t["outlet_topo"], areas=t["areas"], states=states,
+        warm_up_states=kw["warm_up_states"], cache_states=bool((cfg or {}).get("cache_states", False)), events=events)
+    res = {f"out/{k}": v.detach().numpy() for k, v in out.items()}
+    res["states"] = torch.stack([s.detach() for s in ser]).numpy()
+    loss = sum((torch.from_numpy(gc.loss_weight(name, k, out[k].shape)).to(dtype) * out[k]).sum()
+               for k in gc.loss_keys(name))
+    loss.backward()
+    for k in leaves:
+        res[f"grad/{k}"] = (torch.zeros_like(t[k]) if t[k].grad is None else t[k].grad).numpy()
+    return res
+
+
+def abi_hourly(prob: dict, dtype=torch.float64, x_grad: bool = True, backward: bool = True, events=None) -> dict:
+    """An abi_util.make_problem dict of model Hbv_2_hourly through the restatement at the level of the C ABI, in
+    `dtype`: raw parameters [T,B,ny] through the sigmoid (static value = row T-1, dynamic rows where the parameter is
+    dynamic and its basin not dropped), the twelve flux rows (means over the members; Qsim weighted by muwts where
+    given), the loss sum(flux * gflux) as abi_util.run_problem forms it, storages carried in from prob["state_in"].
+    Returns run_problem's keys: flux [12,T,B], traj [5,T+1,B*M], state_out [5,B,M], g_params, g_x, g_muwts (float64
+    numpy).  `events`: see hbv_restate64.pbm_hourly."""
+    from .abi_util import BOUNDS
+    R = restate()
+    T, B, M, names = prob["T"], prob["B"], prob["M"], prob["names"]
+    x = torch.from_numpy(prob["x"]).to(dtype).requires_grad_(x_grad and backward)
+    raw = torch.from_numpy(prob["params"]).to(dtype).requires_grad_(backward)
+    mu = torch.from_numpy(prob["muwts"]).to(dtype).requires_grad_(backward) if "muwts" in prob else None
+    ac = torch.from_numpy(prob["ac"]).to(dtype)
+    elev = torch.from_numpy(prob["elev"]).to(dtype)
+    unit = torch.sigmoid(raw[:, :, :len(names) * M]).reshape(T, B, len(names), M)
+    par = {}
+    for i, nm in enumerate(names):
+        lo, hi = BOUNDS[nm]
+        v = unit[-1, :, i, :]
+        if nm in prob["dyn"]:
+            dyn = unit[:, :, i, :]
+            if "drop" in prob:
+                m = torch.from_numpy(prob["drop"][prob["dyn"].index(nm)].astype(np.float64)).to(dtype).view(1, B, 1)
+                dyn = dyn * (1 - m) + v.unsqueeze(0) * m
+            v = dyn
+        par[nm] = v * (hi - lo) + lo
+    if "state_in" in prob:
+        st = tuple(torch.from_numpy(prob["state_in"][k]).to(dtype) for k in range(5))
+    else:
+        st = tuple(torch.full((B, M), 0.001, dtype=dtype) for _ in range(5))
+    ch = prob.get("channels", (0, 1, 2))
+    s, ser = R.pbm_hourly(x[:, :, ch[0]], x[:, :, ch[1]], x[:, :, ch[2]], par, st, 1e-5, ac, elev, events)
+    rows = [s[k].mean(-1) for k in R.HOURLY_SERIES]
+    if mu is not None:
+        rows[0] = (s["Qsim"] * mu).sum(-1)
+    flux = torch.stack(rows)
+    traj = torch.stack([torch.cat([st[k].unsqueeze(0), ser[k].detach()]).reshape(T + 1, B * M) for k in range(5)])
+    res = {"flux": flux.detach().numpy(), "traj": traj.numpy(),
+           "state_out": (torch.stack([ser[k][-1].detach() for k in range(5)]) if T else torch.stack(st)).numpy()}
+    if backward:
+        (flux * torch.from_numpy(prob["gflux"]).to(dtype)).sum().backward()
+        res["g_params"] = raw.grad.numpy()
+        if x_grad:
+            res["g_x"] = x.grad.numpy()
+        if mu is not None:
+            res["g_muwts"] = mu.grad.numpy()
     return res
 
 

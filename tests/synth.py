@@ -81,3 +81,47 @@ def unit_parameters(shape, seed: int, stream: int = 4) -> np.ndarray:
 
 def loss_weights(shape, seed: int, stream: int = 5) -> np.ndarray:
     return normalish(shape, seed, stream)
+
+
+def _tri(phase: np.ndarray) -> np.ndarray:
+    """Triangular wave on phase in [0,1): -1 at 0, +1 at 0.5."""
+    return np.where(phase < 0.5, 4.0 * phase - 1.0, 3.0 - 4.0 * phase)
+
+
+def forcing_hourly(T: int, B: int, seed: int, storm: float = 4.0, day0: float = 0.0) -> np.ndarray:
+    """Hourly synthetic forcing [T,B,3] (prcp mm/h, tmean degC, pet mm/h) for the sub-daily model.
+
+    The season and a diurnal cycle advance with t / 24 (row t is hour t of day `day0` + t / 24; day 0 is midwinter), so
+    a record of 8760 rows is one water year: snow accumulates, then melts out.  ~12 % wet hours of up to 3 mm/h, and in
+    ~4 % of the 6-hour blocks of a basin a storm burst of `storm` x that (up to 12 mm/h at the default: above the
+    infiltration capacity of a wet soil with a small parFMIN * parF0).  PET follows the season and the hour of the day
+    (a small residual at night, never an exact zero in summer).  Same exact-arithmetic recipe as `forcing`."""
+    u = uniform((T, B, 3), seed, 31).astype(np.float64)
+    hour = np.arange(T, dtype=np.float64)[:, None]
+    day = day0 + hour / 24.0
+    season = _tri((day % 365.0) / 365.0)
+    diurnal = _tri(((day0 * 24.0 + hour) % 24.0) / 24.0)         # -1 at midnight, +1 at noon
+    boff = uniform((1, B), seed, 32).astype(np.float64) * 20.0 - 8.0
+    nblk = (T + 5) // 6
+    burst = (uniform((nblk, B), seed, 33).astype(np.float64) < 0.04)
+    burst = np.repeat(burst, 6, axis=0)[:T]
+    base = np.maximum(0.0, (u[:, :, 0] - 0.88) * 25.0)
+    P = np.where(burst, storm * (0.5 + 2.5 * u[:, :, 0]), base)
+    Tm = 12.0 * season + 3.0 * diurnal + (u[:, :, 1] * 6.0 - 3.0) + boff
+    PET = np.maximum(0.0, 2.5 + 2.5 * season + (u[:, :, 2] - 0.5) * 2.0) * (np.maximum(diurnal, 0.0) / 6.0 + 1.0 / 64.0)
+    return np.stack([P, Tm, PET], axis=-1).astype(np.float32)
+
+
+def wet_states(B: int, M: int, seed: int) -> np.ndarray:
+    """Carried-in storages [5,B,M] (SNOWPACK, MELTWATER, SM, SUZ, SLZ; mm) of a wet catchment: a snowpack of up to 40 mm
+    on half of the lanes, soil moisture up to and above the range of parFC (50-1000), an upper zone across the range of
+    parUZL (0-100), and -- on one lane in eight -- a dry column: soil moisture of 0.0005 mm over a lower zone carried in
+    empty (below the model's storage floor; no capillary rise refills that soil)."""
+    u = uniform((6, B, M), seed, 34).astype(np.float64)
+    SP = np.where(u[0] < 0.5, u[5] * 40.0, 0.0)
+    MW = u[1] * 3.0 * (SP > 0)
+    dry = u[4] < 0.125
+    SM = np.where(dry, 0.0005, u[2] * 1200.0)
+    SUZ = u[3] * 150.0
+    SLZ = np.where(dry, 0.0, u[4] * 80.0)
+    return np.stack([SP, MW, SM, SUZ, SLZ]).astype(np.float32)

@@ -15,6 +15,7 @@ from hydrodl2_amd.ops import GageRoute, GageTopology
 
 from . import synth
 from .abi_util import assert_close, assert_grad_close
+from .restate_util import restate
 
 BOUNDS = ((0.0, 5.0), (0.0, 12.0), (0.0, 48.0))
 
@@ -34,36 +35,12 @@ def _problem(T, U, G, seed, dense=0.4):
 
 
 def _restatement(pb, lag_uh):
-    """float64 torch restatement of distr_routing / _frac_shift1d."""
+    """float64 restatement of distr_routing / _frac_shift1d (oracle/hbv_restate64.py::gage_route, the copy the hourly
+    model's restatement uses)."""
     dt = torch.float64
-    topo = torch.tensor(pb["topo"], dtype=dt)
-    areas = torch.tensor(pb["areas"], dtype=dt)
     qs = torch.tensor(pb["qs"], dtype=dt, requires_grad=True)
     dp = torch.tensor(pb["dp"], dtype=dt, requires_grad=True)
-    T = qs.shape[0]
-    L = min(T, 72)
-    a = dp[:, 0] * BOUNDS[0][1]
-    b = dp[:, 1] * BOUNDS[1][1]
-    tau = dp[:, 2] * BOUNDS[2][1]
-    aa, theta = torch.relu(a) + 0.1, torch.relu(b) + 0.5
-    t = torch.arange(0.5, L * 1.0, dtype=dt).unsqueeze(1)
-    w = 1 / (aa.lgamma().exp() * theta ** aa) * t ** (aa - 1) * torch.exp(-t / theta)
-    w = w / w.sum(0)
-    if lag_uh:
-        k = torch.floor(tau).unsqueeze(0)
-        f = tau.unsqueeze(0) - k
-        tt = torch.arange(L, dtype=dt).unsqueeze(1)
-        i0, i1 = tt - k, tt - (k + 1)
-        w0 = torch.gather(w, 0, i0.clamp(0, L - 1).long()) * ((i0 >= 0) & (i0 <= L - 1)).to(dt)
-        w1 = torch.gather(w, 0, i1.clamp(0, L - 1).long()) * ((i1 >= 0) & (i1 <= L - 1)).to(dt)
-        w = (1.0 - f) * w0 + f * w1
-    pairs = (topo == 1).nonzero()
-    rows, cols = pairs[:, 0], pairs[:, 1]
-    qp = (qs * areas[None, :])[:, cols]
-    y = torch.nn.functional.conv1d(qp.t().unsqueeze(0), torch.flip(w.t().unsqueeze(1), [2]),
-                                   groups=qp.shape[1], padding=L - 1)[0, :, :T].t()
-    acc = torch.zeros((T, topo.shape[0]), dtype=dt).index_add(1, rows, y)
-    out = acc / (topo * areas[None, :]).sum(1).clamp(min=1e-6)[None, :]
+    out = restate().gage_route(qs, dp, torch.tensor(pb["topo"], dtype=dt), torch.tensor(pb["areas"], dtype=dt), lag_uh, BOUNDS)
     (out * torch.tensor(pb["wt"], dtype=dt)).sum().backward()
     return out.detach().numpy(), qs.grad.numpy(), dp.grad.numpy()
 

@@ -1,8 +1,9 @@
-"""CPU tier: oracle/hbv_restate64.py, the float64 restatement of Hbv, Hbv_1_1p and Hbv_2, against the fixtures the
-reference itself produced -- outputs, storages and reverse-mode gradients of every golden case of those models
+"""CPU tier: oracle/hbv_restate64.py, the float64 restatement of Hbv, Hbv_1_1p, Hbv_2 and Hbv_2_hourly, against the
+fixtures the reference itself produced -- outputs, storages and reverse-mode gradients of every golden case of those models
 (tests/golden/<case>.npz, at helpers.compare's committed tolerances) and the output tangents of the 22 forward-mode
 fixtures (tests/golden/jvp_<case>.npz, at the tolerances of tests/test_jvp_gpu.py (a)).  Once pinned here, the
-restatement is the float64 yardstick of tests/test_jvp_f64_gpu.py."""
+restatement is the float64 yardstick of tests/test_jvp_f64_gpu.py and, for the hourly model, of tests/test_hourly_f64.py
+and tests/test_hourly_f64_gpu.py."""
 import os
 
 import numpy as np
@@ -16,13 +17,17 @@ from . import restate_util as ru
 from .helpers import GOLDEN_DIR, compare, load_golden
 from .test_jvp_gpu import BFI_ATOL_REL, TAN_FLOOR, _assert_tangent_close
 
-# every golden case of the three daily models (hbv_cache_states included: two calls, storages carried across)
-CASES = [n for n, s in gc.CASES.items() if s["model"] in ("Hbv", "Hbv_1_1p", "Hbv_2")]
+# every golden case of the three daily models (hbv_cache_states included: two calls, storages carried across) and of
+# the hourly model (the five dry ones and the three that start wet under storm forcing)
+DAILY = [n for n, s in gc.CASES.items() if s["model"] in ("Hbv", "Hbv_1_1p", "Hbv_2")]
+HOURLY = [n for n, s in gc.CASES.items() if s["model"] == "Hbv_2_hourly"]
+CASES = DAILY + HOURLY
 
 
 def test_scope():
-    """The restatement's scope is every Hbv / Hbv_1_1p / Hbv_2 fixture, and every forward-mode fixture."""
-    assert len(CASES) == 33 and set(gj.JVP_CASES) <= set(CASES)
+    """The restatement's scope is every Hbv / Hbv_1_1p / Hbv_2 / Hbv_2_hourly fixture, and every forward-mode fixture."""
+    assert len(DAILY) == 33 and len(HOURLY) == 8 and set(gj.JVP_CASES) <= set(DAILY)
+    assert len(CASES) == len(gc.CASES)
 
 
 # Elements where the float64 restatement and the reference's float32 run part for a reason of precision alone, each
@@ -37,11 +42,20 @@ def test_scope():
 #    float64 against the fixture: hbv2_long_routing (day 180) 0.171422 vs 0.171379 (pack 42.79), hbv2_long_dyn3
 #    (day 187) 0.460176 vs 0.460056 (pack 21.69), hbv2_long_static_cold (day 184) 0.783688 vs 0.783583 (pack 15.51);
 #    the next day both are 0.  Bound: 1e-5 x the member's largest SNOWPACK.
+#  * the wet hourly fixtures, the same thing on a groundwater box in the last hour before it runs empty (the next
+#    hour both sides are 0 to within 4e-9): the box held 32-113 mm, float32 carries 1e-5 .. 7e-5 mm of rounding, and
+#    the last 0.04-0.3 mm are off by that.  float64 against the fixture: hourly_wet_routing SLZ hour 85 0.0352950 vs
+#    0.0352803 (box 71.96) and hour 101 0.2545896 vs 0.2545463 (48.19); hourly_wet_muwts SUZ hours 159 / 188 / 199
+#    0.0846214 vs 0.0846471 (45.58), 0.2950842 vs 0.2950192 (113.49), 0.0558768 vs 0.0558525 (32.23).  Same bound:
+#    1e-5 x the member's largest value of that storage.  (hourly_wet_dyn3_drop has no such element.)
 PRECISION_ONLY = {
-    "hbv11p_long_dyn_all": ("grad/parameters", (slice(None), 4, slice(4, 14 * 16, 16)), None),
-    "hbv2_long_routing": ("states", (0, 180, 5, 2), 1e-5),
-    "hbv2_long_dyn3": ("states", (0, 187, 5, 10), 1e-5),
-    "hbv2_long_static_cold": ("states", (0, 184, 3, 5), 1e-5),
+    "hbv11p_long_dyn_all": [("grad/parameters", (slice(None), 4, slice(4, 14 * 16, 16)), None)],
+    "hbv2_long_routing": [("states", (0, 180, 5, 2), 1e-5)],
+    "hbv2_long_dyn3": [("states", (0, 187, 5, 10), 1e-5)],
+    "hbv2_long_static_cold": [("states", (0, 184, 3, 5), 1e-5)],
+    "hourly_wet_routing": [("states", (4, 85, 2, 1), 1e-5), ("states", (4, 101, 7, 0), 1e-5)],
+    "hourly_wet_muwts": [("states", (3, 159, 2, 0), 1e-5), ("states", (3, 188, 5, 0), 1e-5),
+                         ("states", (3, 199, 0, 0), 1e-5)],
 }
 
 
@@ -52,14 +66,14 @@ def test_restatement_matches_reference(name):
     missing = [k for k in ref.files if k not in ("torch_version", "loss") and k not in res]
     assert not missing, missing
     if name in PRECISION_ONLY:
-        key, idx, bound = PRECISION_ONLY[name]
-        got, want = res[key][idx], ref[key][idx]
-        if bound is not None:          # a snowpack element: within `bound` x the member's largest SNOWPACK
-            scale = float(np.abs(ref[key][(0, slice(None)) + tuple(idx[2:])]).max())
-            assert abs(float(got) - float(want)) <= bound * scale, (name, got, want, scale)
         res = dict(res)
-        res[key] = res[key].copy()
-        res[key][idx] = want           # the rest of the tensor is compared as usual
+        for key, idx, bound in PRECISION_ONLY[name]:
+            got, want = res[key][idx], ref[key][idx]
+            if bound is not None:      # a storage element: within `bound` x the member's largest value of that storage
+                scale = float(np.abs(ref[key][(idx[0], slice(None)) + tuple(idx[2:])]).max())
+                assert abs(float(got) - float(want)) <= bound * scale, (name, got, want, scale)
+            res[key] = res[key].copy()
+            res[key][idx] = want       # the rest of the tensor is compared as usual
         compare(name, ru.case_reverse(name, torch.float32), ref)
     compare(name, res, ref)
 
