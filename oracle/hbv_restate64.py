@@ -64,6 +64,15 @@ ROUTE = [("route_a", 0, 2.9), ("route_b", 0, 6.5)]
 MODELS = tuple(EXTRA)
 
 
+# the branches `_pbm` records on request (name -> [T,B,M] bool): every model's, the capillary models', Hbv_2's
+DAILY_EVENTS = ("rain", "snow", "melt_pack_limited", "melt_potential", "refr_mw_limited", "refr_potential", "tosoil",
+                "wet_clamped", "excs", "ef_clamped", "et_sm_limited", "et_pet_limited", "sm_floor", "perc_suz", "perc_par",
+                "Q0")
+CAP_EVENTS = ("cap_slz_limited", "cap_unlimited", "sm_floor_cap", "slz_floor")
+HBV2_EVENTS = ("elev_hi", "elev_lo", "ac_lo", "ac_hi", "ac_clamp_hi", "ac_clamp_lo", "ac_free", "exp_clamped", "exp_free",
+               "slz_lf_clamped")
+
+
 def table(model: str, dynamic=()) -> list:
     """(name, lo, hi) of the model's physical parameters in table order; Hbv gains parBETAET iff it is dynamic."""
     t = BASE + EXTRA[model]
@@ -112,14 +121,23 @@ def _step_params(model, unit_dyn, unit_sta, dynamic, masks, T):
     return par
 
 
-def _pbm(model, P, Tm, PET, par, states, nearzero, ac=None, elev=None):
+def _pbm(model, P, Tm, PET, par, states, nearzero, ac=None, elev=None, events=None, want_series=False):
     """The daily recurrence over T days.  P / Tm / PET: [T,B] forcing series; par: name -> [T,B,M]; states: the five
-    storages [B,M].  Returns (series name -> [T,B,M], states after the last day, the states series or None)."""
+    storages [B,M].  Returns (series name -> [T,B,M], states after the last day, the states series or None: Hbv_2's
+    always, every model's with `want_series`).  `events` (a dict, optional) receives name -> [T,B,M] bool tensors of
+    the branches taken (DAILY_EVENTS; for Hbv_2 also HBV2_EVENTS) and the snowpack before and after the melt;
+    recording changes no value."""
     SP, MW, SM, SUZ, SLZ = states
     T = P.shape[0]
     names = ["Qsim", "Q0", "Q1", "Q2", "AET", "SWE", "recharge", "excs", "evapfactor", "tosoil", "PERC", "capillary"]
     rows = {k: [] for k in names}
-    series = [] if model == "Hbv_2" else None
+    series = [] if (model == "Hbv_2" or want_series) else None
+    ev = {} if events is not None else None
+
+    def mark(k, v):
+        if ev is not None:
+            ev.setdefault(k, []).append(v.detach())
+
     for t in range(T):
         p = {k: v[t] for k, v in par.items()}
         Pt, Tt, Et = P[t].unsqueeze(-1), Tm[t].unsqueeze(-1), PET[t].unsqueeze(-1)
@@ -131,14 +149,25 @@ def _pbm(model, P, Tm, PET, par, states, nearzero, ac=None, elev=None):
         snow = Pt * (Tt < tt).to(Pt.dtype)
         # snow (hbv.py:440-466)
         SP = SP + snow
+        if ev is not None:
+            full = torch.ones_like(SP, dtype=torch.bool)
+            pot, rpot = p["parCFMAX"] * (Tt - tt), p["parCFR"] * p["parCFMAX"] * (tt - Tt)
+            mark("rain", ((Tt >= tt) & (Pt > 0)) & full); mark("snow", ((Tt < tt) & (Pt > 0)) & full)
+            mark("melt_pack_limited", (pot > 0) & (SP < pot) & (SP > 0)); mark("melt_potential", (pot > 0) & (SP >= pot))
+            mark("SP_before", SP)
         melt = torch.min(torch.clamp(p["parCFMAX"] * (Tt - tt), min=0.0), SP)
         MW = MW + melt
         SP = SP - melt
+        if ev is not None:
+            mark("refr_mw_limited", (rpot > 0) & (MW < rpot) & (MW > 0)); mark("refr_potential", (rpot > 0) & (MW >= rpot))
+            mark("SP_after", SP)
         refr = torch.min(torch.clamp(p["parCFR"] * p["parCFMAX"] * (tt - Tt), min=0.0), MW)
         SP = SP + refr
         MW = MW - refr
         tosoil = torch.clamp(MW - p["parCWH"] * SP, min=0.0)
         MW = MW - tosoil
+        if ev is not None:
+            mark("tosoil", tosoil > 0); mark("wet_clamped", (SM / p["parFC"]) ** p["parBETA"] > 1.0)
         # soil and evaporation (hbv.py:468-480, hbv_1_1p.py:472-479)
         wet = torch.clamp((SM / p["parFC"]) ** p["parBETA"], min=0.0, max=1.0)
         rech = (rain + tosoil) * wet
@@ -148,18 +177,29 @@ def _pbm(model, P, Tm, PET, par, states, nearzero, ac=None, elev=None):
         ef = SM / (p["parLP"] * p["parFC"])
         if "parBETAET" in p:
             ef = ef ** p["parBETAET"]
+        if ev is not None:
+            mark("excs", exc > 0); mark("ef_clamped", ef > 1.0)
         ef = torch.clamp(ef, min=0.0, max=1.0)
         et = torch.min(SM, Et * ef)
+        if ev is not None:
+            mark("et_sm_limited", (SM < Et * ef) & (Et > 0)); mark("et_pet_limited", (SM >= Et * ef) & (Et > 0))
+            mark("sm_floor", SM - et < nearzero)
         SM = torch.clamp(SM - et, min=nearzero)
         # capillary rise (hbv_1_1p.py:481-490, hbv_2.py:518-527)
         if model != "Hbv":
-            cap = torch.min(SLZ, p["parC"] * SLZ * (1.0 - torch.clamp(SM / p["parFC"], max=1.0)))
+            capp = p["parC"] * SLZ * (1.0 - torch.clamp(SM / p["parFC"], max=1.0))
+            cap = torch.min(SLZ, capp)
+            if ev is not None:
+                mark("cap_slz_limited", SLZ < capp); mark("cap_unlimited", (SLZ >= capp) & (capp > 0))
+                mark("sm_floor_cap", SM + cap < nearzero); mark("slz_floor", SLZ - cap < nearzero)
             SM = torch.clamp(SM + cap, min=nearzero)
             SLZ = torch.clamp(SLZ - cap, min=nearzero)
         else:
             cap = None
         # groundwater (hbv.py:482-492, hbv_2.py:529-546)
         SUZ = SUZ + rech + exc
+        if ev is not None:
+            mark("perc_suz", SUZ < p["parPERC"]); mark("perc_par", SUZ >= p["parPERC"])
         perc = torch.min(SUZ, p["parPERC"])
         SUZ = SUZ - perc
         q0 = p["parK0"] * torch.clamp(SUZ - p["parUZL"], min=0.0)
@@ -167,11 +207,22 @@ def _pbm(model, P, Tm, PET, par, states, nearzero, ac=None, elev=None):
         q1 = p["parK1"] * SUZ
         SUZ = SUZ - q1
         SLZ = SLZ + perc
+        if ev is not None:
+            mark("Q0", q0 > 0)
         if model == "Hbv_2":
             a = ac.unsqueeze(-1)
             low = (a < 2500).to(a.dtype)
             lf = (torch.clamp((a - p["parAC"]) / 1000, min=-1, max=1) * p["parRT"] * low
                   + torch.exp(torch.clamp(-(a - 2500) / 50, min=-10.0, max=0.0)) * p["parRT"] * (1 - low))
+            if ev is not None:
+                full = torch.ones_like(SLZ, dtype=torch.bool)
+                d = (a - p["parAC"]) / 1000
+                mark("elev_hi", (elev.unsqueeze(-1) >= 2000) & full); mark("elev_lo", (elev.unsqueeze(-1) < 2000) & full)
+                mark("ac_lo", (a < 2500) & full); mark("ac_hi", (a >= 2500) & full)
+                mark("ac_clamp_hi", (a < 2500) & (d > 1)); mark("ac_clamp_lo", (a < 2500) & (d < -1))
+                mark("ac_free", (a < 2500) & (d >= -1) & (d <= 1))
+                mark("exp_clamped", (a >= 2500) & (-(a - 2500) / 50 < -10.0)); mark("exp_free", (a >= 2500) & (-(a - 2500) / 50 >= -10.0))
+                mark("slz_lf_clamped", SLZ + lf < 0.0)
             SLZ = torch.clamp(SLZ + lf, min=0.0)
         q2 = p["parK2"] * SLZ
         SLZ = SLZ - q2
@@ -182,19 +233,22 @@ def _pbm(model, P, Tm, PET, par, states, nearzero, ac=None, elev=None):
             series.append((SP, MW, SM, SUZ, SLZ))
     out = {k: torch.stack(v) for k, v in rows.items() if v}
     ser = None if series is None else tuple(torch.stack([s[i] for s in series]) for i in range(5))
+    if events is not None:
+        events.update({k: torch.stack(v) for k, v in ev.items()})
     return out, (SP, MW, SM, SUZ, SLZ), ser
 
 
 def run(model: str, x_phy, parameters, *, nmul: int = 1, dynamic=(), warm_up: int = 0, warm_up_states: bool = True,
         masks=None, variables=("prcp", "tmean", "pet"), routing=None, comprout: bool = False, nearzero: float = 1e-5,
-        muwts=None, ac_all=None, elev_all=None, states=None, aux=None) -> tuple:
+        muwts=None, ac_all=None, elev_all=None, states=None, aux=None, events=None) -> tuple:
     """One forward call of `model` ("Hbv", "Hbv_1_1p" or "Hbv_2") as the reference module runs it.
 
     x_phy [T,B,3] in `variables` order; parameters: raw [T,B,ny] (Hbv, Hbv_1_1p) or the tuple (p_dyn [T,B,n_dy*M],
     p_sta [B,n_st*M(+2)]) in [0,1] (Hbv_2); masks: dynamic name -> [B] drop mask (None: nothing dropped); muwts
     broadcastable to [T',B,M] (T' = the simulated days after a state warm-up); states: five [B,M] storages or None.
     Every tensor is used in its own dtype and on its own device.  `aux` (a dict, optional) receives "bfi_sums":
-    (sum over days of the routed Q2, of the routed Qs + nearzero), BFI's numerator and denominator.  Returns (flux dict as the module returns it,
+    (sum over days of the routed Q2, of the routed Qs + nearzero), BFI's numerator and denominator; `events`: see `_pbm`
+    (the days after a state warm-up).  Returns (flux dict as the module returns it,
     states: the five final [B,M] storages, or for Hbv_2 the five [T,B,M] series)."""
     if model not in MODELS:
         raise ValueError(f"not restated: {model}")
@@ -242,7 +296,7 @@ def run(model: str, x_phy, parameters, *, nmul: int = 1, dynamic=(), warm_up: in
         unit_sta = {nm: unit[-1, :, i, :] for i, (nm, _, _) in enumerate(tab)}
     par = _step_params(model, unit_dyn, unit_sta, dynamic, masks, T)
     P, Tm, PET = forcing(x_phy[w:])
-    s, st_out, st_ser = _pbm(model, P, Tm, PET, par, states, nearzero, ac_all, elev_all)
+    s, st_out, st_ser = _pbm(model, P, Tm, PET, par, states, nearzero, ac_all, elev_all, events)
 
     mean = {k: v.mean(-1) for k, v in s.items()}
     qsim = mean["Qsim"] if muwts is None else (s["Qsim"] * muwts).sum(-1)      # hbv.py:507-511

@@ -29,7 +29,8 @@ def make_problem(model="Hbv", T=40, B=5, M=4, dyn=(), betaet=False, drop_frac=0.
                  routing=True, muwts=False, cold=False, raw_scale=1.0, channels=(0, 1, 2), forcing="daily", storm=4.0,
                  day0=0.0, wet=False):
     """numpy inputs + a builder of (cfg, tensors) for a raw [T,B,ny] parameter tensor.  forcing="hourly": the hourly
-    model on synth.forcing_hourly(storm, day0) instead of the daily series scaled to hourly depths; wet: carried-in
+    model on synth.forcing_hourly(storm, day0) instead of the daily series scaled to hourly depths (the daily series
+    starts on day `day0` of the year too); wet: carried-in
     storages synth.wet_states (run_problem hands them to the library as state_in) instead of the default 0.001."""
     names = list(PHY_NAMES[model])
     if model == "Hbv" and (betaet or "parBETAET" in dyn):
@@ -41,7 +42,7 @@ def make_problem(model="Hbv", T=40, B=5, M=4, dyn=(), betaet=False, drop_frac=0.
     if forcing == "hourly":
         prob["x"] = synth.forcing_hourly(T, B, seed, storm=storm, day0=day0)
     else:
-        prob["x"] = synth.forcing(T, B, seed, cold=cold)
+        prob["x"] = synth.forcing(T, B, seed, cold=cold, day0=day0)
     if model == "Hbv_2_hourly":  # per-step depths of an hourly record
         if forcing != "hourly":
             prob["x"] = prob["x"] * np.array([1.0 / 8.0, 1.0, 1.0 / 24.0], np.float32)

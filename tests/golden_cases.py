@@ -164,6 +164,23 @@ CASES = {
     "hourly_wet_muwts": dict(model="Hbv_2_hourly", config=_cfg("Hbv_2_hourly", 4, ("parALPHA",), cache_states=True),
                              T=300, B=6, G=2, seed=63, loss="all", x_grad=True, muwts=True, forcing="hourly", storm=5.0,
                              day0=75.25, wet_start=True, unit_spread=True),
+    # --- the daily models' wet regime: storages carried in wet (synth.wet_states through load_states + cache_states,
+    # hbv.py:148-168,321-324), raw parameters spread over their ranges, a record from a spring day (day 120: PET > 0
+    # while the carried-in soil is saturated) into late autumn, and the forcing gradient.  On these the soil excess, the
+    # fast-runoff box (Q0 > 0), PERC = parPERC and evaporation limited by the soil moisture (the dry lanes of
+    # wet_states) are active in the reference's own tape (tests/test_daily_f64.py counts them).
+    "hbv_wet_dyn3": dict(model="Hbv", config=_cfg("Hbv", 4, ("parBETA", "parK0", "parBETAET"), cache_states=True),
+                         T=200, B=6, seed=78, loss="all", x_grad=True, day0=120.0, wet_start=True, raw_scale=2.5),
+    "hbv11p_wet_list_drop": dict(model="Hbv_1_1p",
+                                 config=_cfg("Hbv_1_1p", 4, ("parK0", "parTT", "parFC", "parC"), dy_drop=0.3,
+                                             cache_states=True),
+                                 T=200, B=6, seed=84, loss="all", x_grad=True, torch_seed=31, day0=120.0, wet_start=True,
+                                 raw_scale=2.0),
+    "hbv2_wet_muwts_routing": dict(model="Hbv_2",
+                                   config=_cfg("Hbv_2", 4, ("parBETA", "parK0", "parBETAET"), routing=True,
+                                               cache_states=True),
+                                   T=200, B=8, seed=90, loss="all", x_grad=True, muwts=True, day0=120.0, wet_start=True,
+                                   unit_spread=True),
 }
 
 LONG_CASES = [n for n, c in CASES.items() if "_long_" in n]
@@ -240,7 +257,7 @@ def build_inputs(name: str) -> dict:
     if spec.get("forcing") == "hourly":       # hourly depths already
         x = synth.forcing_hourly(T, B, seed, storm=spec.get("storm", 4.0), day0=spec.get("day0", 0.0))
     else:
-        x = synth.forcing(T, B, seed, cold=spec.get("cold", False))
+        x = synth.forcing(T, B, seed, cold=spec.get("cold", False), day0=spec.get("day0", 0.0))
     variables = cfg.get("variables", ["prcp", "tmean", "pet"])
     order = [["prcp", "tmean", "pet"].index(v) for v in variables]
     out["x_phy"] = np.ascontiguousarray(x[:, :, order])
@@ -267,11 +284,11 @@ def build_inputs(name: str) -> dict:
             for k in ("p_dyn", "p_sta"):
                 u = out[k].astype(np.float64)
                 out[k] = (u * u * (3.0 - 2.0 * u)).astype(np.float32)
-        if spec.get("wet_start"):             # storages carried into the call, [5,B,nmul]
-            out["states0"] = synth.wet_states(B, nmul, seed)
     else:
         ny = n * nmul + 2
         out["parameters"] = synth.raw_parameters(T, B, ny, seed, spec.get("raw_scale", 1.0))
+    if spec.get("wet_start"):                 # storages carried into the call, [5,B,nmul]
+        out["states0"] = synth.wet_states(B, nmul, seed)
     if spec.get("muwts"):
         Tmu = 1 if spec["muwts"] == "bcast" else T
         u = synth.uniform((Tmu, B, nmul), seed, 9).astype(np.float64) + 0.25

@@ -198,7 +198,7 @@ def compare_f64(prob, got, want64, f32_evals, label, name=None):
             return cache[i][k]
         return f
     got = _named(name, got, want64, prob["M"])
-    bad = []          # every array is compared before anything is raised
+    bad, popped = [], []          # every array is compared before anything is raised
     for k in ("flux", "traj", "state_out", "g_x"):
         if k in got and k in want64:
             tol = _flux_tol if k != "g_x" else (lambda b: _grad_tol(b, np.arange(b.shape[-1])))
@@ -207,8 +207,9 @@ def compare_f64(prob, got, want64, f32_evals, label, name=None):
             except AssertionError as e:
                 bad.append(str(e))
                 got.pop(k)
-    try:
-        au.compare_runs(prob, got, want64, label=label)
+                popped.append(k)
+    try:       # (an array that failed under `admit` is reported by that failure, not compared again)
+        au.compare_runs(prob, got, {k: v for k, v in want64.items() if k not in popped}, label=label)
     except AssertionError as e:
         bad.append(str(e))
     assert not bad, " | ".join(bad)

@@ -48,7 +48,7 @@ def masks_for(model: str, cfg, B: int, torch_seed=None) -> dict:
 
 
 def run_inputs(model: str, cfg, inp: dict, masks: dict, dtype=torch.float64, device="cpu", dirs=None,
-               grad_leaves=(), states=None, aux=None):
+               grad_leaves=(), states=None, aux=None, events=None):
     """hbv_restate64.run on the numpy inputs `inp` (golden_cases.build_inputs form) cast to `dtype`.  `dirs`: input
     name -> tangent (those inputs become duals of the caller's forward-AD level); `grad_leaves`: input names that
     require grad.  Returns (outputs, states, leaves by name)."""
@@ -69,18 +69,20 @@ def run_inputs(model: str, cfg, inp: dict, masks: dict, dtype=torch.float64, dev
     else:
         params = arg("parameters")
     mu = arg("muwts") if "muwts" in inp else None
-    out, st = restate().run(model, arg("x_phy"), params, masks=masks, muwts=mu, states=states, aux=aux,
-                                 **kw, **extra)
+    if states is None and "states0" in inp:      # storages loaded into a cache_states module before the call
+        states = tuple(torch.as_tensor(np.asarray(inp["states0"])).to(device=device, dtype=dtype))
+    out, st = restate().run(model, arg("x_phy"), params, masks=masks, muwts=mu, states=states, aux=aux, events=events,
+                            **kw, **extra)
     return out, st, leaves
 
 
-def case_reverse(name: str, dtype=torch.float64) -> dict:
+def case_reverse(name: str, dtype=torch.float64, events=None) -> dict:
     """Outputs, storages and (for a case with a loss) the loss gradients of golden case `name`, keyed as the fixture
-    tests/golden/<name>.npz is."""
+    tests/golden/<name>.npz is.  `events`: see hbv_restate64._pbm / pbm_hourly (a two-call case records none)."""
     spec = gc.CASES[name]
     model, cfg = spec["model"], spec["config"]
     if model == "Hbv_2_hourly":
-        return hourly_case_reverse(name, dtype)
+        return hourly_case_reverse(name, dtype, events)
     inp = gc.build_inputs(name)
     res = {}
     if spec.get("two_call"):          # cache_states: the second call starts from the storages the first one left
@@ -100,7 +102,7 @@ def case_reverse(name: str, dtype=torch.float64) -> dict:
     if spec.get("x_grad"):
         leaves.append("x_phy")
     keys = gc.loss_keys(name)
-    out, st, lv = run_inputs(model, cfg, inp, masks, dtype, grad_leaves=leaves if keys else ())
+    out, st, lv = run_inputs(model, cfg, inp, masks, dtype, grad_leaves=leaves if keys else (), events=events)
     res.update({f"out/{k}": v.detach().numpy() for k, v in out.items()})
     res["states"] = torch.stack([s.detach() for s in st]).numpy()
     if keys:
@@ -184,6 +186,71 @@ def abi_hourly(prob: dict, dtype=torch.float64, x_grad: bool = True, backward: b
            "state_out": (torch.stack([ser[k][-1].detach() for k in range(5)]) if T else torch.stack(st)).numpy()}
     if backward:
         (flux * torch.from_numpy(prob["gflux"]).to(dtype)).sum().backward()
+        res["g_params"] = raw.grad.numpy()
+        if x_grad:
+            res["g_x"] = x.grad.numpy()
+        if mu is not None:
+            res["g_muwts"] = mu.grad.numpy()
+    return res
+
+
+def abi_daily(prob: dict, dtype=torch.float64, x_grad: bool = True, backward: bool = True, events=None) -> dict:
+    """An abi_util.make_problem dict of a daily model (Hbv, Hbv_1_1p, Hbv_2) through the restatement at the level of the
+    C ABI, in `dtype`: raw parameters [T,B,ny] through the sigmoid (static value = row T-1, dynamic rows where the
+    parameter is dynamic and its basin not dropped), forcing channels prob["channels"], storages carried in from
+    prob["state_in"], the 11 / 12 flux rows (means over the members; Qsim weighted by muwts where given), with
+    prob["routing"] the four 15-tap routed rows (Qsim, Q0, Q1, Q2 through hbv_restate64.gamma_uh / route, routing
+    columns from row T-1 with run_problem's RouteSource bounds), and the loss sum(flux * gflux) + sum(routed * grouted)
+    as abi_util.run_problem forms it.  Returns run_problem's keys: flux, routed, traj [5,T+1,B*M], state_out [5,B,M],
+    g_params, g_x, g_muwts (float64 numpy).  `events`: see hbv_restate64._pbm."""
+    from .abi_util import BOUNDS
+    R = restate()
+    model, T, B, M, names = prob["model"], prob["T"], prob["B"], prob["M"], prob["names"]
+    assert model in R.MODELS, model
+    x = torch.from_numpy(prob["x"]).to(dtype).requires_grad_(x_grad and backward)
+    raw = torch.from_numpy(prob["params"]).to(dtype).requires_grad_(backward)
+    mu = torch.from_numpy(prob["muwts"]).to(dtype).requires_grad_(backward) if "muwts" in prob else None
+    ac = torch.from_numpy(prob["ac"]).to(dtype) if "ac" in prob else None
+    elev = torch.from_numpy(prob["elev"]).to(dtype) if "elev" in prob else None
+    unit = torch.sigmoid(raw[:, :, :len(names) * M]).reshape(T, B, len(names), M)
+    par = {}
+    for i, nm in enumerate(names):
+        lo, hi = BOUNDS[nm]
+        v = unit[-1, :, i, :].unsqueeze(0).expand(T, B, M)
+        if nm in prob["dyn"]:
+            dyn = unit[:, :, i, :]
+            if "drop" in prob:
+                m = torch.from_numpy(prob["drop"][prob["dyn"].index(nm)].astype(np.float64)).to(dtype).view(1, B, 1)
+                dyn = dyn * (1 - m) + v * m
+            v = dyn
+        par[nm] = v * (hi - lo) + lo
+    if "state_in" in prob:
+        st = tuple(torch.from_numpy(prob["state_in"][k]).to(dtype) for k in range(5))
+    else:
+        st = tuple(torch.full((B, M), 0.001, dtype=dtype) for _ in range(5))
+    ch = prob.get("channels", (0, 1, 2))
+    s, st_out, ser = R._pbm(model, x[:, :, ch[0]], x[:, :, ch[1]], x[:, :, ch[2]], par, st, 1e-5, ac, elev, events,
+                            want_series=True)
+    order = ["Qsim", "Q0", "Q1", "Q2", "AET", "SWE", "recharge", "excs", "evapfactor", "tosoil", "PERC"]
+    if model != "Hbv":
+        order.append("capillary")
+    rows = [s[k].mean(-1) for k in order]
+    if mu is not None:
+        rows[0] = (s["Qsim"] * mu).sum(-1)
+    flux = torch.stack(rows)
+    traj = torch.stack([torch.cat([st[k].unsqueeze(0), ser[k].detach()]).reshape(T + 1, B * M) for k in range(5)])
+    res = {"flux": flux.detach().numpy(), "traj": traj.numpy(),
+           "state_out": torch.stack([v.detach() for v in st_out]).numpy()}
+    loss = (flux * torch.from_numpy(prob["gflux"]).to(dtype)).sum()
+    if prob["routing"]:
+        n = len(names)
+        ab = torch.sigmoid(raw[-1, :, n * M:n * M + 2])
+        uh = R.gamma_uh(ab[:, 0] * 2.9, ab[:, 1] * 6.5, min(T, 15))
+        routed = torch.stack([R.route(flux[k], uh) for k in range(4)])
+        res["routed"] = routed.detach().numpy()
+        loss = loss + (routed * torch.from_numpy(prob["grouted"]).to(dtype)).sum()
+    if backward:
+        loss.backward()
         res["g_params"] = raw.grad.numpy()
         if x_grad:
             res["g_x"] = x.grad.numpy()

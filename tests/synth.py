@@ -46,15 +46,16 @@ def normalish(shape, seed: int, stream: int = 0) -> np.ndarray:
     return ((acc - 2.0) * 1.734375).astype(np.float32)
 
 
-def forcing(T: int, B: int, seed: int, cold: bool = False) -> np.ndarray:
+def forcing(T: int, B: int, seed: int, cold: bool = False, day0: float = 0.0) -> np.ndarray:
     """CAMELS-shaped synthetic forcing [T,B,3] (prcp mm/d, tmean degC, pet mm/d).
 
     ~30 % wet days, temperature with a triangular seasonal cycle that crosses
     the parTT range [-2.5, 2.5] so both rain and snow branches are exercised.
-    cold=True forces a cold, dry start (ties: melt = SNOWPACK = 0).
+    cold=True forces a cold, dry start (ties: melt = SNOWPACK = 0).  Row t is day `day0` + t of the year (day 0 is
+    midwinter, where PET is exactly 0 on half of the days).
     """
     u = uniform((T, B, 3), seed, 1).astype(np.float64)
-    day = np.arange(T, dtype=np.float64)[:, None]
+    day = np.arange(T, dtype=np.float64)[:, None] + day0
     phase = (day % 365.0) / 365.0
     tri = np.where(phase < 0.5, 4.0 * phase - 1.0, 3.0 - 4.0 * phase)  # [-1,1]
     boff = uniform((1, B), seed, 2).astype(np.float64) * 20.0 - 8.0

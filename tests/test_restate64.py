@@ -17,7 +17,8 @@ from . import restate_util as ru
 from .helpers import GOLDEN_DIR, compare, load_golden
 from .test_jvp_gpu import BFI_ATOL_REL, TAN_FLOOR, _assert_tangent_close
 
-# every golden case of the three daily models (hbv_cache_states included: two calls, storages carried across) and of
+# every golden case of the three daily models (hbv_cache_states included: two calls, storages carried across; the
+# three that start wet, with storages loaded into a cache_states module) and of
 # the hourly model (the five dry ones and the three that start wet under storm forcing)
 DAILY = [n for n, s in gc.CASES.items() if s["model"] in ("Hbv", "Hbv_1_1p", "Hbv_2")]
 HOURLY = [n for n, s in gc.CASES.items() if s["model"] == "Hbv_2_hourly"]
@@ -26,7 +27,7 @@ CASES = DAILY + HOURLY
 
 def test_scope():
     """The restatement's scope is every Hbv / Hbv_1_1p / Hbv_2 / Hbv_2_hourly fixture, and every forward-mode fixture."""
-    assert len(DAILY) == 33 and len(HOURLY) == 8 and set(gj.JVP_CASES) <= set(DAILY)
+    assert len(DAILY) == 36 and len(HOURLY) == 8 and set(gj.JVP_CASES) <= set(DAILY)
     assert len(CASES) == len(gc.CASES)
 
 
@@ -48,7 +49,15 @@ def test_scope():
 #    0.0352803 (box 71.96) and hour 101 0.2545896 vs 0.2545463 (48.19); hourly_wet_muwts SUZ hours 159 / 188 / 199
 #    0.0846214 vs 0.0846471 (45.58), 0.2950842 vs 0.2950192 (113.49), 0.0558768 vs 0.0558525 (32.23).  Same bound:
 #    1e-5 x the member's largest value of that storage.  (hourly_wet_dyn3_drop has no such element.)
+#  * hbv_wet_dyn3, d loss / d P of day 76 on basin 3 (P = 0): on day 75 evaporation takes all of member 1's soil moisture
+#    (AET = SM < PET * ef) and SM is set to its floor, nearzero = 1e-5.  On day 76 no rain falls and PET * ef is 1.5e-16 mm (FC 61.8, LP 0.226, BETAET 2.68):
+#    in float64 SM - AET is below the floor by that much, the floor acts again and stops the gradient; in float32
+#    1e-5 - 1.5e-16 is 1e-5, the floor does not act and the gradient passes.  float64 -0.0926111, the reference and the
+#    float32 restatement -0.1782486: the two one-sided values of a clamp met exactly at its corner.  Nothing else differs.
+#    Bound ("jump", ...): the jump of the float64 value across the corner, |-0.0926111 - (-0.1782486)| = 0.0856375, the
+#    other side taken from the float32 restatement run.
 PRECISION_ONLY = {
+    "hbv_wet_dyn3": [("grad/x_phy", (76, 3, 0), ("jump", 0.0856375))],
     "hbv11p_long_dyn_all": [("grad/parameters", (slice(None), 4, slice(4, 14 * 16, 16)), None)],
     "hbv2_long_routing": [("states", (0, 180, 5, 2), 1e-5)],
     "hbv2_long_dyn3": [("states", (0, 187, 5, 10), 1e-5)],
@@ -69,7 +78,9 @@ def test_restatement_matches_reference(name):
         res = dict(res)
         for key, idx, bound in PRECISION_ONLY[name]:
             got, want = res[key][idx], ref[key][idx]
-            if bound is not None:      # a storage element: within `bound` x the member's largest value of that storage
+            if isinstance(bound, tuple):       # a tie: within the jump of the float64 value across it
+                assert abs(float(got) - float(want)) <= bound[1] * (1 + 1e-3), (name, got, want, bound)
+            elif bound is not None:      # a storage element: within `bound` x the member's largest value of that storage
                 scale = float(np.abs(ref[key][(idx[0], slice(None)) + tuple(idx[2:])]).max())
                 assert abs(float(got) - float(want)) <= bound * scale, (name, got, want, scale)
             res[key] = res[key].copy()
