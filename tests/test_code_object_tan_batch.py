@@ -1,10 +1,10 @@
-"""CPU tier: the built gfx950 code of the batched tangent-linear kernel (hbvx.hip, k_fwd_tan_batch<MODEL, BETAET, DL>).
-Only DL = 1 is built (one direction per lane is what the measurements left, profiles/r07_jvp_batch.md): an instance
-fits the register file of one wave (512 VGPRs), nothing spills (no scratch traffic in the day loop), and, since the
-directions are resident waves beside each other, it keeps the one-direction kernel's occupancy.  The
-one-direction kernel beside it keeps the figures of DESIGN.md §0 F1."""
+"""CPU tier: the built gfx950 code of the tangent-linear kernels (hbvx.hip).  k_fwd_tan_batch<MODEL, BETAET> carries one
+direction per lane (what the measurements left, profiles/r07_jvp_batch.md): an instance fits the register file of one
+wave (512 VGPRs), nothing spills (no scratch traffic in the day loop), and, since the directions are resident waves
+beside each other, it keeps the one-direction kernel's occupancy.  The one-direction kernel k_fwd_tan beside it
+(kept for its speed, profiles/r09_tan_unify.md) keeps the figures of DESIGN.md §0 F1.  k_route_tan_batch and
+k_bfi_tan_batch serve the one-direction entry points too and keep the figures of the kernels they replaced there."""
 import os
-import re
 import sys
 
 import pytest
@@ -23,31 +23,35 @@ def table():
     return {r["name"].split("(")[0]: r for r in kernel_resources.kernel_table(LIB)}
 
 
+# waves per SIMD of k_fwd_tan<MODEL, BETAET>, which an instance of the batch kernel must keep (profiles/r07_jvp_batch.md)
+WAVES_PER_SIMD = {"<0, false>": 3, "<0, true>": 3, "<1, true>": 2, "<2, true>": 2}
+
+
 def test_batch_instances_do_not_spill_and_fit_one_wave(table):
     names = [n for n in table if "k_fwd_tan_batch<" in n]
-    dls = sorted({int(re.search(r", (\d+)>$", n).group(1)) for n in names})
-    assert dls == [1], names                            # the instances that lost the measurement are not shipped
-    assert len(names) == 4, names                       # HBV 1.0 with and without parBETAET, 1.1p, 2.0
+    # HBV 1.0 with and without parBETAET, 1.1p, 2.0; no directions-per-lane argument (those instances lost, ibid.)
+    assert sorted(n[n.index("<"):] for n in names) == sorted(WAVES_PER_SIMD), names
     for n in names:
         r = table[n]
         assert r["vgpr_spill"] == 0 and r["scratch"] == 0, (n, r)       # nothing goes to memory
         assert r["vgpr"] + r["agpr"] <= 512, (n, r["vgpr"], r["agpr"])
-        assert r["waves_per_simd"] >= 1, (n, r)
-        one = table[n.replace("k_fwd_tan_batch<", "k_fwd_tan<")[:-len(", 1>")] + ">"]
-        assert r["waves_per_simd"] == one["waves_per_simd"], (n, r["vgpr"], one["vgpr"])
+        one = table[n.replace("k_fwd_tan_batch<", "k_fwd_tan<")]
+        assert r["waves_per_simd"] == one["waves_per_simd"] == WAVES_PER_SIMD[n[n.index("<"):]], (n, r["vgpr"], one["vgpr"])
         assert r["lds"] == 0, (n, r["lds"])             # the ensemble sum is a butterfly over lanes
 
 
-def test_route_and_bfi_batch_kernels_match_their_one_direction_siblings(table):
-    for one, many in (("k_route_tan", "k_route_tan_batch"), ("k_bfi_tan", "k_bfi_tan_batch")):
-        a, b = table[one], table[many]
-        assert b["vgpr_spill"] == 0 and b["scratch"] == 0, (many, b)
-        assert b["vgpr"] == a["vgpr"] and b["lds"] == a["lds"], (one, a, many, b)
+def test_route_and_bfi_kernels_keep_the_one_direction_figures(table):
+    """k_route_tan had 102 VGPRs and no LDS, k_bfi_tan 20 VGPRs and 16 KB of LDS; neither is built any more."""
+    for name, vgpr, lds in (("k_route_tan_batch", 102, 0), ("k_bfi_tan_batch", 20, 16384)):
+        r = table[name]
+        assert r["vgpr_spill"] == 0 and r["scratch"] == 0, (name, r)
+        assert r["vgpr"] == vgpr and r["lds"] == lds, (name, r)
+    assert "k_route_tan" not in table and "k_bfi_tan" not in table
 
 
 def test_one_direction_kernels_keep_their_registers(table):
-    names = [n for n in table if "k_fwd_tan<" in n]
-    assert len(names) == 4, names
+    names = [n for n in table if "k_fwd_tan<" in n or "k_fwd_tan_batch<" in n]
+    assert len(names) == 8, names
     for n in names:
         r = table[n]
         assert r["vgpr_spill"] == 0 and r["scratch"] == 0, (n, r)

@@ -1,11 +1,12 @@
-"""GPU tier: the tangent kernels (k_fwd_tan, k_route_tan, k_bfi_tan behind Hbv, Hbv_1_1p and Hbv_2 under
-torch.autograd.forward_ad) against forward AD of oracle/hbv_restate64.py in float64 on the same float32 inputs, at
-_assert_tangent_close's default tolerance (rtol 1e-3, atol 2e-6 x max|float64 tangent| of the key) -- BFI included.
+"""GPU tier: the tangent kernels (k_fwd_tan, and k_route_tan_batch, k_bfi_tan_batch at one direction, behind Hbv,
+Hbv_1_1p and Hbv_2 under torch.autograd.forward_ad) against forward AD of oracle/hbv_restate64.py in float64 on the
+same float32 inputs, at _assert_tangent_close's default tolerance (rtol 1e-3, atol 2e-6 x max|float64 tangent| of the
+key) -- BFI included.
 
 (a') the 22 forward-mode fixture cases of test_jvp_gpu.py (a) against float64 (there BFI is held to 1e-2 only,
      the reference's own float32 BFI tangent being off by up to 8e-3);
 (g)  a fixed-seed slice of tools/fuzz_jvp.py: 32 draws over model, M in {1,3,5,8,16,32,64}, B in {1,17,67,130}
-     (k_bfi_tan's 16-basin and k_route_tan's 64-basin blocks with a partial last block), T in {2,9,33,129,400}
+     (k_bfi_tan_batch's 16-basin and k_route_tan_batch's 64-basin blocks with a partial last block), T in {2,9,33,129,400}
      (a short unit hydrograph, idle BFI slices, several route chunks), warm-up with and without states, dy_drop,
      muwts of every accepted shape, permuted `variables`, Hbv_2 routing on and off across the ac / elevation
      switches, tangents on each input alone and on all at once, non-contiguous inputs; its coverage is printed
@@ -186,7 +187,7 @@ def test_linearity_and_determinism_large():
 @pytest.mark.parametrize("member", ["p_dyn", "p_sta"])
 def test_hbv2_routing_tangent_on_one_tuple_member(member):
     """Hbv_2 with routing: a tangent on one member of (p_dyn, p_sta) only -- with p_dyn alone the routing parameters'
-    tangent comes from a member that has none (ops._hbv_tangent passes a null pointer to k_route_tan)."""
+    tangent comes from a member that has none (ops._hbv_tangent passes a null pointer to k_route_tan_batch)."""
     spec = dict(model="Hbv_2", M=4, B=67, T=129, dyn=["parK0", "parBETA"], seed=4242, torch_seed=3, dy_drop=0.0,
                 variables=["prcp", "tmean", "pet"], cold=False, raw_scale=1.0, routing=True, warm_up=0,
                 warm_up_states=True, muwts=None, tangent=member, noncontig=[])
