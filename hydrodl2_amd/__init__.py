@@ -8,8 +8,9 @@ C ABI of include/hbvx.h.  See DESIGN.md.
 from hydrodl2_amd.api import available_models, available_modules, load_model, load_module
 from hydrodl2_amd.sensitivity import jvp_batch, parameter_jacobian
 from hydrodl2_amd.lstm import lstm_jvp_batch
+from hydrodl2_amd.hourly_jvp import hourly_jvp_batch
 
 __version__ = "0.1.0"
 
 __all__ = ["__version__", "available_models", "available_modules", "load_model", "load_module", "jvp_batch",
-           "parameter_jacobian", "lstm_jvp_batch"]
+           "parameter_jacobian", "lstm_jvp_batch", "hourly_jvp_batch"]

@@ -130,7 +130,9 @@ EXPORTS = ["hbvx_zero", "hbvx_zero_except", "hbvx_preferred_traj_layout", "hbvx_
 # HbvxError naming it.
 OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forward_tangent", "hbvx_route_tangent",
                     "hbvx_bfi_tangent", "hbvx_lstm_tangent", "hbvx_forward_tangent_batch", "hbvx_route_tangent_batch",
-                    "hbvx_bfi_tangent_batch", "hbvx_lstm_tangent_batch", "hbvx_lstm_tangent_batch_workspace_bytes"]
+                    "hbvx_bfi_tangent_batch", "hbvx_lstm_tangent_batch", "hbvx_lstm_tangent_batch_workspace_bytes",
+                    "hbvx_hourly_tangent_batch", "hbvx_gage_route_tangent_batch",
+                    "hbvx_gage_route_tangent_workspace_bytes"]
 
 
 class HbvxError(RuntimeError):
@@ -249,6 +251,18 @@ class Library:
             d.hbvx_bfi_tangent_batch.restype = C.c_int
             d.hbvx_bfi_tangent_batch.argtypes = [C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_int64,
                                                  C.c_float, _fp, C.c_void_p]
+        if "hbvx_hourly_tangent_batch" not in self.missing:
+            d.hbvx_hourly_tangent_batch.restype = C.c_int
+            d.hbvx_hourly_tangent_batch.argtypes = [C.POINTER(Desc), C.POINTER(TanBatch), C.c_void_p]
+            if d.hbvx_sizeof(8) != C.sizeof(TanBatch):
+                raise HbvxError(f"{path}: layout mismatch for TanBatch: {d.hbvx_sizeof(8)} != {C.sizeof(TanBatch)}")
+        if "hbvx_gage_route_tangent_workspace_bytes" not in self.missing:
+            d.hbvx_gage_route_tangent_workspace_bytes.restype = C.c_uint64
+            d.hbvx_gage_route_tangent_workspace_bytes.argtypes = [C.POINTER(GageDesc), C.c_int32]
+        if "hbvx_gage_route_tangent_batch" not in self.missing:
+            d.hbvx_gage_route_tangent_batch.restype = C.c_int
+            d.hbvx_gage_route_tangent_batch.argtypes = [C.POINTER(GageDesc), C.c_int32, _fp, _fp, _fp, C.c_int64, _fp,
+                                                        C.c_int64, _fp, C.c_void_p, C.c_uint64, C.c_void_p]
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -403,6 +417,22 @@ class Library:
         self.require("hbvx_bfi_tangent_batch")
         self._check(self.dll.hbvx_bfi_tangent_batch(T, B, n_dir, qs, q2, qs_dot, q2_dot, dot_ds, C.c_float(nearzero),
                                                     out, C.c_void_p(stream)), "hbvx_bfi_tangent_batch")
+
+    def hourly_tangent_batch(self, desc: Desc, tb: TanBatch, stream: int):
+        self.require("hbvx_hourly_tangent_batch")
+        self._check(self.dll.hbvx_hourly_tangent_batch(C.byref(desc), C.byref(tb), C.c_void_p(stream)),
+                    "hbvx_hourly_tangent_batch")
+
+    def gage_route_tangent_workspace_bytes(self, r: GageDesc, n_dir: int) -> int:
+        self.require("hbvx_gage_route_tangent_workspace_bytes")
+        return int(self.dll.hbvx_gage_route_tangent_workspace_bytes(C.byref(r), n_dir))
+
+    def gage_route_tangent_batch(self, r: GageDesc, n_dir: int, qs: int, uh: int, qs_dot, qs_dot_ds: int, dp_dot,
+                                 dp_dot_ds: int, out_dot: int, ws, ws_bytes: int, stream: int):
+        self.require("hbvx_gage_route_tangent_batch")
+        self._check(self.dll.hbvx_gage_route_tangent_batch(C.byref(r), n_dir, qs, uh, qs_dot, qs_dot_ds, dp_dot,
+                                                           dp_dot_ds, out_dot, ws, C.c_uint64(ws_bytes),
+                                                           C.c_void_p(stream)), "hbvx_gage_route_tangent_batch")
 
     def lstm_check(self, r: LstmDesc, ws, stream: int):
         self._check(self.dll.hbvx_lstm_check(C.byref(r), ws, C.c_void_p(stream)), "hbvx_lstm_check")

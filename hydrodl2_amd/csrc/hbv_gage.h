@@ -346,4 +346,138 @@ __global__ void __launch_bounds__(GAGE_TILE) k_gage_bwd_p(const hbvx_gage_desc r
     gdp[p * 3 + 2] = (r.lag_uh ? gf : 0.0f) * (r.tau_hi - r.tau_lo);
 }
 
+// ---- tangent of the routing (forward mode, several directions) ------------------------------------------------
+// Routing is bilinear in (qs, uh): out_dot = Route(qs_dot; uh) + Route(qs; uh_dot).
+//
+// k_gage_uh_tan: uh_dot [nd,NPAIR,L] from dp_dot (direction d of pair p at dpd + d * dpd_ds + 3 p), the forward
+// counterpart of the closed-form chain at the end of k_gage_bwd_p: normalised taps
+//   d w_k = w_k ((ln t_k - sum_j w_j ln t_j) d aa + (t_k - sum_j w_j t_j) / theta^2 d theta),
+// through the shift (1-f) w[k-kk] + f w[k-kk-1] with zero padding, d / d tau = w[k-kk-1] - w[k-kk] (the floor
+// contributes nothing), relu's slope 0 at 0, chained to the unit-interval inputs by (hi - lo).  One block per pair,
+// one thread per tap; the pair's taps and their two means are formed once (thread 0 adds in tap order) and every
+// direction of the slab reuses them.
+__global__ void __launch_bounds__(128) k_gage_uh_tan(const hbvx_gage_desc r, int nd, const float *__restrict__ dpd,
+                                                      int64_t dpd_ds, float *__restrict__ uhd)
+{
+    __shared__ float w[GAGE_L], t1[GAGE_L], t2[GAGE_L], dw[GAGE_L];
+    __shared__ float s_sc[3];
+    const int p = blockIdx.x, k = threadIdx.x;
+    const int L = r.L;
+    const bool tap = k < L;
+    const GagePair g = gage_pair(r, p);
+    if (tap) w[k] = gamma_tap(g, expf(lgammaf(g.aa)) * powf(g.theta, g.aa), k);
+    __syncthreads();
+    if (k == 0) {
+        float sum = 0.0f;
+        for (int j = 0; j < L; j++) sum += w[j];
+        s_sc[0] = sum;
+    }
+    __syncthreads();
+    const float tj = (float)k + 0.5f;
+    float wj = 0.0f, lt = 0.0f;
+    if (tap) {
+        wj = w[k] / s_sc[0];
+        lt = logf(tj);
+        t1[k] = wj * lt;
+        t2[k] = wj * tj;
+    }
+    __syncthreads();
+    if (tap) w[k] = wj;                         // the normalised taps, for the tau term
+    if (k == 0) {
+        float mlt = 0.0f, mt = 0.0f;
+        for (int j = 0; j < L; j++) {
+            mlt += t1[j];
+            mt += t2[j];
+        }
+        s_sc[1] = mlt;
+        s_sc[2] = mt;
+    }
+    __syncthreads();
+    const float ca = tap ? wj * (lt - s_sc[1]) : 0.0f;                                  // d w_k / d aa
+    const float cb = tap ? wj * (tj - s_sc[2]) / (g.theta * g.theta) : 0.0f;           // d w_k / d theta
+    const int kk = (int)g.kk;
+    const int i0 = k - kk, i1 = k - kk - 1;
+    const bool in0 = i0 >= 0 && i0 <= L - 1, in1 = i1 >= 0 && i1 <= L - 1;
+    const float ctau = (tap && r.lag_uh) ? (in1 ? w[i1] : 0.0f) - (in0 ? w[i0] : 0.0f) : 0.0f;
+    for (int d = 0; d < nd; d++) {
+        const float *v = dpd + d * dpd_ds + (int64_t)p * 3;
+        const float daa = ((g.a > 0.0f) ? v[0] : 0.0f) * (r.a_hi - r.a_lo);
+        const float dth = ((g.b > 0.0f) ? v[1] : 0.0f) * (r.b_hi - r.b_lo);
+        const float dtau = r.lag_uh ? v[2] * (r.tau_hi - r.tau_lo) : 0.0f;
+        __syncthreads();
+        if (tap) dw[k] = ca * daa + cb * dth;
+        __syncthreads();
+        if (!tap) continue;
+        float *dst = uhd + ((int64_t)d * r.NPAIR + p) * L;
+        if (!r.lag_uh) {
+            dst[k] = dw[k];
+            continue;
+        }
+        const float d0 = in0 ? dw[i0] : 0.0f, d1 = in1 ? dw[i1] : 0.0f;
+        dst[k] = ((1.0f - g.f) * d0 + g.f * d1) + ctau * dtau;
+    }
+}
+
+// k_gage_lag_tan: k_gage_lag_fwd with a direction axis (blockIdx.z) and both products in one lag series,
+//   lag[d][p][t] = sum_k uh[p,k] qs_dot[d][t-k,unit(p)] areas + sum_k uh_dot[d][p,k] qs[t-k,unit(p)] areas,
+// the first sum's taps in ascending order, then the second's, into the same accumulators.  A NULL qdT or uhd skips
+// its sum.  qdT [nd,U,T] and uhd [nd,NPAIR,L] are the slab's; qsT [U,T] and uh [NPAIR,L] the primal's.
+__global__ void __launch_bounds__(GAGE_TILE) k_gage_lag_tan(const hbvx_gage_desc r, const float *__restrict__ qsT,
+                                                             const float *__restrict__ uh, const float *__restrict__ qdT,
+                                                             const float *__restrict__ uhd, float *__restrict__ lag)
+{
+    __shared__ __align__(16) float col[GAGE_COLN];
+    __shared__ __align__(16) float wsh[GAGE_L + 4];
+    const int p = blockIdx.x, t0 = blockIdx.y * GAGE_TILE4, tid = threadIdx.x;
+    const int64_t d = blockIdx.z;
+    const int T = r.T, L = r.L, nblk = (L + 3) >> 2;
+    const int u = clampi_(r.pair_unit[p], 0, r.U - 1);
+    const float ar = r.areas[u];
+    float y0 = 0.0f, y1 = 0.0f, y2 = 0.0f, y3 = 0.0f;
+#pragma unroll 1
+    for (int side = 0; side < 2; side++) {
+        const float *src = side == 0 ? (qdT ? qdT + (d * r.U + u) * T : nullptr) : (uhd ? qsT + (int64_t)u * T : nullptr);
+        if (!src) continue;                     // uniform over the grid
+        const float *w = side == 0 ? uh + (int64_t)p * L : uhd + (d * r.NPAIR + p) * L;
+        __syncthreads();
+        for (int x = tid; x < GAGE_TILE4 + 4 * nblk; x += GAGE_TILE) {
+            const int ts = t0 - 4 * nblk + x;
+            col[x] = (ts >= 0 && ts < T) ? src[ts] * ar : 0.0f;
+        }
+        gage_stage_weights(wsh, w, L);
+        __syncthreads();
+        const float4 *c4 = reinterpret_cast<const float4 *>(col) + tid + nblk;
+        float4 cur = c4[0];
+        for (int b = 0; b < nblk; b++) {
+            const float4 nxt = c4[-b - 1];
+            const float4 g = reinterpret_cast<const float4 *>(wsh)[b];
+            y0 += g.x * cur.x; y0 += g.y * nxt.w; y0 += g.z * nxt.z; y0 += g.w * nxt.y;
+            y1 += g.x * cur.y; y1 += g.y * cur.x; y1 += g.z * nxt.w; y1 += g.w * nxt.z;
+            y2 += g.x * cur.z; y2 += g.y * cur.y; y2 += g.z * cur.x; y2 += g.w * nxt.w;
+            y3 += g.x * cur.w; y3 += g.y * cur.z; y3 += g.z * cur.y; y3 += g.w * cur.x;
+            cur = nxt;
+        }
+    }
+    const int t = t0 + tid * 4;
+    float *dst = lag + (d * r.NPAIR + p) * T + t;
+    if (t < T) dst[0] = y0;
+    if (t + 1 < T) dst[1] = y1;
+    if (t + 2 < T) dst[2] = y2;
+    if (t + 3 < T) dst[3] = y3;
+}
+
+// out_dot[d][t,g] = (sum over the pairs of gage g, in CSR order, of lag[d][p][t]) / denom[g]: k_gage_sum_fwd with
+// the direction on blockIdx.z.
+__global__ void __launch_bounds__(256) k_gage_sum_tan(const hbvx_gage_desc r, const float *__restrict__ lag,
+                                                       float *__restrict__ out)
+{
+    const int g = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+    const int64_t d = blockIdx.z;
+    if (t >= r.T) return;
+    const float *ld = lag + d * r.NPAIR * r.T;
+    float acc = 0.0f;
+    for (int p = r.gage_ptr[g]; p < r.gage_ptr[g + 1]; p++) acc += ld[(int64_t)p * r.T + t];
+    out[(d * r.T + t) * r.G + g] = acc / r.denom[g];
+}
+
 } // namespace hbvx

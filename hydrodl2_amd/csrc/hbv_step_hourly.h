@@ -332,6 +332,108 @@ struct Step<MODEL_HOURLY, BETAET_UNUSED> {
         gp[P_TT] += aTTe * mlo;
         a[0] = aSP1 * g0; a[1] = aMW * g1; a[2] = aSM * g2; a[3] = aSUZ * g3; a[4] = aSLZ * g4;
     }
+
+    // Tangent (forward-mode derivative) of fwd(), the transpose of bwd() line for line: the same predicates, tie
+    // weights and power derivatives (guard-rail masks on the incoming storages, minimum ties 1/2 each, clamps
+    // inclusive, d(x**y) = 0 at x == 0).  Reads the intermediates fwd<false>() left.  ds[5]: tangents of the
+    // storages entering the hour in, leaving it out.  dp[]: tangents of the hour's physical parameters; dx[3]: of
+    // (P, T, PET), P and PET as depths per step like the forcings themselves (the factor idt of bwd()'s gx[0] and
+    // gx[2]).  f: tangents of the hour's series.
+    HBVX_HDM void tan(const float *p, float nz, const float *dp, const float *dx, float *ds, FluxTan &f) const
+    {
+        HBVX_ADJ_FMA
+        const float dt = dt_();
+        const float idt = 24.0f;
+        const float BETA = p[P_BETA], FC = p[P_FC], K0 = p[P_K0], K1 = p[P_K1], K2 = p[P_K2],
+                    LP = p[P_LP], CFMAX = p[P_CFMAX], CFR = p[P_CFR], CWH = p[P_CWH], BE = p[P_BETAET],
+                    C = p[P_C], RT = p[P_RT], F0 = p[P_F0], FMIN = p[P_FMIN], ALPHA = p[P_ALPHA];
+        float wa, wb;
+        // guard rails
+        const float dSPc = ds[0] * g0, dMWc = ds[1] * g1, dSMc = ds[2] * g2, dSUZc = ds[3] * g3, dSLZc = ds[4] * g4;
+        // snow
+        const float dPr = dx[0] * idt;
+        const float dTTe = dp[P_TT] * mlo;
+        const float dRAIN = dPr * m_rain;
+        const float dSP1 = dSPc + (dPr * m_snow) * dt;
+        const float ddT = dx[1] - dTTe;
+        const float dmp = dp[P_CFMAX] * dT + CFMAX * ddT;
+        const float dmpcdt = ((mp >= 0.0f) ? dmp : 0.0f) * dt;
+        minw_(mpcdt, SP1, wa, wb);
+        const float dmelt = dmpcdt * wa + dSP1 * wb;
+        const float dMW1 = dMWc + dmelt;
+        const float dSP2 = dSP1 - dmelt;
+        const float dcc = dp[P_CFR] * CFMAX + CFR * dp[P_CFMAX];
+        const float drp = dcc * dT2 + cc * (dTTe - dx[1]);
+        const float drpcdt = ((rp >= 0.0f) ? drp : 0.0f) * dt;
+        minw_(rpcdt, MW1, wa, wb);
+        const float drefr = drpcdt * wa + dMW1 * wb;
+        const float dSP3 = dSP2 + drefr;
+        const float dMW2 = dMW1 - drefr;
+        const float dts0 = (dMW2 - (dp[P_CWH] * SP3 + CWH * dSP3)) * idt;
+        const float dtosoil = (ts0 >= 0.0f) ? dts0 : 0.0f;
+        const float dMW3 = dMW2 - dtosoil * dt;
+        // infiltration capacity
+        const float dW = dRAIN + dtosoil;
+        const float dr = div_approx_(dSMc - r * dp[P_FC], FC);
+        const float dsc = (r >= 0.0f && r <= (float)(1.0 - 0.01)) ? dr : 0.0f;
+        const float dfminF = dp[P_FMIN] * F0 + FMIN * dp[P_F0];
+        const float dpw = (pw * log_fast_(oms)) * dp[P_ALPHA] - (ALPHA * div_approx_(pw, oms)) * dsc; // oms >= 0.01
+        const float dfcap = (dfminF + (dp[P_F0] - dfminF) * pw) + (F0 - fminF) * dpw;
+        minw_(W, fcap, wa, wb);
+        const float dinfil = dW * wa + dfcap * wb;
+        const float dIE = (ie0 >= 0.0f) ? dW - dfcap : 0.0f;
+        // soil
+        const float kr = (r > 0.0f) ? BETA * div_approx_(sw0, r) : 0.0f;
+        const float kb = (r > 0.0f) ? sw0 * log_fast_(r) : 0.0f;
+        const float dsw0 = kr * dr + kb * dp[P_BETA];
+        const float dsw = (sw0 >= 0.0f && sw0 <= 1.0f) ? dsw0 : 0.0f;
+        const float drech = dinfil * sw + infil * dsw;
+        const float dSM1 = dSMc + (dinfil - drech) * dt;
+        // excess
+        const float dexc = (e0 >= 0.0f) ? (dSM1 - dp[P_FC]) * idt : 0.0f;
+        const float dSM2 = dSM1 - dexc * dt;
+        // evapotranspiration
+        const float dlpfc = dp[P_LP] * FC + LP * dp[P_FC];
+        const float dq = div_approx_(dSM2 - q * dlpfc, lpfc);
+        const float kq = (q > 0.0f) ? BE * div_approx_(ef0, q) : 0.0f;
+        const float ke = (q > 0.0f) ? ef0 * log_fast_(q) : 0.0f;
+        const float def0 = kq * dq + ke * dp[P_BETAET];
+        const float def = (ef0 >= 0.0f && ef0 <= 1.0f) ? def0 : 0.0f;
+        const float dpedt = ((dx[2] * idt) * ef + PETr * def) * dt;
+        minw_(SM2, pedt, wa, wb);
+        const float dET = (dSM2 * wa + dpedt * wb) * idt;
+        const float dSM3 = (dd >= nz) ? dSM2 - dET * dt : 0.0f;
+        // capillary rise
+        const float dx1 = div_approx_(dSM3 - x1 * dp[P_FC], FC);
+        const float drc = (x1 <= 1.0f) ? dx1 : 0.0f;
+        const float dcs = dp[P_C] * SLZc + C * dSLZc;
+        const float dcapp = (dcs * om - cs * drc) * dt;
+        minw_(SLZc, capp, wa, wb);
+        const float dcap = (dSLZc * wa + dcapp * wb) * idt;
+        const float dSM4 = (smc >= nz) ? dSM3 + dcap * dt : 0.0f;
+        const float dSLZ0 = (slc >= nz) ? dSLZc - dcap * dt : 0.0f;
+        // upper box
+        const float dSUZ1 = dSUZc + (drech + dexc) * dt;
+        minw_(SUZ1, pdt, wa, wb);
+        const float dPERC = (dSUZ1 * wa + (dp[P_PERC] * dt) * wb) * idt;
+        const float dSUZ2 = dSUZ1 - dPERC * dt;
+        const float du0c = (u0 >= 0.0f) ? dSUZ2 - dp[P_UZL] : 0.0f;
+        const float dQ0 = dp[P_K0] * u0c + K0 * du0c;
+        const float dSUZ3 = dSUZ2 - dQ0 * dt;
+        const float dQ1 = dp[P_K1] * SUZ3 + K1 * dSUZ3;
+        const float dSUZ4 = dSUZ3 - dQ1 * dt;
+        // lower box
+        const float dSLZ1 = dSLZ0 + dPERC * dt;
+        const float da1 = (a0 >= -1.0f && a0 <= 1.0f) ? -(dp[P_AC] * 0.001f) : 0.0f;
+        const float dLF = (da1 * RT + a1 * dp[P_RT]) * m1 + (ee * dp[P_RT]) * m2;
+        const float dSLZ1p = (sl >= 0.0f) ? dSLZ1 + dLF * dt : 0.0f;
+        const float dQ2 = dp[P_K2] * SLZ1p + K2 * dSLZ1p;
+        const float dSLZ2 = dSLZ1p - dQ2 * dt;
+
+        f.Q = ((dQ0 + dQ1) + dQ2) + dIE; f.Q0 = dQ0; f.Q1 = dQ1; f.Q2 = dQ2; f.ET = dET; f.SWE = dSP3; f.rech = drech;
+        f.exc = dexc; f.ef = def; f.tosoil = dtosoil; f.PERC = dPERC; f.cap = dcap;
+        ds[0] = dSP3; ds[1] = dMW3; ds[2] = dSM4; ds[3] = dSUZ4; ds[4] = dSLZ2;
+    }
 };
 
 } // namespace hbvx

@@ -103,11 +103,19 @@ class Hbv_2_hourly(HbvModule):
         """Reference: hbv_2_hourly.py:376-449.  `graph=True`: HIP-graph replay (graphed.py)."""
         if has_tangent(tuple(x_dict.values()), parameters):
             raise NotImplementedError("forward-mode AD (dual inputs) is not implemented for Hbv_2_hourly: "
-                                      "Hbv, Hbv_1_1p and Hbv_2 support it")
+                                      "Hbv, Hbv_1_1p and Hbv_2 support it; explicit directions go through "
+                                      "Hbv_2_hourly.jvp_batch")
         if self.graph and x_dict['x_phy'].is_cuda:
             from hydrodl2_amd.graphed import graphed_forward
             return graphed_forward(self, x_dict, parameters)
         return self._forward_eager(x_dict, parameters)
+
+    def jvp_batch(self, x_dict: dict[str, torch.Tensor], parameters, tangents: dict, keys=None,
+                  max_directions: Optional[int] = None):
+        """Forward-mode derivatives of 'Qs' and 'streamflow' along many directions on one primal run:
+        (outputs, tangents_out) = hydrodl2_amd.hourly_jvp_batch(self, ...), see there."""
+        from hydrodl2_amd.hourly_jvp import hourly_jvp_batch
+        return hourly_jvp_batch(self, x_dict, parameters, tangents, keys, max_directions)
 
     def _topology(self, tag, outlet_topo, areas, T, lag, bounds):
         """GageTopology of (outlet_topo, areas), built once per pair of tensor objects + versions: building it

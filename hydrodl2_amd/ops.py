@@ -887,8 +887,9 @@ def _batch_source(p: torch.Tensor, t: torch.Tensor, off: int):
 
 def hbv_tangent_batch(rec: PathRecord, D: int, x_t=None, mu_t=None, s_t=None, p_t=(), flux_mask: int = 0,
                       n_routed: int = 0, want_bfi: bool = False) -> BatchOut:
-    """Forward-mode derivative of one call of the path along D directions at once: hbvx_forward_tangent_batch,
-    hbvx_route_tangent_batch and hbvx_bfi_tangent_batch on what the forward worked on (`rec`).
+    """Forward-mode derivative of one call of the path along D directions at once: hbvx_forward_tangent_batch
+    (the hourly model: hbvx_hourly_tangent_batch), hbvx_route_tangent_batch and hbvx_bfi_tangent_batch on what the
+    forward worked on (`rec`).
 
     x_t [D, *x.shape], mu_t [D, *muwts.shape], s_t [D,5,B,M], p_t: one tangent per parameter tensor, full or compact
     (_batch_source); None: zero.  Only the flux series of `flux_mask` (bits: enum hbvx_flux) are computed and stored,
@@ -960,7 +961,10 @@ def hbv_tangent_batch(rec: PathRecord, D: int, x_t=None, mu_t=None, s_t=None, p_
     tstate = _out((D, 5, B, M), dev)
     tb.tan_flux, tb.tan_state_out = _ptr(tflux), _ptr(tstate)
     desc = _fill_desc(cfg, x, rec.state_in, rec.muwts, rec.ac, rec.elev, ptensors)
-    _call(lib, 'hbvx_forward_tangent_batch', lib.forward_tangent_batch, desc, tb, stream)
+    if cfg.model == _abi.MODEL_HOURLY:      # a kernel and an entry point of its own (include/hbvx.h)
+        _call(lib, 'hbvx_hourly_tangent_batch', lib.hourly_tangent_batch, desc, tb, stream)
+    else:
+        _call(lib, 'hbvx_forward_tangent_batch', lib.forward_tangent_batch, desc, tb, stream)
 
     troute = None
     if rs is not None:
@@ -1210,6 +1214,49 @@ class Bfi(torch.autograd.Function):
         return g_qs, g_q2, None
 
 
+class GageRecord(NamedTuple):
+    """What one call of the gage routing worked on and produced: what gage_route_tangent_batch differentiates along."""
+    topo: "GageTopology"
+    qs: torch.Tensor
+    dp: torch.Tensor
+    uh: torch.Tensor
+    out: torch.Tensor
+
+
+@contextlib.contextmanager
+def record_gage_routes():
+    """with record_gage_routes() as records: ... -- the GageRecords of the GageRoute calls this thread makes inside
+    the block, in call order (what record_paths is to the recurrence)."""
+    outer = getattr(_TAP, "gage_records", None)
+    _TAP.gage_records = records = []
+    try:
+        yield records
+    finally:
+        _TAP.gage_records = outer
+
+
+def gage_route_tangent_batch(rec: GageRecord, D: int, qs_t=None, dp_t=None) -> torch.Tensor:
+    """Forward-mode derivative of one GageRoute call along D directions: hbvx_gage_route_tangent_batch on what the
+    forward saved.  qs_t [D,T,U], dp_t [D,n_pair,3]; None: zero tangent, its term is skipped.  Returns [D,T,G]."""
+    lib = get_library()
+    topo = rec.topo
+    dev = rec.qs.device
+    for name, t, shape in (("qs_t", qs_t, (D, topo.T, topo.U)), ("dp_t", dp_t, (D, topo.n_pair, 3))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {shape}")
+    qt = None if qs_t is None else qs_t.to(torch.float32).contiguous()
+    dt = None if dp_t is None else dp_t.to(torch.float32).contiguous()
+    out = _out((D, topo.T, topo.G), dev)
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        r = topo.desc(rec.dp)
+        ws_bytes = lib.gage_route_tangent_workspace_bytes(r, D)
+        ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
+        _call(lib, 'hbvx_gage_route_tangent_batch', lib.gage_route_tangent_batch, r, D, _ptr(rec.qs), _ptr(rec.uh),
+              _ptr(qt), topo.T * topo.U if qt is not None else 0, _ptr(dt), topo.n_pair * 3 if dt is not None else 0,
+              _ptr(out), _ptr(ws), ws_bytes, _stream_of(lib, rec.qs))
+    return out
+
+
 @dataclass
 class GageTopology:
     """Index arrays of the (gage, unit) pairs of `outlet_topo == 1` (hbv_2_hourly.py:813-817), in
@@ -1289,6 +1336,9 @@ class GageRoute(torch.autograd.Function):
               _ptr(out), _ptr(ws), ws_bytes, _stream_of(lib, qs_c))
         ctx.topo = topo
         ctx.save_for_backward(qs_c, dp_c, uh)
+        tap = getattr(_TAP, "gage_records", None)
+        if tap is not None:
+            tap.append(GageRecord(topo, qs_c.detach(), dp_c.detach(), uh, out))
         return out
 
     @staticmethod

@@ -10,7 +10,11 @@ Directions that start upstream of the model -- on the inputs or weights of the p
 `SeqLSTM.jvp_batch` (hydrodl2_amd/lstm.py), whose `[D,T,B,ny]` output is a full-form 'parameters' tangent here
 (examples/input_sensitivity.py).
 
-Out of scope: `torch.func.jvp` / `jacfwd` / vmap over `make_dual`, and the hourly, implicit and multi-timescale models.
+The hourly model has an entry point of its own, `hydrodl2_amd.hourly_jvp_batch` / `Hbv_2_hourly.jvp_batch`
+(hydrodl2_amd/hourly_jvp.py): its output is gage streamflow, gages couple the units, so `jvp_batch` and
+`parameter_jacobian` here keep refusing it.
+
+Out of scope: `torch.func.jvp` / `jacfwd` / vmap over `make_dual`, and the implicit and multi-timescale models.
 """
 from __future__ import annotations
 

@@ -23,6 +23,10 @@
  *   hbvx_forward_tangent_batch, hbvx_route_tangent_batch, hbvx_bfi_tangent_batch
  *                        the same over a leading direction axis: many directions on one
  *                        primal (sensitivity series, per-basin Jacobians).
+ *   hbvx_hourly_tangent_batch, hbvx_gage_route_tangent_batch
+ *                        the same for the hourly model: the sub-daily recurrence and the gage routing, many
+ *                        directions per call (one direction is n_dir = 1).  hbvx_forward_tangent and
+ *                        hbvx_forward_tangent_batch keep refusing HBVX_MODEL_HOURLY.
  *
  * Ownership: the caller allocates and owns every buffer; the library keeps no
  * state between calls and allocates nothing persistent.  All device work is
@@ -334,7 +338,8 @@ int hbvx_gage_route_backward(const hbvx_gage_desc *r, const float *qs, const flo
 int hbvx_adj_forward(const hbvx_desc *d, const hbvx_fwd_out *out, void *stream);
 int hbvx_adj_backward(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream);
 
-/* Forward-mode derivative (tangent-linear model) of hbvx_forward, HBV 1.0 / 1.1p / 2.0 only.  One direction per call:
+/* Forward-mode derivative (tangent-linear model) of hbvx_forward, HBV 1.0 / 1.1p / 2.0 only (the hourly model:
+ * hbvx_hourly_tangent_batch below).  One direction per call:
  * given the tangents of the raw inputs, the tangents of the flux series and of the final storages.  The call re-runs
  * the primal day by day beside the five state tangents (one lane per (basin, member)); the primal outputs themselves
  * come from hbvx_forward.  hbvx_route_tangent and hbvx_bfi_tangent run the kernels of the several-direction calls
@@ -417,6 +422,27 @@ int hbvx_route_tangent_batch(const hbvx_route_desc *r, int32_t n_dir, const floa
  * bfi_dot [n_dir,B] (overwritten).  n_dir <= 65535. */
 int hbvx_bfi_tangent_batch(int32_t T, int32_t B, int32_t n_dir, const float *qs, const float *q2, const float *qs_dot,
                            const float *q2_dot, int64_t dot_d_stride, float nearzero, float *bfi_dot, void *stream);
+
+/* The hourly model (optional exports; a library may lack them).
+ * hbvx_hourly_tangent_batch is hbvx_forward_tangent_batch for HBVX_MODEL_HOURLY (any other model:
+ * HBVX_E_UNSUPPORTED): the same struct, rules and layouts, n_flux = 12, `ac` and `elev` read per basin, 19 parameters.
+ * Tangents of the forcings are depths per step, like the forcings.  One direction is n_dir = 1. */
+int hbvx_hourly_tangent_batch(const hbvx_desc *d, const hbvx_tan_batch *tb, void *stream);
+/* Tangent of hbvx_gage_route_forward over n_dir directions.  Routing is bilinear in (qs, uh):
+ *   out_dot = Route(qs_dot; uh) + Route(qs; uh_dot),
+ * uh_dot from the closed forms of the normalised gamma taps and their fractional shift (the floor of tau contributes
+ * nothing, relu's slope is 0 at 0; without lag_uh there is no tau term).  qs [T,U] and uh [NPAIR,L] are the forward
+ * call's; qs_dot of direction d at qs_dot + d * qs_dot_d_stride ([T,U] within it), dp_dot at dp_dot + d *
+ * dp_dot_d_stride ([NPAIR,3], unit-interval like hbvx_gage_desc.dp); NULL or a stride of 0: zero tangent, that term
+ * is skipped.  out_dot [n_dir,T,G] (overwritten).  n_dir in 1..65535.  No atomics: the sum over a gage's pairs keeps
+ * its fixed order, results are bit-reproducible and a direction's result does not depend on n_dir.
+ * `workspace`: caller-owned scratch of at least hbvx_gage_route_tangent_workspace_bytes(r, n_dir); the directions
+ * are processed in slabs so that it stays near 1 GiB however many there are. */
+uint64_t hbvx_gage_route_tangent_workspace_bytes(const hbvx_gage_desc *r, int32_t n_dir);
+int hbvx_gage_route_tangent_batch(const hbvx_gage_desc *r, int32_t n_dir, const float *qs, const float *uh,
+                                  const float *qs_dot, int64_t qs_dot_d_stride, const float *dp_dot,
+                                  int64_t dp_dot_d_stride, float *out_dot, void *workspace, uint64_t workspace_bytes,
+                                  void *stream);
 
 /* Zero `bytes` bytes at `ptr` (streaming non-temporal stores).  The autograd contract of the plug-in wants
  * gradient tensors shaped like the raw parameter tensor [T,B,ny] (hbv.py:211-246: static parameters read
