@@ -132,7 +132,7 @@ OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forwa
                     "hbvx_bfi_tangent", "hbvx_lstm_tangent", "hbvx_forward_tangent_batch", "hbvx_route_tangent_batch",
                     "hbvx_bfi_tangent_batch", "hbvx_lstm_tangent_batch", "hbvx_lstm_tangent_batch_workspace_bytes",
                     "hbvx_hourly_tangent_batch", "hbvx_gage_route_tangent_batch",
-                    "hbvx_gage_route_tangent_workspace_bytes"]
+                    "hbvx_gage_route_tangent_workspace_bytes", "hbvx_adj_tangent_batch"]
 
 
 class HbvxError(RuntimeError):
@@ -263,6 +263,11 @@ class Library:
             d.hbvx_gage_route_tangent_batch.restype = C.c_int
             d.hbvx_gage_route_tangent_batch.argtypes = [C.POINTER(GageDesc), C.c_int32, _fp, _fp, _fp, C.c_int64, _fp,
                                                         C.c_int64, _fp, C.c_void_p, C.c_uint64, C.c_void_p]
+        if "hbvx_adj_tangent_batch" not in self.missing:
+            d.hbvx_adj_tangent_batch.restype = C.c_int
+            d.hbvx_adj_tangent_batch.argtypes = [C.POINTER(Desc), C.POINTER(TanBatch), _fp, C.c_void_p]
+            if d.hbvx_sizeof(8) != C.sizeof(TanBatch):
+                raise HbvxError(f"{path}: layout mismatch for TanBatch: {d.hbvx_sizeof(8)} != {C.sizeof(TanBatch)}")
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -422,6 +427,11 @@ class Library:
         self.require("hbvx_hourly_tangent_batch")
         self._check(self.dll.hbvx_hourly_tangent_batch(C.byref(desc), C.byref(tb), C.c_void_p(stream)),
                     "hbvx_hourly_tangent_batch")
+
+    def adj_tangent_batch(self, desc: Desc, tb: TanBatch, traj, stream: int):
+        self.require("hbvx_adj_tangent_batch")
+        self._check(self.dll.hbvx_adj_tangent_batch(C.byref(desc), C.byref(tb), traj, C.c_void_p(stream)),
+                    "hbvx_adj_tangent_batch")
 
     def gage_route_tangent_workspace_bytes(self, r: GageDesc, n_dir: int) -> int:
         self.require("hbvx_gage_route_tangent_workspace_bytes")

@@ -227,6 +227,174 @@ __global__ void __launch_bounds__(64) k_adj_bwd(const AdjBwdArgs A)
     }
 }
 
+// ---------------------------------------------------------------------------
+// forward-mode AD of the implicit scheme over several directions (hbvx_adj_tangent_batch).
+// The implicit-function derivative is taken at the SOLVED state, so the kernel never runs Newton: per lane-day it
+// reads x_{t+1} from the trajectory hbvx_adj_forward wrote (one day ahead of its use, as the time-parallel adjoint
+// kernels do), evaluates f and df/dx there once (AdjTan::prepare: two powers, two logarithms, the quotients and the
+// pivots) and applies the result to ADJ_TAN_G directions held in registers (AdjTan::apply: multiplications and
+// additions).  Grid: (lane tiles) x (direction groups); a ragged last group skips its missing directions behind a
+// wave-uniform branch, a ragged last wave masks its stores -- nothing is padded in memory.
+//
+// Direction d's arithmetic does not depend on n_dir, on ADJ_TAN_G or on its place in a group: every copy of the
+// unrolled direction loop is the same uncontracted operation sequence on the same day coefficients, so a batched
+// result is bit-identical to the same direction at n_dir = 1.
+//
+// Static-parameter tangents live in REGISTERS, already through the chain rule (hi - lo) sigmoid'(raw) raw_dot: NP
+// VGPRs per direction.  Re-reading them each day would hit the cache (same address every day) but add NP vector
+// loads and NP chain-rule multiplications per direction and day to a loop that is a serial dependency chain; that
+// alternative was NOT built or measured.  What was measured is the group size (profiles/r11_adj_jvp.md, 671 x 16 x
+// 7300): a direction in a wave's registers costs 7.8 ms of the day loop where a wave of its own on an idle SIMD costs
+// nothing until the machine is full, so G = 4 lost to G = 2 and G = 1 at every D up to 16 (41.5 / 27.8 / 20.6 ms at
+// D = 16) and sharing the day's Jacobian only pays at D = 64 (85.6 / 62.7 / 71.6 ms), where G = 2 is the fastest.
+// G = 2 is built: the best at the width of a Jacobian piece, three waves per SIMD in the slot-list instances.
+// ---------------------------------------------------------------------------
+#ifndef ADJ_TAN_G
+#define ADJ_TAN_G 2
+#endif
+struct AdjTanArgs {
+    hbvx_desc d;
+    hbvx_tan_batch tb;
+    const float *traj;
+    int lgMp;
+};
+struct AdjTanRaw {
+    float f[3], x[5];
+};
+__device__ __forceinline__ void adj_tan_issue(const hbvx_desc &d, const float *traj, const AdjLane &L, int t, int64_t N,
+                                              AdjTanRaw &R)
+{
+    const float *xr = d.x + (int64_t)t * d.x_t_stride + (int64_t)L.b * d.x_b_stride;
+    R.f[0] = xr[d.ch_prcp]; R.f[1] = xr[d.ch_tmean]; R.f[2] = xr[d.ch_pet];
+#pragma unroll
+    for (int k = 0; k < 5; k++) R.x[k] = traj[((int64_t)k * (d.T + 1) + (t + 1)) * N + L.n];
+}
+
+// FEW: at most ADJ_FEW dynamic parameters -- the slot-list fetch of the time-parallel adjoint kernels (adj_params_few:
+// static parameters de-scaled once per lane, a day touches the listed rows only); otherwise the generic fetch, whose
+// per-slot addresses and flags take the registers of a second resident wave (it is compiled for one).
+#ifndef ADJ_TAN_WAVES
+#define ADJ_TAN_WAVES 2      // waves per SIMD the slot-list instances are compiled for
+#endif
+template <bool BETAET, bool FEW>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FEW ? ADJ_TAN_WAVES : 1)))
+k_adj_tan_batch(const AdjTanArgs A, const AdjFew F)
+{
+    constexpr int NP = BETAET ? 13 : 12;
+    constexpr int G = ADJ_TAN_G;
+    const hbvx_desc &d = A.d;
+    const hbvx_tan_batch &tb = A.tb;
+    const AdjLane L = adj_lane(d, A.lgMp);
+    const int T = d.T;
+    const int64_t N = (int64_t)d.B * d.M;
+    const bool raw = d.raw_sigmoid != 0;
+    const float invM = 1.0f / (float)d.M;
+    const int64_t dir0 = (int64_t)blockIdx.y * G;
+    const int ng = (int)min((int64_t)G, (int64_t)tb.n_dir - dir0);     // directions of this group (wave-uniform)
+    float usta[NP], dsta[G][NP];    // FEW: usta holds the static PHYSICAL values
+    bool use_dyn[FEW ? ADJ_FEW : NP];
+#pragma unroll
+    for (int i = 0; i < NP; i++) {
+        const hbvx_param_src &s = d.p[i];
+        const hbvx_param_tan &ts = tb.p[i];
+        const float v = s.sta[(int64_t)L.b * s.sta_b_stride + L.j];
+        const float us = raw ? sigmoid_(v) : v;
+        usta[i] = FEW ? descale_(us, s.lo, s.hi) : us;
+        if (!FEW) use_dyn[i] = s.dyn && !(s.drop && s.drop[L.n]);
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            float tv = 0.0f;
+            if (g < ng && ts.sta) tv = ts.sta[(dir0 + g) * tb.sta_d_stride[i] + (int64_t)L.b * ts.sta_b_stride + L.j];
+            dsta[g][i] = (raw ? tv * (us * (1.0f - us)) : tv) * (s.hi - s.lo);
+        }
+    }
+    if (FEW) {
+#pragma unroll
+        for (int k = 0; k < ADJ_FEW; k++) {
+            use_dyn[k] = false;
+            if (k < F.nd) {
+                const hbvx_param_src &s = d.p[F.slot[k]];
+                use_dyn[k] = !(s.drop && s.drop[L.n]);
+            }
+        }
+    }
+    float xd[G][5];
+#pragma unroll
+    for (int g = 0; g < G; g++)
+#pragma unroll
+        for (int k = 0; k < 5; k++)
+            xd[g][k] = (g < ng && tb.state_in) ? tb.state_in[(dir0 + g) * tb.state_d_stride + k * N + L.n] : 0.0f;
+    const int64_t xto = (int64_t)L.b * d.x_b_stride;
+    AdjTanRaw Rn;
+    if (T > 0) adj_tan_issue(d, A.traj, L, 0, N, Rn);
+    for (int t = 0; t < T; t++) {
+        const AdjTanRaw Rc = Rn;
+        if (t + 1 < T) adj_tan_issue(d, A.traj, L, t + 1, N, Rn);      // next day's loads in flight
+        float u[NP], p[NPARAM_MAX];
+        if (FEW) adj_params_few<NP>(d, L, t, raw, F, usta, use_dyn, u, p);
+        else adj_params<NP>(d, L, t, raw, usta, use_dyn, u, p);
+        AdjStep<BETAET> s;
+        s.P = Rc.f[0]; s.Tf = Rc.f[1]; s.PET = Rc.f[2];
+        AdjTan<BETAET> c;
+        c.prepare(s, p, Rc.x, 1.0f);
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            if (g >= ng) continue;
+            const int64_t dir = dir0 + g;
+            float pd[NPARAM_MAX], cd[3] = {0.0f, 0.0f, 0.0f};
+            // a parameter's tangent follows its value: the day's row where the lane uses it, the static one where dropped
+#pragma unroll
+            for (int i = 0; i < NP; i++) pd[i] = dsta[g][i];
+#pragma unroll
+            for (int i = NP; i < NPARAM_MAX; i++) pd[i] = 0.0f;
+            if (FEW) {
+#pragma unroll
+                for (int k = 0; k < ADJ_FEW; k++)
+                    if (k < F.nd) {
+                        const int sl = F.slot[k];
+                        const hbvx_param_tan &ts = tb.p[sl];
+                        const bool on = ts.dyn && t >= tb.dyn_t0;
+                        const float tv = on ? ts.dyn[dir * tb.dyn_d_stride[sl] + (int64_t)(t - tb.dyn_t0) * ts.dyn_t_stride
+                                                     + (int64_t)L.b * ts.dyn_b_stride + L.j] : 0.0f;
+                        const float dv = (raw ? tv * (u[k] * (1.0f - u[k])) : tv) * (d.p[sl].hi - d.p[sl].lo);
+                        const float cur = slot_get<NP>(pd, sl);
+                        slot_set<NP>(pd, sl, use_dyn[k] ? dv : cur);
+                    }
+            } else {
+#pragma unroll
+                for (int i = 0; i < NP; i++)
+                    if (d.p[i].dyn) {
+                        const hbvx_param_tan &ts = tb.p[i];
+                        const bool on = ts.dyn && t >= tb.dyn_t0;
+                        const float tv = on ? ts.dyn[dir * tb.dyn_d_stride[i] + (int64_t)(t - tb.dyn_t0) * ts.dyn_t_stride
+                                                     + (int64_t)L.b * ts.dyn_b_stride + L.j] : 0.0f;
+                        const float dv = (raw ? tv * (u[i] * (1.0f - u[i])) : tv) * (d.p[i].hi - d.p[i].lo);
+                        pd[i] = use_dyn[i] ? dv : pd[i];
+                    }
+            }
+            if (tb.x) {
+                const float *xt = tb.x + dir * tb.x_d_stride + (int64_t)t * d.x_t_stride + xto;
+                cd[0] = xt[d.ch_prcp]; cd[1] = xt[d.ch_tmean]; cd[2] = xt[d.ch_pet];
+            }
+            float Qd;
+            c.apply(s, p, xd[g], pd, cd, xd[g], Qd);
+            if (tb.flux_mask) {
+                // as k_adj_fwd: member reduction by butterfly, then 1/M
+                Qd = adj_ens_sum(L.active ? Qd : 0.0f, A.lgMp) * invM;
+                if (L.leader) tb.tan_flux[(dir * T + t) * d.B + L.b] = Qd;
+            }
+        }
+    }
+    if (L.active) {
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            if (g < ng) {
+#pragma unroll
+                for (int k = 0; k < 5; k++) tb.tan_state_out[((dir0 + g) * 5 + k) * N + L.n] = xd[g][k];
+            }
+    }
+}
+
 } // namespace hbvx
 
 // ---------------------------------------------------------------------------

@@ -512,4 +512,114 @@ HBVX_HD void adj_backstep(AdjStep<BETAET> &s, const float *p, const float *x, fl
     for (int k = 0; k < 5; k++) a[k] = lam[k] * idt;
 }
 
+// Implicit-function TANGENT of one day at the solved state x (= y_{t+1}): the transpose of adj_backstep.
+//   (I/dt - F) x_dot = xt_dot/dt + (df/dp) p_dot + (df/dclim) clim_dot
+//   Q_dot = dQ/dx x_dot + dQ/dp p_dot                          (Q = q0+q1+q2 evaluated at x, hbv_adj.py:309-313,431)
+// The derivative is taken at the solved state, so nothing here iterates.  Conventions are those of eval<true> and
+// adj_backstep: minw_ tie weights, inclusive clamp masks, r > 0 / qe > 0 guards on the power terms, zero slope of the
+// Tf < TT thresholds.  The forcings enter where the adjoint has no gradient to give: P through sf / rf, Tf through
+// mp / rp behind their clamps and min weights, PET through pe behind wbe.
+//
+// Two parts.  prepare() depends on (x, p, clim) only: eval<true>, the pivots of the forward substitution as
+// reciprocals and the partials that cost a quotient or a logarithm.  On the device the quotients of AdjStep::solve are
+// a * rcp(b), so a * r with r = rcp(b) kept is the same number there; on the host solve() divides and the two differ by
+// a rounding.  apply() is one direction on the evaluated day: multiplications and additions only, callable any number
+// of times.  A direction's result must not depend on which of several unrolled copies computed it: that rests on the
+// library being built with -ffp-contract=off (every operation rounds on its own) and on apply() carrying NO
+// contraction pragma -- HBVX_ADJ_FMA here would leave bit-identity to the compiler's fusion choices per copy.
+template <bool BETAET>
+struct AdjTan {
+    float idt, J00, J01, J10, J11, rdet, r22, r33, r44;   // pivots of I/dt - F
+    float msf, mrf;         // [Tf < TT], [Tf >= TT]
+    float wr, wm;           // d refr / d rp, d melt / d mp (min weight behind the clamp)
+    float kr, kb, rfc;      // d sw0 / d r, d sw0 / d BETA, r / FC
+    float kq, ke, qlp;      // d ef0 / d qe, d ef0 / d BETAET, qe / (LP FC)
+    float k0m, cQ3, cQ4;    // K0 mq0; dQ / d x3, dQ / d x4
+
+    HBVX_HDM void prepare(AdjStep<BETAET> &s, const float *p, const float *x, float idt_)
+    {
+        const float BETA = p[P_BETA], FC = p[P_FC], K0 = p[P_K0], K1 = p[P_K1], K2 = p[P_K2], LP = p[P_LP],
+                    TT = p[P_TT];
+        s.template eval<true>(x, p);
+        idt = idt_;
+        J00 = idt - s.F00; J01 = -s.F01; J10 = -s.F10; J11 = idt - s.F11;
+        const float det = J00 * J11 - J01 * J10;
+        rdet = div_approx_(1.0f, det);
+        r22 = div_approx_(1.0f, idt - s.F22);
+        r33 = div_approx_(1.0f, idt - s.F33);
+        r44 = div_approx_(1.0f, idt - s.F44);
+        msf = (s.Tf < TT) ? 1.0f : 0.0f;
+        mrf = (s.Tf >= TT) ? 1.0f : 0.0f;
+        wr = (s.rp >= 0.0f) ? s.war : 0.0f;
+        wm = (s.mp >= 0.0f) ? s.wam : 0.0f;
+        kr = (s.r > 0.0f) ? BETA * div_approx_(s.sw0, s.r) : 0.0f;
+        kb = (s.r > 0.0f) ? s.sw0 * log_fast_(s.r) : 0.0f;
+        rfc = div_approx_(s.r, FC);
+        qlp = div_approx_(s.qe, LP * FC);
+        if (BETAET) {
+            kq = (s.qe > 0.0f) ? p[P_BETAET] * div_approx_(s.ef0, s.qe) : 0.0f;
+            ke = (s.qe > 0.0f) ? s.ef0 * log_fast_(s.qe) : 0.0f;
+        } else {
+            kq = 1.0f;
+            ke = 0.0f;
+        }
+        k0m = K0 * s.mq0;
+        cQ3 = (k0m + K1) * s.c3;
+        cQ4 = K2 * s.c4;
+    }
+
+    //   xt_dot[5]  tangent of the storages entering the day;  p_dot[]  of the day's physical parameters
+    //   c_dot[3]   of (P, Tf, PET);  x_dot[5] (may alias xt_dot), Q_dot: out
+    HBVX_HDM void apply(const AdjStep<BETAET> &s, const float *p, const float *xt_dot, const float *p_dot,
+                        const float *c_dot, float *x_dot, float &Q_dot) const
+    {
+        const float FC = p[P_FC], LP = p[P_LP], CFMAX = p[P_CFMAX], CFR = p[P_CFR];
+        const float dTT = p_dot[P_TT], dFC = p_dot[P_FC];
+        // snow
+        const float dsf = c_dot[0] * msf;
+        const float drf = c_dot[0] * mrf;
+        const float dcc = p_dot[P_CFR] * CFMAX + CFR * p_dot[P_CFMAX];
+        const float drefr = wr * (dcc * s.dT2 + s.cc * (dTT - c_dot[1]));
+        const float dmelt = wm * (p_dot[P_CFMAX] * s.dT + CFMAX * (c_dot[1] - dTT));
+        const float dIs = -(s.mI * (p_dot[P_CWH] * s.SP));
+        // effective precipitation, excess
+        const float dsw = s.msw * (kb * p_dot[P_BETA] - kr * (rfc * dFC));
+        const float dPeff = (drf + dIs) * s.sw + (s.rf + s.Isnow) * dsw;
+        const float dex = -(s.mex * dFC);
+        // evapotranspiration
+        const float dqe = -(qlp * (p_dot[P_LP] * FC + LP * dFC));
+        const float def0 = BETAET ? kq * dqe + ke * p_dot[P_BETAET] : dqe;
+        const float det = s.wbe * (c_dot[2] * s.ef + s.PET * (s.mef * def0));
+        // groundwater
+        const float dperc = s.wbp * p_dot[P_PERC];
+        const float dq0 = p_dot[P_K0] * s.u0c - k0m * p_dot[P_UZL];
+        const float dq1 = p_dot[P_K1] * s.SUZ;
+        const float dq2 = p_dot[P_K2] * s.SLZ;
+        // right-hand side, in the association order of f (hbv_adj.py:425-429)
+        const float g0 = xt_dot[0] * idt + ((dsf + drefr) - dmelt);
+        const float g1 = xt_dot[1] * idt + ((dmelt - drefr) - dIs);
+        const float g2 = xt_dot[2] * idt + ((((dIs + drf) - dPeff) - dex) - det);
+        const float g3 = xt_dot[3] * idt + ((((dPeff + dex) - dperc) - dq0) - dq1);
+        const float g4 = xt_dot[4] * idt + (dperc - dq2);
+        // forward substitution: AdjStep::solve with the pivots kept
+        const float d0 = (g0 * J11 - J01 * g1) * rdet;
+        const float d1 = (J00 * g1 - g0 * J10) * rdet;
+        const float d2 = (g2 + s.F20 * d0 + s.F21 * d1) * r22;
+        const float d3 = (g3 + s.F30 * d0 + s.F31 * d1 + s.F32 * d2) * r33;
+        const float d4 = (g4 + s.F43 * d3) * r44;
+        x_dot[0] = d0; x_dot[1] = d1; x_dot[2] = d2; x_dot[3] = d3; x_dot[4] = d4;
+        Q_dot = (((cQ3 * d3 + cQ4 * d4) + dq0) + dq1) + dq2;
+    }
+};
+
+// One direction on one day: both parts (s.P, s.Tf, s.PET set by the caller, as for adj_backstep).
+template <bool BETAET>
+HBVX_HD void adj_tanstep(AdjStep<BETAET> &s, const float *p, const float *x, float idt, const float *xt_dot,
+                         const float *p_dot, const float *c_dot, float *x_dot, float &Q_dot)
+{
+    AdjTan<BETAET> c;
+    c.prepare(s, p, x, idt);
+    c.apply(s, p, xt_dot, p_dot, c_dot, x_dot, Q_dot);
+}
+
 } // namespace hbvx

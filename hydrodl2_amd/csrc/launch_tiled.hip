@@ -252,3 +252,58 @@ extern "C" int hbvx_adj_backward(const hbvx_desc *d, const hbvx_bwd_io *io, void
     if (e != hipSuccess) return hip_fail(e, "hbvx_adj_backward launch");
     return HBVX_OK;
 }
+
+// Forward-mode AD of the implicit scheme, several directions per call (include/hbvx.h).  Every refusal happens here,
+// before the launch.
+extern "C" int hbvx_adj_tangent_batch(const hbvx_desc *d, const hbvx_tan_batch *tb, const float *traj, void *stream)
+{
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (d->model != HBVX_MODEL_HBVADJ)
+        return fail(HBVX_E_UNSUPPORTED, "hbvx_adj_tangent_batch: the implicit scheme (HBVADJ) only");
+    if (!tb) return fail(HBVX_E_NULL, "tan_batch is NULL");
+    if (tb->n_dir < 1) return fail(HBVX_E_SHAPE, "hbvx_adj_tangent_batch: n_dir must be >= 1");
+    if (tb->n_dir > 65535) return fail(HBVX_E_SHAPE, "hbvx_adj_tangent_batch: too many directions for one launch");
+    if (tb->n_flux != 1) return fail(HBVX_E_SHAPE, "hbvx_adj_tangent_batch: n_flux must be 1");
+    if (tb->flux_mask >> tb->n_flux) return fail(HBVX_E_SHAPE, "flux_mask selects a series at or above n_flux");
+    if (!traj) return fail(HBVX_E_NULL, "hbvx_adj_tangent_batch: traj is NULL (the trajectory of hbvx_adj_forward)");
+    if (!tb->tan_state_out) return fail(HBVX_E_NULL, "tan_state_out is NULL");
+    if (tb->flux_mask && !tb->tan_flux) return fail(HBVX_E_NULL, "tan_flux is NULL although flux_mask selects series");
+    if (tb->muwts) return fail(HBVX_E_UNSUPPORTED, "hbvx_adj_tangent_batch: muwts must be NULL (the implicit scheme has no ensemble weights)");
+    if (tb->dyn_t0 < 0 || tb->dyn_t0 > (d->T > 0 ? d->T - 1 : 0)) return fail(HBVX_E_SHAPE, "dyn_t0 outside the call's days");
+    for (int i = d->n_param; i < HBVX_MAX_PARAM; i++)
+        if (tb->p[i].dyn || tb->p[i].sta) return fail(HBVX_E_SHAPE, "tangent for a parameter slot the model lacks");
+    for (int i = 0; i < d->n_param; i++)
+        if (tb->p[i].dyn && !d->p[i].dyn) return fail(HBVX_E_SHAPE, "dynamic tangent for a static parameter");
+    AdjTanArgs a;
+    a.d = *d;
+    a.tb = *tb;
+    a.traj = traj;
+    a.lgMp = lg_members(d->M);
+    // a stride of 0 is a zero tangent, like a NULL pointer (include/hbvx.h)
+    if (!a.tb.x_d_stride) a.tb.x = nullptr;
+    if (!a.tb.state_d_stride) a.tb.state_in = nullptr;
+    for (int i = 0; i < d->n_param; i++) {
+        if (!a.tb.dyn_d_stride[i]) a.tb.p[i].dyn = nullptr;
+        if (!a.tb.sta_d_stride[i]) a.tb.p[i].sta = nullptr;
+    }
+    const int bpw = 64 >> a.lgMp;
+    const dim3 grid((d->B + bpw - 1) / bpw, (tb->n_dir + ADJ_TAN_G - 1) / ADJ_TAN_G);
+    // at most ADJ_FEW dynamic parameters: the slot-list instances (hbv_adj_kernels.h, "few" mode)
+    AdjFew few{};
+    const bool is_few = count_dyn(d) <= ADJ_FEW;
+    if (is_few)
+        for (int i = 0; i < d->n_param; i++)
+            if (d->p[i].dyn) few.slot[few.nd++] = i;
+    hipStream_t st = (hipStream_t)stream;
+    if (d->n_param == 13) {
+        if (is_few) hipLaunchKernelGGL((k_adj_tan_batch<true, true>), grid, dim3(64), 0, st, a, few);
+        else hipLaunchKernelGGL((k_adj_tan_batch<true, false>), grid, dim3(64), 0, st, a, few);
+    } else {
+        if (is_few) hipLaunchKernelGGL((k_adj_tan_batch<false, true>), grid, dim3(64), 0, st, a, few);
+        else hipLaunchKernelGGL((k_adj_tan_batch<false, false>), grid, dim3(64), 0, st, a, few);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "hbvx_adj_tangent_batch launch");
+    return HBVX_OK;
+}

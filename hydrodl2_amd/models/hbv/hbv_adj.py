@@ -133,6 +133,7 @@ class HbvAdj(torch.nn.Module):
                 tuple(map(tuple, self.routing_parameter_bounds.values())))
 
     _graph_state_attrs = ()
+    _model_id = _abi.MODEL_HBVADJ
 
     def _sources(self, T_total, B, ny, t_first, sta_row, dy_list, device):
         M = self.nmul
@@ -152,11 +153,26 @@ class HbvAdj(torch.nn.Module):
         """hbv_adj.py:227-330.  `graph=True`: HIP-graph replay of the call (graphed.py)."""
         if has_tangent(tuple(x_dict.values()), parameters):
             raise NotImplementedError("forward-mode AD (dual inputs) is not implemented for HbvAdj: "
-                                      "Hbv, Hbv_1_1p and Hbv_2 support it")
+                                      "Hbv, Hbv_1_1p and Hbv_2 support it; explicit directions go through "
+                                      "HbvAdj.jvp_batch")
         if self.graph and x_dict['x_phy'].is_cuda:
             from hydrodl2_amd.graphed import graphed_forward
             return graphed_forward(self, x_dict, parameters)
         return self._forward_eager(x_dict, parameters)
+
+    def jvp_batch(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor, tangents: dict,
+                  max_directions: Optional[int] = None):
+        """Implicit-function forward-mode derivatives of 'flow_sim' along many directions on one primal run:
+        (outputs, tangents_out) = hydrodl2_amd.adj_jvp_batch(self, ...), see there."""
+        from hydrodl2_amd.adj_jvp import adj_jvp_batch
+        return adj_jvp_batch(self, x_dict, parameters, tangents, max_directions)
+
+    def parameter_jacobian(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor, names=None,
+                           max_directions: int = 64) -> dict:
+        """Per-basin Jacobian of 'flow_sim' with respect to the static parameters:
+        hydrodl2_amd.adj_parameter_jacobian(self, ...), see there."""
+        from hydrodl2_amd.adj_jvp import adj_parameter_jacobian
+        return adj_parameter_jacobian(self, x_dict, parameters, names, max_directions)
 
     def _forward_eager(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor):
         """hbv_adj.py:227-330."""

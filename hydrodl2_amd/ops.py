@@ -526,6 +526,7 @@ class PathRecord(NamedTuple):
     uh: Optional[torch.Tensor]
     routed: Optional[torch.Tensor]
     state_out: torch.Tensor
+    traj: Optional[torch.Tensor] = None     # the implicit scheme only: its tangent is taken at the solved states
 
 
 # sensitivity.jvp_batch runs the primal through the module's own forward (warm-up pass, dy_drop draws, caches and
@@ -889,7 +890,8 @@ def hbv_tangent_batch(rec: PathRecord, D: int, x_t=None, mu_t=None, s_t=None, p_
                       n_routed: int = 0, want_bfi: bool = False) -> BatchOut:
     """Forward-mode derivative of one call of the path along D directions at once: hbvx_forward_tangent_batch
     (the hourly model: hbvx_hourly_tangent_batch), hbvx_route_tangent_batch and hbvx_bfi_tangent_batch on what the
-    forward worked on (`rec`).
+    forward worked on (`rec`).  A record of the implicit scheme (HbvAdjPath) goes to hbvx_adj_tangent_batch with the
+    trajectory it kept: one series, so flux_mask is 0 or 1 and n_routed 0 or 1, no muwts, no BFI.
 
     x_t [D, *x.shape], mu_t [D, *muwts.shape], s_t [D,5,B,M], p_t: one tangent per parameter tensor, full or compact
     (_batch_source); None: zero.  Only the flux series of `flux_mask` (bits: enum hbvx_flux) are computed and stored,
@@ -963,6 +965,8 @@ def hbv_tangent_batch(rec: PathRecord, D: int, x_t=None, mu_t=None, s_t=None, p_
     desc = _fill_desc(cfg, x, rec.state_in, rec.muwts, rec.ac, rec.elev, ptensors)
     if cfg.model == _abi.MODEL_HOURLY:      # a kernel and an entry point of its own (include/hbvx.h)
         _call(lib, 'hbvx_hourly_tangent_batch', lib.hourly_tangent_batch, desc, tb, stream)
+    elif cfg.model == _abi.MODEL_HBVADJ:    # likewise; differentiates at the solved states of the recorded call
+        _call(lib, 'hbvx_adj_tangent_batch', lib.adj_tangent_batch, desc, tb, _ptr(rec.traj), stream)
     else:
         _call(lib, 'hbvx_forward_tangent_batch', lib.forward_tangent_batch, desc, tb, stream)
 
@@ -1063,7 +1067,8 @@ class HbvAdjPath(torch.autograd.Function):
         out = _abi.FwdOut()
         flux = _out((1, T, B), dev) if cfg.want_flux else None
         state_out = _out((5, B, M), dev)
-        traj = _out((5, T + 1, B * M), dev) if needs_grad else None
+        tap = getattr(_TAP, "records", None)    # inside record_paths(): the tangent needs the solved states too
+        traj = _out((5, T + 1, B * M), dev) if (needs_grad or tap is not None) else None
         out.flux, out.state_out, out.traj, out.n_flux = _ptr(flux), _ptr(state_out), _ptr(traj), 1
         if state_in is not None:
             state_in = state_in.contiguous()
@@ -1084,6 +1089,8 @@ class HbvAdjPath(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         if needs_grad:
             ctx.save_for_backward(x, state_in, traj, flux, uh, *ptensors)
+        if tap is not None:
+            tap.append(PathRecord(cfg, x, state_in, None, None, None, tuple(ptensors), flux, uh, routed, state_out, traj))
         return flux, routed, state_out
 
     @staticmethod

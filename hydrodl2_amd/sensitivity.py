@@ -12,9 +12,11 @@ Directions that start upstream of the model -- on the inputs or weights of the p
 
 The hourly model has an entry point of its own, `hydrodl2_amd.hourly_jvp_batch` / `Hbv_2_hourly.jvp_batch`
 (hydrodl2_amd/hourly_jvp.py): its output is gage streamflow, gages couple the units, so `jvp_batch` and
-`parameter_jacobian` here keep refusing it.
+`parameter_jacobian` here keep refusing it.  So has the implicit scheme, `hydrodl2_amd.adj_jvp_batch` /
+`HbvAdj.jvp_batch` and `adj_parameter_jacobian` (hydrodl2_amd/adj_jvp.py): its tangent is the implicit-function
+derivative at the solved states of a saved trajectory, a different kernel and call.
 
-Out of scope: `torch.func.jvp` / `jacfwd` / vmap over `make_dual`, and the implicit and multi-timescale models.
+Out of scope: `torch.func.jvp` / `jacfwd` / vmap over `make_dual`, and the multi-timescale model.
 """
 from __future__ import annotations
 

@@ -27,6 +27,9 @@
  *                        the same for the hourly model: the sub-daily recurrence and the gage routing, many
  *                        directions per call (one direction is n_dir = 1).  hbvx_forward_tangent and
  *                        hbvx_forward_tangent_batch keep refusing HBVX_MODEL_HOURLY.
+ *   hbvx_adj_tangent_batch
+ *                        the same for the implicit scheme: implicit-function tangents at the solved states of
+ *                        hbvx_adj_forward, many directions per call.
  *
  * Ownership: the caller allocates and owns every buffer; the library keeps no
  * state between calls and allocates nothing persistent.  All device work is
@@ -443,6 +446,21 @@ int hbvx_gage_route_tangent_batch(const hbvx_gage_desc *r, int32_t n_dir, const 
                                   const float *qs_dot, int64_t qs_dot_d_stride, const float *dp_dot,
                                   int64_t dp_dot_d_stride, float *out_dot, void *workspace, uint64_t workspace_bytes,
                                   void *stream);
+
+/* The implicit scheme (optional export; a library may lack it).
+ * hbvx_adj_tangent_batch is the forward-mode derivative of hbvx_adj_forward over n_dir directions, model
+ * HBVX_MODEL_HBVADJ only (any other: HBVX_E_UNSUPPORTED).  The derivative is the implicit-function one at the SOLVED
+ * state: per day (I/dt - df/dx) x_dot = x_t_dot/dt + df/dtheta theta_dot + df/dclim clim_dot, evaluated at the
+ * storages hbvx_adj_forward saved -- no Newton iteration is repeated, the Newton policy of the descriptor is not
+ * looked at.  `traj` is the [5,T+1,B*M] trajectory (HBVX_TRAJ_ROWS) of the call being differentiated and is required.
+ * hbvx_tan_batch as for hbvx_forward_tangent_batch, with n_flux = 1, flux_mask 0 or 1, muwts NULL (the scheme has no
+ * ensemble weights: a non-NULL pointer is refused), state_in / tan_state_out [n_dir,5,B,M], tan_flux [n_dir,1,T,B]
+ * (the ensemble mean of q0+q1+q2, member reduction and add order of hbvx_adj_forward); dyn_t0 and the per-direction
+ * strides follow the rules above, `x` carries tangents of all three forcings.  Conventions are those of
+ * hbvx_adj_backward (binary minimum 1/2 each at a tie, inclusive clamps, zero slope of the Tf < TT threshold), of which
+ * this is the transpose.  n_dir in 1..65535; a direction's result does not depend on n_dir (bit-identical to the same
+ * direction alone).  Argument errors are reported before anything is launched. */
+int hbvx_adj_tangent_batch(const hbvx_desc *d, const hbvx_tan_batch *tb, const float *traj, void *stream);
 
 /* Zero `bytes` bytes at `ptr` (streaming non-temporal stores).  The autograd contract of the plug-in wants
  * gradient tensors shaped like the raw parameter tensor [T,B,ny] (hbv.py:211-246: static parameters read
