@@ -174,8 +174,10 @@ class HbvAdj(torch.nn.Module):
         from hydrodl2_amd.adj_jvp import adj_parameter_jacobian
         return adj_parameter_jacobian(self, x_dict, parameters, names, max_directions)
 
-    def _forward_eager(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor):
-        """hbv_adj.py:227-330."""
+    def _forward_eager(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor,
+                       state: Optional[torch.Tensor] = None):
+        """hbv_adj.py:227-330.  `state` [5,B,nmul] (private: the tests' way to start from filled storages): the
+        storages the first pass starts from -- the warm-up pass if there is one -- instead of zeros; differentiable."""
         x = x_dict['x_phy']
         T_total, B = x.shape[0], x.shape[1]
         M = self.nmul
@@ -220,9 +222,9 @@ class HbvAdj(torch.nn.Module):
                 if len(self._memo_cache) > 8:
                     self._memo_cache.clear()
                 cfg.__dict__["_memo"] = self._memo_cache.setdefault(key, {})
-        state = None  # zeros (hbv_adj.py:254)
+        # state is None: zeros (hbv_adj.py:254)
         if cfg_w is not None:
-            _, _, state = HbvAdjPath.apply(cfg_w, x, None, parameters)
+            _, _, state = HbvAdjPath.apply(cfg_w, x, state, parameters)
         flux, routed, _ = HbvAdjPath.apply(cfg, x, state, parameters)
         q = routed if routed is not None else flux
         return {'flow_sim': q[0].unsqueeze(-1)}

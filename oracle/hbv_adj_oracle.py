@@ -30,8 +30,9 @@ BOUNDS = {  # hbv_adj.py:59-76,94-95
 NAMES12 = list(BOUNDS)[:12]
 
 
-def rhs(y, theta, clim, names):
-    """hbv_adj.py:341-442: dS [N,5] and Q [N] from storages y [N,5], unit parameters theta [N,n]."""
+def fluxes(y, theta, clim, names):
+    """hbv_adj.py:385-498: the clamped storages, the potentials and every flux of the right-hand side, by name, from
+    storages y [N,5] and unit parameters theta [N,n]."""
     P = {n: BOUNDS[n][0] + theta[:, i] * (BOUNDS[n][1] - BOUNDS[n][0]) for i, n in enumerate(names)}
     SNOWPACK = torch.clamp(y[:, 0], min=0.0)   # :387-391
     MELTWATER = torch.clamp(y[:, 1], min=0.0)
@@ -41,28 +42,63 @@ def rhs(y, theta, clim, names):
     Pr, T, Ep = clim[:, 0], clim[:, 1], clim[:, 2]
     TT, CFMAX, CFR = P['parTT'], P['parCFMAX'], P['parCFR']
     sf = Pr * (T < TT)                                                          # :444-446
-    refr = torch.min(torch.clamp(CFR * CFMAX * (TT - T), min=0.0), MELTWATER)   # :448-452
-    melt = torch.min(torch.clamp(CFMAX * (T - TT), min=0.0), SNOWPACK)          # :454-458
+    rpot = torch.clamp(CFR * CFMAX * (TT - T), min=0.0)
+    refr = torch.min(rpot, MELTWATER)                                           # :448-452
+    mpot = torch.clamp(CFMAX * (T - TT), min=0.0)
+    melt = torch.min(mpot, SNOWPACK)                                            # :454-458
     rf = Pr * (T >= TT)                                                         # :460-462
     Isnow = torch.clamp(MELTWATER - P['parCWH'] * SNOWPACK, min=0.0)            # :464-468
     sw = torch.clamp((SM / P['parFC']) ** P['parBETA'], min=0.0, max=1.0)       # :470-474
     Peff = (rf + Isnow) * sw
     ex = torch.clamp(SM - P['parFC'], min=0.0)                                  # :476-479
-    ef = SM / (P['parLP'] * P['parFC'])                                         # :481-486
+    ef0 = SM / (P['parLP'] * P['parFC'])                                        # :481-486
     if 'parBETAET' in P:
-        ef = ef ** P['parBETAET']
-    ef = torch.clamp(ef, min=0.0, max=1.0)
-    et = torch.min(SM, Ep * ef)
+        ef0 = ef0 ** P['parBETAET']
+    ef = torch.clamp(ef0, min=0.0, max=1.0)
+    pe = Ep * ef
+    et = torch.min(SM, pe)
     perc = torch.min(SUZ, P['parPERC'])                                         # :492-494
     q0 = P['parK0'] * torch.clamp(SUZ - P['parUZL'], min=0.0)                   # :488-490
     q1 = P['parK1'] * SUZ                                                       # :496-498
     q2 = P['parK2'] * SLZ
-    dS = torch.stack([sf + refr - melt,                                         # :425-429
-                      melt - refr - Isnow,
-                      Isnow + rf - Peff - ex - et,
-                      Peff + ex - perc - q0 - q1,
-                      perc - q2], dim=1)
-    return dS, q0 + q1 + q2                                                     # :431
+    return dict(SNOWPACK=SNOWPACK, MELTWATER=MELTWATER, SM=SM, SUZ=SUZ, SLZ=SLZ, sf=sf, rf=rf, rpot=rpot, refr=refr,
+                mpot=mpot, melt=melt, Isnow=Isnow, Peff=Peff, ex=ex, ef0=ef0, pe=pe, et=et, perc=perc, q0=q0, q1=q1,
+                q2=q2, y2=y[:, 2], warm=T > TT, T=T, TT=TT, CFMAX=CFMAX, CFR=CFR, FC=P['parFC'], PERC=P['parPERC'],
+                UZL=P['parUZL'])
+
+
+def rhs(y, theta, clim, names):
+    """hbv_adj.py:341-442: dS [N,5] and Q [N] from storages y [N,5], unit parameters theta [N,n]."""
+    f = fluxes(y, theta, clim, names)
+    dS = torch.stack([f['sf'] + f['refr'] - f['melt'],                          # :425-429
+                      f['melt'] - f['refr'] - f['Isnow'],
+                      f['Isnow'] + f['rf'] - f['Peff'] - f['ex'] - f['et'],
+                      f['Peff'] + f['ex'] - f['perc'] - f['q0'] - f['q1'],
+                      f['perc'] - f['q2']], dim=1)
+    return dS, f['q0'] + f['q1'] + f['q2']                                      # :431
+
+
+def branches(y, theta, clim, names):
+    """Which side of every min / max / threshold of the right-hand side the state y [N,5] lies on: name -> bool [N].
+    A limited flux counts only where it flows (melt limited by a pack that is there, and so on)."""
+    with torch.no_grad():
+        f = fluxes(y, theta, clim, names)
+        wet, q0a = f['SM'] > f['FC'], f['SUZ'] > f['UZL']
+        lin = f['SUZ'] <= f['PERC']                                             # perc = SUZ
+        return {
+            'rain': f['rf'] > 0, 'snow': f['sf'] > 0,
+            'melt_pack_limited': (f['melt'] > 0) & (f['SNOWPACK'] < f['mpot']),
+            'melt_potential': (f['melt'] > 0) & (f['SNOWPACK'] > f['mpot']),
+            'refr_mw_limited': (f['refr'] > 0) & (f['MELTWATER'] < f['rpot']),
+            'refr_potential': (f['refr'] > 0) & (f['MELTWATER'] > f['rpot']),
+            'isnow_warm': (f['Isnow'] > 0) & f['warm'], 'isnow_cold': (f['Isnow'] > 0) & ~f['warm'],
+            'sm_above_fc': wet, 'sm_below_fc': ~wet,
+            'ef_clamped': f['ef0'] > 1, 'ef_free': f['ef0'] <= 1,
+            'et_sm_limited': f['SM'] < f['pe'], 'et_pet_limited': f['SM'] >= f['pe'],
+            'sm_floor': f['y2'] < 1e-8,
+            'perc_suz': lin, 'perc_par': ~lin, 'q0_active': q0a, 'q0_idle': ~q0a,
+            'gw_suz_idle': lin & ~q0a, 'gw_suz_q0': lin & q0a, 'gw_par_idle': ~lin & ~q0a, 'gw_par_q0': ~lin & q0a,
+        }
 
 
 def _G(x, theta, xt, clim, names, dt=1.0):
@@ -142,10 +178,11 @@ def uh_conv(q, w):
     return y
 
 
-def hbv_adj_forward(x_phy, parameters, nmul=1, warm_up=0, dynamic_params=(), dy_drop=0.0,
-                    gtol=1e-3, max_iter=3, stop='lane', routing=True, dtype=torch.float64):
-    """hbv_adj.py:227-330.  x_phy [T,B,3], raw parameters [T,B,ny] -> flow_sim [T',B,1]
-    (differentiable w.r.t. `parameters`); also returns the Newton update counts [T',N]."""
+def lane_inputs(x_phy, parameters, nmul=1, warm_up=0, dynamic_params=(), dy_drop=0.0, routing=True,
+                dtype=torch.float64):
+    """hbv_adj.py:133-196,261-262: what every day of the run works on, in the member-major lane order (lane j*B + b).
+    Returns names, the warm-up pass's unit parameters [warm_up,N,n] (None without one), the main pass's [T',N,n] (the
+    dy_drop masks are drawn here, from the default generator), the forcing [T,N,3] and the routing parameters."""
     names = list(NAMES12) + (['parBETAET'] if 'parBETAET' in dynamic_params else [])
     n = len(names)
     T, B = x_phy.shape[0], x_phy.shape[1]
@@ -173,20 +210,38 @@ def hbv_adj_forward(x_phy, parameters, nmul=1, warm_up=0, dynamic_params=(), dy_
         return torch.stack(cols, dim=2)
 
     clim = x_phy.unsqueeze(1).repeat(1, nmul, 1, 1).view(T, N, 3)   # :261-262,285-286
-    y = torch.zeros((N, 5), dtype=dtype)                            # :254
-    kw = dict(gtol=gtol, max_iter=max_iter, stop=stop)
-    if warm_up > 0:                                                 # :257-274
-        pw = make(phy[:warm_up], [])
-        for t in range(warm_up):
-            y, _ = implicit_step(pw[t], y, clim[t], names, **kw)
+    pw = make(phy[:warm_up], []) if warm_up > 0 else None           # :257-274
     pr = make(phy[warm_up:], list(dynamic_params))
+    return names, pw, pr, clim, rout
+
+
+def hbv_adj_forward(x_phy, parameters, nmul=1, warm_up=0, dynamic_params=(), dy_drop=0.0,
+                    gtol=1e-3, max_iter=3, stop='lane', routing=True, dtype=torch.float64, y0=None, events=None):
+    """hbv_adj.py:227-330.  x_phy [T,B,3], raw parameters [T,B,ny] -> flow_sim [T',B,1]
+    (differentiable w.r.t. `parameters`); also returns the Newton update counts [T',N].
+
+    y0      [N,5]: the storages the run starts from (the warm-up pass, if there is one), in the member-major lane
+            order, differentiable; None: zeros (hbv_adj.py:254).
+    events  a dict: receives name -> bool [T',N], the branches of the right-hand side taken at the solved state of
+            every day of the main pass (`branches`)."""
+    T, B = x_phy.shape[0], x_phy.shape[1]
+    N = B * nmul
+    names, pw, pr, clim, rout = lane_inputs(x_phy, parameters, nmul, warm_up, dynamic_params, dy_drop, routing, dtype)
+    y = torch.zeros((N, 5), dtype=dtype) if y0 is None else y0.to(dtype)    # :254
+    kw = dict(gtol=gtol, max_iter=max_iter, stop=stop)
+    for t in range(warm_up):                                        # :257-274
+        y, _ = implicit_step(pw[t], y, clim[t], names, **kw)
     nt = T - warm_up
-    sims, its = [], []
+    sims, its, evs = [], [], []
     for t in range(nt):                                             # :689-712, :309-313
         y, it = implicit_step(pr[t], y, clim[warm_up + t], names, **kw)
         _, Q = rhs(y, pr[t], clim[warm_up + t], names)
         sims.append(Q)
         its.append(it)
+        if events is not None:
+            evs.append(branches(y, pr[t], clim[warm_up + t], names))
+    if events is not None:
+        events.update({k: torch.stack([e[k] for e in evs]) for k in evs[0]})
     sim = torch.stack(sims).view(nt, nmul, B).mean(dim=1)           # :315-317
     if routing:
         a = rout[:, 0] * 2.9

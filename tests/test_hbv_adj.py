@@ -2,6 +2,10 @@
 importable and its own tests skip it); these tests pin the product to the independent float64
 autograd oracle (oracle/hbv_adj_oracle.py) and the oracle to finite differences.
 
+The CASES below are dry: 36-90 days of synth.forcing from empty storages never reach SM > FC or SUZ > UZL, SUZ > PERC
+on at most 0.08 % and a clamped evaporation factor on at most 0.6 % of the lane-days; the wet side (filled storages,
+storm forcing, the gradient and the tangent to the start) lives in tests/test_adj_f64.py and tests/test_adj_f64_gpu.py.
+
 CPU tier: the product's math header compiled for the host (tests/hosttest) driven through the
 package's HbvAdj module.  GPU tier (-m gpu): the HIP kernels."""
 import importlib.util
