@@ -111,6 +111,12 @@ class GageDesc(C.Structure):
                 ("tau_lo", C.c_float), ("tau_hi", C.c_float)]
 
 
+class GramDesc(C.Structure):
+    """hbvx_gram_desc: C series on a [T,B] grid, series_stride elements apart (include/hbvx.h)."""
+    _fields_ = [("abi_version", C.c_int32), ("T", C.c_int32), ("B", C.c_int32), ("C", C.c_int32),
+                ("series_stride", C.c_int64)]
+
+
 class LstmDesc(C.Structure):
     """include/hbvx_lstm.h"""
     _fields_ = [("abi_version", C.c_int32), ("T", C.c_int32), ("B", C.c_int32), ("H", C.c_int32)]
@@ -132,7 +138,8 @@ OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forwa
                     "hbvx_bfi_tangent", "hbvx_lstm_tangent", "hbvx_forward_tangent_batch", "hbvx_route_tangent_batch",
                     "hbvx_bfi_tangent_batch", "hbvx_lstm_tangent_batch", "hbvx_lstm_tangent_batch_workspace_bytes",
                     "hbvx_hourly_tangent_batch", "hbvx_gage_route_tangent_batch",
-                    "hbvx_gage_route_tangent_workspace_bytes", "hbvx_adj_tangent_batch"]
+                    "hbvx_gage_route_tangent_workspace_bytes", "hbvx_adj_tangent_batch", "hbvx_gram",
+                    "hbvx_gram_workspace_bytes"]
 
 
 class HbvxError(RuntimeError):
@@ -268,6 +275,15 @@ class Library:
             d.hbvx_adj_tangent_batch.argtypes = [C.POINTER(Desc), C.POINTER(TanBatch), _fp, C.c_void_p]
             if d.hbvx_sizeof(8) != C.sizeof(TanBatch):
                 raise HbvxError(f"{path}: layout mismatch for TanBatch: {d.hbvx_sizeof(8)} != {C.sizeof(TanBatch)}")
+        if "hbvx_gram" not in self.missing:
+            d.hbvx_gram.restype = C.c_int
+            d.hbvx_gram.argtypes = [C.POINTER(GramDesc), _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_uint64,
+                                    C.c_void_p]
+            if d.hbvx_sizeof(9) != C.sizeof(GramDesc):
+                raise HbvxError(f"{path}: layout mismatch for GramDesc: {d.hbvx_sizeof(9)} != {C.sizeof(GramDesc)}")
+        if "hbvx_gram_workspace_bytes" not in self.missing:
+            d.hbvx_gram_workspace_bytes.restype = C.c_uint64
+            d.hbvx_gram_workspace_bytes.argtypes = [C.POINTER(GramDesc)]
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -432,6 +448,15 @@ class Library:
         self.require("hbvx_adj_tangent_batch")
         self._check(self.dll.hbvx_adj_tangent_batch(C.byref(desc), C.byref(tb), traj, C.c_void_p(stream)),
                     "hbvx_adj_tangent_batch")
+
+    def gram_workspace_bytes(self, g: GramDesc) -> int:
+        self.require("hbvx_gram_workspace_bytes")
+        return int(self.dll.hbvx_gram_workspace_bytes(C.byref(g)))
+
+    def gram(self, g: GramDesc, s: int, w, r, gram: int, rhs, cost, ws, ws_bytes: int, stream: int):
+        self.require("hbvx_gram")
+        self._check(self.dll.hbvx_gram(C.byref(g), s, w, r, gram, rhs, cost, ws, C.c_uint64(ws_bytes),
+                                       C.c_void_p(stream)), "hbvx_gram")
 
     def gage_route_tangent_workspace_bytes(self, r: GageDesc, n_dir: int) -> int:
         self.require("hbvx_gage_route_tangent_workspace_bytes")

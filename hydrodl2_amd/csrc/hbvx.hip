@@ -66,6 +66,7 @@ extern "C" uint64_t hbvx_sizeof(int which)
     case 5: return sizeof(hbvx_param_grad);
     case 7: return sizeof(hbvx_tan_io);
     case 8: return sizeof(hbvx_tan_batch);
+    case 9: return sizeof(hbvx_gram_desc);
     default: return 0;
     }
 }

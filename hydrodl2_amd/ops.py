@@ -998,6 +998,43 @@ def hbv_tangent_batch(rec: PathRecord, D: int, x_t=None, mu_t=None, s_t=None, p_
     return BatchOut(tflux, troute, tbfi, tstate)
 
 
+def gram(series: torch.Tensor, w: Optional[torch.Tensor] = None, r: Optional[torch.Tensor] = None):
+    """Per-basin normal equations of C series on a [T,B] grid through hbvx_gram (include/hbvx.h), on the current stream:
+        gram[b,c,e] = sum_t w s_c s_e [B,C,C],  rhs[b,c] = sum_t w s_c r [B,C],  cost[b] = sum_t w r^2 [B].
+    series [C,T,B] float32 with [T,B] contiguous inside each series (any stride >= T*B between series: the layout the
+    tangent kernels write, a slice of it included); w, r [T,B] or None (w: ones; r: rhs and cost come back None).
+    The kernel multiplies what it is given: w = 0 does not neutralise a NaN in r or series (masking is the caller's)."""
+    lib = get_library()
+    lib.require("hbvx_gram")
+    _check_tensor(lib, series, "series")
+    if series.dim() != 3 or min(series.shape) < 1:
+        raise ValueError(f"series must be a non-empty [C,T,B] tensor, got {tuple(series.shape)}")
+    Cn, T, B = (int(n) for n in series.shape)
+    if series.stride(2) != 1 or series.stride(1) != B or (Cn > 1 and series.stride(0) < T * B):
+        series = series.contiguous()
+    g = _abi.GramDesc(abi_version=_abi.ABI_VERSION, T=T, B=B, C=Cn, series_stride=series.stride(0) if Cn > 1 else T * B)
+    for name, t in (("w", w), ("r", r)):
+        if t is None:
+            continue
+        _check_tensor(lib, t, name)
+        if tuple(t.shape) != (T, B):
+            raise ValueError(f"{name} must be [{T},{B}] like a series, got {tuple(t.shape)}")
+        if t.device != series.device:
+            raise ValueError(f"{name} lives on {t.device}, series on {series.device}")
+    wc = None if w is None else w.contiguous()
+    rc = None if r is None else r.contiguous()
+    dev = series.device
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        out = _out((B, Cn, Cn), dev)
+        rhs = _out((B, Cn), dev) if rc is not None else None
+        cost = _out((B,), dev) if rc is not None else None
+        ws_bytes = lib.gram_workspace_bytes(g)
+        ws = _out(((max(ws_bytes, 4) + 3) // 4,), dev)      # poisoned with the outputs: the call must not need it cleared
+        _call(lib, 'hbvx_gram', lib.gram, g, _ptr(series), _ptr(wc), _ptr(rc), _ptr(out), _ptr(rhs), _ptr(cost), _ptr(ws),
+              ws_bytes, _stream_of(lib, series))
+    return out, rhs, cost
+
+
 class PathOut(NamedTuple):
     """What one call of the path returns.  `flux`: tuple of the n_flux series [T,B,1] (index it with the hbvx_flux
     enum) or None when cfg.want_flux is False; `routed`: tuple of the four UH-routed runoff series [T,B,1] or

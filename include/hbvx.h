@@ -30,6 +30,9 @@
  *   hbvx_adj_tangent_batch
  *                        the same for the implicit scheme: implicit-function tangents at the solved states of
  *                        hbvx_adj_forward, many directions per call.
+ *   hbvx_gram            has no counterpart in the reference: the per-basin normal equations J^T W J, J^T W r and the
+ *                        cost of a Gauss-Newton / Levenberg-Marquardt calibration, straight from the direction-major
+ *                        series the tangent calls write.
  *
  * Ownership: the caller allocates and owns every buffer; the library keeps no
  * state between calls and allocates nothing persistent.  All device work is
@@ -247,8 +250,8 @@ int hbvx_version(void);                 /* HBVX_ABI_VERSION */
 const char *hbvx_last_error(void);
 const char *hbvx_backend(void);         /* "hip:gfx950" or "cpu-oracle" */
 uint64_t hbvx_sizeof(int which);        /* 0 desc, 1 fwd_out, 2 bwd_io, 3 route_desc,
-                                           4 param_src, 5 param_grad, 6 gage_desc, 7 tan_io, 8 tan_batch:
-                                           layout check */
+                                           4 param_src, 5 param_grad, 6 gage_desc, 7 tan_io, 8 tan_batch,
+                                           9 gram_desc: layout check */
 /* Diagnostic: the kernel family that took the process's last hbvx_forward (direction 0) / hbvx_backward (1) call --
  * "pipe", "stream2", "stream", "tiled", "simple", "chunked", "ckpt-block:<family>", "ckpt-lds"; "oracle" in the CPU
  * restatement.  The parity tests assert that the family they mean to pin against the reference is the one that ran. */
@@ -461,6 +464,37 @@ int hbvx_gage_route_tangent_batch(const hbvx_gage_desc *r, int32_t n_dir, const 
  * this is the transpose.  n_dir in 1..65535; a direction's result does not depend on n_dir (bit-identical to the same
  * direction alone).  Argument errors are reported before anything is launched. */
 int hbvx_adj_tangent_batch(const hbvx_desc *d, const hbvx_tan_batch *tb, const float *traj, void *stream);
+
+/* Per-basin normal equations (optional exports; a library may lack them).  C series that share a [T,B] grid:
+ *   gram[b,c,e] = sum_t w[t,b] s[c,t,b] s[e,t,b]
+ *   rhs[b,c]    = sum_t w[t,b] s[c,t,b] r[t,b]
+ *   cost[b]     = sum_t w[t,b] r[t,b]^2
+ * s: series c at s + c*series_stride ([T,B] contiguous inside, series_stride >= T*B): the layout the tangent kernels
+ *    write, [n_dir,T,B] with the basin as the unit-stride axis, so a Jacobian's columns need no transpose.
+ * w: [T,B] or NULL (= 1).  r: [T,B] or NULL (rhs and cost are then not written and may be NULL).
+ * gram [B,C,C], rhs [B,C], cost [B]: overwritten completely; both triangles of gram are written.
+ * workspace: caller-owned scratch of at least hbvx_gram_workspace_bytes(g), contents undefined before and after (the
+ *    call does not need it cleared: every word it reads it has written).
+ * Arithmetic: float32 throughout, fused multiply-adds, no atomics.  The days are cut into slices whose number and
+ * length depend on (T, B) alone; a slice is summed over ascending t, the slice sums are added in ascending order.
+ * Guarantees: (1) two calls on the same inputs give the same bits; (2) gram[b,c,e] and gram[b,e,c] have the same bits
+ * (only c <= e is computed, as sum_t fma(w * s_c, s_e, .), the other triangle is a copy); (3) the bits of gram[b,c,e],
+ * rhs[b,c] and cost[b] do not depend on which other columns are present (C and the column tiling do not enter the
+ * order of any sum).
+ * Masking is the caller's job: the kernel multiplies what it is given, so w = 0 does NOT neutralise a NaN or an
+ * infinity in s or r (0 * NaN = NaN).  A caller with missing observations sets both the weight and the residual of
+ * those (t, b) to 0 before the call (hydrodl2_amd.normal_equations does).
+ * Errors: HBVX_E_NULL (descriptor, s, gram, workspace; rhs / cost with r given), HBVX_E_SHAPE (T/B/C <= 0,
+ * C > HBVX_GRAM_MAX_C, series_stride < T*B), HBVX_E_ABI. */
+#define HBVX_GRAM_MAX_C 2880
+typedef struct hbvx_gram_desc {
+    int32_t abi_version;
+    int32_t T, B, C;       /* steps, basins, series (Jacobian columns) */
+    int64_t series_stride; /* elements between two series */
+} hbvx_gram_desc;          /* hbvx_sizeof(9) */
+uint64_t hbvx_gram_workspace_bytes(const hbvx_gram_desc *g);   /* 0 for a descriptor hbvx_gram would refuse */
+int hbvx_gram(const hbvx_gram_desc *g, const float *s, const float *w, const float *r, float *gram, float *rhs,
+              float *cost, void *workspace, uint64_t workspace_bytes, void *stream);
 
 /* Zero `bytes` bytes at `ptr` (streaming non-temporal stores).  The autograd contract of the plug-in wants
  * gradient tensors shaped like the raw parameter tensor [T,B,ny] (hbv.py:211-246: static parameters read
