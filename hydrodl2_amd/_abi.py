@@ -139,7 +139,7 @@ OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forwa
                     "hbvx_bfi_tangent_batch", "hbvx_lstm_tangent_batch", "hbvx_lstm_tangent_batch_workspace_bytes",
                     "hbvx_hourly_tangent_batch", "hbvx_gage_route_tangent_batch",
                     "hbvx_gage_route_tangent_workspace_bytes", "hbvx_adj_tangent_batch", "hbvx_gram",
-                    "hbvx_gram_workspace_bytes"]
+                    "hbvx_gram_workspace_bytes", "hbvx_quadform", "hbvx_quadform_workspace_bytes"]
 
 
 class HbvxError(RuntimeError):
@@ -279,11 +279,17 @@ class Library:
             d.hbvx_gram.restype = C.c_int
             d.hbvx_gram.argtypes = [C.POINTER(GramDesc), _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_uint64,
                                     C.c_void_p]
-            if d.hbvx_sizeof(9) != C.sizeof(GramDesc):
-                raise HbvxError(f"{path}: layout mismatch for GramDesc: {d.hbvx_sizeof(9)} != {C.sizeof(GramDesc)}")
         if "hbvx_gram_workspace_bytes" not in self.missing:
             d.hbvx_gram_workspace_bytes.restype = C.c_uint64
             d.hbvx_gram_workspace_bytes.argtypes = [C.POINTER(GramDesc)]
+        if "hbvx_quadform" not in self.missing:
+            d.hbvx_quadform.restype = C.c_int
+            d.hbvx_quadform.argtypes = [C.POINTER(GramDesc), _fp, _fp, _fp, C.c_void_p, C.c_uint64, C.c_void_p]
+        if "hbvx_quadform_workspace_bytes" not in self.missing:
+            d.hbvx_quadform_workspace_bytes.restype = C.c_uint64
+            d.hbvx_quadform_workspace_bytes.argtypes = [C.POINTER(GramDesc)]
+        if not {"hbvx_gram", "hbvx_quadform"} <= set(self.missing) and d.hbvx_sizeof(9) != C.sizeof(GramDesc):
+            raise HbvxError(f"{path}: layout mismatch for GramDesc: {d.hbvx_sizeof(9)} != {C.sizeof(GramDesc)}")
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -457,6 +463,15 @@ class Library:
         self.require("hbvx_gram")
         self._check(self.dll.hbvx_gram(C.byref(g), s, w, r, gram, rhs, cost, ws, C.c_uint64(ws_bytes),
                                        C.c_void_p(stream)), "hbvx_gram")
+
+    def quadform_workspace_bytes(self, g: GramDesc) -> int:
+        self.require("hbvx_quadform_workspace_bytes")
+        return int(self.dll.hbvx_quadform_workspace_bytes(C.byref(g)))
+
+    def quadform(self, g: GramDesc, s: int, m: int, q: int, ws, ws_bytes: int, stream: int):
+        self.require("hbvx_quadform")
+        self._check(self.dll.hbvx_quadform(C.byref(g), s, m, q, ws, C.c_uint64(ws_bytes), C.c_void_p(stream)),
+                    "hbvx_quadform")
 
     def gage_route_tangent_workspace_bytes(self, r: GageDesc, n_dir: int) -> int:
         self.require("hbvx_gage_route_tangent_workspace_bytes")

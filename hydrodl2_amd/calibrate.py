@@ -35,23 +35,28 @@ def _static_tensor(req_or_two, parameters):
     return parameters[1] if req_or_two else parameters
 
 
-def _check_request(model, x_dict, parameters, target, names, key, weights, max_directions) -> _Request:
-    """Everything that can be refused without running the model; what the call works on."""
+_NO_TARGET = object()     # predictive_variance (uncertainty.py) fits nothing: the same refusals without a target
+
+
+def _check_request(model, x_dict, parameters, target, names, key, weights, max_directions,
+                   what: str = "normal_equations") -> _Request:
+    """Everything that can be refused without running the model; what the call works on.  `what` names the caller in
+    the messages; target = _NO_TARGET skips the checks of target and weights."""
     adj = getattr(model, '_model_id', None) == _abi.MODEL_HBVADJ
     explicit = isinstance(model, HbvModule) and model._model_id in sensitivity._TANGENT_MODELS
     if not (adj or explicit):
-        raise NotImplementedError(f"normal_equations is not implemented for {type(model).__name__}: Hbv, Hbv_1_1p, Hbv_2 "
+        raise NotImplementedError(f"{what} is not implemented for {type(model).__name__}: Hbv, Hbv_1_1p, Hbv_2 "
                                   "and HbvAdj only (the hourly and multi-timescale models route to gages, which couple "
                                   "the units: their Jacobian is not one block per basin)")
     if model.graph:
         raise ValueError(f"{type(model).__name__}(graph=True) does not support forward-mode AD (batched directions); "
                          "use graph=False")
     if getattr(model, 'initialize', False):
-        raise ValueError("normal_equations: the module is in initialize mode (it returns states, no flux dictionary)")
+        raise ValueError(f"{what}: the module is in initialize mode (it returns states, no flux dictionary)")
     if key is None:
         key = 'flow_sim' if adj else 'streamflow'
     if key == 'BFI':
-        raise ValueError("normal_equations: 'BFI' is one number per basin, not a series to fit")
+        raise ValueError(f"{what}: 'BFI' is one number per basin, not a series")
     if adj:
         if key != 'flow_sim':
             raise KeyError(f"HbvAdj has no flux key {key!r}")
@@ -61,7 +66,7 @@ def _check_request(model, x_dict, parameters, target, names, key, weights, max_d
         raise ValueError("max_directions must be >= 1")
     tname, cols = jacobian_columns(model, names)
     if not cols:
-        raise ValueError("normal_equations needs at least one column")
+        raise ValueError(f"{what} needs at least one column")
     two = tname == 'p_sta'
     ptensor = _static_tensor(two, parameters)
     x = x_dict['x_phy']
@@ -71,7 +76,9 @@ def _check_request(model, x_dict, parameters, target, names, key, weights, max_d
     # Hbv_2 has no warm-up pass of its own: every day of the record is an output day
     T_out = int(x.shape[0]) - (0 if two else int(model.warm_up))
     if T_out < 1:
-        raise ValueError("normal_equations: no day is left after the warm-up")
+        raise ValueError(f"{what}: no day is left after the warm-up")
+    if target is _NO_TARGET:
+        return _Request(adj, key, tname, list(cols), T_out, B, width)
     if not torch.is_tensor(target) or tuple(target.shape) not in ((T_out, B), (T_out, B, 1)):
         raise ValueError(f"target must be [{T_out},{B}] or [{T_out},{B},1] (the days after the warm-up), got "
                          f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
@@ -101,12 +108,35 @@ def _residual(req: _Request, sim: torch.Tensor, target, weights):
     return torch.where(miss, torch.zeros_like(w), w).contiguous(), r
 
 
+def _primal_and_series(model, req: _Request, x_dict, parameters, max_directions: int):
+    """ONE run of the module, then its one-hot directions through the tangent kernels `max_directions` at a time into a
+    single direction-major buffer.  Returns (outputs, sim [T_out,B], series [C,T_out,B] float32)."""
+    with ops.record_paths() as records:
+        outputs = model(x_dict, parameters)
+    sim = outputs[req.key].detach()[..., 0]
+    if tuple(sim.shape) != (req.T_out, req.B):
+        raise RuntimeError(f"{type(model).__name__} returned {req.key} of shape {tuple(sim.shape)}, expected "
+                           f"({req.T_out}, {req.B})")
+    dev = sim.device
+    C = len(req.cols)
+    series = torch.empty((C, req.T_out, req.B), dtype=torch.float32, device=dev)
+    for c0, c1 in direction_chunks(C, max_directions):
+        tangents = {req.tname: one_hot_directions(req.cols[c0:c1], req.B, req.width, dev)}
+        if req.adj:
+            tan = adj_jvp._directional(model, records, tangents, None)
+        else:
+            tan = sensitivity._directional(model, records, tangents, [req.key])[req.key]
+        series[c0:c1].copy_(tan[..., 0])
+    return outputs, sim, series
+
+
 def normal_equations(model, x_dict: dict, parameters, target, names: Optional[Sequence[str]] = None,
                      key: Optional[str] = None, weights=None, max_directions: int = 64) -> dict:
     """Per-basin normal equations of a least-squares fit of one output series to `target`.
 
     With r = outputs[key][..., 0] - target and J as `parameter_jacobian` (HbvAdj: `adj_parameter_jacobian`) defines it,
-        {'JtJ': J^T W J [B,C,C], 'Jtr': J^T W r [B,C], 'cost': sum_t w r^2 [B], 'columns': [C indices],
+        {'JtJ': J^T W J [B,C,C], 'Jtr': J^T W r [B,C], 'cost': sum_t w r^2 [B], 'n_obs': [B] int64, the number of
+         (t, b) with a positive weight once NaN targets are masked, 'columns': [C indices],
          'outputs': the primal flux dictionary}.
     model     Hbv, Hbv_1_1p, Hbv_2 (key default 'streamflow', any series key) or HbvAdj (key 'flow_sim').
     names     as in `jacobian_columns`: static physical parameters (their nmul columns each) and routing parameters;
@@ -126,25 +156,12 @@ def normal_equations(model, x_dict: dict, parameters, target, names: Optional[Se
     simulated value raises ValueError after it."""
     req = _check_request(model, x_dict, parameters, target, names, key, weights, max_directions)
     get_library().require("hbvx_gram")
-    with ops.record_paths() as records:
-        outputs = model(x_dict, parameters)
-    sim = outputs[req.key].detach()[..., 0]
-    if tuple(sim.shape) != (req.T_out, req.B):
-        raise RuntimeError(f"{type(model).__name__} returned {req.key} of shape {tuple(sim.shape)}, expected "
-                           f"({req.T_out}, {req.B})")
+    outputs, sim, series = _primal_and_series(model, req, x_dict, parameters, max_directions)
     w, r = _residual(req, sim, target, weights)
-    dev = sim.device
-    C = len(req.cols)
-    series = torch.empty((C, req.T_out, req.B), dtype=torch.float32, device=dev)
-    for c0, c1 in direction_chunks(C, max_directions):
-        tangents = {req.tname: one_hot_directions(req.cols[c0:c1], req.B, req.width, dev)}
-        if req.adj:
-            tan = adj_jvp._directional(model, records, tangents, None)
-        else:
-            tan = sensitivity._directional(model, records, tangents, [req.key])[req.key]
-        series[c0:c1].copy_(tan[..., 0])
+    n_obs = (torch.full((req.B,), req.T_out, dtype=torch.int64, device=sim.device) if w is None
+             else (w > 0).sum(0, dtype=torch.int64))
     JtJ, Jtr, cost = ops.gram(series, w, r.contiguous())
-    return {'JtJ': JtJ, 'Jtr': Jtr, 'cost': cost, 'columns': list(req.cols), 'outputs': outputs}
+    return {'JtJ': JtJ, 'Jtr': Jtr, 'cost': cost, 'n_obs': n_obs, 'columns': list(req.cols), 'outputs': outputs}
 
 
 def lm_step(neq: dict, damping, eps: float = 1e-12):

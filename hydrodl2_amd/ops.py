@@ -1035,6 +1035,37 @@ def gram(series: torch.Tensor, w: Optional[torch.Tensor] = None, r: Optional[tor
     return out, rhs, cost
 
 
+def quadform(series: torch.Tensor, factor: torch.Tensor) -> torch.Tensor:
+    """Per-basin quadratic form of C series on a [T,B] grid through hbvx_quadform (include/hbvx.h), on the current
+    stream:  q[t,b] = |factor[b] @ series[:,t,b]|^2 = s^T (factor[b]^T factor[b]) s, [T,B] float32, >= 0.
+    series [C,T,B] float32 with [T,B] contiguous inside each series (any stride >= T*B between series: the layout the
+    tangent kernels write, a slice of it included); factor [B,C,C] float32, lower-triangular: what lies above the
+    diagonal is never read."""
+    lib = get_library()
+    lib.require("hbvx_quadform")
+    _check_tensor(lib, series, "series")
+    _check_tensor(lib, factor, "factor")
+    if series.dim() != 3 or min(series.shape) < 1:
+        raise ValueError(f"series must be a non-empty [C,T,B] tensor, got {tuple(series.shape)}")
+    Cn, T, B = (int(n) for n in series.shape)
+    if tuple(factor.shape) != (B, Cn, Cn):
+        raise ValueError(f"factor must be [{B},{Cn},{Cn}] (one lower-triangular matrix per basin), got {tuple(factor.shape)}")
+    if factor.device != series.device:
+        raise ValueError(f"factor lives on {factor.device}, series on {series.device}")
+    if series.stride(2) != 1 or series.stride(1) != B or (Cn > 1 and series.stride(0) < T * B):
+        series = series.contiguous()
+    g = _abi.GramDesc(abi_version=_abi.ABI_VERSION, T=T, B=B, C=Cn, series_stride=series.stride(0) if Cn > 1 else T * B)
+    fc = factor.contiguous()
+    dev = series.device
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        out = _out((T, B), dev)
+        ws_bytes = lib.quadform_workspace_bytes(g)
+        ws = _out(((max(ws_bytes, 4) + 3) // 4,), dev)      # poisoned with the output: the call must not need it cleared
+        _call(lib, 'hbvx_quadform', lib.quadform, g, _ptr(series), _ptr(fc), _ptr(out), _ptr(ws), ws_bytes,
+              _stream_of(lib, series))
+    return out
+
+
 class PathOut(NamedTuple):
     """What one call of the path returns.  `flux`: tuple of the n_flux series [T,B,1] (index it with the hbvx_flux
     enum) or None when cfg.want_flux is False; `routed`: tuple of the four UH-routed runoff series [T,B,1] or

@@ -496,6 +496,29 @@ uint64_t hbvx_gram_workspace_bytes(const hbvx_gram_desc *g);   /* 0 for a descri
 int hbvx_gram(const hbvx_gram_desc *g, const float *s, const float *w, const float *r, float *gram, float *rhs,
               float *cost, void *workspace, uint64_t workspace_bytes, void *stream);
 
+/* Per-basin quadratic form of the same series (optional exports; a library may lack them): with a lower-triangular
+ * factor M_b per basin,
+ *   q[t,b] = | M_b s[:,t,b] |^2 = s[:,t,b]^T (M_b^T M_b) s[:,t,b].
+ * With M_b^T M_b the parameter covariance of basin b and s the Jacobian's columns this is the first-order predictive
+ * variance of the series; with M_b the inverse Cholesky factor of J^T W J it is the leverage (times the weight).
+ * g: hbvx_gram_desc as for hbvx_gram (T, B, C, series_stride).  s: as for hbvx_gram.
+ * m: [B,C,C] row-major, lower-triangular: elements with column > row are NEVER READ and may hold anything, NaN included.
+ * q: [T,B], overwritten completely.
+ * workspace: caller-owned scratch of at least hbvx_quadform_workspace_bytes(g) (the lower triangles with the basin as
+ *    the unit-stride axis, C(C+1)/2 * B floats), contents undefined before and after; the call does not need it cleared.
+ * Arithmetic (csrc/hbv_quadform.h), float32 throughout, per (t, b):
+ *   y_e = chain over ascending c = 0..e:    acc = fmaf(m[b,e,c], s[c,t,b], acc), from 0
+ *   q   = chain over ascending e = 0..C-1:  q = fmaf(y_e, y_e, q), from 0
+ * The factor form halves the multiply-adds of s^T Sigma s and makes the result a sum of squares.
+ * Guarantees: (1) two calls on the same inputs give the same bits; (2) q >= 0, and finite for finite inputs whose
+ * result is in range; (3) the bits of q[t,b] depend on m[b] and s[:,t,b] alone -- not on T, B, the other days or
+ * basins, series_stride or any tiling; (4) the upper triangle of m is not read; (5) no atomics are used.
+ * Errors, reported before anything is launched: HBVX_E_NULL (descriptor, s, m, q, a missing or too small workspace),
+ * HBVX_E_SHAPE (T/B/C <= 0, C > HBVX_GRAM_MAX_C, series_stride < T*B), HBVX_E_ABI. */
+uint64_t hbvx_quadform_workspace_bytes(const hbvx_gram_desc *g);   /* 0 for a descriptor hbvx_quadform would refuse */
+int hbvx_quadform(const hbvx_gram_desc *g, const float *s, const float *m, float *q, void *workspace,
+                  uint64_t workspace_bytes, void *stream);
+
 /* Zero `bytes` bytes at `ptr` (streaming non-temporal stores).  The autograd contract of the plug-in wants
  * gradient tensors shaped like the raw parameter tensor [T,B,ny] (hbv.py:211-246: static parameters read
  * one row of it), so the dense zero fill is part of every backward step. */
