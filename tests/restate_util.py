@@ -194,22 +194,14 @@ def abi_hourly(prob: dict, dtype=torch.float64, x_grad: bool = True, backward: b
     return res
 
 
-def abi_daily(prob: dict, dtype=torch.float64, x_grad: bool = True, backward: bool = True, events=None) -> dict:
-    """An abi_util.make_problem dict of a daily model (Hbv, Hbv_1_1p, Hbv_2) through the restatement at the level of the
-    C ABI, in `dtype`: raw parameters [T,B,ny] through the sigmoid (static value = row T-1, dynamic rows where the
-    parameter is dynamic and its basin not dropped), forcing channels prob["channels"], storages carried in from
-    prob["state_in"], the 11 / 12 flux rows (means over the members; Qsim weighted by muwts where given), with
-    prob["routing"] the four 15-tap routed rows (Qsim, Q0, Q1, Q2 through hbv_restate64.gamma_uh / route, routing
-    columns from row T-1 with run_problem's RouteSource bounds), and the loss sum(flux * gflux) + sum(routed * grouted)
-    as abi_util.run_problem forms it.  Returns run_problem's keys: flux, routed, traj [5,T+1,B*M], state_out [5,B,M],
-    g_params, g_x, g_muwts (float64 numpy).  `events`: see hbv_restate64._pbm."""
+def daily_forward(prob: dict, x, raw, mu, st, dtype=torch.float64, events=None):
+    """The forward of abi_daily on tensors the caller made (leaves of a backward pass, or duals of a forward-AD
+    level): x [T,B,C], raw parameters [T,B,ny], mu [T,B,M] or None, st the five storages [B,M] carried in.  Returns
+    (flux [11 or 12,T,B], routed [4,T,B] or None, the five final storages, the five storage series [T,B,M])."""
     from .abi_util import BOUNDS
     R = restate()
     model, T, B, M, names = prob["model"], prob["T"], prob["B"], prob["M"], prob["names"]
     assert model in R.MODELS, model
-    x = torch.from_numpy(prob["x"]).to(dtype).requires_grad_(x_grad and backward)
-    raw = torch.from_numpy(prob["params"]).to(dtype).requires_grad_(backward)
-    mu = torch.from_numpy(prob["muwts"]).to(dtype).requires_grad_(backward) if "muwts" in prob else None
     ac = torch.from_numpy(prob["ac"]).to(dtype) if "ac" in prob else None
     elev = torch.from_numpy(prob["elev"]).to(dtype) if "elev" in prob else None
     unit = torch.sigmoid(raw[:, :, :len(names) * M]).reshape(T, B, len(names), M)
@@ -224,10 +216,6 @@ def abi_daily(prob: dict, dtype=torch.float64, x_grad: bool = True, backward: bo
                 dyn = dyn * (1 - m) + v * m
             v = dyn
         par[nm] = v * (hi - lo) + lo
-    if "state_in" in prob:
-        st = tuple(torch.from_numpy(prob["state_in"][k]).to(dtype) for k in range(5))
-    else:
-        st = tuple(torch.full((B, M), 0.001, dtype=dtype) for _ in range(5))
     ch = prob.get("channels", (0, 1, 2))
     s, st_out, ser = R._pbm(model, x[:, :, ch[0]], x[:, :, ch[1]], x[:, :, ch[2]], par, st, 1e-5, ac, elev, events,
                             want_series=True)
@@ -238,15 +226,38 @@ def abi_daily(prob: dict, dtype=torch.float64, x_grad: bool = True, backward: bo
     if mu is not None:
         rows[0] = (s["Qsim"] * mu).sum(-1)
     flux = torch.stack(rows)
-    traj = torch.stack([torch.cat([st[k].unsqueeze(0), ser[k].detach()]).reshape(T + 1, B * M) for k in range(5)])
-    res = {"flux": flux.detach().numpy(), "traj": traj.numpy(),
-           "state_out": torch.stack([v.detach() for v in st_out]).numpy()}
-    loss = (flux * torch.from_numpy(prob["gflux"]).to(dtype)).sum()
+    routed = None
     if prob["routing"]:
         n = len(names)
         ab = torch.sigmoid(raw[-1, :, n * M:n * M + 2])
         uh = R.gamma_uh(ab[:, 0] * 2.9, ab[:, 1] * 6.5, min(T, 15))
         routed = torch.stack([R.route(flux[k], uh) for k in range(4)])
+    return flux, routed, st_out, ser
+
+
+def abi_daily(prob: dict, dtype=torch.float64, x_grad: bool = True, backward: bool = True, events=None) -> dict:
+    """An abi_util.make_problem dict of a daily model (Hbv, Hbv_1_1p, Hbv_2) through the restatement at the level of the
+    C ABI, in `dtype`: raw parameters [T,B,ny] through the sigmoid (static value = row T-1, dynamic rows where the
+    parameter is dynamic and its basin not dropped), forcing channels prob["channels"], storages carried in from
+    prob["state_in"], the 11 / 12 flux rows (means over the members; Qsim weighted by muwts where given), with
+    prob["routing"] the four 15-tap routed rows (Qsim, Q0, Q1, Q2 through hbv_restate64.gamma_uh / route, routing
+    columns from row T-1 with run_problem's RouteSource bounds), and the loss sum(flux * gflux) + sum(routed * grouted)
+    as abi_util.run_problem forms it.  Returns run_problem's keys: flux, routed, traj [5,T+1,B*M], state_out [5,B,M],
+    g_params, g_x, g_muwts (float64 numpy).  `events`: see hbv_restate64._pbm."""
+    T, B, M = prob["T"], prob["B"], prob["M"]
+    x = torch.from_numpy(prob["x"]).to(dtype).requires_grad_(x_grad and backward)
+    raw = torch.from_numpy(prob["params"]).to(dtype).requires_grad_(backward)
+    mu = torch.from_numpy(prob["muwts"]).to(dtype).requires_grad_(backward) if "muwts" in prob else None
+    if "state_in" in prob:
+        st = tuple(torch.from_numpy(prob["state_in"][k]).to(dtype) for k in range(5))
+    else:
+        st = tuple(torch.full((B, M), 0.001, dtype=dtype) for _ in range(5))
+    flux, routed, st_out, ser = daily_forward(prob, x, raw, mu, st, dtype, events)
+    traj = torch.stack([torch.cat([st[k].unsqueeze(0), ser[k].detach()]).reshape(T + 1, B * M) for k in range(5)])
+    res = {"flux": flux.detach().numpy(), "traj": traj.numpy(),
+           "state_out": torch.stack([v.detach() for v in st_out]).numpy()}
+    loss = (flux * torch.from_numpy(prob["gflux"]).to(dtype)).sum()
+    if routed is not None:
         res["routed"] = routed.detach().numpy()
         loss = loss + (routed * torch.from_numpy(prob["grouted"]).to(dtype)).sum()
     if backward:
