@@ -1,9 +1,9 @@
 // hbvx_host.h -- host-side plumbing shared by the translation units of libhbvx.so.
 //
 // The library is built from several .hip files compiled in parallel (one per kernel family:
-// pipelined / streaming / tiled / time-parallel / implicit / LSTM) so that touching one family
-// rebuilds one file.  The C ABI (include/hbvx.h) lives in hbvx.hip; its dispatchers call the
-// family launchers declared here.  A launcher returns true when its family took the call and has
+// pipelined / streaming / tiled / time-parallel / implicit / tangent recurrence / LSTM) so that touching
+// one family rebuilds one file.  The C ABI (include/hbvx.h) lives in hbvx.hip, apart from the entry points
+// that are a family's own (launch_tan.hip); its dispatchers call the family launchers declared here.  A launcher returns true when its family took the call and has
 // then set *rc to the ABI return code.
 #pragma once
 

@@ -349,8 +349,9 @@ int hbvx_adj_backward(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream);
  * given the tangents of the raw inputs, the tangents of the flux series and of the final storages.  The call re-runs
  * the primal day by day beside the five state tangents (one lane per (basin, member)); the primal outputs themselves
  * come from hbvx_forward.  hbvx_route_tangent and hbvx_bfi_tangent run the kernels of the several-direction calls
- * below with one direction; hbvx_forward_tangent has a kernel of its own (every series, no direction strides: 3 %
- * faster than the several-direction kernel at one direction) with the same arithmetic.  Conventions are torch's forward formulas (binary minimum: 1/2 each at a tie; clamps
+ * below with one direction; hbvx_forward_tangent runs an instantiation of its own of the several-direction kernel's
+ * text (every series, no direction strides: 3 % faster than the several-direction instance at one direction) with the
+ * same arithmetic.  Conventions are torch's forward formulas (binary minimum: 1/2 each at a tie; clamps
  * inclusive; d(x**y) = 0 at x == 0), the transpose of hbvx_backward's.  dy_drop masks (hbvx_param_src.drop) blend
  * the tangents as they blend the values.  Tangents of `ac` / `elev` are not supported.
  * Tangent of a raw parameter tensor: same addressing as hbvx_param_src (dyn rows for every (t,b,j) of the call

@@ -1,8 +1,8 @@
-"""GPU tier: the daily models' tangent kernels at the level of the C ABI -- hbvx_forward_tangent_batch
-(k_fwd_tan_batch around Step<HBV10 / HBV11P / HBV20>::tan), hbvx_route_tangent_batch, hbvx_bfi_tangent_batch and
-the one-direction hbvx_forward_tangent (k_fwd_tan) -- on the problems of tests/daily_jvp_util.py::TAN_PROBLEMS, whose
-wet branches are taken (tests/test_daily_jvp_f64.py asserts the coverage and that the reference alone stays within
-the protocol).
+"""GPU tier: the daily models' tangent kernels at the level of the C ABI -- hbvx_forward_tangent_batch (k_tan<..,
+TanBatchArgs> around Step<HBV10 / HBV11P / HBV20>::tan), hbvx_route_tangent_batch, hbvx_bfi_tangent_batch and the
+one-direction hbvx_forward_tangent (k_tan<.., TanArgs>) -- on the problems of tests/daily_jvp_util.py::TAN_PROBLEMS,
+whose wet branches are taken (tests/test_daily_jvp_f64.py asserts the coverage and that the reference alone stays
+within the protocol).
 
 (a) Against forward AD of oracle/hbv_restate64.py in float64 along one direction over x, params, muwts and state_in:
     the 11 / 12 flux rows, tan_state_out and the four routed rows at TAN_RTOL + TAN_ATOL_REL x max|float64 tangent of
@@ -14,7 +14,7 @@ the protocol).
     the kernel's own branches.
 (c) On wet400, wet2(-all-drop) and wet65-channels of each model: directions 0, 3 and 4 of a D = 5 call are
     bit-identical to D = 1 calls, a mask of rows {0, 5, 10} to those rows of the full mask, and the one-direction
-    entry point (k_fwd_tan; ops._hbv_tangent on the recorded call) to D = 1 at the full mask.
+    entry point (k_tan<.., TanArgs>; ops._hbv_tangent on the recorded call) to D = 1 at the full mask.
 
 Measured on the MI355X.  (a) elements outside tolerance against float64, every one admitted -- the same counts, problem
 by problem, as the float32 restatement's in tests/test_daily_jvp_f64.py: flux 2 / 74800 (Hbv wet400, wet400-d3), 2 / 95073

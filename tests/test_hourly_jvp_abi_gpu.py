@@ -1,10 +1,10 @@
-"""GPU tier: hbvx_hourly_tangent_batch (k_hourly_tan_batch around Step<MODEL_HOURLY>::tan) at the level of the C ABI
-against forward AD of oracle/hbv_restate64.py's pbm_hourly in float64, on problems of tests/hourly_sets.py whose wet
-branches are taken: all twelve series and tan_state_out at TAN_RTOL + TAN_ATOL_REL x max|float64 tangent of the
-series| under hourly_sets.admit (an element outside tolerance is admitted only where it agrees with the restatement
-run in float32; at most ADMIT_CAP of an array).  On the same problems: the per-basin transpose identity against
-hbvx_backward's gradients, direction d of a D = 5 call bit-identical to D = 1, and a mask of rows {0, 5, 10}
-bit-identical to those rows of the full mask."""
+"""GPU tier: hbvx_hourly_tangent_batch (k_tan<MODEL_HOURLY, true, TanBatchArgs> around Step<MODEL_HOURLY>::tan) at the
+level of the C ABI against forward AD of oracle/hbv_restate64.py's pbm_hourly in float64, on problems of
+tests/hourly_sets.py whose wet branches are taken: all twelve series and tan_state_out at TAN_RTOL + TAN_ATOL_REL x
+max|float64 tangent of the series| under hourly_sets.admit (an element outside tolerance is admitted only where it
+agrees with the restatement run in float32; at most ADMIT_CAP of an array).  On the same problems: the per-basin
+transpose identity against hbvx_backward's gradients, direction d of a D = 5 call bit-identical to D = 1, and a mask of
+rows {0, 5, 10} bit-identical to those rows of the full mask."""
 import numpy as np
 import pytest
 import torch

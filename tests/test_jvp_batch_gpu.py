@@ -5,10 +5,10 @@ tolerances are those of tests/test_jvp_gpu.py: the same quantity against the sam
 (a) every JVP case with the three directions [v, 0, 2 v]: [0] against the reference's tangents
     (tests/golden/jvp_<case>.npz), [1] exactly zero, [2] twice [0] (a tangent-linear chain scaled by two is exact in
     binary floating point short of underflow);
-(b) D in {1, 5, 37} directions against D one-direction forward_ad calls (several directions on the grid's second
-    axis, direction strides); routing and BFI run the same kernels on both sides, the recurrence two (k_fwd_tan and
-    k_fwd_tan_batch, two schedules): whether the results are bit-identical is recorded in the parity report, not
-    asserted;
+(b) D in {1, 5, 37} directions against D one-direction forward_ad calls (several directions on the grid's second axis,
+    direction strides); routing and BFI run the same kernels on both sides, the recurrence two (k_tan<.., TanArgs> and
+    k_tan<.., TanBatchArgs>, two schedules): whether the results are bit-identical is recorded in the parity report,
+    not asserted;
 (c) the primal outputs are bit-identical to a plain call and the generator advances as in one plain call;
 (d) parameter_jacobian contracted with the loss weights against row T-1 of the module's own backward gradient, at
     twice the gradient tolerance of tests/abi_util.py (both sides are float32 kernels, each with its own error of that

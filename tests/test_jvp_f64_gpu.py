@@ -1,7 +1,7 @@
-"""GPU tier: the tangent kernels (k_fwd_tan, and k_route_tan_batch, k_bfi_tan_batch at one direction, behind Hbv,
-Hbv_1_1p and Hbv_2 under torch.autograd.forward_ad) against forward AD of oracle/hbv_restate64.py in float64 on the
-same float32 inputs, at _assert_tangent_close's default tolerance (rtol 1e-3, atol 2e-6 x max|float64 tangent| of the
-key) -- BFI included.
+"""GPU tier: the tangent kernels (k_tan<.., TanArgs>, and k_route_tan_batch, k_bfi_tan_batch at one direction, behind
+Hbv, Hbv_1_1p and Hbv_2 under torch.autograd.forward_ad) against forward AD of oracle/hbv_restate64.py in float64 on
+the same float32 inputs, at _assert_tangent_close's default tolerance (rtol 1e-3, atol 2e-6 x max|float64 tangent| of
+the key) -- BFI included.
 
 (a') the 22 forward-mode fixture cases of test_jvp_gpu.py (a) against float64 (there BFI is held to 1e-2 only,
      the reference's own float32 BFI tangent being off by up to 8e-3);

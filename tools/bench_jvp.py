@@ -61,7 +61,7 @@ def _alternating_ms(fns, steps, warmup):
 
 
 def _grid(B, M, D):
-    """The launch of hbvx_forward_tangent_batch: one direction per lane (k_fwd_tan_batch in csrc/hbvx.hip), one wavefront
+    """The launch of hbvx_forward_tangent_batch: one direction per lane (k_tan<.., TanBatchArgs> in csrc/hbv_tan.h), one wavefront
     per 64 / Mp basins (Mp: the next power of two >= M), the directions on the grid's second axis."""
     Mp = 1
     while Mp < M:
