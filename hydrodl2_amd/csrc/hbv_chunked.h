@@ -17,6 +17,11 @@
 //   B4 k_bwd_chunk_reduce per (parameter, lane): fixed-order sum of the chunk partials (deterministic),
 //                         sigmoid' chain, accumulate into the static-row gradient.
 //
+// With every parameter static (HBV 1.0, no muwts, no forcing gradient) B1 and B3 are one kernel, k_bwd_chunk_onepass:
+// it carries the parameter-Jacobian sums G_c, g0_c of the chunk's unit adjoints and offset beside the map, runs as a
+// workgroup of ChunkArgs::group waves on consecutive chunks and composes their maps on chip (hbv_onepass_compose.h),
+// so that B2, k_bwd_chunk_fold and B4 see one map per group.
+//
 // ~19 000 independent waves at cfg2 instead of 168 serial ones: the adjoint becomes throughput/HBM
 // bound.  B1 and B3 are plain one-wave-per-block kernels with direct global loads -- there is now
 // enough thread-level parallelism to hide memory latency without LDS staging.
@@ -28,6 +33,7 @@
 
 #include "../../include/hbvx.h"
 #include "hbv_step.h"
+#include "hbv_onepass_compose.h"
 
 namespace hbvx {
 
@@ -44,6 +50,8 @@ struct ChunkArgs {
     int nd;       // DYN == 1: number of dynamic parameters (<= CHUNK_FEW) and their slots
     int dslot[3];
     int per_xcd;  // basin groups per XCD of the block map below (host: chunk_per_xcd)
+    int group;    // k_bwd_chunk_onepass only: consecutive chunks composed per workgroup (1 .. ONEPASS_GMAX); its scan,
+                  // fold and reduce see the groups as their chunks (nchunk = number of groups)
 };
 
 // XCD-aware block -> (basin group, chunk) map of the two chunk-parallel kernels.  Workgroups are dealt round-robin
@@ -470,24 +478,53 @@ __global__ void __launch_bounds__(64) k_bwd_chunk_phi(const ChunkArgs A)
 // stay in the snow block (4 parameters), Phi[2] reaches snow and soil (7 / 8), Phi[3..4] and the offset all NP.
 // Workspace rows of a chunk (ChunkArgs::gpart, [nchunk][onepass_rows(NP)][N]): per parameter i, the rows of G_c for
 // k = onepass_kmin(i) .. 4, then g0_c[i].  k_bwd_chunk_fold + k_bwd_chunk_reduce finish sum_c (G_c a_c + g0_c).
-__host__ __device__ constexpr int onepass_kmin(int i)
-{
-    return (i == P_TT || i == P_CFMAX || i == P_CFR || i == P_CWH) ? 0
-         : ((i == P_BETA || i == P_FC || i == P_LP || i == P_BETAET) ? 2 : 3);
-}
-__host__ __device__ constexpr int onepass_row(int i)
-{
-    int r = 0;
-    for (int j = 0; j < i; j++) r += 6 - onepass_kmin(j);
-    return r;
-}
-__host__ __device__ constexpr int onepass_rows(int NP) { return onepass_row(NP); }
+// (onepass_kmin / onepass_row / onepass_rows: hbv_onepass_compose.h)
+//
+// Grouped form: a workgroup of A.group waves takes A.group consecutive chunks of the same 64 lanes, wave w the chunk
+// grp * group + w with the day loop above unchanged.  Consecutive chunks compose exactly (onepass_compose), so behind
+// the loops the waves fold their maps into one, latest chunk first, through one LDS hand-over slot that holds the
+// rows of a map as they lie in the workspace ([30 + onepass_rows(NP)][64] floats): the latest wave writes its map,
+// and behind a workgroup barrier the next earlier wave composes itself onto the slot and writes the result back, down
+// to wave 0, which stores the group's rows to phi[grp] / gpart[grp].  One map per group instead of one per chunk: the
+// scan hops nchunk / group times and the fold reads 1 / group of the rows.  The stages are written out one by one,
+// so that the day loop stays the kernel's largest loop; every barrier sits in control flow that is
+// uniform over the workgroup, and waves of a last, short group whose chunk lies past the record run no day loop and
+// only keep the barriers company.  With group == 1 no LDS is allocated or touched and the rows are the chunk's own.
+#define ONEPASS_GMAX 4
+__host__ __device__ constexpr int onepass_slot_bytes(int NP) { return (30 + onepass_rows(NP)) * 64 * (int)sizeof(float); }
+
+// The hand-over slot (s = slot + lane) and the workspace rows of a group (phi[grp], gpart[grp], + lane) as
+// onepass_compose's source and sinks: both hold the rows of a map in the same order.
+template <int NP>
+struct OnepassSlot {
+    float *s;
+    __device__ __forceinline__ float Phi(int k, int j) const { return s[(k * 5 + j) * 64]; }
+    __device__ __forceinline__ float phi(int j) const { return s[(25 + j) * 64]; }
+    __device__ __forceinline__ float G(int k, int p) const { return s[(30 + onepass_row(p) + k - onepass_kmin(p)) * 64]; }
+    __device__ __forceinline__ void Phi(int k, int i, float v) { s[(k * 5 + i) * 64] = v; }
+    __device__ __forceinline__ void phi(int i, float v) { s[(25 + i) * 64] = v; }
+    __device__ __forceinline__ void G(int k, int p, float v) { s[(30 + onepass_row(p) + k - onepass_kmin(p)) * 64] = v; }
+};
+template <int NP>
+struct OnepassRows {
+    float *m, *g;     // the lane's column of phi[grp] and of gpart[grp]
+    int64_t N;
+    bool active;
+    __device__ __forceinline__ void Phi(int k, int i, float v) { if (active) m[(int64_t)(k * 5 + i) * N] = v; }
+    __device__ __forceinline__ void phi(int i, float v) { if (active) m[(int64_t)(25 + i) * N] = v; }
+    __device__ __forceinline__ void G(int k, int p, float v)
+    {
+        if (active) g[(int64_t)(onepass_row(p) + k - onepass_kmin(p)) * N] = v;
+    }
+};
 
 // Registers: 156 / 161 VGPRs (three waves per SIMD) with the runoff-only loss, 179 / 187 (two) with GFULL's full adjoint
 // step on the offset.  Forced to 128 (four waves) the compiler spills 19-33 values (runoff-only) and 84-98 (GFULL).
 template <bool BETAET, bool GFULL>
-__global__ void __launch_bounds__(64) k_bwd_chunk_onepass(const ChunkArgs A)
+__global__ void __launch_bounds__(64 * ONEPASS_GMAX) __attribute__((amdgpu_waves_per_eu(GFULL ? 2 : 3)))
+k_bwd_chunk_onepass(const ChunkArgs A)
 {
+    extern __shared__ float onepass_slot[];
     constexpr int MODEL = MODEL_HBV10, DYN = 0;
     constexpr int NP = ChunkNP<MODEL, BETAET>::value;
     typedef Step<MODEL, BETAET> S;
@@ -497,7 +534,10 @@ __global__ void __launch_bounds__(64) k_bwd_chunk_onepass(const ChunkArgs A)
     ChunkBlock blk;
     if (!chunk_block(d, A.lgMp, A.per_xcd, blk)) return;
     const ChunkLane L = chunk_lane(d, A.lgMp, blk.bx);
-    const int chunk = blk.chunk;
+    const int grp = blk.chunk;                                              // the block map deals groups
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);    // wave of the workgroup
+    const int nw = min(min(A.group, ONEPASS_GMAX), A.nchunk - grp * A.group);   // waves of this group with a chunk
+    const int chunk = grp * A.group + w;
     const int t0 = chunk * A.C, t1 = min(d.T, t0 + A.C);
     const int64_t N = (int64_t)d.B * d.M;
     const bool raw = d.raw_sigmoid != 0;
@@ -518,6 +558,7 @@ __global__ void __launch_bounds__(64) k_bwd_chunk_onepass(const ChunkArgs A)
     for (int k = 0; k < 6; k++)
 #pragma unroll
         for (int i = 0; i < NPARAM_MAX; i++) G[k][i] = 0.0f;
+    if (w < nw) {   // (a wave past the record's last chunk has no days: nothing to load)
     ChunkRaw<NP> Rn;
     chunk_issue<NP, DYN, GFULL>(d, io, L, t1 - 1, io.n_flux, Rn, 0, ds_);
     for (int t = t1 - 1; t >= t0; t--) {
@@ -540,23 +581,34 @@ __global__ void __launch_bounds__(64) k_bwd_chunk_onepass(const ChunkArgs A)
             D.s.bwd(D.p, nz, D.g, phi, G[5], gx);   // its gp output is g0_c
         }
     }
-    if (L.active) {
-        float *dst = A.phi + ((int64_t)chunk * 30) * N + L.n;
-#pragma unroll
-        for (int k = 0; k < 5; k++)
-#pragma unroll
-            for (int i = 0; i < 5; i++) dst[(int64_t)(k * 5 + i) * N] = Phi[k][i];
-#pragma unroll
-        for (int i = 0; i < 5; i++) dst[(int64_t)(25 + i) * N] = phi[i];
-        float *gdst = A.gpart + ((int64_t)chunk * onepass_rows(NP)) * N + L.n;
-#pragma unroll
-        for (int i = 0; i < NP; i++) {
-            const int r0 = onepass_row(i), k0 = onepass_kmin(i);
-#pragma unroll
-            for (int kk = 0; kk < 5; kk++)
-                if (kk >= k0) gdst[(int64_t)(r0 + kk - k0) * N] = G[kk][i];
-            gdst[(int64_t)(r0 + 5 - k0) * N] = G[5][i];
+    }
+    OnepassRows<NP> rows{A.phi + ((int64_t)grp * 30) * N + L.n, A.gpart + ((int64_t)grp * onepass_rows(NP)) * N + L.n, N,
+                         L.active};
+    if (A.group == 1) {
+        onepass_put<float, NP>(Phi, phi, G, rows);
+        return;
+    }
+    // Hand-over, latest chunk first: the last wave with a chunk puts its map into the slot, then stage s belongs to wave
+    // s.  nw and s are the same for every wave of the workgroup, so all of them (those without a chunk too) meet at
+    // every barrier.
+    OnepassSlot<NP> slot{onepass_slot + (threadIdx.x & 63)};
+    if (w == nw - 1 && w > 0) onepass_put<float, NP>(Phi, phi, G, slot);
+    // (Written out stage by stage and nested, so that no stage tests nw again behind a barrier: as a loop over s, or as
+    // three tests in a row, the compiler lays branches back across the compositions and the day loop is no longer the
+    // kernel's largest loop.)
+    static_assert(ONEPASS_GMAX == 4, "one stage per wave above wave 0");
+    if (nw > 1) {
+        if (nw > 2) {
+            if (nw > 3) __syncthreads();                                      // stage 3: wave 3 has put its map
+            if (w == 2 && nw > 3) onepass_compose<float, NP, false>(slot, Phi, phi, G, slot);
+            __syncthreads();
         }
+        if (w == 1 && nw > 2) onepass_compose<float, NP, false>(slot, Phi, phi, G, slot);
+        __syncthreads();
+    }
+    if (w == 0) {
+        if (nw == 1) onepass_put<float, NP>(Phi, phi, G, rows);
+        else onepass_compose<float, NP, true>(slot, Phi, phi, G, rows);
     }
 }
 
@@ -794,7 +846,7 @@ __global__ void __launch_bounds__(256) k_bwd_chunk_reduce(const ChunkArgs A, int
 }
 
 // ---- B4 of the one-pass form --------------------------------------------------------------------
-// Two fixed-order stages (deterministic).  k_bwd_chunk_fold: per (lane, group of ONEPASS_GROUP chunks), every
+// Two fixed-order stages (deterministic).  k_bwd_chunk_fold: per (lane, group of ONEPASS_FOLD_GROUP chunks), every
 // parameter at once: sum over the group's chunks of G_c a_c + g0_c, times (hi - lo) -- each G_c row and boundary
 // adjoint is read once, by ~4 900 waves at config 2 (a first version with one thread per (parameter, lane) walking
 // all 115 chunks read the boundary adjoints 39 times over on 2 000 waves: 0.26 ms).  The group partials go to the
@@ -804,7 +856,7 @@ __global__ void __launch_bounds__(256) k_bwd_chunk_reduce(const ChunkArgs A, int
 // aPERC = SLZ share - SUZ share), which the two-pass sweep does day by day on the true adjoint instead.  In float32
 // the one-pass parPERC gradient missed float64 by 2.3 x the two-pass error at 32 x 16 x 730
 // (tests/test_chunk_onepass_f64_gpu.py); the fold is memory-bound, the float64 arithmetic is free.
-#define ONEPASS_GROUP 4
+#define ONEPASS_FOLD_GROUP 4
 template <int NP>
 __global__ void __launch_bounds__(256) k_bwd_chunk_fold(const ChunkArgs A)
 {
@@ -814,7 +866,7 @@ __global__ void __launch_bounds__(256) k_bwd_chunk_fold(const ChunkArgs A)
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
     const int grp = blockIdx.y;
-    const int c0 = grp * ONEPASS_GROUP, c1 = min(A.nchunk, c0 + ONEPASS_GROUP);
+    const int c0 = grp * ONEPASS_FOLD_GROUP, c1 = min(A.nchunk, c0 + ONEPASS_FOLD_GROUP);
     double acc[NP];
 #pragma unroll
     for (int i = 0; i < NP; i++) acc[i] = 0.0;

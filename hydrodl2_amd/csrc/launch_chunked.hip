@@ -60,6 +60,16 @@ extern "C" uint64_t hbvx_backward_workspace_bytes(const hbvx_desc *d)
 static std::atomic<int> g_chunk_form{0};
 extern "C" int hbvx_chunk_form(void) { return g_chunk_form.load(); }
 
+// Chunks composed per workgroup of the one-pass form (hbv_chunked.h, k_bwd_chunk_onepass).  HBVX_ONEPASS_GROUP is a
+// test / tool knob like HBVX_CHUNK_ONEPASS; 1 writes one map per chunk.  Default: profiles/r15_onepass_group.md.
+#define ONEPASS_GROUP_DEFAULT 4
+static int onepass_group() { return std::min(std::max(env_int("HBVX_ONEPASS_GROUP", ONEPASS_GROUP_DEFAULT), 1), ONEPASS_GMAX); }
+// Diagnostics for tests and tools: the group size of the last one-pass call (0: none yet), and the LDS a workgroup of
+// a grouped call takes (its hand-over slot) for a model of n_param parameters.
+static std::atomic<int> g_onepass_group{0};
+extern "C" int hbvx_onepass_group(void) { return g_onepass_group.load(); }
+extern "C" int hbvx_onepass_slot_bytes(int n_param) { return onepass_slot_bytes(n_param); }
+
 template <int MODEL, bool BETAET, int DYN, bool GFULL>
 static hipError_t launch_chunked_t(const ChunkArgs &a, hipStream_t st, bool onepass)
 {
@@ -70,14 +80,22 @@ static hipError_t launch_chunked_t(const ChunkArgs &a, hipStream_t st, bool onep
     dim3 g2((unsigned)(8 * a.per_xcd * a.nchunk));      // XCD-aware 1-D block map (hbv_chunked.h::chunk_block)
     if constexpr (MODEL == MODEL_HBV10 && DYN == 0) {
         if (onepass) {   // static parameters only: the trajectory is read once (hbv_chunked.h, k_bwd_chunk_onepass)
+            constexpr int NP = ChunkNP<MODEL, BETAET>::value;
             g_chunk_form = 1;
-            hipLaunchKernelGGL((k_bwd_chunk_onepass<BETAET, GFULL>), g2, dim3(64), 0, st, a);
-            hipLaunchKernelGGL(k_bwd_chunk_scan, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, a);
+            ChunkArgs o = a;            // a workgroup per group of o.group chunks, composed into one map on chip
+            o.group = onepass_group();
+            g_onepass_group = o.group;
+            const int ngrp = (a.nchunk + o.group - 1) / o.group;
+            hipLaunchKernelGGL((k_bwd_chunk_onepass<BETAET, GFULL>), dim3((unsigned)(8 * a.per_xcd * ngrp)),
+                               dim3(64 * o.group), o.group > 1 ? onepass_slot_bytes(NP) : 0, st, o);
+            ChunkArgs s = a;            // scan and fold walk the groups' maps and boundary adjoints
+            s.nchunk = ngrp;
+            hipLaunchKernelGGL(k_bwd_chunk_scan, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, s);
             store_gate(&a.io, st);
-            const int ngroup = (a.nchunk + ONEPASS_GROUP - 1) / ONEPASS_GROUP;
-            hipLaunchKernelGGL((k_bwd_chunk_fold<ChunkNP<MODEL, BETAET>::value>),
-                               dim3((unsigned)((N + 255) / 256), (unsigned)ngroup), dim3(256), 0, st, a);
-            ChunkArgs r = a;            // the group partials, in the maps' rows (hbv_chunked.h, B4 of the one-pass form)
+            const int ngroup = (ngrp + ONEPASS_FOLD_GROUP - 1) / ONEPASS_FOLD_GROUP;
+            hipLaunchKernelGGL((k_bwd_chunk_fold<NP>), dim3((unsigned)((N + 255) / 256), (unsigned)ngroup), dim3(256), 0,
+                               st, s);
+            ChunkArgs r = a;            // the fold's partials, in the maps' rows (hbv_chunked.h, B4 of the one-pass form)
             r.gpart = a.phi;
             r.nchunk = ngroup;
             hipLaunchKernelGGL(k_bwd_chunk_reduce, dim3((unsigned)((N + 255) / 256), d.n_param), dim3(256), 0, st,
@@ -163,6 +181,7 @@ static hipError_t launch_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, hipS
     a.C = chunk_days();
     a.nchunk = (d->T + a.C - 1) / a.C;
     a.per_xcd = chunk_per_xcd(d->B, a.lgMp);
+    a.group = 1;
     const int64_t N = (int64_t)d->B * d->M;
     a.phi = (float *)io->workspace;
     a.abnd = a.phi + (int64_t)a.nchunk * 30 * N;

@@ -211,6 +211,7 @@ extern "C" int hbvx_adj_backward(const hbvx_desc *d, const hbvx_bwd_io *io, void
         ca.gpart = ca.abnd + (int64_t)ca.nchunk * 5 * N;
         hipStream_t st = (hipStream_t)stream;
         ca.per_xcd = chunk_per_xcd(d->B, ca.lgMp);
+        ca.group = 1;
         dim3 g2((unsigned)(8 * ca.per_xcd * ca.nchunk));      // XCD-aware 1-D block map (hbv_chunked.h::chunk_block)
         // at most ADJ_FEW dynamic parameters: the slot-list instances (hbv_adj_kernels.h, "few" mode)
         AdjFew few{};
