@@ -1,13 +1,19 @@
-// hbv_adj_kernels.h -- implicit HBV ("HBV adjoint") forward / backward kernels.
-// One wave per workgroup, lane = (basin, member) as everywhere else; per day a modified Newton
-// solve in registers (hbv_adj_step.h).  First-cut launch geometry (round 1): correctness and
-// parity against the oracle; the wave-specialised tiling of hbv_tiled.h is the next step here.
+// hbv_adj_kernels.h -- the implicit scheme's own kernels ("HBV adjoint", hbv_adj.py; day math in hbv_adj_step.h), all
+// one wave per workgroup with the lane mapping of hbv_lane.h; launch_adj.hip launches them.
+//   k_adj_fwd / k_adj_bwd        the one-wave forward (a Newton solve per day, in registers) and serial adjoint: what
+//                                runs under HBVX_KERNEL=simple, the adjoint also whenever no workspace is given.  The
+//                                forward otherwise is the tiled stepper (hbv_tiled.h) or the staged pipeline (hbv_pipe.h).
+//   k_adj_tan_batch              forward-mode AD over several directions, at the solved states of the trajectory.
+//   k_adj_chunk_phi / _sweep     the time-parallel adjoint, B1 and B3 of hbv_chunked.h (whose scan and reduce kernels
+//                                are B2 and B4 here too).
+// BETAET: 13 parameters instead of 12.  FEW: the slot-list instances for at most ADJ_FEW dynamic parameters.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "../../include/hbvx.h"
 #include "hbv_adj_step.h"
+#include "hbv_lane.h"
 
 namespace hbvx {
 
@@ -22,36 +28,9 @@ struct AdjBwdArgs {
     int lgMp;
 };
 
-struct AdjLane {
-    int jm, b, j;
-    bool active, leader;
-    int64_t n;
-};
-
-__device__ __forceinline__ AdjLane adj_lane(const hbvx_desc &d, int lgMp, int bx = -1)
-{
-    AdjLane L;
-    const int lane = threadIdx.x & 63;
-    const int Mp = 1 << lgMp;
-    L.jm = lane & (Mp - 1);
-    int b = (bx < 0 ? (int)blockIdx.x : bx) * (64 >> lgMp) + (lane >> lgMp);
-    L.active = (b < d.B) && (L.jm < d.M);
-    L.leader = (b < d.B) && (L.jm == 0);
-    L.b = b < d.B ? b : d.B - 1;
-    L.j = L.jm < d.M ? L.jm : d.M - 1;
-    L.n = (int64_t)L.b * d.M + L.j;
-    return L;
-}
-
-__device__ __forceinline__ float adj_ens_sum(float v, int lgMp)
-{
-    for (int s = 0; s < lgMp; s++) v += __shfl_xor(v, 1 << s, 64);
-    return v;
-}
-
 // per-lane parameter fetch for day t: unit value u[i] and physical p[i]
 template <int NP>
-__device__ __forceinline__ void adj_params(const hbvx_desc &d, const AdjLane &L, int t, bool raw,
+__device__ __forceinline__ void adj_params(const hbvx_desc &d, const LaneId &L, int t, bool raw,
                                            const float *usta, const bool *use_dyn, float *u, float *p)
 {
 #pragma unroll
@@ -80,7 +59,7 @@ struct AdjFew {
     int nd, slot[ADJ_FEW];
 };
 template <int NP>
-__device__ __forceinline__ void adj_params_few(const hbvx_desc &d, const AdjLane &L, int t, bool raw, const AdjFew &F,
+__device__ __forceinline__ void adj_params_few(const hbvx_desc &d, const LaneId &L, int t, bool raw, const AdjFew &F,
                                                const float *psta, const bool *use_k, float *uk, float *p)
 {
 #pragma unroll
@@ -100,26 +79,65 @@ __device__ __forceinline__ void adj_params_few(const hbvx_desc &d, const AdjLane
         }
 }
 
+// The two pieces below are TEXT, not __device__ functions: pasted into a kernel they leave its instructions as they
+// were; as functions (with pointers or with array references) they changed the instructions of every kernel that
+// called them and brought scratch to four (profiles/r16_adj_family.md).  They use the kernel's own names: NP, d, L,
+// raw, and what each comment lists.
+//
+// ADJ_STATIC_ROW(FEW, F[, statement]) -- the static row of a lane, once per kernel: usta[i] is its unit value (FEW: its
+// PHYSICAL value, de-scaled here once); use_dyn says where the lane takes the day's row instead, per slot i or (FEW)
+// per entry k of the slot list F.  Drop is per lane: a dynamic parameter whose drop mask is set for this (basin,
+// member) stays at its static value (hbv_adj.py:182-189).  `statement` runs per slot i in the same loop: the adjoint
+// kernels clear their gradient sums there, and k_adj_bwd's instructions change with any other place for that.
+#define ADJ_STATIC_ROW(FEW_, F_, ...)                                                                                  \
+    _Pragma("unroll") for (int i = 0; i < NP; i++) {                                                                   \
+        const hbvx_param_src &s = d.p[i];                                                                              \
+        float v = s.sta[(int64_t)L.b * s.sta_b_stride + L.j];                                                          \
+        usta[i] = raw ? sigmoid_(v) : v;                                                                               \
+        if (FEW_) usta[i] = descale_(usta[i], s.lo, s.hi);                                                             \
+        else use_dyn[i] = s.dyn && !(s.drop && s.drop[L.n]);                                                           \
+        __VA_ARGS__;                                                                                                   \
+    }                                                                                                                  \
+    if (FEW_) {                                                                                                        \
+        _Pragma("unroll") for (int k = 0; k < ADJ_FEW; k++) {                                                          \
+            use_dyn[k] = false;                                                                                        \
+            if (k < (F_).nd) {                                                                                         \
+                const hbvx_param_src &s = d.p[(F_).slot[k]];                                                           \
+                use_dyn[k] = !(s.drop && s.drop[L.n]);                                                                 \
+            }                                                                                                          \
+        }                                                                                                              \
+    }
+// ADJ_GRAD_DAY() -- day t's parameter gradients gp (physical space) of the generic fetch, with io, u, use_dyn, gsta:
+// to unit space; a dynamic parameter's goes to its day's row (zero where the lane dropped the row: that share belongs
+// to the static row), everything else is summed in gsta.
+#define ADJ_GRAD_DAY()                                                                                                 \
+    _Pragma("unroll") for (int i = 0; i < NP; i++) {                                                                   \
+        const float gu = gp[i] * (d.p[i].hi - d.p[i].lo);                                                              \
+        if (d.p[i].dyn) {                                                                                              \
+            const float gr = raw ? gu * (u[i] * (1.0f - u[i])) : gu;                                                   \
+            if (io.g[i].dyn && L.active)                                                                               \
+                io.g[i].dyn[(int64_t)t * io.g[i].dyn_t_stride + (int64_t)L.b * io.g[i].dyn_b_stride + L.j] =           \
+                    use_dyn[i] ? gr : 0.0f;                                                                            \
+            gsta[i] += use_dyn[i] ? 0.0f : gu;                                                                         \
+        } else {                                                                                                       \
+            gsta[i] += gu;                                                                                             \
+        }                                                                                                              \
+    }
+
 template <bool BETAET>
 __global__ void __launch_bounds__(64) k_adj_fwd(const AdjFwdArgs A)
 {
     constexpr int NP = BETAET ? 13 : 12;
     const hbvx_desc &d = A.d;
     const hbvx_fwd_out &o = A.o;
-    const AdjLane L = adj_lane(d, A.lgMp);
+    const LaneId L = lane_id(d, A.lgMp);
     const int T = d.T;
     const int64_t N = (int64_t)d.B * d.M;
     const bool raw = d.raw_sigmoid != 0;
     const float invM = 1.0f / (float)d.M;
     float usta[NP];
     bool use_dyn[NP];
-#pragma unroll
-    for (int i = 0; i < NP; i++) {
-        const hbvx_param_src &s = d.p[i];
-        float v = s.sta[(int64_t)L.b * s.sta_b_stride + L.j];
-        usta[i] = raw ? sigmoid_(v) : v;
-        use_dyn[i] = s.dyn && !(s.drop && s.drop[L.n]); // per-lane drop (hbv_adj.py:182-189)
-    }
+    ADJ_STATIC_ROW(false, AdjFew{});
     float x[5];
 #pragma unroll
     for (int k = 0; k < 5; k++) x[k] = d.state_in ? d.state_in[k * N + L.n] : 0.0f; // :254
@@ -145,7 +163,7 @@ __global__ void __launch_bounds__(64) k_adj_fwd(const AdjFwdArgs A)
             const float q0 = p[P_K0] * fmaxf(SUZ - p[P_UZL], 0.0f);
             const float q1 = p[P_K1] * SUZ, q2 = p[P_K2] * SLZ;
             float Q = (q0 + q1) + q2;
-            Q = adj_ens_sum(L.active ? Q : 0.0f, A.lgMp) * invM;
+            Q = ens_sum(L.active ? Q : 0.0f, A.lgMp) * invM;
             if (L.leader) o.flux[(int64_t)t * d.B + L.b] = Q;
         }
     }
@@ -164,21 +182,14 @@ __global__ void __launch_bounds__(64) k_adj_bwd(const AdjBwdArgs A)
     constexpr int NP = BETAET ? 13 : 12;
     const hbvx_desc &d = A.d;
     const hbvx_bwd_io &io = A.io;
-    const AdjLane L = adj_lane(d, A.lgMp);
+    const LaneId L = lane_id(d, A.lgMp);
     const int T = d.T;
     const int64_t N = (int64_t)d.B * d.M;
     const bool raw = d.raw_sigmoid != 0;
     const float invM = 1.0f / (float)d.M;
     float usta[NP], gsta[NP];
     bool use_dyn[NP];
-#pragma unroll
-    for (int i = 0; i < NP; i++) {
-        const hbvx_param_src &s = d.p[i];
-        float v = s.sta[(int64_t)L.b * s.sta_b_stride + L.j];
-        usta[i] = raw ? sigmoid_(v) : v;
-        use_dyn[i] = s.dyn && !(s.drop && s.drop[L.n]);
-        gsta[i] = 0.0f;
-    }
+    ADJ_STATIC_ROW(false, AdjFew{}, gsta[i] = 0.0f);
     const float *xb = d.x + (int64_t)L.b * d.x_b_stride;
     float a[5];
 #pragma unroll
@@ -198,19 +209,7 @@ __global__ void __launch_bounds__(64) k_adj_bwd(const AdjBwdArgs A)
 #pragma unroll
         for (int i = 0; i < NPARAM_MAX; i++) gp[i] = 0.0f;
         adj_backstep<BETAET>(s, p, x, 1.0f, gQ, a, gp);
-#pragma unroll
-        for (int i = 0; i < NP; i++) {
-            const float gu = gp[i] * (d.p[i].hi - d.p[i].lo);
-            if (d.p[i].dyn) {
-                const float gr = raw ? gu * (u[i] * (1.0f - u[i])) : gu;
-                if (io.g[i].dyn && L.active)
-                    io.g[i].dyn[(int64_t)t * io.g[i].dyn_t_stride + (int64_t)L.b * io.g[i].dyn_b_stride + L.j] =
-                        use_dyn[i] ? gr : 0.0f;
-                gsta[i] += use_dyn[i] ? 0.0f : gu;
-            } else {
-                gsta[i] += gu;
-            }
-        }
+        ADJ_GRAD_DAY();
     }
     if (L.active) {
 #pragma unroll
@@ -261,7 +260,7 @@ struct AdjTanArgs {
 struct AdjTanRaw {
     float f[3], x[5];
 };
-__device__ __forceinline__ void adj_tan_issue(const hbvx_desc &d, const float *traj, const AdjLane &L, int t, int64_t N,
+__device__ __forceinline__ void adj_tan_issue(const hbvx_desc &d, const float *traj, const LaneId &L, int t, int64_t N,
                                               AdjTanRaw &R)
 {
     const float *xr = d.x + (int64_t)t * d.x_t_stride + (int64_t)L.b * d.x_b_stride;
@@ -284,7 +283,7 @@ k_adj_tan_batch(const AdjTanArgs A, const AdjFew F)
     constexpr int G = ADJ_TAN_G;
     const hbvx_desc &d = A.d;
     const hbvx_tan_batch &tb = A.tb;
-    const AdjLane L = adj_lane(d, A.lgMp);
+    const LaneId L = lane_id(d, A.lgMp);
     const int T = d.T;
     const int64_t N = (int64_t)d.B * d.M;
     const bool raw = d.raw_sigmoid != 0;
@@ -380,7 +379,7 @@ k_adj_tan_batch(const AdjTanArgs A, const AdjFew F)
             c.apply(s, p, xd[g], pd, cd, xd[g], Qd);
             if (tb.flux_mask) {
                 // as k_adj_fwd: member reduction by butterfly, then 1/M
-                Qd = adj_ens_sum(L.active ? Qd : 0.0f, A.lgMp) * invM;
+                Qd = ens_sum(L.active ? Qd : 0.0f, A.lgMp) * invM;
                 if (L.leader) tb.tan_flux[(dir * T + t) * d.B + L.b] = Qd;
             }
         }
@@ -410,16 +409,13 @@ struct ChunkArgs; // hbv_chunked.h
 // What a day of the time-parallel kernels reads, loaded ONE DAY AHEAD of its use (the adjoint runs t1-1 .. t0): the
 // kernels are a wave per (64 lanes, chunk) walking 64 days, and with the loads at the top of the day that consumes
 // them every day paid a full HBM round trip; the dynamic-parameter rows (any subset) stay in the day itself.
-struct AdjRaw {
-    float f[3], x[5], gQ, g4;   // gQ + g4 (the routing adjoint's share) is formed where it is used: adj_gq
+struct AdjRaw : AdjTanRaw {
+    float gQ, g4;           // gQ + g4 (the routing adjoint's share) is formed where it is used: adj_gq
 };
-__device__ __forceinline__ void adj_issue(const hbvx_desc &d, const hbvx_bwd_io &io, const AdjLane &L, int t, int64_t N,
+__device__ __forceinline__ void adj_issue(const hbvx_desc &d, const hbvx_bwd_io &io, const LaneId &L, int t, int64_t N,
                                           AdjRaw &R)
 {
-    const float *xr = d.x + (int64_t)t * d.x_t_stride + (int64_t)L.b * d.x_b_stride;
-    R.f[0] = xr[d.ch_prcp]; R.f[1] = xr[d.ch_tmean]; R.f[2] = xr[d.ch_pet];
-#pragma unroll
-    for (int k = 0; k < 5; k++) R.x[k] = io.traj[((int64_t)k * (d.T + 1) + (t + 1)) * N + L.n];
+    adj_tan_issue(d, io.traj, L, t, N, R);      // the forcings and the state, as the tangent kernel reads them
     const int64_t gi = (int64_t)t * d.B + L.b;
     // loads only: an add here makes the compiler wait for all of the day's loads where they were just issued
     // (hbv_chunked.h::chunk_issue, profiles/r04_ab_chunk_prefetch.txt)
@@ -438,7 +434,7 @@ __global__ void __launch_bounds__(64) k_adj_chunk_phi(const hbvx_desc d, const h
     constexpr int NP = BETAET ? 13 : 12;
     ChunkBlock blk;                          // XCD-aware block map (hbv_chunked.h)
     if (!chunk_block(d, lgMp, per_xcd, blk)) return;
-    const AdjLane L = adj_lane(d, lgMp, blk.bx);
+    const LaneId L = lane_id(d, lgMp, blk.bx);
     const int chunk = blk.chunk;
     const int T = d.T, t0 = chunk * C, t1 = min(T, t0 + C);
     const int64_t N = (int64_t)d.B * d.M;
@@ -446,24 +442,7 @@ __global__ void __launch_bounds__(64) k_adj_chunk_phi(const hbvx_desc d, const h
     const float invM = 1.0f / (float)d.M;
     float usta[NP];                 // FEW: the static PHYSICAL values
     bool use_dyn[FEW ? ADJ_FEW : NP];
-#pragma unroll
-    for (int i = 0; i < NP; i++) {
-        const hbvx_param_src &s = d.p[i];
-        float v = s.sta[(int64_t)L.b * s.sta_b_stride + L.j];
-        usta[i] = raw ? sigmoid_(v) : v;
-        if (FEW) usta[i] = descale_(usta[i], s.lo, s.hi);
-        else use_dyn[i] = s.dyn && !(s.drop && s.drop[L.n]);
-    }
-    if (FEW) {
-#pragma unroll
-        for (int k = 0; k < ADJ_FEW; k++) {
-            use_dyn[k] = false;
-            if (k < F.nd) {
-                const hbvx_param_src &s = d.p[F.slot[k]];
-                use_dyn[k] = !(s.drop && s.drop[L.n]);
-            }
-        }
-    }
+    ADJ_STATIC_ROW(FEW, F);
     float Phi[5][5], phi[5];
 #pragma unroll
     for (int k = 0; k < 5; k++) {
@@ -516,7 +495,7 @@ __global__ void __launch_bounds__(64) k_adj_chunk_sweep(const hbvx_desc d, const
     constexpr int NP = BETAET ? 13 : 12;
     ChunkBlock blk;
     if (!chunk_block(d, lgMp, per_xcd, blk)) return;
-    const AdjLane L = adj_lane(d, lgMp, blk.bx);
+    const LaneId L = lane_id(d, lgMp, blk.bx);
     const int chunk = blk.chunk;
     const int T = d.T, t0 = chunk * C, t1 = min(T, t0 + C);
     const int64_t N = (int64_t)d.B * d.M;
@@ -525,25 +504,7 @@ __global__ void __launch_bounds__(64) k_adj_chunk_sweep(const hbvx_desc d, const
     float usta[NP], gsta[NP];       // FEW: usta holds the static PHYSICAL values
     bool use_dyn[FEW ? ADJ_FEW : NP];
     float gused[ADJ_FEW] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int i = 0; i < NP; i++) {
-        const hbvx_param_src &s = d.p[i];
-        float v = s.sta[(int64_t)L.b * s.sta_b_stride + L.j];
-        usta[i] = raw ? sigmoid_(v) : v;
-        if (FEW) usta[i] = descale_(usta[i], s.lo, s.hi);
-        else use_dyn[i] = s.dyn && !(s.drop && s.drop[L.n]);
-        gsta[i] = 0.0f;
-    }
-    if (FEW) {
-#pragma unroll
-        for (int k = 0; k < ADJ_FEW; k++) {
-            use_dyn[k] = false;
-            if (k < F.nd) {
-                const hbvx_param_src &s = d.p[F.slot[k]];
-                use_dyn[k] = !(s.drop && s.drop[L.n]);
-            }
-        }
-    }
+    ADJ_STATIC_ROW(FEW, F, gsta[i] = 0.0f);
     float a[5];
 #pragma unroll
     for (int k = 0; k < 5; k++) a[k] = abnd[((int64_t)chunk * 5 + k) * N + L.n];
@@ -580,19 +541,7 @@ __global__ void __launch_bounds__(64) k_adj_chunk_sweep(const hbvx_desc d, const
                 }
             continue;
         }
-#pragma unroll
-        for (int i = 0; i < NP; i++) {
-            const float gu = gp[i] * (d.p[i].hi - d.p[i].lo);
-            if (d.p[i].dyn) {
-                const float gr = raw ? gu * (u[i] * (1.0f - u[i])) : gu;
-                if (io.g[i].dyn && L.active)
-                    io.g[i].dyn[(int64_t)t * io.g[i].dyn_t_stride + (int64_t)L.b * io.g[i].dyn_b_stride + L.j] =
-                        use_dyn[i] ? gr : 0.0f;
-                gsta[i] += use_dyn[i] ? 0.0f : gu;
-            } else {
-                gsta[i] += gu;
-            }
-        }
+        ADJ_GRAD_DAY();
     }
     if (FEW) {
         // the same daily terms were added to gsta and gused in the same order: exact cancellation
@@ -607,3 +556,6 @@ __global__ void __launch_bounds__(64) k_adj_chunk_sweep(const hbvx_desc d, const
 }
 
 } // namespace hbvx
+
+#undef ADJ_STATIC_ROW
+#undef ADJ_GRAD_DAY

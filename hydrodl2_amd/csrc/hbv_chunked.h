@@ -33,6 +33,7 @@
 
 #include "../../include/hbvx.h"
 #include "hbv_step.h"
+#include "hbv_lane.h"
 #include "hbv_onepass_compose.h"
 
 namespace hbvx {
@@ -110,27 +111,6 @@ __device__ __forceinline__ float slot_get(const float *p, int slot)
     return v;
 }
 
-struct ChunkLane {
-    int jm, b, j;
-    bool active, leader;
-    int64_t n;
-};
-
-__device__ __forceinline__ ChunkLane chunk_lane(const hbvx_desc &d, int lgMp, int bx)
-{
-    ChunkLane L;
-    const int lane = threadIdx.x & 63;
-    const int Mp = 1 << lgMp;
-    L.jm = lane & (Mp - 1);
-    int b = bx * (64 >> lgMp) + (lane >> lgMp);
-    L.active = (b < d.B) && (L.jm < d.M);
-    L.leader = (b < d.B) && (L.jm == 0);
-    L.b = b < d.B ? b : d.B - 1;
-    L.j = L.jm < d.M ? L.jm : d.M - 1;
-    L.n = (int64_t)L.b * d.M + L.j;
-    return L;
-}
-
 template <int MODEL, bool BETAET>
 struct ChunkNP {
     static constexpr int value = MODEL == MODEL_HBV10 ? (BETAET ? 13 : 12)
@@ -168,7 +148,7 @@ struct ChunkDay {
 // parameter the kernels needed 14 x 6 scalar registers for addressing alone: 56 lane-spill reads, 70 scalar
 // multiplications and their hazard no-ops per day in config 3's sweep, a third of its instruction stream.)
 template <int NP>
-__device__ __forceinline__ void chunk_dma_dyn(const hbvx_desc &d, const ChunkLane &L, int t, float *lds)
+__device__ __forceinline__ void chunk_dma_dyn(const hbvx_desc &d, const LaneId &L, int t, float *lds)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     const hbvx_param_src &ps = d.p[0];
@@ -194,7 +174,7 @@ __device__ __forceinline__ void chunk_pull_dyn(ChunkRaw<NP> &R, const float *lds
 // generic mode (DYN == 2) tests the pointer at run time, the "all" mode never has them.
 template <int NP, int DYN, bool GFULL, bool LDSDV = false, bool MU = false>
 __device__ __forceinline__ void chunk_issue(const hbvx_desc &d, const hbvx_bwd_io &io,
-                                            const ChunkLane &L, int t, int nf, ChunkRaw<NP> &R,
+                                            const LaneId &L, int t, int nf, ChunkRaw<NP> &R,
                                             int nd, const int *dslot)
 {
     const int T = d.T;
@@ -320,7 +300,7 @@ __device__ __forceinline__ void chunk_finish(const hbvx_desc &d, const ChunkRaw<
 }
 
 template <int NP, int DYN>
-__device__ __forceinline__ void chunk_static(const hbvx_desc &d, const ChunkLane &L, bool raw,
+__device__ __forceinline__ void chunk_static(const hbvx_desc &d, const LaneId &L, bool raw,
                                              float *usta, float *psta, bool *use_dyn, int nd,
                                              const int *dslot)
 {
@@ -372,7 +352,7 @@ __global__ void __launch_bounds__(64) k_bwd_chunk_phi(const ChunkArgs A)
     const hbvx_bwd_io &io = A.io;
     ChunkBlock blk;
     if (!chunk_block(d, A.lgMp, A.per_xcd, blk)) return;
-    const ChunkLane L = chunk_lane(d, A.lgMp, blk.bx);
+    const LaneId L = lane_id(d, A.lgMp, blk.bx);
     const int chunk = blk.chunk;
     const int t0 = chunk * A.C, t1 = min(d.T, t0 + A.C);
     const int64_t N = (int64_t)d.B * d.M;
@@ -533,7 +513,7 @@ k_bwd_chunk_onepass(const ChunkArgs A)
     const hbvx_bwd_io &io = A.io;
     ChunkBlock blk;
     if (!chunk_block(d, A.lgMp, A.per_xcd, blk)) return;
-    const ChunkLane L = chunk_lane(d, A.lgMp, blk.bx);
+    const LaneId L = lane_id(d, A.lgMp, blk.bx);
     const int grp = blk.chunk;                                              // the block map deals groups
     const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);    // wave of the workgroup
     const int nw = min(min(A.group, ONEPASS_GMAX), A.nchunk - grp * A.group);   // waves of this group with a chunk
@@ -668,12 +648,6 @@ __global__ void __launch_bounds__(64) k_bwd_chunk_scan(const ChunkArgs A)
 #endif
 
 // ---- B3 -------------------------------------------------------------------------------------
-__device__ __forceinline__ float chunk_ens_sum(float v, int lgMp)
-{
-    for (int s = 0; s < lgMp; s++) v += __shfl_xor(v, 1 << s, 64);
-    return v;
-}
-
 // ROWST (DYN == 3 only): the NP gradients of a lane-day are transposed through LDS and leave as whole
 // rows -- a wave's (64/Mp) basins x NP x M floats are contiguous in the [T,B,ny] gradient tensor, so
 // 8-byte stores of 512 contiguous bytes per instruction replace NP four-byte stores that each touch
@@ -690,7 +664,7 @@ __global__ void __launch_bounds__(64) k_bwd_chunk_sweep(const ChunkArgs A)
     const hbvx_bwd_io &io = A.io;
     ChunkBlock blk;
     if (!chunk_block(d, A.lgMp, A.per_xcd, blk)) return;
-    const ChunkLane L = chunk_lane(d, A.lgMp, blk.bx);
+    const LaneId L = lane_id(d, A.lgMp, blk.bx);
     const int chunk = blk.chunk;
     const int t0 = chunk * A.C, t1 = min(d.T, t0 + A.C);
     const int64_t N = (int64_t)d.B * d.M;
@@ -794,8 +768,8 @@ __global__ void __launch_bounds__(64) k_bwd_chunk_sweep(const ChunkArgs A)
         }
         if (io.grad_x) {
             const float act = L.active ? 1.0f : 0.0f;
-            const float g0 = chunk_ens_sum(gx[0] * act, A.lgMp), g1 = chunk_ens_sum(gx[1] * act, A.lgMp),
-                        g2 = chunk_ens_sum(gx[2] * act, A.lgMp);
+            const float g0 = ens_sum(gx[0] * act, A.lgMp), g1 = ens_sum(gx[1] * act, A.lgMp),
+                        g2 = ens_sum(gx[2] * act, A.lgMp);
             if (L.leader) {
                 float *gr = io.grad_x + (int64_t)t * d.x_t_stride + (int64_t)L.b * d.x_b_stride;
                 gr[d.ch_prcp] = g0; gr[d.ch_tmean] = g1; gr[d.ch_pet] = g2;

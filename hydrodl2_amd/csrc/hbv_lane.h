@@ -1,6 +1,8 @@
-// hbv_lane.h -- the lane mapping of the one-wave recurrence kernels (k_fwd and k_bwd in hbvx.hip, k_tan in
-// hbv_tan.h): one wavefront lane per (basin, ensemble member), a basin's Mp members in adjacent lanes, so that the
-// ensemble mean is a butterfly over lanes.  (The tiled families have their own NParamT / LaneT in hbv_tiled.h.)
+// hbv_lane.h -- the lane mapping of every one-wave-per-64-lanes kernel: the recurrence kernels (k_fwd and k_bwd in
+// hbvx.hip, k_tan in hbv_tan.h), the implicit scheme (hbv_adj_kernels.h) and the time-parallel adjoint
+// (hbv_chunked.h), whose block index comes from its XCD-aware block map.  One wavefront lane per (basin, ensemble
+// member), a basin's Mp members in adjacent lanes, so that the ensemble mean is a butterfly over lanes.  (The tiled
+// families have their own NParamT / LaneT in hbv_tiled.h.)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -23,13 +25,14 @@ struct LaneId {
     int64_t n;      // b*M + j
 };
 
-__device__ __forceinline__ LaneId lane_id(const hbvx_desc &d, int lgMp)
+// bx: the index of the wave's group of 64 >> lgMp basins
+__device__ __forceinline__ LaneId lane_id(const hbvx_desc &d, int lgMp, int bx)
 {
     LaneId L;
     const int lane = threadIdx.x & 63;
     const int Mp = 1 << lgMp;
     L.jm = lane & (Mp - 1);
-    int b = blockIdx.x * (64 >> lgMp) + (lane >> lgMp);
+    int b = bx * (64 >> lgMp) + (lane >> lgMp);
     L.active = (b < d.B) && (L.jm < d.M);
     L.leader = (b < d.B) && (L.jm == 0);
     L.b = b < d.B ? b : d.B - 1;
@@ -37,6 +40,7 @@ __device__ __forceinline__ LaneId lane_id(const hbvx_desc &d, int lgMp)
     L.n = (int64_t)L.b * d.M + L.j;
     return L;
 }
+__device__ __forceinline__ LaneId lane_id(const hbvx_desc &d, int lgMp) { return lane_id(d, lgMp, blockIdx.x); }
 
 // sum over the Mp lanes of one basin (xor butterfly; every lane gets the sum)
 __device__ __forceinline__ float ens_sum(float v, int lgMp)

@@ -3,8 +3,8 @@
 // The library is built from several .hip files compiled in parallel (one per kernel family:
 // pipelined / streaming / tiled / time-parallel / implicit / tangent recurrence / LSTM) so that touching
 // one family rebuilds one file.  The C ABI (include/hbvx.h) lives in hbvx.hip, apart from the entry points
-// that are a family's own (launch_tan.hip); its dispatchers call the family launchers declared here.  A launcher returns true when its family took the call and has
-// then set *rc to the ABI return code.
+// that are a family's own (launch_tan.hip, launch_adj.hip); its dispatchers call the family launchers declared here.
+// A launcher returns true when its family took the call and has then set *rc to the ABI return code.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -57,6 +57,36 @@ auto with_model(const hbvx_desc *d, F &&f)
     }
 }
 
+// The template instance of the implicit scheme (HBVADJ): f(BETAET, FEW) as std::bool_constant.  BETAET as for HBV 1.0;
+// few: the slot-list ("few") instance of the kernels that have one (hbv_adj_kernels.h) -- the others ignore it.
+template <typename F>
+auto with_adj(const hbvx_desc *d, bool few, F &&f)
+{
+    if (d->n_param == 13) return few ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+    return few ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
+
+// What every tangent entry point checks of the parameter tangents (launch_tan.hip, launch_adj.hip)
+inline int check_tan_params(const hbvx_desc *d, const hbvx_param_tan *p)
+{
+    for (int i = d->n_param; i < HBVX_MAX_PARAM; i++)
+        if (p[i].dyn || p[i].sta) return fail(HBVX_E_SHAPE, "tangent for a parameter slot the model lacks");
+    for (int i = 0; i < d->n_param; i++)
+        if (p[i].dyn && !d->p[i].dyn) return fail(HBVX_E_SHAPE, "dynamic tangent for a static parameter");
+    return HBVX_OK;
+}
+// a stride of 0 is a zero tangent, like a NULL pointer (include/hbvx.h): applied to the kernel's copy of the batch
+inline void zero_stride_tangents(hbvx_tan_batch &tb, int n_param)
+{
+    if (!tb.x_d_stride) tb.x = nullptr;
+    if (!tb.mu_d_stride) tb.muwts = nullptr;
+    if (!tb.state_d_stride) tb.state_in = nullptr;
+    for (int i = 0; i < n_param; i++) {
+        if (!tb.dyn_d_stride[i]) tb.p[i].dyn = nullptr;
+        if (!tb.sta_d_stride[i]) tb.p[i].sta = nullptr;
+    }
+}
+
 // launch_pipe.hip
 bool try_fwd_pipe(const hbvx_desc *d, const hbvx_fwd_out *out, void *stream, int *rc);
 // launch_stream.hip
@@ -86,7 +116,7 @@ bool try_bwd_stream(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int
 // wanted: hbvx_ckpt_workspace_bytes returns 0), and the launch
 bool stream_ckpt_applicable(const hbvx_desc *d, int K);
 bool try_bwd_stream_ckpt(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc);
-// launch_tiled.hip
+// launch_tiled.hip (try_fwd_tiled also takes the implicit model, for launch_adj.hip)
 bool try_fwd_tiled(const hbvx_desc *d, const hbvx_fwd_out *out, void *stream, int *rc);
 bool try_bwd_tiled(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc);
 // launch_chunked.hip

@@ -18,15 +18,6 @@ static int check_tan_model(const hbvx_desc *d, const char *unsupported)
     return HBVX_OK;
 }
 
-static int check_tan_params(const hbvx_desc *d, const hbvx_param_tan *p)
-{
-    for (int i = d->n_param; i < HBVX_MAX_PARAM; i++)
-        if (p[i].dyn || p[i].sta) return fail(HBVX_E_SHAPE, "tangent for a parameter slot the model lacks");
-    for (int i = 0; i < d->n_param; i++)
-        if (p[i].dyn && !d->p[i].dyn) return fail(HBVX_E_SHAPE, "dynamic tangent for a static parameter");
-    return HBVX_OK;
-}
-
 // k_tan<model, BETAET, Args> of the descriptor's model, one wave per workgroup.  The entry points have refused the
 // models they do not serve; the hourly model has no one-direction instance.
 template <typename Args>
@@ -83,14 +74,7 @@ static int prep_tan_batch(const hbvx_desc *d, const hbvx_tan_batch *tb, int want
     a.d = *d;
     a.tb = *tb;
     a.lgMp = lg_members(d->M);
-    // a stride of 0 is a zero tangent, like a NULL pointer (include/hbvx.h)
-    if (!a.tb.x_d_stride) a.tb.x = nullptr;
-    if (!a.tb.mu_d_stride) a.tb.muwts = nullptr;
-    if (!a.tb.state_d_stride) a.tb.state_in = nullptr;
-    for (int i = 0; i < d->n_param; i++) {
-        if (!a.tb.dyn_d_stride[i]) a.tb.p[i].dyn = nullptr;
-        if (!a.tb.sta_d_stride[i]) a.tb.p[i].sta = nullptr;
-    }
+    zero_stride_tangents(a.tb, d->n_param);
     return HBVX_OK;
 }
 

@@ -75,6 +75,9 @@ CASES = [
     dict(T=44, B=4, M=8, seed=85,
          cfg=dict(nmul=8, dy_drop=0.3,
                   dynamic_params={"HbvAdj": ["parBETA", "parK1", "parLP", "parTT", "parBETAET"]})),
+    # four dynamic parameters with drops and no parBETAET: 12 parameters above ADJ_FEW, the <false, false> instances
+    dict(T=45, B=4, M=8, seed=86,
+         cfg=dict(nmul=8, dy_drop=0.3, dynamic_params={"HbvAdj": ["parBETA", "parK1", "parLP", "parTT"]})),
 ]
 
 
@@ -232,10 +235,12 @@ def test_hip_time_parallel_adjoint_matches_oracle(case, hip_backend, monkeypatch
 
 
 @pytest.mark.gpu
-def test_hip_one_wave_kernels_still_match(hip_backend, monkeypatch):
-    """HBVX_KERNEL=simple: the first-cut one-wave forward (kept as a cross-check)."""
+@pytest.mark.parametrize("case", CASES[:2], ids=lambda c: f"M{c['M']}-T{c['T']}")
+def test_hip_one_wave_kernels_still_match(case, hip_backend, monkeypatch):
+    """HBVX_KERNEL=simple: the first-cut one-wave forward and adjoint (kept as a cross-check), with 12 and with 13
+    parameters."""
     monkeypatch.setenv("HBVX_KERNEL", "simple")
-    got, ggot, want, gwant, _ = _run_case("cuda:0", CASES[1], tight=True)
+    got, ggot, want, gwant, _ = _run_case("cuda:0", case, tight=True)
     _close("flow_sim", got, want, 2e-4, 2e-5)
     _close("grad", ggot, gwant, 2e-3, 2e-4)
 
