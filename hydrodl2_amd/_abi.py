@@ -117,6 +117,19 @@ class GramDesc(C.Structure):
                 ("series_stride", C.c_int64)]
 
 
+class PopSrc(C.Structure):
+    """hbvx_pop_src: where the candidates' static values of one parameter lie (include/hbvx.h)."""
+    _fields_ = [("sta", _fp), ("c_stride", C.c_int64), ("b_stride", C.c_int64)]
+
+
+class Pop(C.Structure):
+    """hbvx_pop: the candidates, the observations and the outputs of hbvx_population_cost (include/hbvx.h)."""
+    _fields_ = [("n_cand", C.c_int32), ("t_first", C.c_int32), ("p", PopSrc * MAX_PARAM),
+                ("route", C.POINTER(RouteDesc)), ("ra", _fp), ("rb", _fp),
+                ("r_c_stride", C.c_int64), ("r_b_stride", C.c_int64),
+                ("target", _fp), ("w", _fp), ("cost", _fp), ("sim", _fp)]
+
+
 class LstmDesc(C.Structure):
     """include/hbvx_lstm.h"""
     _fields_ = [("abi_version", C.c_int32), ("T", C.c_int32), ("B", C.c_int32), ("H", C.c_int32)]
@@ -139,7 +152,8 @@ OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forwa
                     "hbvx_bfi_tangent_batch", "hbvx_lstm_tangent_batch", "hbvx_lstm_tangent_batch_workspace_bytes",
                     "hbvx_hourly_tangent_batch", "hbvx_gage_route_tangent_batch",
                     "hbvx_gage_route_tangent_workspace_bytes", "hbvx_adj_tangent_batch", "hbvx_gram",
-                    "hbvx_gram_workspace_bytes", "hbvx_quadform", "hbvx_quadform_workspace_bytes"]
+                    "hbvx_gram_workspace_bytes", "hbvx_quadform", "hbvx_quadform_workspace_bytes",
+                    "hbvx_population_cost"]
 
 
 class HbvxError(RuntimeError):
@@ -290,6 +304,11 @@ class Library:
             d.hbvx_quadform_workspace_bytes.argtypes = [C.POINTER(GramDesc)]
         if not {"hbvx_gram", "hbvx_quadform"} <= set(self.missing) and d.hbvx_sizeof(9) != C.sizeof(GramDesc):
             raise HbvxError(f"{path}: layout mismatch for GramDesc: {d.hbvx_sizeof(9)} != {C.sizeof(GramDesc)}")
+        if "hbvx_population_cost" not in self.missing:
+            d.hbvx_population_cost.restype = C.c_int
+            d.hbvx_population_cost.argtypes = [C.POINTER(Desc), C.POINTER(Pop), C.c_void_p]
+            if d.hbvx_sizeof(10) != C.sizeof(Pop):
+                raise HbvxError(f"{path}: layout mismatch for Pop: {d.hbvx_sizeof(10)} != {C.sizeof(Pop)}")
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -472,6 +491,13 @@ class Library:
         self.require("hbvx_quadform")
         self._check(self.dll.hbvx_quadform(C.byref(g), s, m, q, ws, C.c_uint64(ws_bytes), C.c_void_p(stream)),
                     "hbvx_quadform")
+
+    def population_cost(self, desc, pop, stream: int):
+        """hbvx_population_cost; `desc` / `pop` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_population_cost")
+        self._check(self.dll.hbvx_population_cost(None if desc is None else C.byref(desc),
+                                                  None if pop is None else C.byref(pop), C.c_void_p(stream)),
+                    "hbvx_population_cost")
 
     def gage_route_tangent_workspace_bytes(self, r: GageDesc, n_dir: int) -> int:
         self.require("hbvx_gage_route_tangent_workspace_bytes")

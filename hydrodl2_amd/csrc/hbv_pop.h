@@ -1,0 +1,232 @@
+// hbv_pop.h -- population evaluation (hbvx_population_cost, include/hbvx.h): the weighted squared error of the routed
+// ensemble-mean streamflow of P candidate static-parameter sets per basin, one number per (candidate, basin), from one
+// launch that writes nothing else.
+//
+// What happens to a basin's ensemble mean after the day step -- the normalised gamma unit hydrograph, the 15-day
+// window, the causal convolution and the residual chain -- is hbvx_popk::Basin below and compiles for the host as
+// well (tests/hosttest/pop_host.cpp), so the CPU tier checks it without a GPU; the kernel maps lanes onto it.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define HBVX_POP_HD __host__ __device__ __forceinline__
+#else
+#define HBVX_POP_HD inline
+#endif
+
+namespace hbvx_popk {
+
+constexpr int UH = 15;      // HBVX_UH_MAXLEN
+
+// The normalised gamma unit hydrograph (uh_routing.py:5-22) of physical route_a = a, route_b = bb: taps 0..L-1 as
+// k_uh_gamma stores them and k_route_fwd loads them back, zero from L on.  A restatement of k_uh_gamma's lines
+// (hbvx.hip), operation for operation -- the sum runs over all 15 values, zeros included.  k_uh_gamma keeps its own
+// text: calling this from it changed that kernel's instruction schedule (tools/compare_code.py), and the forward's
+// kernels are pinned.  A change to either belongs in both.
+HBVX_POP_HD void gamma_taps(float a, float bb, int L, float (&w)[UH])
+{
+    float aa = fmaxf(a, 0.0f) + 0.1f;
+    float theta = fmaxf(bb, 0.0f) + 0.5f;
+    float denom = expf(lgammaf(aa)) * powf(theta, aa);
+    float sum = 0.0f;
+#pragma unroll
+    for (int k = 0; k < UH; k++) {
+        float t = (float)k + 0.5f;
+        float mid = powf(t, aa - 1.0f);
+        float right = expf(-t / theta);
+        w[k] = (k < L) ? 1.0f / denom * mid * right : 0.0f;
+        sum += w[k];
+    }
+#pragma unroll
+    for (int k = 0; k < UH; k++) w[k] = (k < L) ? w[k] / sum : 0.0f;
+}
+
+// One (candidate, basin).  push() takes the days in ascending order:
+//   routed:  win[0] = q;  y = chain over ascending k = 0..14:  acc += uh[k] * win[k]  from 0 (the product rounded, then
+//            the sum: k_route_fwd's line under -ffp-contract=off), zero history before the first day; else y = q;
+//   counted: r = y - target;  cost = fmaf(w * r, r, cost)  (w * r rounded once).  Without weights the caller passes
+//            w = 1, which gives fmaf(r, r, cost) bit for bit (1 * r is exact).
+// A day that is not counted moves the window and leaves the cost alone.
+struct Basin {
+    float uh[UH], win[UH];
+    float cost;
+    bool routed;
+
+    HBVX_POP_HD void start(bool with_routing)
+    {
+#pragma unroll
+        for (int k = 0; k < UH; k++) uh[k] = win[k] = 0.0f;
+        cost = 0.0f;
+        routed = with_routing;
+    }
+
+    HBVX_POP_HD float push(float q, float target, float w, bool counted)
+    {
+        float y = q;
+        if (routed) {
+            win[0] = q;
+            float acc = 0.0f;
+#pragma unroll
+            for (int k = 0; k < UH; k++) acc += uh[k] * win[k];
+#pragma unroll
+            for (int k = UH - 1; k > 0; k--) win[k] = win[k - 1];
+            y = acc;
+        }
+        if (counted) {
+            const float r = y - target;
+            cost = __builtin_fmaf(w * r, r, cost);
+        }
+        return y;
+    }
+};
+
+} // namespace hbvx_popk
+
+#if defined(__HIPCC__)
+
+#include "hbv_lane.h"
+
+namespace hbvx {
+
+struct PopArgs {
+    hbvx_desc d;
+    hbvx_pop pop;
+    hbvx_route_desc r;      // *pop.route (the pointer is the host's); read only with has_route
+    int has_route;
+    int lgMp;
+};
+
+// ---------------------------------------------------------------------------
+// k_pop<MODEL, BETAET>: k_fwd's day loop (the same Step::fwd instance, the same one-day-ahead register prefetch of the
+// forcings and the dynamic rows, the same ensemble sum and weights) with the lane mapping of k_tan's several-direction
+// form: one wave per workgroup, blockIdx.x the wave's group of basins, blockIdx.y the CANDIDATE, one lane per (basin,
+// member).  A candidate is a wave of its own that reads the forcings itself -- they come out of the L2 / Infinity
+// Cache after the first candidate's pass -- and nothing is shared between candidates inside the kernel: what many
+// candidates in one launch gain over a forward each is that their waves fill the SIMDs one forward leaves idle, and
+// that nothing but [P,B] costs is written.  The candidate index is uniform over the wave, so a candidate's base
+// address is scalar.  Several candidates per lane are not tried: k_tan measured that form and lost at every size
+// (hbv_tan.h), for a reason that holds here too (the loop is bound by instruction issue, registers cost resident waves).
+//
+// After ens_sum every lane of a basin holds the mean, so every lane carries the basin's window and cost chain (the
+// same values: no shuffle, no divergence) and the leader stores.  The bits of cost[c,b] and sim[c,:,b] depend on
+// candidate c's values alone: c enters addresses only.
+// ---------------------------------------------------------------------------
+template <int MODEL, bool BETAET>
+__global__ void __launch_bounds__(64) k_pop(const PopArgs A)
+{
+    constexpr int NP = NParam<MODEL, BETAET>::value;
+    const hbvx_desc &d = A.d;
+    const hbvx_pop &pp = A.pop;
+    const int lgMp = A.lgMp;
+    const LaneId L = lane_id(d, lgMp);
+    const int T = d.T;
+    const int t_first = pp.t_first;
+    const int64_t N = (int64_t)d.B * d.M;
+    const int64_t c = blockIdx.y;
+    const bool raw = d.raw_sigmoid != 0;
+    const float nz = d.nearzero;
+    const float ac = (MODEL == MODEL_HBV20) ? d.ac[L.b] : 0.0f;
+    const float elev = (MODEL == MODEL_HBV20) ? d.elev[L.b] : 0.0f;
+
+    float p[NPARAM_MAX];
+    const float *dynp[NP];
+    bool use_dyn[NP];
+    unsigned dmask = 0;
+#pragma unroll
+    for (int i = 0; i < NP; i++) {
+        const hbvx_param_src &s = d.p[i];
+        const hbvx_pop_src &cs = pp.p[i];
+        float v = cs.sta ? cs.sta[c * cs.c_stride + (int64_t)L.b * cs.b_stride + L.j]
+                         : s.sta[(int64_t)L.b * s.sta_b_stride + L.j];
+        v = raw ? sigmoid_(v) : v;
+        p[i] = descale_(v, s.lo, s.hi);
+        dynp[i] = s.dyn ? s.dyn + (int64_t)L.b * s.dyn_b_stride + L.j : s.sta;
+        use_dyn[i] = s.dyn && !(s.drop && s.drop[L.b]);
+        if (s.dyn) dmask |= 1u << i;
+    }
+#pragma unroll
+    for (int i = NP; i < NPARAM_MAX; i++) p[i] = 0.0f;
+
+    float st[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) st[k] = d.state_in ? d.state_in[k * N + L.n] : 0.001f;
+
+    hbvx_popk::Basin bs;
+    bs.start(A.has_route != 0);
+    if (A.has_route) {      // route_ab's lines (hbvx.hip) on the candidate's routing inputs
+        const hbvx_route_desc &r = A.r;
+        const float va = pp.ra ? pp.ra[c * pp.r_c_stride + (int64_t)L.b * pp.r_b_stride] : r.ra[(int64_t)L.b * r.r_stride];
+        const float vb = pp.rb ? pp.rb[c * pp.r_c_stride + (int64_t)L.b * pp.r_b_stride] : r.rb[(int64_t)L.b * r.r_stride];
+        const float ua = r.raw_sigmoid ? sigmoid_(va) : va;
+        const float ub = r.raw_sigmoid ? sigmoid_(vb) : vb;
+        hbvx_popk::gamma_taps(descale_(ua, r.a_lo, r.a_hi), descale_(ub, r.b_lo, r.b_hi), r.L, bs.uh);
+    }
+
+    const float *xb = d.x + (int64_t)L.b * d.x_b_stride;
+    const float *mu = d.muwts ? d.muwts + (int64_t)L.b * d.mu_b_stride + L.j : nullptr;
+    const float invM = 1.0f / (float)d.M;
+    const float act = L.active ? 1.0f : 0.0f;
+    const float *tg = pp.target + L.b;              // row t - t_first of [T - t_first, B]
+    const float *wt = pp.w ? pp.w + L.b : nullptr;
+    float *sim = pp.sim ? pp.sim + c * (int64_t)(T - t_first) * d.B + L.b : nullptr;
+
+    // one-step-ahead register prefetch of the per-step inputs (k_fwd's), the observation and its weight with them
+    float nxf[3], nxd[NP], nxo = 0.0f, nxw = 1.0f;
+    {
+        const float *xr = xb;
+        nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
+#pragma unroll
+        for (int i = 0; i < NP; i++) nxd[i] = ((dmask >> i) & 1) ? dynp[i][0] : 0.f;
+        if (t_first == 0) {
+            nxo = tg[0];
+            if (wt) nxw = wt[0];
+        }
+    }
+
+    for (int t = 0; t < T; t++) {
+        Step<MODEL, BETAET> s;
+        s.P = nxf[0]; s.Tf = nxf[1]; s.PET = nxf[2];
+        float cur[NP];
+#pragma unroll
+        for (int i = 0; i < NP; i++) cur[i] = nxd[i];
+        const float obs = nxo, wobs = nxw;
+        {
+            const int tn = t + 1 < T ? t + 1 : t;
+            const float *xr = xb + (int64_t)tn * d.x_t_stride;
+            nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
+#pragma unroll
+            for (int i = 0; i < NP; i++)
+                if ((dmask >> i) & 1) nxd[i] = dynp[i][(int64_t)tn * d.p[i].dyn_t_stride];
+            if (tn >= t_first) {
+                const int64_t row = (int64_t)(tn - t_first) * d.B;
+                nxo = tg[row];
+                if (wt) nxw = wt[row];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NP; i++)
+            if ((dmask >> i) & 1) {
+                float v = raw ? sigmoid_dyn_(cur[i]) : cur[i];
+                float pv = descale_(v, d.p[i].lo, d.p[i].hi);
+                if (use_dyn[i]) p[i] = pv;
+            }
+        s.SP = st[0]; s.MW = st[1]; s.SM = st[2]; s.SUZ = st[3]; s.SLZ = st[4];
+        s.template fwd<false, true>(p, nz, ac, elev, 0.f, 0.f);
+        st[0] = s.SP3; st[1] = s.MW3; st[2] = s.SM4; st[3] = s.SUZ4; st[4] = s.SLZ2;
+
+        // the ensemble mean of Q as k_fwd forms series HBVX_F_QSIM
+        const float wq = mu ? mu[(int64_t)t * d.mu_t_stride] : 1.0f;
+        float q = ens_sum((mu ? s.Q * wq : s.Q) * act, lgMp);
+        if (!mu) q = q * invM;
+        const bool counted = t >= t_first;
+        const float y = bs.push(q, obs, wobs, counted);
+        if (counted && sim && L.leader) sim[(int64_t)(t - t_first) * d.B] = y;
+    }
+    if (L.leader) pp.cost[c * d.B + L.b] = bs.cost;
+}
+
+} // namespace hbvx
+
+#endif // __HIPCC__

@@ -68,6 +68,7 @@ extern "C" uint64_t hbvx_sizeof(int which)
     case 7: return sizeof(hbvx_tan_io);
     case 8: return sizeof(hbvx_tan_batch);
     case 9: return sizeof(hbvx_gram_desc);
+    case 10: return sizeof(hbvx_pop);
     default: return 0;
     }
 }

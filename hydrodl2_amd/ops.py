@@ -1066,6 +1066,85 @@ def quadform(series: torch.Tensor, factor: torch.Tensor) -> torch.Tensor:
     return out
 
 
+POP_MAX_CAND = 65535       # candidates of one hbvx_population_cost launch (a grid dimension)
+
+
+def population_cost(rec: PathRecord, cand_sources: dict, route_cands, target: torch.Tensor, w: Optional[torch.Tensor],
+                    t_first: int = 0, want_sim: bool = False):
+    """The weighted squared error of the (routed) streamflow of P candidate static-parameter sets on one recorded call
+    of the path, through hbvx_population_cost (include/hbvx.h) on the current stream: (cost [P,B], sim [P,T_out,B] or
+    None), T_out = rec.cfg.T - t_first.
+
+    cand_sources  {parameter slot: (cands, column)}: candidate c's values of that slot for basin b are
+                  cands[c, b, column : column + M] of the compact float32 [P,B,C] tensor `cands`; slots not named keep
+                  the recorded call's static values.
+    route_cands   (a, b), each None or (cands, column): the candidates' routing inputs; None keeps the recorded one.
+                  Ignored when the recorded call does not route.
+    target, w     [T_out,B] float32; w may be None (ones).  The kernel multiplies what it is given: the caller masks.
+    More than POP_MAX_CAND candidates go in several launches; a candidate's bits do not depend on the split."""
+    lib = get_library()
+    lib.require("hbvx_population_cost")
+    cfg = rec.cfg
+    x, ptensors = rec.x, rec.ptensors
+    dev = x.device
+    T, B, M = cfg.T, cfg.B, cfg.M
+    T_out = T - t_first
+    if not 0 <= t_first < T:
+        raise ValueError(f"t_first must be in 0..{T - 1}, got {t_first}")
+    named = list(cand_sources.values()) + [s for s in (route_cands or ()) if s is not None]
+    if not named:
+        raise ValueError("population_cost needs at least one candidate column")
+    cands = named[0][0]
+    _check_tensor(lib, cands, "candidates")
+    if cands.dim() != 3 or int(cands.shape[1]) != B or not cands.is_contiguous() or cands.device != dev:
+        raise ValueError(f"candidates must be a contiguous [P,{B},C] tensor on {dev}, got {tuple(cands.shape)} on {cands.device}")
+    P, Cn = int(cands.shape[0]), int(cands.shape[2])
+    if P < 1:
+        raise ValueError("population_cost needs at least one candidate")
+    for t, col in named:
+        if t is not cands:
+            raise ValueError("all candidate columns must lie in one compact tensor")
+    for slot, (_, col) in cand_sources.items():
+        if not 0 <= col <= Cn - M:
+            raise ValueError(f"candidate column {col} of slot {slot} does not hold {M} members in {Cn} columns")
+    for s in (route_cands or ()):
+        if s is not None and not 0 <= s[1] < Cn:
+            raise ValueError(f"routing candidate column {s[1]} outside the {Cn} columns")
+    for name, t in (("target", target), ("w", w)):
+        if t is None:
+            continue
+        _check_tensor(lib, t, name)
+        if tuple(t.shape) != (T_out, B) or t.device != dev:
+            raise ValueError(f"{name} must be [{T_out},{B}] on {dev}, got {tuple(t.shape)} on {t.device}")
+    tc = target.contiguous()
+    wc = None if w is None else w.contiguous()
+    stream = _stream_of(lib, x)
+    desc = _fill_desc(cfg, x, rec.state_in, rec.muwts, rec.ac, rec.elev, ptensors)
+    route = _route_desc(cfg, ptensors, S=1) if cfg.route is not None else None
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        cost = _out((P, B), dev)
+        sim = _out((P, T_out, B), dev) if want_sim else None
+        for c0 in range(0, P, POP_MAX_CAND):
+            pop = _abi.Pop()
+            pop.n_cand, pop.t_first = min(POP_MAX_CAND, P - c0), t_first
+            for slot, (_, col) in cand_sources.items():
+                s = pop.p[slot]
+                s.sta, s.c_stride, s.b_stride = _ptr(cands, c0 * B * Cn + col), B * Cn, Cn
+            if route is not None:
+                pop.route = _C.pointer(route)
+                ra, rb = route_cands or (None, None)
+                if ra is not None:
+                    pop.ra = _ptr(cands, c0 * B * Cn + ra[1])
+                if rb is not None:
+                    pop.rb = _ptr(cands, c0 * B * Cn + rb[1])
+                pop.r_c_stride, pop.r_b_stride = B * Cn, Cn
+            pop.target, pop.w = _ptr(tc), _ptr(wc)
+            pop.cost = _ptr(cost, c0 * B)
+            pop.sim = _ptr(sim, c0 * T_out * B)
+            _call(lib, 'hbvx_population_cost', lib.population_cost, desc, pop, stream)
+    return cost, sim
+
+
 class PathOut(NamedTuple):
     """What one call of the path returns.  `flux`: tuple of the n_flux series [T,B,1] (index it with the hbvx_flux
     enum) or None when cfg.want_flux is False; `routed`: tuple of the four UH-routed runoff series [T,B,1] or

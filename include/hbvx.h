@@ -33,6 +33,8 @@
  *   hbvx_gram            has no counterpart in the reference: the per-basin normal equations J^T W J, J^T W r and the
  *                        cost of a Gauss-Newton / Levenberg-Marquardt calibration, straight from the direction-major
  *                        series the tangent calls write.
+ *   hbvx_population_cost has no counterpart either: the weighted squared error of the routed streamflow of many
+ *                        candidate parameter sets per basin in one launch (random / SCE-UA / DDS-style searches).
  *
  * Ownership: the caller allocates and owns every buffer; the library keeps no
  * state between calls and allocates nothing persistent.  All device work is
@@ -251,7 +253,7 @@ const char *hbvx_last_error(void);
 const char *hbvx_backend(void);         /* "hip:gfx950" or "cpu-oracle" */
 uint64_t hbvx_sizeof(int which);        /* 0 desc, 1 fwd_out, 2 bwd_io, 3 route_desc,
                                            4 param_src, 5 param_grad, 6 gage_desc, 7 tan_io, 8 tan_batch,
-                                           9 gram_desc: layout check */
+                                           9 gram_desc, 10 pop: layout check */
 /* Diagnostic: the kernel family that took the process's last hbvx_forward (direction 0) / hbvx_backward (1) call --
  * "pipe", "stream2", "stream", "tiled", "simple", "chunked", "ckpt-block:<family>", "ckpt-lds"; "oracle" in the CPU
  * restatement.  The parity tests assert that the family they mean to pin against the reference is the one that ran. */
@@ -519,6 +521,48 @@ int hbvx_gram(const hbvx_gram_desc *g, const float *s, const float *w, const flo
 uint64_t hbvx_quadform_workspace_bytes(const hbvx_gram_desc *g);   /* 0 for a descriptor hbvx_quadform would refuse */
 int hbvx_quadform(const hbvx_gram_desc *g, const float *s, const float *m, float *q, void *workspace,
                   uint64_t workspace_bytes, void *stream);
+
+/* Population evaluation (optional export; a library may lack it): the cost of many candidate static-parameter sets on
+ * one descriptor, one launch, nothing written but the costs.  For every candidate c and basin b the recurrence of
+ * hbvx_forward runs on `d` (HBV 1.0 / 1.1p / 2.0; HBVX_MODEL_HBVADJ and HBVX_MODEL_HOURLY: HBVX_E_UNSUPPORTED) with the
+ * candidate's static values in place of d->p[i].sta wherever pop->p[i].sta is set.  Dynamic parameters, drop masks,
+ * muwts, state_in, ac, elev and the forcings are the descriptor's, shared by all candidates.  The ensemble mean of Q is
+ * formed (with muwts) as hbvx_forward forms series HBVX_F_QSIM, routed -- when `route` is given -- through the
+ * normalised gamma unit hydrograph of (c, b) with the arithmetic of hbvx_route_forward (causal, zero history before
+ * day 0 of the call, taps ascending: acc += uh[k] * q[t-k]), and from day t_first on
+ *   r = y - target,  cost = fmaf(w * r, r, cost)   (fmaf(r, r, cost) when w is NULL),
+ * days ascending, one chain per (c, b), no atomics.  csrc/hbv_pop.h has the kernel and the per-basin arithmetic.
+ * Masking is the caller's job, as for hbvx_gram: the kernel multiplies what it is given (w = 0 does not neutralise a
+ * NaN in target).
+ * Guarantees: (1) two calls on the same inputs give the same bits; (2) the bits of cost[c,b] and sim[c,:,b] do not
+ * depend on n_cand or on the other candidates: a candidate evaluated alone or in any subset gives the same bits;
+ * (3) sim == NULL changes no bit of cost; (4) argument errors are reported before anything is launched: HBVX_E_NULL
+ * (descriptor, pop, target, cost, a routing input that neither pop nor route supplies), HBVX_E_SHAPE (n_cand outside
+ * 1..65535, t_first outside 0..T-1, route->L != min(T, 15), route->T / route->B unlike the descriptor's, candidate
+ * values for a slot the model lacks), HBVX_E_UNSUPPORTED (model), HBVX_E_ABI.
+ * Bit equality with hbvx_forward + hbvx_route_forward is not promised: the forward may be taken by another kernel
+ * family. */
+typedef struct hbvx_pop_src {      /* where candidate c's static value of one parameter comes from */
+    const float *sta;              /* (c,b,j) at sta[c*c_stride + b*b_stride + j]; NULL: not a candidate column, */
+    int64_t c_stride, b_stride;    /*   every candidate uses desc->p[i].sta                                      */
+} hbvx_pop_src;
+
+typedef struct hbvx_pop {
+    int32_t n_cand;                /* P, 1..65535 */
+    int32_t t_first;               /* days 0..t_first-1 of the call are simulated and enter the routing
+                                      history but neither the cost nor `sim` (the module's pred_cutoff) */
+    hbvx_pop_src p[HBVX_MAX_PARAM];
+    const hbvx_route_desc *route;  /* NULL: cost on the un-routed ensemble mean.  Else the bounds, L, raw_sigmoid
+                                      of the module's routing; ra/rb/r_stride are the NON-candidate values */
+    const float *ra, *rb;          /* candidate routing inputs at ra[c*r_c_stride + b*r_b_stride]; either NULL:
+                                      that one comes from route->ra / route->rb for every candidate */
+    int64_t r_c_stride, r_b_stride;
+    const float *target;           /* [T - t_first, B], required */
+    const float *w;                /* [T - t_first, B] or NULL (= 1) */
+    float *cost;                   /* [P,B], overwritten completely */
+    float *sim;                    /* optional [P, T - t_first, B]: each candidate's (routed) streamflow */
+} hbvx_pop;                        /* hbvx_sizeof(10) */
+int hbvx_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream);
 
 /* Zero `bytes` bytes at `ptr` (streaming non-temporal stores).  The autograd contract of the plug-in wants
  * gradient tensors shaped like the raw parameter tensor [T,B,ny] (hbv.py:211-246: static parameters read
