@@ -10,9 +10,13 @@ wide).  Two routes from that start, both per basin:
                                       one launch) picks the row LM starts from
 
     python examples/calibrate_global.py [--basins 32] [--days 730] [--nmul 4] [--candidates 256] [--rounds 3] [--lm-iters 8]
+                                        [--objective sse|nse|kge|kge12] [--transform none|sqrt|log]
 
+--objective / --transform choose what the search minimises (hbvx_population_stats: NSE, KGE on the raw, square-root or
+log flow); Levenberg-Marquardt after it is least squares on the raw flow either way.
 Prints one JSON line: per route the summed cost and the number of basins in which it ended lower, with the cost of
-the start and of the search's pick beside them.  Synthetic forcings (tests/synth.py), a fixed seed.
+the start and of the search's pick beside them, and -- whichever objective was searched -- the basin means of SSE, NSE
+and KGE on the raw flow at the start and at the end of every route.  Synthetic forcings (tests/synth.py), a fixed seed.
 """
 import argparse
 import json
@@ -36,6 +40,10 @@ def main():
     ap.add_argument("--candidates", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--lm-iters", type=int, default=8)
+    ap.add_argument("--objective", default="sse", choices=["sse", "nse", "kge", "kge12"],
+                    help="what the population search minimises (1 - score for nse / kge / kge12)")
+    ap.add_argument("--transform", default="none", choices=["none", "sqrt", "log"],
+                    help="the flow the search scores: raw, square root or log(Q + eps)")
     ap.add_argument("--names", default="parBETA,parFC,parK0,parK1,parK2,parLP,parPERC,parUZL,route_a,route_b")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "the example runs on the GPU; there is no CPU fallback"
@@ -56,14 +64,25 @@ def main():
     lm_only, h_lm = hydrodl2_amd.calibrate(model, x, start, obs, names=names, n_iter=args.lm_iters)
     gen = torch.Generator().manual_seed(74)
     picked, h_ps = hydrodl2_amd.population_search(model, x, start, obs, names=names, n_candidates=args.candidates,
-                                                  n_rounds=args.rounds, generator=gen)
+                                                  n_rounds=args.rounds, generator=gen, objective=args.objective,
+                                                  transform=args.transform)
     both, h_both = hydrodl2_amd.calibrate(model, x, picked, obs, names=names, n_iter=args.lm_iters)
+
+    def worth(row):
+        """Basin means of SSE, NSE and KGE of a parameter tensor on the raw flow, whichever objective was searched: one
+        population_stats call with the row as its only candidate."""
+        cand = row[-1][:, cols].unsqueeze(0).contiguous()
+        st = hydrodl2_amd.population_stats(model, x, row, cand, obs, names=names)
+        return {m: float(hydrodl2_amd.population_score(st, m).mean()) for m in ("sse", "nse", "kge")}
 
     c_start, c_lm = h_lm["cost"][0], h_lm["cost"][-1]
     c_pick, c_both = h_both["cost"][0], h_both["cost"][-1]
     print(json.dumps({
         "basins": B, "days": T, "nmul": M, "columns": len(cols), "candidates": args.candidates, "rounds": args.rounds,
-        "lm_iters": args.lm_iters,
+        "lm_iters": args.lm_iters, "objective": args.objective, "transform": args.transform,
+        "mean_scores_start": worth(start), "mean_scores_calibrate_alone": worth(lm_only),
+        "mean_scores_after_population_search": worth(picked),
+        "mean_scores_population_search_then_calibrate": worth(both),
         "cost_start": float(c_start.sum()),
         "cost_calibrate_alone": float(c_lm.sum()),
         "cost_after_population_search": float(c_pick.sum()),

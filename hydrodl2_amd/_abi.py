@@ -130,6 +130,16 @@ class Pop(C.Structure):
                 ("target", _fp), ("w", _fp), ("cost", _fp), ("sim", _fp)]
 
 
+POP_T_NONE, POP_T_SQRT, POP_T_LOG = 0, 1, 2     # enum hbvx_pop_transform
+POP_TRANSFORMS = {"none": POP_T_NONE, "sqrt": POP_T_SQRT, "log": POP_T_LOG}
+
+
+class PopStats(C.Structure):
+    """hbvx_pop_stats: hbvx_pop, the transform, its per-basin shift / eps and the three moment outputs (include/hbvx.h)."""
+    _fields_ = [("pop", Pop), ("transform", C.c_int32), ("shift", _fp), ("eps", _fp),
+                ("s1", _fp), ("s2", _fp), ("s3", _fp)]
+
+
 class LstmDesc(C.Structure):
     """include/hbvx_lstm.h"""
     _fields_ = [("abi_version", C.c_int32), ("T", C.c_int32), ("B", C.c_int32), ("H", C.c_int32)]
@@ -153,7 +163,7 @@ OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forwa
                     "hbvx_hourly_tangent_batch", "hbvx_gage_route_tangent_batch",
                     "hbvx_gage_route_tangent_workspace_bytes", "hbvx_adj_tangent_batch", "hbvx_gram",
                     "hbvx_gram_workspace_bytes", "hbvx_quadform", "hbvx_quadform_workspace_bytes",
-                    "hbvx_population_cost"]
+                    "hbvx_population_cost", "hbvx_population_stats"]
 
 
 class HbvxError(RuntimeError):
@@ -309,6 +319,11 @@ class Library:
             d.hbvx_population_cost.argtypes = [C.POINTER(Desc), C.POINTER(Pop), C.c_void_p]
             if d.hbvx_sizeof(10) != C.sizeof(Pop):
                 raise HbvxError(f"{path}: layout mismatch for Pop: {d.hbvx_sizeof(10)} != {C.sizeof(Pop)}")
+        if "hbvx_population_stats" not in self.missing:
+            d.hbvx_population_stats.restype = C.c_int
+            d.hbvx_population_stats.argtypes = [C.POINTER(Desc), C.POINTER(PopStats), C.c_void_p]
+            if d.hbvx_sizeof(11) != C.sizeof(PopStats):
+                raise HbvxError(f"{path}: layout mismatch for PopStats: {d.hbvx_sizeof(11)} != {C.sizeof(PopStats)}")
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -498,6 +513,13 @@ class Library:
         self._check(self.dll.hbvx_population_cost(None if desc is None else C.byref(desc),
                                                   None if pop is None else C.byref(pop), C.c_void_p(stream)),
                     "hbvx_population_cost")
+
+    def population_stats(self, desc, ps, stream: int):
+        """hbvx_population_stats; `desc` / `ps` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_population_stats")
+        self._check(self.dll.hbvx_population_stats(None if desc is None else C.byref(desc),
+                                                   None if ps is None else C.byref(ps), C.c_void_p(stream)),
+                    "hbvx_population_stats")
 
     def gage_route_tangent_workspace_bytes(self, r: GageDesc, n_dir: int) -> int:
         self.require("hbvx_gage_route_tangent_workspace_bytes")

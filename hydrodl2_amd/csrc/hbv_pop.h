@@ -1,10 +1,14 @@
 // hbv_pop.h -- population evaluation (hbvx_population_cost, include/hbvx.h): the weighted squared error of the routed
 // ensemble-mean streamflow of P candidate static-parameter sets per basin, one number per (candidate, basin), from one
-// launch that writes nothing else.
+// launch that writes nothing else -- and (hbvx_population_stats) the same launch with three more chains per (candidate,
+// basin), on the raw, the square-root or the log flow, from which NSE, KGE, correlation, variability and bias follow on
+// the host: four [P,B] numbers instead of one, still no series.
 //
 // What happens to a basin's ensemble mean after the day step -- the normalised gamma unit hydrograph, the 15-day
 // window, the causal convolution and the residual chain -- is hbvx_popk::Basin below and compiles for the host as
 // well (tests/hosttest/pop_host.cpp), so the CPU tier checks it without a GPU; the kernel maps lanes onto it.
+// hbvx_popk::BasinStats is Basin plus the transform and the three moment chains (tests/hosttest/popstats_host.cpp).
+// k_pop maps lanes onto the one struct, k_pop_stats<TR> onto the other.
 #pragma once
 
 #include <math.h>
@@ -82,6 +86,51 @@ struct Basin {
     }
 };
 
+constexpr int T_NONE = 0, T_SQRT = 1, T_LOG = 2;      // HBVX_POP_T_*
+
+// Basin with the sums a score other than the squared error needs.  The window and the routed value y are Basin's own
+// lines (its push with counted = false), so y is the same in every transform; a counted day then takes
+//   y' = y | sqrtf(y) | logf(y + eps)          r = y' - o'      d = y' - m      e = o' - m
+//   cost = fmaf(w * r, r, cost)                (Basin's line: under T_NONE the same operations on the same values)
+//   s1 = fmaf(w, d, s1)    s2 = fmaf(w * d, d, s2)    s3 = fmaf(w * d, e, s3)      (w * r, w * d rounded once)
+// with o' the target ALREADY transformed and m the caller's shift, the weighted mean of o': the moments are taken about
+// m because raw float32 sums of y'^2 and y' o' over twenty years cancel to nothing when the flow varies little about a
+// large mean (the population kernel).  eps is read under T_LOG only.
+struct BasinStats : Basin {
+    float m, eps;
+    float s1, s2, s3;
+
+    HBVX_POP_HD void start(bool with_routing, float shift, float log_eps)
+    {
+        Basin::start(with_routing);
+        m = shift;
+        eps = log_eps;
+        s1 = s2 = s3 = 0.0f;
+    }
+
+    template <int TR>
+    HBVX_POP_HD float transform(float y) const
+    {
+        return TR == T_SQRT ? sqrtf(y) : TR == T_LOG ? logf(y + eps) : y;
+    }
+
+    template <int TR>
+    HBVX_POP_HD float push(float q, float target, float w, bool counted)
+    {
+        const float y = Basin::push(q, 0.0f, 0.0f, false);
+        if (counted) {
+            const float yt = transform<TR>(y);
+            const float r = yt - target;
+            cost = __builtin_fmaf(w * r, r, cost);
+            const float dd = yt - m, e = target - m;
+            s1 = __builtin_fmaf(w, dd, s1);
+            s2 = __builtin_fmaf(w * dd, dd, s2);
+            s3 = __builtin_fmaf(w * dd, e, s3);
+        }
+        return y;
+    }
+};
+
 } // namespace hbvx_popk
 
 #if defined(__HIPCC__)
@@ -96,6 +145,12 @@ struct PopArgs {
     hbvx_route_desc r;      // *pop.route (the pointer is the host's); read only with has_route
     int has_route;
     int lgMp;
+};
+
+struct PopStatsArgs {
+    PopArgs a;
+    const float *shift, *eps;   // hbvx_pop_stats': [B] each
+    float *s1, *s2, *s3;        // [P,B] each
 };
 
 // ---------------------------------------------------------------------------
@@ -225,6 +280,139 @@ __global__ void __launch_bounds__(64) k_pop(const PopArgs A)
         if (counted && sim && L.leader) sim[(int64_t)(t - t_first) * d.B] = y;
     }
     if (L.leader) pp.cost[c * d.B + L.b] = bs.cost;
+}
+
+// ---------------------------------------------------------------------------
+// k_pop_stats<MODEL, BETAET, TR>: k_pop on a BasinStats -- the same lanes, the same day loop, the same y; the shift
+// and eps of the lane's basin are two more registers, the three chains three more, and the leader stores four numbers.
+// TR is a template parameter: a wave-uniform switch inside the day loop would keep the log's registers live in every
+// transform.
+//
+// A restatement of k_pop's lines, not a shared body: one body for both (an inlined function template on the struct,
+// with overloads or `if constexpr` at the three places that differ) was built, and every form of it changed k_pop's
+// registers (138 -> 140 for HBV 1.0) and schedule (tools/compare_code.py), which are pinned; so k_pop keeps its text, as
+// k_uh_gamma does above.  A change to either belongs in both: tests/test_population_stats_gpu.py holds the two to the
+// same bits of the squared error and of the series.
+// ---------------------------------------------------------------------------
+template <int MODEL, bool BETAET, int TR>
+__global__ void __launch_bounds__(64) k_pop_stats(const PopStatsArgs S)
+{
+    constexpr int NP = NParam<MODEL, BETAET>::value;
+    const PopArgs &A = S.a;
+    const hbvx_desc &d = A.d;
+    const hbvx_pop &pp = A.pop;
+    const int lgMp = A.lgMp;
+    const LaneId L = lane_id(d, lgMp);
+    const int T = d.T;
+    const int t_first = pp.t_first;
+    const int64_t N = (int64_t)d.B * d.M;
+    const int64_t c = blockIdx.y;
+    const bool raw = d.raw_sigmoid != 0;
+    const float nz = d.nearzero;
+    const float ac = (MODEL == MODEL_HBV20) ? d.ac[L.b] : 0.0f;
+    const float elev = (MODEL == MODEL_HBV20) ? d.elev[L.b] : 0.0f;
+
+    float p[NPARAM_MAX];
+    const float *dynp[NP];
+    bool use_dyn[NP];
+    unsigned dmask = 0;
+#pragma unroll
+    for (int i = 0; i < NP; i++) {
+        const hbvx_param_src &s = d.p[i];
+        const hbvx_pop_src &cs = pp.p[i];
+        float v = cs.sta ? cs.sta[c * cs.c_stride + (int64_t)L.b * cs.b_stride + L.j]
+                         : s.sta[(int64_t)L.b * s.sta_b_stride + L.j];
+        v = raw ? sigmoid_(v) : v;
+        p[i] = descale_(v, s.lo, s.hi);
+        dynp[i] = s.dyn ? s.dyn + (int64_t)L.b * s.dyn_b_stride + L.j : s.sta;
+        use_dyn[i] = s.dyn && !(s.drop && s.drop[L.b]);
+        if (s.dyn) dmask |= 1u << i;
+    }
+#pragma unroll
+    for (int i = NP; i < NPARAM_MAX; i++) p[i] = 0.0f;
+
+    float st[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) st[k] = d.state_in ? d.state_in[k * N + L.n] : 0.001f;
+
+    hbvx_popk::BasinStats bs;
+    bs.start(A.has_route != 0, S.shift[L.b], TR == hbvx_popk::T_LOG ? S.eps[L.b] : 0.0f);
+    if (A.has_route) {      // route_ab's lines (hbvx.hip) on the candidate's routing inputs
+        const hbvx_route_desc &r = A.r;
+        const float va = pp.ra ? pp.ra[c * pp.r_c_stride + (int64_t)L.b * pp.r_b_stride] : r.ra[(int64_t)L.b * r.r_stride];
+        const float vb = pp.rb ? pp.rb[c * pp.r_c_stride + (int64_t)L.b * pp.r_b_stride] : r.rb[(int64_t)L.b * r.r_stride];
+        const float ua = r.raw_sigmoid ? sigmoid_(va) : va;
+        const float ub = r.raw_sigmoid ? sigmoid_(vb) : vb;
+        hbvx_popk::gamma_taps(descale_(ua, r.a_lo, r.a_hi), descale_(ub, r.b_lo, r.b_hi), r.L, bs.uh);
+    }
+
+    const float *xb = d.x + (int64_t)L.b * d.x_b_stride;
+    const float *mu = d.muwts ? d.muwts + (int64_t)L.b * d.mu_b_stride + L.j : nullptr;
+    const float invM = 1.0f / (float)d.M;
+    const float act = L.active ? 1.0f : 0.0f;
+    const float *tg = pp.target + L.b;              // row t - t_first of [T - t_first, B]: the TRANSFORMED target
+    const float *wt = pp.w ? pp.w + L.b : nullptr;
+    float *sim = pp.sim ? pp.sim + c * (int64_t)(T - t_first) * d.B + L.b : nullptr;
+
+    // one-step-ahead register prefetch of the per-step inputs (k_fwd's), the observation and its weight with them
+    float nxf[3], nxd[NP], nxo = 0.0f, nxw = 1.0f;
+    {
+        const float *xr = xb;
+        nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
+#pragma unroll
+        for (int i = 0; i < NP; i++) nxd[i] = ((dmask >> i) & 1) ? dynp[i][0] : 0.f;
+        if (t_first == 0) {
+            nxo = tg[0];
+            if (wt) nxw = wt[0];
+        }
+    }
+
+    for (int t = 0; t < T; t++) {
+        Step<MODEL, BETAET> s;
+        s.P = nxf[0]; s.Tf = nxf[1]; s.PET = nxf[2];
+        float cur[NP];
+#pragma unroll
+        for (int i = 0; i < NP; i++) cur[i] = nxd[i];
+        const float obs = nxo, wobs = nxw;
+        {
+            const int tn = t + 1 < T ? t + 1 : t;
+            const float *xr = xb + (int64_t)tn * d.x_t_stride;
+            nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
+#pragma unroll
+            for (int i = 0; i < NP; i++)
+                if ((dmask >> i) & 1) nxd[i] = dynp[i][(int64_t)tn * d.p[i].dyn_t_stride];
+            if (tn >= t_first) {
+                const int64_t row = (int64_t)(tn - t_first) * d.B;
+                nxo = tg[row];
+                if (wt) nxw = wt[row];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NP; i++)
+            if ((dmask >> i) & 1) {
+                float v = raw ? sigmoid_dyn_(cur[i]) : cur[i];
+                float pv = descale_(v, d.p[i].lo, d.p[i].hi);
+                if (use_dyn[i]) p[i] = pv;
+            }
+        s.SP = st[0]; s.MW = st[1]; s.SM = st[2]; s.SUZ = st[3]; s.SLZ = st[4];
+        s.template fwd<false, true>(p, nz, ac, elev, 0.f, 0.f);
+        st[0] = s.SP3; st[1] = s.MW3; st[2] = s.SM4; st[3] = s.SUZ4; st[4] = s.SLZ2;
+
+        // the ensemble mean of Q as k_fwd forms series HBVX_F_QSIM
+        const float wq = mu ? mu[(int64_t)t * d.mu_t_stride] : 1.0f;
+        float q = ens_sum((mu ? s.Q * wq : s.Q) * act, lgMp);
+        if (!mu) q = q * invM;
+        const bool counted = t >= t_first;
+        const float y = bs.template push<TR>(q, obs, wobs, counted);
+        if (counted && sim && L.leader) sim[(int64_t)(t - t_first) * d.B] = y;      // y, not y'
+    }
+    if (L.leader) {
+        const int64_t at = c * d.B + L.b;
+        pp.cost[at] = bs.cost;
+        S.s1[at] = bs.s1;
+        S.s2[at] = bs.s2;
+        S.s3[at] = bs.s3;
+    }
 }
 
 } // namespace hbvx

@@ -69,6 +69,7 @@ extern "C" uint64_t hbvx_sizeof(int which)
     case 8: return sizeof(hbvx_tan_batch);
     case 9: return sizeof(hbvx_gram_desc);
     case 10: return sizeof(hbvx_pop);
+    case 11: return sizeof(hbvx_pop_stats);
     default: return 0;
     }
 }

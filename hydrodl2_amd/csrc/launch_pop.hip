@@ -1,32 +1,39 @@
-// launch_pop.hip -- the entry point of the population evaluation (hbv_pop.h): hbvx_population_cost.
+// launch_pop.hip -- the entry points of the population evaluation (hbv_pop.h): hbvx_population_cost and
+// hbvx_population_stats.
 #include "hbvx_host.h"
 #include "hbv_pop.h"
 
 using namespace hbvx;
 using namespace hbvx_host;
 
-extern "C" int hbvx_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream)
+namespace {
+
+int fail_as(const char *who, int code, const char *msg)
 {
-    int rc = check_desc(d);
-    if (rc) return rc;
+    char text[160];
+    snprintf(text, sizeof text, "%s: %s", who, msg);
+    return fail(code, text);
+}
+
+// The argument checks both entry points share, and the kernel's arguments; `who` names the entry point in the messages.
+int prepare(const char *who, const hbvx_desc *d, const hbvx_pop *pop, PopArgs &a)
+{
     if (d->model != HBVX_MODEL_HBV10 && d->model != HBVX_MODEL_HBV11P && d->model != HBVX_MODEL_HBV20)
-        return fail(HBVX_E_UNSUPPORTED, "hbvx_population_cost: HBV 1.0 / 1.1p / 2.0 only");
-    if (!pop) return fail(HBVX_E_NULL, "hbvx_population_cost: pop is NULL");
-    if (!pop->target) return fail(HBVX_E_NULL, "hbvx_population_cost: target is NULL");
-    if (!pop->cost) return fail(HBVX_E_NULL, "hbvx_population_cost: cost is NULL");
-    if (pop->n_cand < 1 || pop->n_cand > 65535) return fail(HBVX_E_SHAPE, "hbvx_population_cost: n_cand must be in 1..65535");
-    if (pop->t_first < 0 || pop->t_first >= d->T) return fail(HBVX_E_SHAPE, "hbvx_population_cost: t_first outside the call's days");
+        return fail_as(who, HBVX_E_UNSUPPORTED, "HBV 1.0 / 1.1p / 2.0 only");
+    if (!pop->target) return fail_as(who, HBVX_E_NULL, "target is NULL");
+    if (!pop->cost) return fail_as(who, HBVX_E_NULL, "cost is NULL");
+    if (pop->n_cand < 1 || pop->n_cand > 65535) return fail_as(who, HBVX_E_SHAPE, "n_cand must be in 1..65535");
+    if (pop->t_first < 0 || pop->t_first >= d->T) return fail_as(who, HBVX_E_SHAPE, "t_first outside the call's days");
     for (int i = d->n_param; i < HBVX_MAX_PARAM; i++)
-        if (pop->p[i].sta) return fail(HBVX_E_SHAPE, "hbvx_population_cost: candidate values for a parameter slot the model lacks");
-    PopArgs a;
+        if (pop->p[i].sta) return fail_as(who, HBVX_E_SHAPE, "candidate values for a parameter slot the model lacks");
     memset(&a.r, 0, sizeof a.r);
     a.has_route = 0;
     if (const hbvx_route_desc *r = pop->route) {
-        if (r->abi_version != HBVX_ABI_VERSION) return fail(HBVX_E_ABI, "hbvx_population_cost: route abi_version mismatch");
-        if (r->L != (d->T < HBVX_UH_MAXLEN ? d->T : HBVX_UH_MAXLEN)) return fail(HBVX_E_SHAPE, "hbvx_population_cost: route L must be min(T, 15)");
-        if (r->T != d->T || r->B != d->B) return fail(HBVX_E_SHAPE, "hbvx_population_cost: route T / B differ from the descriptor's");
+        if (r->abi_version != HBVX_ABI_VERSION) return fail_as(who, HBVX_E_ABI, "route abi_version mismatch");
+        if (r->L != (d->T < HBVX_UH_MAXLEN ? d->T : HBVX_UH_MAXLEN)) return fail_as(who, HBVX_E_SHAPE, "route L must be min(T, 15)");
+        if (r->T != d->T || r->B != d->B) return fail_as(who, HBVX_E_SHAPE, "route T / B differ from the descriptor's");
         if ((!pop->ra && !r->ra) || (!pop->rb && !r->rb))
-            return fail(HBVX_E_NULL, "hbvx_population_cost: a routing input is neither in pop nor in route");
+            return fail_as(who, HBVX_E_NULL, "a routing input is neither in pop nor in route");
         a.r = *r;
         a.has_route = 1;
     }
@@ -34,13 +41,97 @@ extern "C" int hbvx_population_cost(const hbvx_desc *d, const hbvx_pop *pop, voi
     a.pop = *pop;
     a.pop.route = nullptr;      // a host pointer: the kernel reads its copy in a.r
     a.lgMp = lg_members(d->M);
+    return HBVX_OK;
+}
+
+dim3 pop_grid(const PopArgs &a)
+{
     const int bpw = 64 >> a.lgMp;
-    const dim3 grid((d->B + bpw - 1) / bpw, pop->n_cand);
+    return dim3((a.d.B + bpw - 1) / bpw, a.pop.n_cand);
+}
+
+} // namespace
+
+extern "C" int hbvx_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream)
+{
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!pop) return fail(HBVX_E_NULL, "hbvx_population_cost: pop is NULL");
+    PopArgs a;
+    rc = prepare("hbvx_population_cost", d, pop, a);
+    if (rc) return rc;
+    const dim3 grid = pop_grid(a);
     with_model(d, [&](auto m, auto be) {
         if constexpr (m != MODEL_HOURLY)
             hipLaunchKernelGGL((k_pop<m, be>), grid, dim3(64), 0, (hipStream_t)stream, a);
     });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "hbvx_population_cost launch");
+    return HBVX_OK;
+}
+
+extern "C" int hbvx_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void *stream)
+{
+    const char *who = "hbvx_population_stats";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!ps) return fail_as(who, HBVX_E_NULL, "ps is NULL");
+    PopStatsArgs s;
+    rc = prepare(who, d, &ps->pop, s.a);
+    if (rc) return rc;
+    if (ps->transform != HBVX_POP_T_NONE && ps->transform != HBVX_POP_T_SQRT && ps->transform != HBVX_POP_T_LOG)
+        return fail_as(who, HBVX_E_UNSUPPORTED, "transform must be HBVX_POP_T_NONE, _SQRT or _LOG");
+    if (!ps->shift) return fail_as(who, HBVX_E_NULL, "shift is NULL");
+    if (ps->transform == HBVX_POP_T_LOG && !ps->eps) return fail_as(who, HBVX_E_NULL, "eps is NULL under HBVX_POP_T_LOG");
+    if (!ps->s1 || !ps->s2 || !ps->s3) return fail_as(who, HBVX_E_NULL, "s1 / s2 / s3 is NULL");
+    s.shift = ps->shift;
+    s.eps = ps->eps;
+    s.s1 = ps->s1;
+    s.s2 = ps->s2;
+    s.s3 = ps->s3;
+    const dim3 grid = pop_grid(s.a);
+    with_model(d, [&](auto m, auto be) {
+        if constexpr (m != MODEL_HOURLY) {
+            switch (ps->transform) {
+            case HBVX_POP_T_SQRT:
+                hipLaunchKernelGGL((k_pop_stats<m, be, hbvx_popk::T_SQRT>), grid, dim3(64), 0, (hipStream_t)stream, s);
+                break;
+            case HBVX_POP_T_LOG:
+                hipLaunchKernelGGL((k_pop_stats<m, be, hbvx_popk::T_LOG>), grid, dim3(64), 0, (hipStream_t)stream, s);
+                break;
+            default:
+                hipLaunchKernelGGL((k_pop_stats<m, be, hbvx_popk::T_NONE>), grid, dim3(64), 0, (hipStream_t)stream, s);
+            }
+        }
+    });
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "hbvx_population_stats launch");
+    return HBVX_OK;
+}
+
+// Diagnostics (tests only): the transform as the kernel applies it -- BasinStats::transform on the device.
+template <int TR>
+__global__ void k_selftest_pop_transform(const float *y, const float *eps, float *out, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    hbvx_popk::BasinStats bs;
+    bs.start(false, 0.0f, TR == hbvx_popk::T_LOG ? eps[i] : 0.0f);
+    out[i] = bs.transform<TR>(y[i]);
+}
+
+extern "C" int hbvx_selftest_pop_transform(const float *y, const float *eps, float *out, int n, int transform, void *stream)
+{
+    if (!y || !out || n <= 0 || transform < HBVX_POP_T_NONE || transform > HBVX_POP_T_LOG || (transform == HBVX_POP_T_LOG && !eps))
+        return fail(HBVX_E_NULL, "selftest_pop_transform: bad arguments");
+    const dim3 grid((n + 255) / 256), block(256);
+    if (transform == HBVX_POP_T_SQRT)
+        hipLaunchKernelGGL(k_selftest_pop_transform<hbvx_popk::T_SQRT>, grid, block, 0, (hipStream_t)stream, y, eps, out, n);
+    else if (transform == HBVX_POP_T_LOG)
+        hipLaunchKernelGGL(k_selftest_pop_transform<hbvx_popk::T_LOG>, grid, block, 0, (hipStream_t)stream, y, eps, out, n);
+    else
+        hipLaunchKernelGGL(k_selftest_pop_transform<hbvx_popk::T_NONE>, grid, block, 0, (hipStream_t)stream, y, eps, out, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "selftest_pop_transform launch");
     return HBVX_OK;
 }

@@ -1082,8 +1082,35 @@ def population_cost(rec: PathRecord, cand_sources: dict, route_cands, target: to
                   Ignored when the recorded call does not route.
     target, w     [T_out,B] float32; w may be None (ones).  The kernel multiplies what it is given: the caller masks.
     More than POP_MAX_CAND candidates go in several launches; a candidate's bits do not depend on the split."""
+    cost, _, sim = _population("population_cost", rec, cand_sources, route_cands, target, w, t_first, want_sim, None)
+    return cost, sim
+
+
+def population_stats(rec: PathRecord, cand_sources: dict, route_cands, target_t: torch.Tensor, w: Optional[torch.Tensor],
+                     shift: torch.Tensor, eps: Optional[torch.Tensor], transform: str, t_first: int = 0,
+                     want_sim: bool = False):
+    """`population_cost` with the three moment chains of hbvx_population_stats (include/hbvx.h) beside the squared
+    error, on the transformed flow: (sse, s1, s2, s3 [P,B] each, sim [P,T_out,B] or None).
+
+    target_t      [T_out,B] float32, the target ALREADY transformed; shift [B] float32, the point the moments are taken
+                  about (the weighted mean of target_t); eps [B] float32, needed for transform 'log' only;
+                  transform 'none' | 'sqrt' | 'log'.  `sim` is the flow itself in every transform.
+    Everything else as `population_cost`: the same checks, the same split above POP_MAX_CAND."""
+    if transform not in _abi.POP_TRANSFORMS:
+        raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
+    if transform == "log" and eps is None:
+        raise ValueError("population_stats: transform 'log' needs eps")
+    sse, moments, sim = _population("population_stats", rec, cand_sources, route_cands, target_t, w, t_first, want_sim,
+                                    (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None))
+    return (sse,) + moments + (sim,)
+
+
+def _population(what: str, rec: PathRecord, cand_sources: dict, route_cands, target, w, t_first, want_sim, stats):
+    """What `population_cost` (stats None) and `population_stats` (stats = (transform id, shift, eps)) share: the
+    checks, the descriptors, the NaN-poisoned outputs and the launches.  -> (cost, (s1, s2, s3) or None, sim)."""
+    entry = "hbvx_" + what
     lib = get_library()
-    lib.require("hbvx_population_cost")
+    lib.require(entry)
     cfg = rec.cfg
     x, ptensors = rec.x, rec.ptensors
     dev = x.device
@@ -1093,14 +1120,14 @@ def population_cost(rec: PathRecord, cand_sources: dict, route_cands, target: to
         raise ValueError(f"t_first must be in 0..{T - 1}, got {t_first}")
     named = list(cand_sources.values()) + [s for s in (route_cands or ()) if s is not None]
     if not named:
-        raise ValueError("population_cost needs at least one candidate column")
+        raise ValueError(f"{what} needs at least one candidate column")
     cands = named[0][0]
     _check_tensor(lib, cands, "candidates")
     if cands.dim() != 3 or int(cands.shape[1]) != B or not cands.is_contiguous() or cands.device != dev:
         raise ValueError(f"candidates must be a contiguous [P,{B},C] tensor on {dev}, got {tuple(cands.shape)} on {cands.device}")
     P, Cn = int(cands.shape[0]), int(cands.shape[2])
     if P < 1:
-        raise ValueError("population_cost needs at least one candidate")
+        raise ValueError(f"{what} needs at least one candidate")
     for t, col in named:
         if t is not cands:
             raise ValueError("all candidate columns must lie in one compact tensor")
@@ -1116,16 +1143,27 @@ def population_cost(rec: PathRecord, cand_sources: dict, route_cands, target: to
         _check_tensor(lib, t, name)
         if tuple(t.shape) != (T_out, B) or t.device != dev:
             raise ValueError(f"{name} must be [{T_out},{B}] on {dev}, got {tuple(t.shape)} on {t.device}")
+    transform, shift, eps = stats if stats is not None else (None, None, None)
+    for name, t in (("shift", shift), ("eps", eps)):
+        if t is None:
+            continue
+        _check_tensor(lib, t, name)
+        if tuple(t.shape) != (B,) or t.device != dev:
+            raise ValueError(f"{name} must be [{B}] on {dev}, got {tuple(t.shape)} on {t.device}")
     tc = target.contiguous()
     wc = None if w is None else w.contiguous()
+    shc = None if shift is None else shift.contiguous()
+    epc = None if eps is None else eps.contiguous()
     stream = _stream_of(lib, x)
     desc = _fill_desc(cfg, x, rec.state_in, rec.muwts, rec.ac, rec.elev, ptensors)
     route = _route_desc(cfg, ptensors, S=1) if cfg.route is not None else None
     with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
         cost = _out((P, B), dev)
+        moments = tuple(_out((P, B), dev) for _ in range(3)) if stats is not None else None
         sim = _out((P, T_out, B), dev) if want_sim else None
         for c0 in range(0, P, POP_MAX_CAND):
-            pop = _abi.Pop()
+            ps = _abi.PopStats() if stats is not None else None
+            pop = ps.pop if stats is not None else _abi.Pop()
             pop.n_cand, pop.t_first = min(POP_MAX_CAND, P - c0), t_first
             for slot, (_, col) in cand_sources.items():
                 s = pop.p[slot]
@@ -1141,8 +1179,13 @@ def population_cost(rec: PathRecord, cand_sources: dict, route_cands, target: to
             pop.target, pop.w = _ptr(tc), _ptr(wc)
             pop.cost = _ptr(cost, c0 * B)
             pop.sim = _ptr(sim, c0 * T_out * B)
-            _call(lib, 'hbvx_population_cost', lib.population_cost, desc, pop, stream)
-    return cost, sim
+            if stats is None:
+                _call(lib, entry, lib.population_cost, desc, pop, stream)
+            else:
+                ps.transform, ps.shift, ps.eps = transform, _ptr(shc), _ptr(epc)
+                ps.s1, ps.s2, ps.s3 = (_ptr(m, c0 * B) for m in moments)
+                _call(lib, entry, lib.population_stats, desc, ps, stream)
+    return cost, moments, sim
 
 
 class PathOut(NamedTuple):

@@ -8,8 +8,11 @@ warm-up pass, its dy_drop draws and the recorded descriptor of its main pass), t
 (include/hbvx.h) runs the recurrence, the ensemble mean, the routing and the residual sum of every candidate in
 registers and writes [P,B] costs -- no flux series, no trajectory, no [P,B,ny] copy of the parameters.
 `population_search` is a per-basin shrinking random search on top, for a start that `calibrate` can refine.
+`population_stats` is the same launch with three more sums per (candidate, basin), on the raw, the square-root or the
+log flow (hbvx_population_stats), from which `population_score` forms NSE, KGE, correlation, variability and bias in
+float64 -- so a search can run in the metric its result is reported in.
 
-Hbv, Hbv_1_1p and Hbv_2 only; the score is the weighted squared error of 'streamflow'.
+Hbv, Hbv_1_1p and Hbv_2 only; the series scored is 'streamflow'.
 """
 from __future__ import annotations
 
@@ -52,6 +55,44 @@ def _column_groups(model, names):
     return groups
 
 
+def _check_candidates(req, x_dict, candidates):
+    x = x_dict['x_phy']
+    C = len(req.cols)
+    if not torch.is_tensor(candidates) or candidates.dim() != 3 or tuple(candidates.shape[1:]) != (req.B, C) \
+            or candidates.shape[0] < 1:
+        raise ValueError(f"candidates must be [P,{req.B},{C}] (P >= 1 sets for the {C} columns of `names`), got "
+                         f"{tuple(candidates.shape) if torch.is_tensor(candidates) else type(candidates).__name__}")
+    if candidates.dtype != torch.float32:
+        raise ValueError(f"candidates must be float32, got {candidates.dtype}")
+    if candidates.device != x.device:
+        raise ValueError(f"candidates live on {candidates.device}, x_phy on {x.device}")
+
+
+def _primal(model, req, x_dict, parameters):
+    """The one run of the module at `parameters`: (outputs, the recorded call of its main pass, t_first)."""
+    with torch.no_grad(), ops.record_paths() as records:
+        outputs = model(x_dict, parameters)
+    main = records[-1]
+    cfg = main.cfg
+    t_first = cfg.T - req.T_out          # warm_up_states=False: the warm-up days are simulated, not scored
+    if t_first < 0 or cfg.B != req.B:
+        raise RuntimeError(f"{type(model).__name__} ran {cfg.T} days on {cfg.B} basins, expected at least {req.T_out} on {req.B}")
+    return outputs, main, t_first
+
+
+def _candidate_sources(model, names, candidates):
+    """({parameter slot: (cands, column)}, (route_a, route_b) each None or (cands, column)) as ops.population_cost
+    takes them."""
+    cands = candidates.detach().contiguous()
+    sources, route = {}, [None, None]
+    for name, col, _ in _column_groups(model, names):
+        if name in model.routing_parameter_bounds:
+            route[list(model.routing_parameter_bounds).index(name)] = (cands, col)
+        else:
+            sources[_abi.PARAM_SLOTS.index(name)] = (cands, col)
+    return sources, tuple(route)
+
+
 def population_cost(model, x_dict: dict, parameters, candidates: torch.Tensor, target,
                     names: Optional[Sequence[str]] = None, weights=None, return_series: bool = False) -> dict:
     """sum_t w (streamflow - target)^2 per basin for each of P candidate static-parameter sets.
@@ -76,25 +117,10 @@ def population_cost(model, x_dict: dict, parameters, candidates: torch.Tensor, t
     weights, infinite targets, negative or non-finite weights (ValueError); a library without hbvx_population_cost
     (HbvxError)."""
     req = _check(model, x_dict, parameters, target, names, weights, "population_cost")
-    x = x_dict['x_phy']
-    C = len(req.cols)
-    if not torch.is_tensor(candidates) or candidates.dim() != 3 or tuple(candidates.shape[1:]) != (req.B, C) \
-            or candidates.shape[0] < 1:
-        raise ValueError(f"candidates must be [P,{req.B},{C}] (P >= 1 sets for the {C} columns of `names`), got "
-                         f"{tuple(candidates.shape) if torch.is_tensor(candidates) else type(candidates).__name__}")
-    if candidates.dtype != torch.float32:
-        raise ValueError(f"candidates must be float32, got {candidates.dtype}")
-    if candidates.device != x.device:
-        raise ValueError(f"candidates live on {candidates.device}, x_phy on {x.device}")
+    _check_candidates(req, x_dict, candidates)
     get_library().require("hbvx_population_cost")
 
-    with torch.no_grad(), ops.record_paths() as records:
-        outputs = model(x_dict, parameters)
-    main = records[-1]
-    cfg = main.cfg
-    t_first = cfg.T - req.T_out          # warm_up_states=False: the warm-up days are simulated, not scored
-    if t_first < 0 or cfg.B != req.B:
-        raise RuntimeError(f"{type(model).__name__} ran {cfg.T} days on {cfg.B} basins, expected at least {req.T_out} on {req.B}")
+    outputs, main, t_first = _primal(model, req, x_dict, parameters)
     dev = main.x.device
     tgt = target.to(device=dev, dtype=torch.float32).reshape(req.T_out, req.B)
     miss = torch.isnan(tgt)
@@ -107,19 +133,181 @@ def population_cost(model, x_dict: dict, parameters, candidates: torch.Tensor, t
         tgt = torch.where(miss, torch.zeros_like(tgt), tgt)     # 0 * NaN would be NaN: the kernel multiplies what it gets
         n_obs = (w > 0).sum(0, dtype=torch.int64)
 
-    cands = candidates.detach().contiguous()
-    sources, route = {}, [None, None]
-    for name, col, _ in _column_groups(model, names):
-        if name in model.routing_parameter_bounds:
-            route[list(model.routing_parameter_bounds).index(name)] = (cands, col)
-        else:
-            sources[_abi.PARAM_SLOTS.index(name)] = (cands, col)
-    cost, series = ops.population_cost(main, sources, tuple(route), tgt.contiguous(), w, t_first, return_series)
+    sources, route = _candidate_sources(model, names, candidates)
+    cost, series = ops.population_cost(main, sources, route, tgt.contiguous(), w, t_first, return_series)
     cost = torch.where(torch.isfinite(cost), cost, torch.full_like(cost, float('inf')))
     out = {'cost': cost, 'n_obs': n_obs, 'columns': list(req.cols), 'outputs': outputs}
     if return_series:
         out['series'] = series
     return out
+
+
+TRANSFORMS = tuple(_abi.POP_TRANSFORMS)                 # 'none', 'sqrt', 'log'
+METRICS = ('sse', 'mse', 'nse', 'kge', 'kge12', 'r', 'alpha', 'beta', 'pbias')
+OBJECTIVES = ('sse', 'nse', 'kge', 'kge12')
+# A variance of float32 chains at or below this fraction of the mean square about the shift is rounding noise, not a
+# variance (a constant series leaves about T_out * 2^-24 of it): the scores that divide by it are NaN there.
+_VAR_FLOOR = 1e-6
+
+
+def _observations(req, x_dict, target, weights, transform, eps, what):
+    """The observation side of `population_stats`, everything that can be refused about it, before the model runs.
+    float64 on the device of x_phy -> {'target' [T_out,B] float32 transformed (0 where missing), 'w' [T_out,B] float32
+    or None, 'shift' [B] float32, 'eps' [B] float32 or None, 'obs': {'W','e1','e2'} [B] float64, 'n_obs' [B] int64}."""
+    if transform not in _abi.POP_TRANSFORMS:
+        raise ValueError(f"{what}: transform must be one of {list(TRANSFORMS)}, got {transform!r}")
+    dev = x_dict['x_phy'].device
+    tgt = target.to(device=dev, dtype=torch.float32).reshape(req.T_out, req.B)
+    miss = torch.isnan(tgt)
+    plain = weights is None and not bool(miss.any())
+    w = torch.ones_like(tgt) if weights is None else weights.to(device=dev, dtype=torch.float32)
+    w = torch.where(miss, torch.zeros_like(w), w).contiguous()
+    w8 = w.double()
+    W = w8.sum(0)
+    some = W > 0
+    o8 = torch.where(miss, torch.zeros_like(tgt), tgt).double()
+    eps8 = None
+    if eps is not None:                                 # checked under every transform, read under 'log'
+        eps8 = torch.as_tensor(eps, dtype=torch.float64, device=dev)
+        if eps8.dim() == 0:
+            eps8 = eps8.expand(req.B)
+        if tuple(eps8.shape) != (req.B,):
+            raise ValueError(f"{what}: eps must be a scalar or [{req.B}], got {tuple(eps8.shape)}")
+    elif transform == 'log':
+        # a hundredth of the basin's weighted mean observed flow (1 where nothing is observed: never read)
+        eps8 = torch.where(some, 0.01 * (w8 * o8).sum(0) / W.clamp_min(1e-300), torch.ones_like(W))
+    if eps8 is not None:
+        eps8 = eps8.float().double()                    # the float32 the kernel adds
+        if not bool((torch.isfinite(eps8) & (eps8 > 0)).all()):
+            raise ValueError(f"{what}: eps must be finite and > 0 in every basin (the default, a hundredth of the weighted "
+                             "mean observed flow, needs a positive mean)")
+    if transform != 'log':
+        eps8 = None
+    if transform == 'log':
+        if bool(((o8 <= -eps8) & ~miss).any()):
+            raise ValueError(f"{what}: a target <= -eps has no logarithm")
+        o8 = torch.log(o8 + eps8)
+    elif transform == 'sqrt':
+        if bool(((o8 < 0) & ~miss).any()):
+            raise ValueError(f"{what}: a negative target has no square root")
+        o8 = torch.sqrt(o8)
+    ot = torch.where(miss, torch.zeros_like(tgt), o8.float())     # o' as the kernel reads it
+    shift = torch.where(some, (w8 * ot.double()).sum(0) / W.clamp_min(1e-300), torch.zeros_like(W)).float()
+    e = ot.double() - shift.double()
+    return {'target': ot.contiguous(), 'w': None if plain else w, 'shift': shift,
+            'eps': None if eps8 is None else eps8.float(),
+            'obs': {'W': W, 'e1': (w8 * e).sum(0), 'e2': (w8 * e * e).sum(0)},
+            'n_obs': (w > 0).sum(0, dtype=torch.int64)}
+
+
+def _stats(model, req, x_dict, parameters, candidates, names, ob, transform, return_series):
+    outputs, main, t_first = _primal(model, req, x_dict, parameters)
+    sources, route = _candidate_sources(model, names, candidates)
+    sse, s1, s2, s3, series = ops.population_stats(main, sources, route, ob['target'], ob['w'], ob['shift'], ob['eps'],
+                                                   transform, t_first, return_series)
+    out = {'sse': sse, 's1': s1, 's2': s2, 's3': s3, 'shift': ob['shift'], 'obs': ob['obs'], 'transform': transform,
+           'eps': ob['eps'], 'n_obs': ob['n_obs'], 'columns': list(req.cols), 'outputs': outputs}
+    if return_series:
+        out['series'] = series
+    return out
+
+
+def population_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, target,
+                     names: Optional[Sequence[str]] = None, weights=None, transform: str = 'none', eps=None,
+                     return_series: bool = False) -> dict:
+    """The sums from which `population_score` forms NSE, KGE, correlation, variability and bias of each of P candidate
+    static-parameter sets, on the raw flow (transform 'none'), its square root ('sqrt') or log(flow + eps) ('log'):
+    `population_cost`'s launch with three more chains per (candidate, basin) and still nothing but [P,B] numbers.
+
+    candidates, target, names, weights: as `population_cost`.  eps: a scalar, [B] or None -- None is a hundredth of the
+    basin's weighted mean observed flow under 'log'; unused otherwise.
+    With y' the transformed streamflow, o' the transformed target, m = `shift` the float32 weighted mean of o' and
+    d = y' - m, e = o' - m, returns
+      {'sse': sum w (y' - o')^2, 's1': sum w d, 's2': sum w d^2, 's3': sum w d e   -- [P,B] float32 chains over
+       ascending days (include/hbvx.h states them line by line), non-finite where a candidate's flow has no transform,
+       'shift': [B] float32, 'obs': {'W': sum w, 'e1': sum w e, 'e2': sum w e^2} [B] float64, 'transform', 'eps': [B]
+       float32 or None, 'n_obs': [B] int64, 'columns', 'outputs': the primal flux dictionary,
+       'series': [P,T_out,B] the streamflow itself (NOT transformed), only with return_series}.
+    Under 'none', 'sse' has the bits of `population_cost`'s 'cost' (before its +inf rule), and 'series' has them under
+    every transform.  The moments are taken about m because raw float32 sums cancel: see DESIGN.md.
+
+    Refused before the model runs: everything `population_cost` refuses; an unknown transform; eps <= 0 or non-finite;
+    a negative target under 'sqrt'; a target <= -eps under 'log' (ValueError); a library without hbvx_population_stats
+    (HbvxError)."""
+    req = _check(model, x_dict, parameters, target, names, weights, "population_stats")
+    _check_candidates(req, x_dict, candidates)
+    ob = _observations(req, x_dict, target, weights, transform, eps, "population_stats")
+    get_library().require("hbvx_population_stats")
+    return _stats(model, req, x_dict, parameters, candidates, names, ob, transform, return_series)
+
+
+def population_score(stats: dict, metric: str) -> torch.Tensor:
+    """[P,B] float64 score of every candidate from what `population_stats` returned.  Weighted population moments in the
+    transformed space, W = sum w:
+        mean_o = m + e1/W      var_o = e2/W - (e1/W)^2
+        mean_s = m + s1/W      var_s = s2/W - (s1/W)^2      cov = s3/W - (s1/W)(e1/W)
+      'sse'    sum w (y' - o')^2                 'mse'   sse / W
+      'nse'    1 - sse / (e2 - e1^2 / W)
+      'r'      cov / sqrt(var_s var_o)           'alpha' sqrt(var_s / var_o)
+      'beta'   mean_s / mean_o                   'pbias' 100 (mean_s - mean_o) / mean_o
+      'kge'    1 - sqrt((r-1)^2 + (alpha-1)^2 + (beta-1)^2)                    (Gupta et al. 2009)
+      'kge12'  the same with the ratio of the coefficients of variation, (sd_s/mean_s) / (sd_o/mean_o), in place of
+               alpha (Kling et al. 2012)
+    A score is NaN where it is undefined: a non-finite chain (every metric); no observation ('mse'); fewer than two
+    observations or no observed variance ('nse', 'r', 'alpha', 'kge', 'kge12'); no simulated variance -- at or below
+    1e-6 of the mean square about m, the noise a float32 chain leaves of a constant series -- ('r', 'kge', 'kge12'); a
+    zero observed mean ('beta', 'pbias', 'kge', 'kge12'); a zero simulated mean ('kge12').
+
+    beta and pbias on a transformed flow compare the means of sqrt(Q) or log(Q + eps), not volumes: under 'sqrt' beta
+    still reads as a bias of the mid-range flows; under 'log' the mean of the logarithms can lie anywhere around zero
+    (it changes sign with the unit of Q), so beta, pbias, kge and kge12 on log flows seldom mean anything -- use 'nse',
+    'r' and 'alpha' there."""
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {list(METRICS)}, got {metric!r}")
+    sse, s1, s2, s3 = (stats[k].double() for k in ('sse', 's1', 's2', 's3'))
+    dev = sse.device
+    W, e1, e2 = (stats['obs'][k].to(device=dev, dtype=torch.float64) for k in ('W', 'e1', 'e2'))
+    m = stats['shift'].to(device=dev, dtype=torch.float64)
+    n_obs = stats['n_obs'].to(dev)
+    nan = torch.full_like(sse, float('nan'))
+    Ws = W.clamp_min(1e-300)
+    finite = torch.isfinite(sse) & torch.isfinite(s1) & torch.isfinite(s2) & torch.isfinite(s3)
+    if metric == 'sse':
+        return torch.where(finite, sse, nan)
+    if metric == 'mse':
+        return torch.where(finite & (W > 0), sse / Ws, nan)
+    var_o = e2 / Ws - (e1 / Ws) ** 2
+    obs_ok = (n_obs >= 2) & (var_o > _VAR_FLOOR * e2 / Ws)
+    if metric == 'nse':
+        return torch.where(finite & obs_ok, 1.0 - sse / (e2 - e1 * e1 / Ws), nan)
+    mean_o, mean_s = m + e1 / Ws, m + s1 / Ws
+    var_s = s2 / Ws - (s1 / Ws) ** 2
+    sim_ok = var_s > _VAR_FLOOR * s2 / Ws
+    cov = s3 / Ws - (s1 / Ws) * (e1 / Ws)
+    sd_o, sd_s = var_o.clamp_min(0).sqrt(), var_s.clamp_min(0).sqrt()
+    if metric == 'beta':
+        return torch.where(finite & (W > 0) & (mean_o != 0), mean_s / mean_o, nan)
+    if metric == 'pbias':
+        return torch.where(finite & (W > 0) & (mean_o != 0), 100.0 * (mean_s - mean_o) / mean_o, nan)
+    if metric == 'alpha':
+        return torch.where(finite & obs_ok, sd_s / sd_o, nan)
+    r = cov / (sd_s * sd_o)
+    if metric == 'r':
+        return torch.where(finite & obs_ok & sim_ok, r, nan)
+    ok = finite & obs_ok & sim_ok & (mean_o != 0)
+    if metric == 'kge12':
+        ok = ok & (mean_s != 0)
+        ratio = (sd_s / mean_s) / (sd_o / mean_o)
+    else:
+        ratio = sd_s / sd_o
+    kge = 1.0 - torch.sqrt((r - 1.0) ** 2 + (ratio - 1.0) ** 2 + (mean_s / mean_o - 1.0) ** 2)
+    return torch.where(ok, kge, nan)
+
+
+def _objective_cost(score: torch.Tensor, objective: str) -> torch.Tensor:
+    """What `population_search` minimises: 1 - score (the squared error itself for 'sse'), +inf where the score is NaN."""
+    cost = score if objective == 'sse' else 1.0 - score
+    return torch.where(torch.isnan(cost), torch.full_like(cost, float('inf')), cost)
 
 
 def _to_input_space(u: torch.Tensor, raw: bool) -> torch.Tensor:
@@ -131,7 +319,8 @@ def _to_input_space(u: torch.Tensor, raw: bool) -> torch.Tensor:
 
 def population_search(model, x_dict: dict, parameters, target, names: Optional[Sequence[str]] = None,
                       n_candidates: int = 256, n_rounds: int = 1, shrink: float = 0.5, weights=None,
-                      generator: Optional[torch.Generator] = None):
+                      generator: Optional[torch.Generator] = None, objective: str = 'sse', transform: str = 'none',
+                      eps=None):
     """Per-basin shrinking random search over the static row, for a start that `calibrate` can refine.
 
     Round 0 evaluates the current row as candidate 0 and n_candidates - 1 uniform draws in the unit interval per
@@ -144,7 +333,13 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
     (p_dyn, new p_sta)); history = {'cost': [n_rounds+1,B] float64 (row 0: the start, row k+1: the best after round k),
     'best_index': [n_rounds,B] int64 (the winning candidate of the round; 0: nothing better was drawn), 'columns'}.
     The inputs are not modified.  Deterministic for a given `generator` (default: torch's global CPU generator).
-    dy_drop > 0 makes the cost stochastic: ValueError."""
+    dy_drop > 0 makes the cost stochastic: ValueError.
+
+    objective 'sse' with transform 'none' (the defaults) is the search above, bit for bit.  objective 'nse', 'kge' or
+    'kge12', or a transform 'sqrt' / 'log' (eps as `population_stats` takes it), makes every round one
+    `population_stats` call: the quantity minimised, and what history['cost'] holds, is then 1 - score (the squared error
+    of the transformed flow for 'sse'), +inf where `population_score` gives NaN, and history['score'] [n_rounds+1,B]
+    holds the score itself ('nse', 'kge', 'kge12' only).  A basin whose observations admit no score keeps its row."""
     if float(getattr(model, 'dy_drop', 0.0)) > 0:
         raise ValueError("population_search: dy_drop > 0 draws new masks in every run, the cost is stochastic; set dy_drop = 0")
     if n_candidates < 2:
@@ -153,7 +348,22 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
         raise ValueError("n_rounds must be >= 1")
     if not 0 < shrink <= 1:
         raise ValueError("population_search wants 0 < shrink <= 1")
+    if objective not in OBJECTIVES:
+        raise ValueError(f"population_search: objective must be one of {list(OBJECTIVES)}, got {objective!r}")
     req = _check(model, x_dict, parameters, target, names, weights, "population_search")
+    by_stats = objective != 'sse' or transform != 'none'
+    if by_stats:
+        ob = _observations(req, x_dict, target, weights, transform, eps, "population_search")
+        get_library().require("hbvx_population_stats")
+
+    def evaluate(cands):
+        """(cost, score or None) [P,B] of one round's candidates."""
+        if not by_stats:
+            return population_cost(model, x_dict, parameters, cands, target, names, weights)['cost'], None
+        st = _stats(model, req, x_dict, parameters, cands, names, ob, transform, False)
+        score = population_score(st, objective)
+        return _objective_cost(score, objective), score
+
     two = req.tname == 'p_sta'
     raw = not two
     cur = _static_tensor(two, parameters).detach().clone()
@@ -166,22 +376,31 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
     best = row[:, cols].to(device=dev, dtype=torch.float32)                     # [B,C], input space
     best_u = torch.sigmoid(best) if raw else best.clone()
     hist = {'cost': [], 'best_index': [], 'columns': list(req.cols)}
+    keep_score = objective != 'sse'
+    if keep_score:
+        hist['score'] = []
     for k in range(n_rounds):
         draws = torch.rand((n_candidates - 1, req.B, C), generator=generator, device=gdev).to(dev)
         if k > 0:
             draws = best_u.unsqueeze(0) + (draws - 0.5) * float(shrink) ** k
         cands = torch.cat([best.unsqueeze(0), _to_input_space(draws, raw)]).contiguous()
-        cost = population_cost(model, x_dict, parameters, cands, target, names, weights)['cost']
+        cost, score = evaluate(cands)
         low, idx = cost.min(0)
         idx = torch.where(cost[0] <= low, torch.zeros_like(idx), idx)          # a tie keeps the row that is held
         if k == 0:
             hist['cost'].append(cost[0].double().cpu())
+            if keep_score:
+                hist['score'].append(score[0].cpu())
         pick = idx.view(1, req.B, 1).expand(1, req.B, C)
         best = cands.gather(0, pick)[0]
         best_u = torch.sigmoid(best) if raw else best.clone()
         hist['cost'].append(cost.gather(0, idx.unsqueeze(0))[0].double().cpu())
+        if keep_score:
+            hist['score'].append(score.gather(0, idx.unsqueeze(0))[0].cpu())
         hist['best_index'].append(idx.cpu())
     row[:, cols] = best.to(cur.device)
     hist['cost'] = torch.stack(hist['cost'])
     hist['best_index'] = torch.stack(hist['best_index'])
+    if keep_score:
+        hist['score'] = torch.stack(hist['score'])
     return ((parameters[0], cur) if two else cur), hist

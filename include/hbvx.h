@@ -253,7 +253,7 @@ const char *hbvx_last_error(void);
 const char *hbvx_backend(void);         /* "hip:gfx950" or "cpu-oracle" */
 uint64_t hbvx_sizeof(int which);        /* 0 desc, 1 fwd_out, 2 bwd_io, 3 route_desc,
                                            4 param_src, 5 param_grad, 6 gage_desc, 7 tan_io, 8 tan_batch,
-                                           9 gram_desc, 10 pop: layout check */
+                                           9 gram_desc, 10 pop, 11 pop_stats: layout check */
 /* Diagnostic: the kernel family that took the process's last hbvx_forward (direction 0) / hbvx_backward (1) call --
  * "pipe", "stream2", "stream", "tiled", "simple", "chunked", "ckpt-block:<family>", "ckpt-lds"; "oracle" in the CPU
  * restatement.  The parity tests assert that the family they mean to pin against the reference is the one that ran. */
@@ -564,6 +564,36 @@ typedef struct hbvx_pop {
 } hbvx_pop;                        /* hbvx_sizeof(10) */
 int hbvx_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream);
 
+/* Population scores (optional export; a library may lack it): hbvx_population_cost with three more sums per (c, b), on
+ * the raw, the square-root or the log flow, from which NSE, KGE, correlation, variability ratio and bias follow on the
+ * host.  The model, the candidates, the ensemble mean, the routing, t_first and `sim` are hbvx_population_cost's: y is
+ * the same number in every transform, and `sim` stores y.  Per counted day, days ascending, one chain each per (c, b),
+ * no atomics, every product written here rounded once:
+ *   y' = y                       (HBVX_POP_T_NONE)
+ *   y' = sqrtf(y)                (HBVX_POP_T_SQRT)
+ *   y' = logf(y + eps[b])        (HBVX_POP_T_LOG)
+ *   r = y' - o'      d = y' - m      e = o' - m          o' = pop.target[t,b], m = shift[b]
+ *   sse = fmaf(w * r, r, sse)                             -> pop.cost
+ *   s1  = fmaf(w,     d, s1)
+ *   s2  = fmaf(w * d, d, s2)
+ *   s3  = fmaf(w * d, e, s3)                              (w = 1 when pop.w is NULL)
+ * pop.target holds the target ALREADY transformed by the caller; `shift` is meant to be the weighted mean of o' (any
+ * finite value is legal: the moments are about it, and the closer it lies to the mean the less they cancel).
+ * Guarantees: those of hbvx_population_cost, for all four outputs; and (5) under HBVX_POP_T_NONE pop.cost has the bits
+ * hbvx_population_cost gives for the same candidate, and `sim` has them under every transform.
+ * Errors, before anything is launched: hbvx_population_cost's, and HBVX_E_NULL (ps, shift, s1, s2, s3; eps under
+ * HBVX_POP_T_LOG), HBVX_E_UNSUPPORTED (a transform other than the three). */
+enum hbvx_pop_transform { HBVX_POP_T_NONE = 0, HBVX_POP_T_SQRT = 1, HBVX_POP_T_LOG = 2 };
+
+typedef struct hbvx_pop_stats {
+    hbvx_pop pop;                  /* as above; pop.target: the TRANSFORMED target, pop.cost receives sse */
+    int32_t transform;             /* HBVX_POP_T_* */
+    const float *shift;            /* [B], required */
+    const float *eps;              /* [B], read with HBVX_POP_T_LOG only */
+    float *s1, *s2, *s3;           /* [P,B] each, overwritten completely */
+} hbvx_pop_stats;                  /* hbvx_sizeof(11) */
+int hbvx_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void *stream);
+
 /* Zero `bytes` bytes at `ptr` (streaming non-temporal stores).  The autograd contract of the plug-in wants
  * gradient tensors shaped like the raw parameter tensor [T,B,ny] (hbv.py:211-246: static parameters read
  * one row of it), so the dense zero fill is part of every backward step. */
@@ -583,6 +613,9 @@ int hbvx_zero_except(float *ptr, int64_t rows, int32_t width, int64_t r0, int64_
 int hbvx_selftest_pow(const float *x, const float *y, float *out, int n, void *stream);
 /* Diagnostics (tests only): out[i] = the device quotient used for SM/FC on x[i] / y[i]. */
 int hbvx_selftest_div(const float *x, const float *y, float *out, int n, void *stream);
+/* Diagnostics (tests only): out[i] = y' as hbvx_population_stats forms it from y[i] (and eps[i] under HBVX_POP_T_LOG;
+ * eps may be NULL otherwise). */
+int hbvx_selftest_pop_transform(const float *y, const float *eps, float *out, int n, int transform, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,279 @@
+"""GPU tier: `population_stats` / `population_score` / `population_search(objective=...)` (hydrodl2_amd/population.py)
+on hbvx_population_stats.
+
+The cases are those of tests/test_population_gpu.py (its `Case` / `case`, with the reasons for every shape); the
+targets are twin targets -- the module's streamflow at a hidden candidate times exp(noise) -- under that file's NaN
+masks and weights, so that the scores lie where calibration works and no basin's observed mean or variance is near
+zero (asserted first: no comparison below is empty, and no score of the yardstick is NaN).
+
+  same model  under 'none' the squared error has the bits of `population_cost`'s cost, and under every transform the
+              series has the bits of its series: k_pop_stats restates k_pop's day loop, and this is what holds the two
+              texts together.
+  the sums    each of sse, s1, s2, s3 against the float64 sum over the kernel's OWN float32 series, transformed in
+              float64.  'none': the bounds of tests/test_popstats_host.py.  'sqrt' / 'log': widened by the device
+              function's own error, |y'_device - y'| <= k u (1 + |y'|) per value, propagated to first order:
+              sum w k u (1+|y'|) times 1, 2|d|, |e|, 2|r| for s1, s2, s3, sse.  ROCm ships no accuracy table for the
+              device math functions, so k is measured here on the test records through hbvx_selftest_pop_transform (the
+              transform as the kernel applies it) against float64 -- K_MEASURED below, MI355X, worst of the six records:
+              sqrt 0.81 (the wet 400-day record; 0.58 .. 0.79 on the others), log 2.03 (the same record; 1.47 .. 1.82:
+              the logarithm of a value near 1 is near 0, where an absolute error of two u shows) -- and asserted at
+              four times that.
+  the scores  against the module route (`Case.yardstick`: the forward kernels plus hbvx_route_forward, one module call
+              per candidate -- the parent's code), float64 NSE / KGE / r / alpha / beta from the series by their
+              definitions.  Two float32 forwards feed a float32 chain: the tolerance is measured, not derived.  Worst
+              |score - yardstick| / (1 + |1 - yardstick|) over the cases, transforms and metrics on the MI355X of
+              profiles/r16_population_stats.md: 9.44e-6 (r on the square-root flow of the 7-day record, where some
+              candidates barely vary; 3.1e-7 .. 1.7e-6 on the other records); asserted: four times that (the margin
+              COST_RTOL takes), and held below 1e-4 -- ranking candidates whose scores differ in the third decimal is then
+              safe by a factor of ten.  Under 'log' beta and kge are left out: the mean of log(Q + eps) can lie
+              anywhere around zero, a ratio of two such means has no scale to hold an error against
+              (`population_score` says so); nse, r and alpha are compared there."""
+import ctypes as C
+import functools
+
+import pytest
+import torch
+
+import hydrodl2_amd
+from hydrodl2_amd import ops
+from hydrodl2_amd.population import (_observations, population_cost, population_score, population_search,
+                                     population_stats)
+
+from . import synth
+from .test_population_gpu import CASES, DEV, U, bits, case, gamma
+from .test_population_score_host import textbook
+
+TRANSFORMS = ("none", "sqrt", "log")
+K_MEASURED = {"sqrt": 0.81, "log": 2.03}
+K_BOUND = {"none": 0.0, **{t: 4 * k for t, k in K_MEASURED.items()}}
+MEASURED_SCORE_DIFF = 9.44e-6
+SCORE_TOL = 4 * MEASURED_SCORE_DIFF
+assert SCORE_TOL < 1e-4
+SCORED = {"none": ("nse", "kge", "r", "alpha", "beta"), "sqrt": ("nse", "kge", "r", "alpha", "beta"),
+          "log": ("nse", "r", "alpha")}
+
+
+def g64(y, transform, eps):
+    """The transform in float64; eps [B] float32 or None."""
+    y = y.double()
+    return y if transform == "none" else y.sqrt() if transform == "sqrt" else torch.log(y + eps.double())
+
+
+@functools.lru_cache(maxsize=None)
+def twin(name):
+    """The case's twin target [T_out,B]: streamflow at a hidden candidate (half a draw away from the row) times
+    exp(0.2 noise), NaN where the case's own target is NaN.  Computed once."""
+    cs = case(name)
+    n_cols = len(cs.cols)
+    row = cs.cand[0]
+    if cs.two:
+        hidden = 0.5 * (row + torch.from_numpy(synth.unit_parameters((cs.B, n_cols), 191)).to(DEV))
+    else:
+        hidden = row + 0.35 * torch.from_numpy(synth.normalish((cs.B, n_cols), 192)).to(DEV)
+    cs.prepare()
+    with torch.no_grad():
+        flow = cs.model(cs.xd, cs.with_row(hidden))["streamflow"][..., 0].clone()
+    noise = torch.from_numpy(synth.normalish((cs.T_out, cs.B), 193)).to(DEV)
+    target = flow * torch.exp(0.2 * noise)
+    return torch.where(torch.isnan(cs.target), cs.target, target).contiguous()
+
+
+def stats(name, transform, cand=None, **kw):
+    cs = case(name)
+    tgt = twin(name)            # (runs the module when it is first asked for: before prepare(), not after)
+    cs.prepare()
+    return population_stats(cs.model, cs.xd, cs.p, cs.cand if cand is None else cand, tgt, cs.names, cs.weights,
+                            transform=transform, **kw)
+
+
+def weights_of(name):
+    cs = case(name)
+    tgt = twin(name)
+    w = torch.ones_like(tgt) if cs.weights is None else cs.weights
+    return torch.where(torch.isnan(tgt), torch.zeros_like(w), w).double()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(CASES))
+def test_same_model_as_population_cost(hip_backend, name):
+    assert ops._POISON, "the GPU tier runs with NaN-poisoned output buffers"
+    cs = case(name)
+    tgt = twin(name)            # (runs the module when it is first asked for: before prepare(), not after)
+    cs.prepare()
+    cost = population_cost(cs.model, cs.xd, cs.p, cs.cand, tgt, cs.names, cs.weights, return_series=True)
+    for transform in TRANSFORMS:
+        got = stats(name, transform, return_series=True)
+        for key in ("sse", "s1", "s2", "s3"):
+            assert tuple(got[key].shape) == (cs.P, cs.B) and got[key].dtype == torch.float32
+            assert bool(torch.isfinite(got[key]).all()), f"{transform}: a poisoned or non-finite element in {key}"
+        assert tuple(got["series"].shape) == (cs.P, cs.T_out, cs.B) and bool(torch.isfinite(got["series"]).all())
+        assert torch.equal(bits(got["series"]), bits(cost["series"])), f"{transform}: the series is not population_cost's"
+        assert got["columns"] == cs.cols and got["transform"] == transform
+        assert torch.equal(got["n_obs"], cost["n_obs"])
+        assert (got["eps"] is None) == (transform != "log")
+        if transform == "none":
+            assert torch.equal(bits(got["sse"]), bits(cost["cost"])), "sse under 'none' is not population_cost's cost"
+        else:
+            assert not torch.equal(bits(got["sse"]), bits(cost["cost"]))
+
+
+def device_transform(lib, y, eps, transform):
+    """y' as the kernel forms it (hbvx_selftest_pop_transform), y and eps float32 of one shape."""
+    y = y.contiguous()
+    out = torch.full_like(y, float("nan"))
+    fn = lib.dll.hbvx_selftest_pop_transform
+    fn.restype = C.c_int
+    rc = fn(C.c_void_p(y.data_ptr()), C.c_void_p(eps.contiguous().data_ptr()) if eps is not None else None,
+            C.c_void_p(out.data_ptr()), C.c_int(y.numel()), C.c_int({"none": 0, "sqrt": 1, "log": 2}[transform]),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(CASES))
+def test_the_sums_against_float64_over_the_kernels_own_series(hip_backend, name):
+    cs = case(name)
+    w8 = weights_of(name)
+    for transform in TRANSFORMS:
+        got = stats(name, transform, return_series=True)
+        ob = _observations(cs.req, cs.xd, twin(name), cs.weights, transform, None, "test")
+        assert torch.equal(bits(ob["shift"]), bits(got["shift"]))
+        series, eps = got["series"], got["eps"]
+        y8 = g64(series, transform, eps)                                       # [P,T_out,B]
+        k = K_BOUND[transform]
+        if transform != "none":
+            # the device function's own error on this record, in units of u (1 + |y'|)
+            dev = device_transform(hip_backend, series, None if eps is None else eps.expand_as(series), transform)
+            measured = float(((dev.double() - y8).abs() / (U * (1 + y8.abs()))).max())
+            print(f"{name} {transform}: device transform error {measured:.3f} u (1 + |y'|), asserted {k:.2f}")
+            assert measured <= k
+        o8, m8 = ob["target"].double(), ob["shift"].double()
+        d, e, r = y8 - m8, o8 - m8, y8 - o8
+        delta = k * U * (1 + y8.abs())
+        T = cs.T_out
+        rows = (("sse", w8 * r * r, w8 * r * r, w8 * 2 * r.abs() * delta, T + 2), ("s1", w8 * d, w8 * d.abs(), w8 * delta, T + 1),
+                ("s2", w8 * d * d, w8 * d * d, w8 * 2 * d.abs() * delta, T + 3),
+                ("s3", w8 * d * e, w8 * (d * e).abs(), w8 * e.abs() * delta, T + 3))
+        for key, terms, mags, spread, n in rows:
+            err = (got[key].double() - terms.sum(1)).abs()
+            bound = gamma(n) * mags.sum(1) + spread.sum(1)
+            need = float((err / torch.where(bound > 0, bound, torch.ones_like(bound))).max())
+            print(f"{name} {transform}: {key} against its own series: worst error / bound {need:.3f}")
+            assert bool((err <= bound).all()), f"{transform}: {key} misses the float64 sum of its own series by {need:.2f} x the bound"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(CASES))
+def test_scores_against_the_module_route(hip_backend, name):
+    cs = case(name)
+    tgt, w8 = twin(name), weights_of(name)
+    want_series = cs.yardstick[0]
+    # first: the observations carry a mean and a variance in every basin, in the raw flow
+    W = w8.sum(0)
+    o = torch.where(torch.isnan(tgt), torch.zeros_like(tgt), tgt).double()
+    mean_o = (w8 * o).sum(0) / W
+    sd_o = ((w8 * (o - mean_o) ** 2).sum(0) / W).sqrt()
+    assert bool((W > 0).all()) and bool((mean_o > 0.05).all()) and bool((sd_o > 0.05 * mean_o).all()), \
+        "a basin's observations have no mean or no variance to speak of: the comparison would be empty"
+    worst = 0.0
+    for transform in TRANSFORMS:
+        got = stats(name, transform)
+        eps = got["eps"]
+        want = textbook(g64(want_series, transform, eps), g64(tgt, transform, eps), w8)
+        if transform == "none":
+            # the range where calibration works is among the candidates (the draws far from the row score far below it)
+            assert bool(((want["kge"] > 0.3) & (want["kge"] < 0.99)).any()), "no candidate scores a KGE in 0.3 .. 0.99"
+        for metric in SCORED[transform]:
+            assert bool(torch.isfinite(want[metric]).all()), f"{transform} {metric}: the yardstick has no score"
+            score = population_score(got, metric)
+            assert tuple(score.shape) == (cs.P, cs.B) and score.dtype == torch.float64
+            assert bool(torch.isfinite(score).all()), f"{transform} {metric}: a candidate has no score"
+            diff = float(((score - want[metric]).abs() / (1 + (1 - want[metric]).abs())).max())
+            worst = max(worst, diff)
+            print(f"{name} {transform} {metric}: yardstick {float(want[metric].min()):.3f} .. {float(want[metric].max()):.3f}, "
+                  f"worst difference {diff:.3e} (asserted {SCORE_TOL:.1e})")
+    print(f"{name}: worst score difference {worst:.3e}")
+    assert worst <= SCORE_TOL
+
+
+@pytest.mark.gpu
+def test_bit_rules(hip_backend):
+    name = "hbv-m2-b5-t15-drop-masked"
+    cs = case(name)
+    keys = ("sse", "s1", "s2", "s3")
+    pick = [0, 3, 8]
+    for transform in TRANSFORMS:
+        a = stats(name, transform, return_series=True)
+        b = stats(name, transform, return_series=True)
+        assert all(torch.equal(bits(a[k]), bits(b[k])) for k in keys + ("series",)), f"{transform}: two calls differ"
+        plain = stats(name, transform)
+        assert "series" not in plain and all(torch.equal(bits(plain[k]), bits(a[k])) for k in keys), \
+            f"{transform}: return_series changes the sums"
+        for c in pick:
+            alone = stats(name, transform, cs.cand[c:c + 1].contiguous(), return_series=True)
+            assert all(torch.equal(bits(alone[k][0]), bits(a[k][c])) for k in keys + ("series",)), \
+                f"{transform}: candidate {c} alone has other bits"
+        sub = stats(name, transform, cs.cand[pick].contiguous(), return_series=True)
+        assert all(torch.equal(bits(sub[k]), bits(a[k][pick])) for k in keys + ("series",))
+        # the candidates differ, and so does every sum: the candidate index reaches the parameters
+        for k in keys:
+            assert len({float(v) for v in a[k][:, 0]}) == cs.P, f"{transform}: {k} repeats between candidates"
+
+
+@pytest.mark.gpu
+def test_population_search_on_kge(hip_backend):
+    """The twin problem of tests/test_population_gpu.py::test_population_search, searched in KGE."""
+    T, B, M = 40, 5, 2
+    model = hydrodl2_amd.load_model("hbv", "Hbv")({"nmul": M, "dynamic_params": {"Hbv": []}}, DEV)
+    x = {"x_phy": torch.from_numpy(synth.forcing(T, B, seed=61)).to(DEV)}
+    truth = torch.from_numpy(synth.raw_parameters(T, B, model.learnable_param_count, seed=62)).to(DEV)
+    with torch.no_grad():
+        obs = model(x, truth)["streamflow"][..., 0].clone()
+    start = torch.from_numpy(synth.raw_parameters(T, B, model.learnable_param_count, seed=63, scale=1.5)).to(DEV)
+    keep = [t.clone() for t in (start, obs, x["x_phy"])]
+
+    def search(seed, target=obs, **kw):
+        g = torch.Generator().manual_seed(seed)
+        return population_search(model, x, start, target, n_candidates=32, n_rounds=3, generator=g, **kw)
+
+    def kge_by_the_module(params):
+        with torch.no_grad():
+            sim = model(x, params)["streamflow"][..., 0]
+        return textbook(sim.double().unsqueeze(0), obs.double(), torch.ones_like(obs).double())["kge"][0].cpu()
+
+    best, hist = search(5, objective="kge")
+    assert all(torch.equal(a, b) for a, b in zip((start, obs, x["x_phy"]), keep)), "an input was modified"
+    cost, score = hist["cost"], hist["score"]
+    assert tuple(cost.shape) == (4, B) and tuple(score.shape) == (4, B) and tuple(hist["best_index"].shape) == (3, B)
+    assert cost.dtype == torch.float64 and score.dtype == torch.float64
+    assert bool(torch.isfinite(cost).all()) and bool((cost[1:] <= cost[:-1]).all()), "a basin's recorded cost rose"
+    assert torch.equal(cost, 1.0 - score)
+    assert bool((cost[-1] < cost[0]).any()), "32 candidates x 3 rounds improved no basin"
+    assert torch.equal(hist["best_index"] != 0, cost[1:] < cost[:-1])
+    final, first = kge_by_the_module(best), kge_by_the_module(start)
+    diff = float(((final - score[-1]).abs() / (1 + (1 - final).abs())).max())
+    print(f"population_search(kge): mean KGE {float(first.mean()):.4f} -> {float(final.mean()):.4f}; history against the "
+          f"module route: worst difference {diff:.3e}")
+    assert diff <= SCORE_TOL and bool((final >= first - SCORE_TOL * (1 + (1 - first).abs())).all())
+    assert tuple(best.shape) == tuple(start.shape) and torch.equal(best[:-1], start[:-1])
+    again, hist2 = search(5, objective="kge")
+    assert torch.equal(bits(again), bits(best)) and torch.equal(hist2["cost"], cost) and torch.equal(hist2["score"], score)
+    assert torch.equal(hist2["best_index"], hist["best_index"])
+
+    # objective 'sse' with the default transform is the call without the new arguments: bits and history keys
+    old, hist_old = search(5)
+    new, hist_new = search(5, objective="sse", transform="none")
+    assert torch.equal(bits(old), bits(new)) and set(hist_old) == set(hist_new) == {"cost", "best_index", "columns"}
+    assert torch.equal(hist_old["cost"], hist_new["cost"]) and torch.equal(hist_old["best_index"], hist_new["best_index"])
+    assert not torch.equal(bits(old), bits(best))                               # another objective, another optimum
+
+    # a basin without observations admits no score: +inf throughout, and its row stays
+    blind = obs.clone()
+    blind[:, 2] = float("nan")
+    kept, hist3 = search(5, target=blind, objective="kge")
+    assert bool(torch.isinf(hist3["cost"][:, 2]).all()) and bool((hist3["cost"][:, 2] > 0).all())
+    assert bool(torch.isnan(hist3["score"][:, 2]).all()) and bool((hist3["best_index"][:, 2] == 0).all())
+    assert torch.equal(bits(kept[-1, 2]), bits(start[-1, 2]))
+    others = [b for b in range(B) if b != 2]
+    assert bool(torch.isfinite(hist3["cost"][:, others]).all())
