@@ -10,8 +10,11 @@ wide).  Two routes from that start, both per basin:
                                       one launch) picks the row LM starts from
 
     python examples/calibrate_global.py [--basins 32] [--days 730] [--nmul 4] [--candidates 256] [--rounds 3] [--lm-iters 8]
-                                        [--objective sse|nse|kge|kge12] [--transform none|sqrt|log]
+                                        [--objective sse|nse|kge|kge12] [--transform none|sqrt|log] [--model Hbv|HbvAdj]
 
+--model HbvAdj runs the same experiment on the implicit scheme: adj_population_search (hbvx_adj_population_cost: every
+candidate's days solved in registers) in front of calibrate, scored on 'flow_sim', from the module's own start (empty
+storages); the routing parameters are then 'rout_a' and 'rout_b'.
 --objective / --transform choose what the search minimises (hbvx_population_stats: NSE, KGE on the raw, square-root or
 log flow); Levenberg-Marquardt after it is least squares on the raw flow either way.
 Prints one JSON line: per route the summed cost and the number of basins in which it ended lower, with the cost of
@@ -44,18 +47,28 @@ def main():
                     help="what the population search minimises (1 - score for nse / kge / kge12)")
     ap.add_argument("--transform", default="none", choices=["none", "sqrt", "log"],
                     help="the flow the search scores: raw, square root or log(Q + eps)")
-    ap.add_argument("--names", default="parBETA,parFC,parK0,parK1,parK2,parLP,parPERC,parUZL,route_a,route_b")
+    ap.add_argument("--names", default=None,
+                    help="default: parBETA,parFC,parK0,parK1,parK2,parLP,parPERC,parUZL and the two routing parameters")
+    ap.add_argument("--model", default="Hbv", choices=["Hbv", "HbvAdj"])
     args = ap.parse_args()
     assert torch.cuda.is_available(), "the example runs on the GPU; there is no CPU fallback"
     dev = torch.device("cuda:0")
     T, B, M = args.days, args.basins, args.nmul
-    names = args.names.split(",")
-    model = hydrodl2_amd.load_model("hbv", "Hbv")({"nmul": M, "dynamic_params": {"Hbv": []}}, dev)
+    adj = args.model == "HbvAdj"
+    key = "flow_sim" if adj else "streamflow"
+    names = (args.names or "parBETA,parFC,parK0,parK1,parK2,parLP,parPERC,parUZL,"
+             + ("rout_a,rout_b" if adj else "route_a,route_b")).split(",")
+    if adj:
+        model = hydrodl2_amd.load_model("hbv_adj", "HbvAdj")({"nmul": M, "dynamic_params": {"HbvAdj": []}}, dev)
+        search, stats = hydrodl2_amd.adj_population_search, hydrodl2_amd.adj_population_stats
+    else:
+        model = hydrodl2_amd.load_model("hbv", "Hbv")({"nmul": M, "dynamic_params": {"Hbv": []}}, dev)
+        search, stats = hydrodl2_amd.population_search, hydrodl2_amd.population_stats
     x = {"x_phy": torch.from_numpy(synth.forcing(T, B, seed=71)).to(dev)}
     ny = model.learnable_param_count
     truth = torch.from_numpy(synth.raw_parameters(T, B, ny, seed=72)).to(dev)
     with torch.no_grad():
-        obs = model(x, truth)["streamflow"][..., 0].clone()
+        obs = model(x, truth)[key][..., 0].clone()
     # the poor start: the named columns of the static row drawn anew, three times as wide; everything else is the truth's
     _, cols = hydrodl2_amd.sensitivity.jacobian_columns(model, names)
     start = truth.clone()
@@ -63,21 +76,21 @@ def main():
 
     lm_only, h_lm = hydrodl2_amd.calibrate(model, x, start, obs, names=names, n_iter=args.lm_iters)
     gen = torch.Generator().manual_seed(74)
-    picked, h_ps = hydrodl2_amd.population_search(model, x, start, obs, names=names, n_candidates=args.candidates,
-                                                  n_rounds=args.rounds, generator=gen, objective=args.objective,
-                                                  transform=args.transform)
+    picked, h_ps = search(model, x, start, obs, names=names, n_candidates=args.candidates, n_rounds=args.rounds,
+                          generator=gen, objective=args.objective, transform=args.transform)
     both, h_both = hydrodl2_amd.calibrate(model, x, picked, obs, names=names, n_iter=args.lm_iters)
 
     def worth(row):
         """Basin means of SSE, NSE and KGE of a parameter tensor on the raw flow, whichever objective was searched: one
         population_stats call with the row as its only candidate."""
         cand = row[-1][:, cols].unsqueeze(0).contiguous()
-        st = hydrodl2_amd.population_stats(model, x, row, cand, obs, names=names)
+        st = stats(model, x, row, cand, obs, names=names)
         return {m: float(hydrodl2_amd.population_score(st, m).mean()) for m in ("sse", "nse", "kge")}
 
     c_start, c_lm = h_lm["cost"][0], h_lm["cost"][-1]
     c_pick, c_both = h_both["cost"][0], h_both["cost"][-1]
     print(json.dumps({
+        **({"model": args.model} if adj else {}),
         "basins": B, "days": T, "nmul": M, "columns": len(cols), "candidates": args.candidates, "rounds": args.rounds,
         "lm_iters": args.lm_iters, "objective": args.objective, "transform": args.transform,
         "mean_scores_start": worth(start), "mean_scores_calibrate_alone": worth(lm_only),

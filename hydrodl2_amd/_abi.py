@@ -163,7 +163,8 @@ OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forwa
                     "hbvx_hourly_tangent_batch", "hbvx_gage_route_tangent_batch",
                     "hbvx_gage_route_tangent_workspace_bytes", "hbvx_adj_tangent_batch", "hbvx_gram",
                     "hbvx_gram_workspace_bytes", "hbvx_quadform", "hbvx_quadform_workspace_bytes",
-                    "hbvx_population_cost", "hbvx_population_stats"]
+                    "hbvx_population_cost", "hbvx_population_stats",
+                    "hbvx_adj_population_cost", "hbvx_adj_population_stats"]
 
 
 class HbvxError(RuntimeError):
@@ -322,6 +323,16 @@ class Library:
         if "hbvx_population_stats" not in self.missing:
             d.hbvx_population_stats.restype = C.c_int
             d.hbvx_population_stats.argtypes = [C.POINTER(Desc), C.POINTER(PopStats), C.c_void_p]
+            if d.hbvx_sizeof(11) != C.sizeof(PopStats):
+                raise HbvxError(f"{path}: layout mismatch for PopStats: {d.hbvx_sizeof(11)} != {C.sizeof(PopStats)}")
+        if "hbvx_adj_population_cost" not in self.missing:      # the structs of the two above
+            d.hbvx_adj_population_cost.restype = C.c_int
+            d.hbvx_adj_population_cost.argtypes = [C.POINTER(Desc), C.POINTER(Pop), C.c_void_p]
+            if d.hbvx_sizeof(10) != C.sizeof(Pop):
+                raise HbvxError(f"{path}: layout mismatch for Pop: {d.hbvx_sizeof(10)} != {C.sizeof(Pop)}")
+        if "hbvx_adj_population_stats" not in self.missing:
+            d.hbvx_adj_population_stats.restype = C.c_int
+            d.hbvx_adj_population_stats.argtypes = [C.POINTER(Desc), C.POINTER(PopStats), C.c_void_p]
             if d.hbvx_sizeof(11) != C.sizeof(PopStats):
                 raise HbvxError(f"{path}: layout mismatch for PopStats: {d.hbvx_sizeof(11)} != {C.sizeof(PopStats)}")
         if d.hbvx_version() != ABI_VERSION:
@@ -520,6 +531,20 @@ class Library:
         self._check(self.dll.hbvx_population_stats(None if desc is None else C.byref(desc),
                                                    None if ps is None else C.byref(ps), C.c_void_p(stream)),
                     "hbvx_population_stats")
+
+    def adj_population_cost(self, desc, pop, stream: int):
+        """hbvx_adj_population_cost; `desc` / `pop` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_adj_population_cost")
+        self._check(self.dll.hbvx_adj_population_cost(None if desc is None else C.byref(desc),
+                                                      None if pop is None else C.byref(pop), C.c_void_p(stream)),
+                    "hbvx_adj_population_cost")
+
+    def adj_population_stats(self, desc, ps, stream: int):
+        """hbvx_adj_population_stats; `desc` / `ps` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_adj_population_stats")
+        self._check(self.dll.hbvx_adj_population_stats(None if desc is None else C.byref(desc),
+                                                       None if ps is None else C.byref(ps), C.c_void_p(stream)),
+                    "hbvx_adj_population_stats")
 
     def gage_route_tangent_workspace_bytes(self, r: GageDesc, n_dir: int) -> int:
         self.require("hbvx_gage_route_tangent_workspace_bytes")

@@ -1,7 +1,11 @@
-// launch_pop.hip -- the entry points of the population evaluation (hbv_pop.h): hbvx_population_cost and
-// hbvx_population_stats.
+// launch_pop.hip -- the entry points of the population evaluation: hbvx_population_cost and hbvx_population_stats
+// (hbv_pop.h), and their twins for the implicit scheme, hbvx_adj_population_cost and hbvx_adj_population_stats
+// (hbv_adj_pop.h).
 #include "hbvx_host.h"
 #include "hbv_pop.h"
+#define HBVX_CHUNK_NO_SHARED_KERNELS
+#include "hbv_chunked.h"        // (first: hbv_adj_kernels.h uses its XCD-aware block map)
+#include "hbv_adj_pop.h"
 
 using namespace hbvx;
 using namespace hbvx_host;
@@ -15,10 +19,20 @@ int fail_as(const char *who, int code, const char *msg)
     return fail(code, text);
 }
 
-// The argument checks both entry points share, and the kernel's arguments; `who` names the entry point in the messages.
-int prepare(const char *who, const hbvx_desc *d, const hbvx_pop *pop, PopArgs &a)
+// The argument checks all entry points share, and the kernel's arguments; `who` names the entry point in the messages.
+// adj: the implicit scheme's entry points -- the model test, and what check_adj (launch_adj.hip) asks of the Newton policy.
+int prepare(const char *who, const hbvx_desc *d, const hbvx_pop *pop, PopArgs &a, bool adj = false)
 {
-    if (d->model != HBVX_MODEL_HBV10 && d->model != HBVX_MODEL_HBV11P && d->model != HBVX_MODEL_HBV20)
+    if (adj) {
+        if (d->model != HBVX_MODEL_HBVADJ) return fail_as(who, HBVX_E_UNSUPPORTED, "the implicit scheme (HBVADJ) only");
+        if (!(d->adj_gtol >= 0.0f) || d->adj_max_iter < 0 || d->adj_max_iter > 64)
+            return fail_as(who, HBVX_E_SHAPE, "bad Newton policy (adj_gtol / adj_max_iter)");
+        if (d->adj_stop < 0 || d->adj_stop > 2) return fail_as(who, HBVX_E_SHAPE, "adj_stop must be 0, 1 or 2");
+        if (d->adj_stop == 1)
+            return fail_as(who, HBVX_E_UNSUPPORTED, "adj_stop = 1 (the batch-wide stopping rule) would make a candidate's "
+                                                    "cost depend on the lanes that share its wave");
+        if (d->muwts) return fail_as(who, HBVX_E_UNSUPPORTED, "muwts must be NULL (the implicit scheme has no ensemble weights)");
+    } else if (d->model != HBVX_MODEL_HBV10 && d->model != HBVX_MODEL_HBV11P && d->model != HBVX_MODEL_HBV20)
         return fail_as(who, HBVX_E_UNSUPPORTED, "HBV 1.0 / 1.1p / 2.0 only");
     if (!pop->target) return fail_as(who, HBVX_E_NULL, "target is NULL");
     if (!pop->cost) return fail_as(who, HBVX_E_NULL, "cost is NULL");
@@ -41,6 +55,22 @@ int prepare(const char *who, const hbvx_desc *d, const hbvx_pop *pop, PopArgs &a
     a.pop = *pop;
     a.pop.route = nullptr;      // a host pointer: the kernel reads its copy in a.r
     a.lgMp = lg_members(d->M);
+    return HBVX_OK;
+}
+
+// The stats entry points' own checks and arguments, after prepare.
+int prepare_stats(const char *who, const hbvx_pop_stats *ps, PopStatsArgs &s)
+{
+    if (ps->transform != HBVX_POP_T_NONE && ps->transform != HBVX_POP_T_SQRT && ps->transform != HBVX_POP_T_LOG)
+        return fail_as(who, HBVX_E_UNSUPPORTED, "transform must be HBVX_POP_T_NONE, _SQRT or _LOG");
+    if (!ps->shift) return fail_as(who, HBVX_E_NULL, "shift is NULL");
+    if (ps->transform == HBVX_POP_T_LOG && !ps->eps) return fail_as(who, HBVX_E_NULL, "eps is NULL under HBVX_POP_T_LOG");
+    if (!ps->s1 || !ps->s2 || !ps->s3) return fail_as(who, HBVX_E_NULL, "s1 / s2 / s3 is NULL");
+    s.shift = ps->shift;
+    s.eps = ps->eps;
+    s.s1 = ps->s1;
+    s.s2 = ps->s2;
+    s.s3 = ps->s3;
     return HBVX_OK;
 }
 
@@ -79,16 +109,8 @@ extern "C" int hbvx_population_stats(const hbvx_desc *d, const hbvx_pop_stats *p
     PopStatsArgs s;
     rc = prepare(who, d, &ps->pop, s.a);
     if (rc) return rc;
-    if (ps->transform != HBVX_POP_T_NONE && ps->transform != HBVX_POP_T_SQRT && ps->transform != HBVX_POP_T_LOG)
-        return fail_as(who, HBVX_E_UNSUPPORTED, "transform must be HBVX_POP_T_NONE, _SQRT or _LOG");
-    if (!ps->shift) return fail_as(who, HBVX_E_NULL, "shift is NULL");
-    if (ps->transform == HBVX_POP_T_LOG && !ps->eps) return fail_as(who, HBVX_E_NULL, "eps is NULL under HBVX_POP_T_LOG");
-    if (!ps->s1 || !ps->s2 || !ps->s3) return fail_as(who, HBVX_E_NULL, "s1 / s2 / s3 is NULL");
-    s.shift = ps->shift;
-    s.eps = ps->eps;
-    s.s1 = ps->s1;
-    s.s2 = ps->s2;
-    s.s3 = ps->s3;
+    rc = prepare_stats(who, ps, s);
+    if (rc) return rc;
     const dim3 grid = pop_grid(s.a);
     with_model(d, [&](auto m, auto be) {
         if constexpr (m != MODEL_HOURLY) {
@@ -106,6 +128,65 @@ extern "C" int hbvx_population_stats(const hbvx_desc *d, const hbvx_pop_stats *p
     });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "hbvx_population_stats launch");
+    return HBVX_OK;
+}
+
+// "Few" mode (hbv_adj_kernels.h): whether the call has at most ADJ_FEW dynamic parameters, and then their slot list
+static bool adj_pop_few(const hbvx_desc *d, AdjFew &few)
+{
+    few = AdjFew{};
+    if (count_dyn(d) > ADJ_FEW) return false;
+    for (int i = 0; i < d->n_param; i++)
+        if (d->p[i].dyn) few.slot[few.nd++] = i;
+    return true;
+}
+
+template <int TR>
+static void launch_adj_pop(const PopStatsArgs &s, void *stream)
+{
+    AdjFew few;
+    const bool is_few = adj_pop_few(&s.a.d, few);
+    const dim3 grid = pop_grid(s.a);
+    with_adj(&s.a.d, is_few, [&](auto be, auto fw) {
+        hipLaunchKernelGGL((k_adj_pop<be, fw, TR>), grid, dim3(64), 0, (hipStream_t)stream, s, few);
+    });
+}
+
+extern "C" int hbvx_adj_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream)
+{
+    const char *who = "hbvx_adj_population_cost";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!pop) return fail_as(who, HBVX_E_NULL, "pop is NULL");
+    PopStatsArgs s;
+    rc = prepare(who, d, pop, s.a, true);
+    if (rc) return rc;
+    s.shift = s.eps = nullptr;
+    s.s1 = s.s2 = s.s3 = nullptr;
+    launch_adj_pop<T_COST>(s, stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "hbvx_adj_population_cost launch");
+    return HBVX_OK;
+}
+
+extern "C" int hbvx_adj_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void *stream)
+{
+    const char *who = "hbvx_adj_population_stats";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!ps) return fail_as(who, HBVX_E_NULL, "ps is NULL");
+    PopStatsArgs s;
+    rc = prepare(who, d, &ps->pop, s.a, true);
+    if (rc) return rc;
+    rc = prepare_stats(who, ps, s);
+    if (rc) return rc;
+    switch (ps->transform) {
+    case HBVX_POP_T_SQRT: launch_adj_pop<hbvx_popk::T_SQRT>(s, stream); break;
+    case HBVX_POP_T_LOG: launch_adj_pop<hbvx_popk::T_LOG>(s, stream); break;
+    default: launch_adj_pop<hbvx_popk::T_NONE>(s, stream);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "hbvx_adj_population_stats launch");
     return HBVX_OK;
 }
 

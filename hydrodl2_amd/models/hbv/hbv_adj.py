@@ -174,6 +174,27 @@ class HbvAdj(torch.nn.Module):
         from hydrodl2_amd.adj_jvp import adj_parameter_jacobian
         return adj_parameter_jacobian(self, x_dict, parameters, names, max_directions)
 
+    def population_cost(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor, candidates: torch.Tensor,
+                        target, names=None, weights=None, return_series: bool = False) -> dict:
+        """The squared error of 'flow_sim' for many candidate static-parameter sets in one launch:
+        hydrodl2_amd.adj_population_cost(self, ...), see there."""
+        from hydrodl2_amd.adj_population import adj_population_cost
+        return adj_population_cost(self, x_dict, parameters, candidates, target, names, weights, return_series)
+
+    def population_stats(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor, candidates: torch.Tensor,
+                         target, names=None, weights=None, transform: str = 'none', eps=None,
+                         return_series: bool = False) -> dict:
+        """The sums `hydrodl2_amd.population_score` turns into NSE, KGE and the like, per candidate:
+        hydrodl2_amd.adj_population_stats(self, ...), see there."""
+        from hydrodl2_amd.adj_population import adj_population_stats
+        return adj_population_stats(self, x_dict, parameters, candidates, target, names, weights, transform, eps,
+                                    return_series)
+
+    def population_search(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor, target, **kwargs):
+        """Per-basin shrinking random search over the static row: hydrodl2_amd.adj_population_search(self, ...)."""
+        from hydrodl2_amd.adj_population import adj_population_search
+        return adj_population_search(self, x_dict, parameters, target, **kwargs)
+
     def _forward_eager(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor,
                        state: Optional[torch.Tensor] = None):
         """hbv_adj.py:227-330.  `state` [5,B,nmul] (private: the tests' way to start from filled storages): the

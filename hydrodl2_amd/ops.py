@@ -536,14 +536,17 @@ _TAP = threading.local()
 
 
 @contextlib.contextmanager
-def record_paths():
-    """with record_paths() as records: ... -- the PathRecords of the path calls this thread makes inside the block."""
-    outer = getattr(_TAP, "records", None)
+def record_paths(want_traj: bool = True):
+    """with record_paths() as records: ... -- the PathRecords of the path calls this thread makes inside the block.
+    want_traj=False: the implicit scheme does not keep its trajectory of solved states for the record (the population
+    calls re-solve every day themselves; at 671 x 16 x 7300 the trajectory is 1.5 GB)."""
+    outer = getattr(_TAP, "records", None), getattr(_TAP, "want_traj", True)
     _TAP.records = records = []
+    _TAP.want_traj = want_traj
     try:
         yield records
     finally:
-        _TAP.records = outer
+        _TAP.records, _TAP.want_traj = outer
 
 
 def _hbv_forward(ctx, cfg: StepConfig, x, state_in, muwts, ac, elev, ptensors):
@@ -1082,7 +1085,8 @@ def population_cost(rec: PathRecord, cand_sources: dict, route_cands, target: to
                   Ignored when the recorded call does not route.
     target, w     [T_out,B] float32; w may be None (ones).  The kernel multiplies what it is given: the caller masks.
     More than POP_MAX_CAND candidates go in several launches; a candidate's bits do not depend on the split."""
-    cost, _, sim = _population("population_cost", rec, cand_sources, route_cands, target, w, t_first, want_sim, None)
+    cost, _, sim = _population("population_cost", "hbvx_population_cost", lambda lib: lib.population_cost, rec,
+                               cand_sources, route_cands, target, w, t_first, want_sim, None)
     return cost, sim
 
 
@@ -1100,17 +1104,55 @@ def population_stats(rec: PathRecord, cand_sources: dict, route_cands, target_t:
         raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
     if transform == "log" and eps is None:
         raise ValueError("population_stats: transform 'log' needs eps")
-    sse, moments, sim = _population("population_stats", rec, cand_sources, route_cands, target_t, w, t_first, want_sim,
+    sse, moments, sim = _population("population_stats", "hbvx_population_stats", lambda lib: lib.population_stats, rec,
+                                    cand_sources, route_cands, target_t, w, t_first, want_sim,
                                     (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None))
     return (sse,) + moments + (sim,)
 
 
-def _population(what: str, rec: PathRecord, cand_sources: dict, route_cands, target, w, t_first, want_sim, stats):
-    """What `population_cost` (stats None) and `population_stats` (stats = (transform id, shift, eps)) share: the
-    checks, the descriptors, the NaN-poisoned outputs and the launches.  -> (cost, (s1, s2, s3) or None, sim)."""
-    entry = "hbvx_" + what
+def _require_adj_record(what: str, rec: PathRecord) -> None:
+    cfg = rec.cfg
+    if cfg.model != _abi.MODEL_HBVADJ:
+        raise ValueError(f"{what}: the record is not a call of the implicit scheme (HbvAdjPath)")
+    if cfg.adj_stop == 1:
+        raise ValueError(f"{what}: the batch-wide Newton stopping rule (newton_stop='global') votes over the 64 lanes of a "
+                         "wave; a candidate's cost must not depend on that")
+
+
+def adj_population_cost(rec: PathRecord, cand_sources: dict, route_cands, target: torch.Tensor,
+                        w: Optional[torch.Tensor], t_first: int = 0, want_sim: bool = False):
+    """`population_cost` for a recorded call of HbvAdjPath, through hbvx_adj_population_cost (include/hbvx.h): every
+    candidate's days are solved in registers under the record's Newton policy.  Same arguments, same results."""
+    _require_adj_record("adj_population_cost", rec)
+    cost, _, sim = _population("adj_population_cost", "hbvx_adj_population_cost", lambda lib: lib.adj_population_cost,
+                               rec, cand_sources, route_cands, target, w, t_first, want_sim, None)
+    return cost, sim
+
+
+def adj_population_stats(rec: PathRecord, cand_sources: dict, route_cands, target_t: torch.Tensor,
+                         w: Optional[torch.Tensor], shift: torch.Tensor, eps: Optional[torch.Tensor], transform: str,
+                         t_first: int = 0, want_sim: bool = False):
+    """`population_stats` for a recorded call of HbvAdjPath, through hbvx_adj_population_stats (include/hbvx.h)."""
+    if transform not in _abi.POP_TRANSFORMS:
+        raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
+    if transform == "log" and eps is None:
+        raise ValueError("adj_population_stats: transform 'log' needs eps")
+    _require_adj_record("adj_population_stats", rec)
+    sse, moments, sim = _population("adj_population_stats", "hbvx_adj_population_stats",
+                                    lambda lib: lib.adj_population_stats, rec, cand_sources, route_cands, target_t, w,
+                                    t_first, want_sim,
+                                    (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None))
+    return (sse,) + moments + (sim,)
+
+
+def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: dict, route_cands, target, w, t_first,
+                want_sim, stats):
+    """What the four population calls share -- stats None: the cost, stats = (transform id, shift, eps): the cost and the
+    moment chains; `entry` the export's name and `call_of(lib)` its Library method -- the checks, the descriptors, the
+    NaN-poisoned outputs and the launches.  -> (cost, (s1, s2, s3) or None, sim)."""
     lib = get_library()
     lib.require(entry)
+    call = call_of(lib)
     cfg = rec.cfg
     x, ptensors = rec.x, rec.ptensors
     dev = x.device
@@ -1180,11 +1222,11 @@ def _population(what: str, rec: PathRecord, cand_sources: dict, route_cands, tar
             pop.cost = _ptr(cost, c0 * B)
             pop.sim = _ptr(sim, c0 * T_out * B)
             if stats is None:
-                _call(lib, entry, lib.population_cost, desc, pop, stream)
+                _call(lib, entry, call, desc, pop, stream)
             else:
                 ps.transform, ps.shift, ps.eps = transform, _ptr(shc), _ptr(epc)
                 ps.s1, ps.s2, ps.s3 = (_ptr(m, c0 * B) for m in moments)
-                _call(lib, entry, lib.population_stats, desc, ps, stream)
+                _call(lib, entry, call, desc, ps, stream)
     return cost, moments, sim
 
 
@@ -1258,7 +1300,7 @@ class HbvAdjPath(torch.autograd.Function):
         flux = _out((1, T, B), dev) if cfg.want_flux else None
         state_out = _out((5, B, M), dev)
         tap = getattr(_TAP, "records", None)    # inside record_paths(): the tangent needs the solved states too
-        traj = _out((5, T + 1, B * M), dev) if (needs_grad or tap is not None) else None
+        traj = _out((5, T + 1, B * M), dev) if (needs_grad or (tap is not None and _TAP.want_traj)) else None
         out.flux, out.state_out, out.traj, out.n_flux = _ptr(flux), _ptr(state_out), _ptr(traj), 1
         if state_in is not None:
             state_in = state_in.contiguous()

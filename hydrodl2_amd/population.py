@@ -12,7 +12,7 @@ registers and writes [P,B] costs -- no flux series, no trajectory, no [P,B,ny] c
 log flow (hbvx_population_stats), from which `population_score` forms NSE, KGE, correlation, variability and bias in
 float64 -- so a search can run in the metric its result is reported in.
 
-Hbv, Hbv_1_1p and Hbv_2 only; the series scored is 'streamflow'.
+Hbv, Hbv_1_1p and Hbv_2 only; the series scored is 'streamflow'.  HbvAdj has the same three calls in adj_population.py.
 """
 from __future__ import annotations
 
@@ -33,7 +33,9 @@ def _check(model, x_dict, parameters, target, names, weights, what):
     'streamflow', and what this path adds to them."""
     if getattr(model, '_model_id', None) == _abi.MODEL_HBVADJ:
         raise NotImplementedError(f"{what} is not implemented for {type(model).__name__}: the implicit scheme needs its "
-                                  "Newton solve inside the day loop, which is not this kernel; Hbv, Hbv_1_1p and Hbv_2 only")
+                                  "Newton solve inside the day loop, which is not this kernel; Hbv, Hbv_1_1p and Hbv_2 only "
+                                  "-- HbvAdj goes through hydrodl2_amd.adj_population_cost / adj_population_stats / "
+                                  "adj_population_search")
     req = _check_request(model, x_dict, parameters, target, names, 'streamflow', weights, 1, what=what)
     if model.comprout:
         raise ValueError(f"{what}: comprout=True routes every member, not the ensemble mean; not supported")
@@ -340,16 +342,7 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
     `population_stats` call: the quantity minimised, and what history['cost'] holds, is then 1 - score (the squared error
     of the transformed flow for 'sse'), +inf where `population_score` gives NaN, and history['score'] [n_rounds+1,B]
     holds the score itself ('nse', 'kge', 'kge12' only).  A basin whose observations admit no score keeps its row."""
-    if float(getattr(model, 'dy_drop', 0.0)) > 0:
-        raise ValueError("population_search: dy_drop > 0 draws new masks in every run, the cost is stochastic; set dy_drop = 0")
-    if n_candidates < 2:
-        raise ValueError("n_candidates must be >= 2 (the current row and at least one draw)")
-    if n_rounds < 1:
-        raise ValueError("n_rounds must be >= 1")
-    if not 0 < shrink <= 1:
-        raise ValueError("population_search wants 0 < shrink <= 1")
-    if objective not in OBJECTIVES:
-        raise ValueError(f"population_search: objective must be one of {list(OBJECTIVES)}, got {objective!r}")
+    _check_search(model, n_candidates, n_rounds, shrink, objective, "population_search")
     req = _check(model, x_dict, parameters, target, names, weights, "population_search")
     by_stats = objective != 'sse' or transform != 'none'
     if by_stats:
@@ -364,8 +357,28 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
         score = population_score(st, objective)
         return _objective_cost(score, objective), score
 
+    return _search(req, x_dict, parameters, evaluate, req.tname != 'p_sta', n_candidates, n_rounds, shrink, generator,
+                   objective != 'sse')
+
+
+def _check_search(model, n_candidates, n_rounds, shrink, objective, what):
+    """The search's own refusals, before anything else."""
+    if float(getattr(model, 'dy_drop', 0.0)) > 0:
+        raise ValueError(f"{what}: dy_drop > 0 draws new masks in every run, the cost is stochastic; set dy_drop = 0")
+    if n_candidates < 2:
+        raise ValueError("n_candidates must be >= 2 (the current row and at least one draw)")
+    if n_rounds < 1:
+        raise ValueError("n_rounds must be >= 1")
+    if not 0 < shrink <= 1:
+        raise ValueError(f"{what} wants 0 < shrink <= 1")
+    if objective not in OBJECTIVES:
+        raise ValueError(f"{what}: objective must be one of {list(OBJECTIVES)}, got {objective!r}")
+
+
+def _search(req, x_dict, parameters, evaluate, raw, n_candidates, n_rounds, shrink, generator, keep_score):
+    """The search loop of `population_search` and `adj_population_search`: `evaluate(cands)` -> (cost, score or None)
+    [P,B] is the front end's route to one round's numbers; raw: the module applies a sigmoid to the row."""
     two = req.tname == 'p_sta'
-    raw = not two
     cur = _static_tensor(two, parameters).detach().clone()
     row = cur if two else cur[-1]           # [B,width] view of the row that moves
     dev = x_dict['x_phy'].device
@@ -376,7 +389,6 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
     best = row[:, cols].to(device=dev, dtype=torch.float32)                     # [B,C], input space
     best_u = torch.sigmoid(best) if raw else best.clone()
     hist = {'cost': [], 'best_index': [], 'columns': list(req.cols)}
-    keep_score = objective != 'sse'
     if keep_score:
         hist['score'] = []
     for k in range(n_rounds):

@@ -594,6 +594,31 @@ typedef struct hbvx_pop_stats {
 } hbvx_pop_stats;                  /* hbvx_sizeof(11) */
 int hbvx_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void *stream);
 
+/* Population evaluation of the implicit scheme (optional exports; a library may lack them): hbvx_population_cost and
+ * hbvx_population_stats for HBVX_MODEL_HBVADJ, on the same structs.  For every candidate c and basin b the day loop of
+ * hbvx_adj_forward's one-wave kernel runs on `d` -- per lane and day the system G(x) = 0 is solved in registers by the
+ * day function d->adj_stop selects (2: the staged solve; 0: the joint Newton iteration with the per-lane stopping
+ * rule), under d->adj_gtol / d->adj_max_iter -- with the candidate's static values in place of d->p[i].sta wherever
+ * pop->p[i].sta is set.  Dynamic parameters, the drop masks (per LANE in this model: drop[b*M + j]), state_in (NULL:
+ * zeros) and the forcings are the descriptor's, shared by all candidates.  Per day
+ *   Q = (q0 + q1) + q2 at the solved state,   q = sum over the members of Q (xor butterfly) * (1 / M),
+ * and from there on everything is hbvx_population_cost's / hbvx_population_stats' text above: the gamma unit hydrograph
+ * of (c, b), the causal 15-day window, t_first, the residual chain cost = fmaf(w * r, r, cost), the transform and the
+ * three moment chains, `sim`.  csrc/hbv_adj_pop.h has the kernel.
+ * Guarantees: (1) two calls on the same inputs give the same bits; (2) the bits of cost[c,b], s1..s3[c,b] and
+ * sim[c,:,b] do not depend on n_cand or on the other candidates; (3) sim == NULL changes no bit; (4) under
+ * HBVX_POP_T_NONE pop.cost of hbvx_adj_population_stats has the bits hbvx_adj_population_cost gives, and `sim` has
+ * them under every transform; (5) argument errors are reported before anything is launched.
+ * Errors: those of hbvx_population_cost / hbvx_population_stats, except that the model must be HBVX_MODEL_HBVADJ
+ * (else HBVX_E_UNSUPPORTED), and: HBVX_E_SHAPE (adj_gtol < 0 or NaN, adj_max_iter outside 0..64, adj_stop outside
+ * 0..2), HBVX_E_UNSUPPORTED (adj_stop == 1: the batch-wide stopping rule votes over the 64 lanes of a wave, and a
+ * candidate's cost must not depend on which basins share its wave; a non-NULL d->muwts: the implicit scheme has no
+ * ensemble weights).
+ * Bit equality with hbvx_adj_forward + hbvx_route_forward is not promised: the forward may be taken by another kernel
+ * family (the tiled stepper, the staged pipeline). */
+int hbvx_adj_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream);
+int hbvx_adj_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void *stream);
+
 /* Zero `bytes` bytes at `ptr` (streaming non-temporal stores).  The autograd contract of the plug-in wants
  * gradient tensors shaped like the raw parameter tensor [T,B,ny] (hbv.py:211-246: static parameters read
  * one row of it), so the dense zero fill is part of every backward step. */
