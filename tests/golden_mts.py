@@ -1,5 +1,7 @@
 """Multi-timescale golden cases (Hbv_2_mts): inputs, configs and the runner shared by
-tests/golden/make_golden_mts.py (reference side) and tests/test_mts.py (this package)."""
+tests/golden/make_golden_mts.py (reference side), tests/test_mts.py (this package) and the
+float64 problem set tests/mts_sets.py.  Every function takes a case name or a spec dict of the
+same keys."""
 from __future__ import annotations
 
 import numpy as np
@@ -8,8 +10,12 @@ import torch
 from . import synth
 
 DYN = ["parBETA", "parK0", "parBETAET"]
+DYN_HIGH_F4 = ["parF0", "parALPHA", "parFMIN", "parBETA"]
 M = 4
 N_LOW, N_HIGH = 16, 19
+# the wet recipe: a spring start (day 60), daily precipitation x 4, then hourly storm forcing that continues the
+# calendar; the daily model starts from its default storages, so the wetness of the hand-off comes from the forcing
+WET = dict(day0=60.0, prcp_scale=4.0, storm=6.0)
 
 CASES = {
     # all units fit one block, training mode: only the unit runoff 'Qs' is produced
@@ -22,28 +28,54 @@ CASES = {
     "mts_chunked": dict(T_low=30, T_high=120, B=7, G=3, seed=42, simulate=True,
                         chunks=dict(train_spatial_chunk_size=16, simulate_spatial_chunk_size=3,
                                     simulate_temporal_chunk_size=40, train_warmup=24)),
+    # a wet record with DIFFERING dynamic lists on the daily and the hourly side: the positional hand-off
+    # (hbv_2_mts.py:310-331) is no longer "daily block, then the tail of the hourly block"
+    "mts_wet_lists": dict(T_low=150, T_high=130, B=7, G=3, seed=43, simulate=False, wet=WET,
+                          low_dyn=DYN, high_dyn=DYN_HIGH_F4,
+                          chunks=dict(train_spatial_chunk_size=16, simulate_spatial_chunk_size=3,
+                                      simulate_temporal_chunk_size=40, train_warmup=24)),
 }
 
 
-def configs(name: str):
-    spec = CASES[name]
-    low = {"nmul": M, "dynamic_params": {"Hbv_2": list(DYN)}, "cache_states": True}
-    high = {"nmul": M, "dynamic_params": {"Hbv_2_hourly": list(DYN)}}
+def spec_of(case) -> dict:
+    return CASES[case] if isinstance(case, str) else case
+
+
+def dyn_lists(case):
+    """(daily, hourly) dynamic-parameter lists of a case, in config order."""
+    spec = spec_of(case)
+    return list(spec.get("low_dyn", DYN)), list(spec.get("high_dyn", DYN))
+
+
+def configs(case):
+    spec = spec_of(case)
+    m = spec.get("M", M)
+    dl, dh = dyn_lists(spec)
+    low = {"nmul": m, "dynamic_params": {"Hbv_2": dl}, "cache_states": True}
+    high = {"nmul": m, "dynamic_params": {"Hbv_2_hourly": dh}}
     high.update(spec["chunks"])
     return low, high
 
 
-def build_inputs(name: str) -> dict:
-    spec = CASES[name]
+def build_inputs(case) -> dict:
+    spec = spec_of(case)
     Tl, Th, B, G, seed = spec["T_low"], spec["T_high"], spec["B"], spec["G"], spec["seed"]
+    m = spec.get("M", M)
+    dl, dh = dyn_lists(spec)
     out = {}
-    out["x_low"] = synth.forcing(Tl, B, seed)
-    out["x_high"] = (synth.forcing(Th, B, seed + 1000)
-                     * np.array([1.0 / 8.0, 1.0, 1.0 / 24.0], np.float32))
-    out["low_dyn"] = synth.unit_parameters((Tl, B, len(DYN) * M), seed, 4)
-    out["low_sta"] = synth.unit_parameters((B, (N_LOW - len(DYN)) * M), seed, 6)
-    out["high_dyn"] = synth.unit_parameters((Th, B, len(DYN) * M), seed, 16)
-    out["high_sta"] = synth.unit_parameters((B, (N_HIGH - len(DYN)) * M), seed, 17)
+    wet = spec.get("wet")
+    if wet:
+        out["x_low"] = (synth.forcing(Tl, B, seed, day0=wet["day0"])
+                        * np.array([wet["prcp_scale"], 1.0, 1.0], np.float32))
+        out["x_high"] = synth.forcing_hourly(Th, B, seed + 1000, storm=wet["storm"], day0=wet["day0"] + Tl)
+    else:
+        out["x_low"] = synth.forcing(Tl, B, seed)
+        out["x_high"] = (synth.forcing(Th, B, seed + 1000)
+                         * np.array([1.0 / 8.0, 1.0, 1.0 / 24.0], np.float32))
+    out["low_dyn"] = synth.unit_parameters((Tl, B, len(dl) * m), seed, 4)
+    out["low_sta"] = synth.unit_parameters((B, (N_LOW - len(dl)) * m), seed, 6)
+    out["high_dyn"] = synth.unit_parameters((Th, B, len(dh) * m), seed, 16)
+    out["high_sta"] = synth.unit_parameters((B, (N_HIGH - len(dh)) * m), seed, 17)
     out["ac_all"] = (synth.uniform((B,), seed, 7) * np.float32(5000.0)).astype(np.float32)
     out["elev_all"] = (synth.uniform((B,), seed, 8) * np.float32(3000.0)).astype(np.float32)
     topo = (synth.uniform((G, B), seed, 13) < np.float32(0.45)).astype(np.float32)
@@ -57,10 +89,11 @@ def build_inputs(name: str) -> dict:
 LEAVES = ["low_dyn", "low_sta", "high_dyn", "high_sta", "p_distr"]
 
 
-def run(model, name: str, dev) -> dict:
-    """Forward + backward of case `name` through `model` (reference or this package)."""
-    spec = CASES[name]
-    inp = build_inputs(name)
+def run(model, case, dev) -> dict:
+    """Forward + backward of a case through `model` (reference or this package) with the inputs on `dev` (the
+    model may compute elsewhere: the loss is formed where the outputs are)."""
+    spec = spec_of(case)
+    inp = build_inputs(spec)
     t = {k: torch.from_numpy(v).to(dev) for k, v in inp.items()}
     for k in LEAVES:
         t[k].requires_grad_(True)
@@ -72,10 +105,11 @@ def run(model, name: str, dev) -> dict:
     res = {f"out/{k}": v.detach().cpu().numpy().copy() for k, v in out.items()}
     loss = 0.0
     for i, (k, v) in enumerate(sorted(out.items())):
-        w = torch.from_numpy(synth.loss_weights(tuple(v.shape), spec["seed"], 50 + i)).to(dev)
+        w = torch.from_numpy(synth.loss_weights(tuple(v.shape), spec["seed"], 50 + i)).to(v.device)
         loss = loss + (w * v).sum()
     loss.backward()
     for k in LEAVES:
         g = t[k].grad if t[k].grad is not None else torch.zeros_like(t[k])
+        assert g.device == t[k].device, (k, g.device, t[k].device)
         res[f"grad/{k}"] = g.detach().cpu().numpy().copy()
     return res
