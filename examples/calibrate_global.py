@@ -11,12 +11,19 @@ wide).  Two routes from that start, both per basin:
 
     python examples/calibrate_global.py [--basins 32] [--days 730] [--nmul 4] [--candidates 256] [--rounds 3] [--lm-iters 8]
                                         [--objective sse|nse|kge|kge12] [--transform none|sqrt|log] [--model Hbv|HbvAdj]
+                                        [--aux-key AET_hydro|SWE|srflow_no_rout|ssflow_no_rout|gwflow_no_rout] [--aux-share 0.5]
 
 --model HbvAdj runs the same experiment on the implicit scheme: adj_population_search (hbvx_adj_population_cost: every
 candidate's days solved in registers) in front of calibrate, scored on 'flow_sim', from the module's own start (empty
 storages); the routing parameters are then 'rout_a' and 'rout_b'.
 --objective / --transform choose what the search minimises (hbvx_population_stats: NSE, KGE on the raw, square-root or
 log flow); Levenberg-Marquardt after it is least squares on the raw flow either way.
+--aux-key (Hbv, with --objective nse / kge / kge12) makes the twin problem also observe the hidden row's series of that
+key every 8th day, and adds a third route: the search on (1 - share) * flow cost + share * (1 - NSE of the aux series)
+(hbvx_population_joint: both scores of every candidate from one launch) in front of the same Levenberg-Marquardt.  The
+line then carries, for the search with and without the aux term, the basin means of the flow and the aux scores at the
+start and at the search's pick, and the distance of the picked row from the hidden one in unit space (the root mean
+square over the searched columns of sigmoid(raw) differences, mean over the basins).
 Prints one JSON line: per route the summed cost and the number of basins in which it ended lower, with the cost of
 the start and of the search's pick beside them, and -- whichever objective was searched -- the basin means of SSE, NSE
 and KGE on the raw flow at the start and at the end of every route.  Synthetic forcings (tests/synth.py), a fixed seed.
@@ -50,7 +57,12 @@ def main():
     ap.add_argument("--names", default=None,
                     help="default: parBETA,parFC,parK0,parK1,parK2,parLP,parPERC,parUZL and the two routing parameters")
     ap.add_argument("--model", default="Hbv", choices=["Hbv", "HbvAdj"])
+    ap.add_argument("--aux-key", default=None, choices=["AET_hydro", "SWE", "srflow_no_rout", "ssflow_no_rout", "gwflow_no_rout"],
+                    help="also observe this series of the hidden row every 8th day and search on both scores")
+    ap.add_argument("--aux-share", type=float, default=0.5, help="the aux term's share of the searched cost")
     args = ap.parse_args()
+    if args.aux_key and (args.model != "Hbv" or args.objective == "sse"):
+        ap.error("--aux-key goes with --model Hbv and --objective nse, kge or kge12")
     assert torch.cuda.is_available(), "the example runs on the GPU; there is no CPU fallback"
     dev = torch.device("cuda:0")
     T, B, M = args.days, args.basins, args.nmul
@@ -68,7 +80,8 @@ def main():
     ny = model.learnable_param_count
     truth = torch.from_numpy(synth.raw_parameters(T, B, ny, seed=72)).to(dev)
     with torch.no_grad():
-        obs = model(x, truth)[key][..., 0].clone()
+        hidden = model(x, truth)
+    obs = hidden[key][..., 0].clone()
     # the poor start: the named columns of the static row drawn anew, three times as wide; everything else is the truth's
     _, cols = hydrodl2_amd.sensitivity.jacobian_columns(model, names)
     start = truth.clone()
@@ -87,6 +100,40 @@ def main():
         st = stats(model, x, row, cand, obs, names=names)
         return {m: float(hydrodl2_amd.population_score(st, m).mean()) for m in ("sse", "nse", "kge")}
 
+    joint = {}
+    if args.aux_key:
+        aux_obs = torch.full_like(obs, float("nan"))
+        aux_obs[::8] = hidden[args.aux_key][..., 0][::8]
+        picked_aux, h_aux = search(model, x, start, obs, names=names, n_candidates=args.candidates, n_rounds=args.rounds,
+                                   generator=torch.Generator().manual_seed(74), objective=args.objective,
+                                   transform=args.transform, aux_target=aux_obs, aux_key=args.aux_key,
+                                   aux_share=args.aux_share)
+        both_aux, h_both_aux = hydrodl2_amd.calibrate(model, x, picked_aux, obs, names=names, n_iter=args.lm_iters)
+
+        def both_scores(row):
+            cand = row[-1][:, cols].unsqueeze(0).contiguous()
+            st = hydrodl2_amd.population_joint_stats(model, x, row, cand, obs, aux_obs, args.aux_key, names=names)
+            return {f"{term}_{m}": float(hydrodl2_amd.population_score(st[term], m).nanmean())
+                    for term in ("flow", "aux") for m in ("nse", "kge")}
+
+        def distance(row):
+            d = torch.sigmoid(row[-1][:, cols]) - torch.sigmoid(truth[-1][:, cols])
+            return float(d.pow(2).mean(1).sqrt().mean())
+
+        joint = {
+            "aux_key": args.aux_key, "aux_share": args.aux_share, "aux_days_observed": int((~torch.isnan(aux_obs[:, 0])).sum()),
+            "both_scores_start": both_scores(start),
+            "both_scores_after_search_flow_only": both_scores(picked),
+            "both_scores_after_search_with_aux": both_scores(picked_aux),
+            "unit_distance_to_hidden_row": {"start": distance(start), "search_flow_only": distance(picked),
+                                            "search_with_aux": distance(picked_aux),
+                                            "search_flow_only_then_calibrate": distance(both),
+                                            "search_with_aux_then_calibrate": distance(both_aux)},
+            "mean_scores_search_with_aux_then_calibrate": worth(both_aux),
+            "cost_search_with_aux_then_calibrate": float(h_both_aux["cost"][-1].sum()),
+            "search_with_aux_history_mean": {k: [float(v) for v in h_aux[k].nanmean(1)] for k in ("cost", "score", "score_aux")},
+        }
+
     c_start, c_lm = h_lm["cost"][0], h_lm["cost"][-1]
     c_pick, c_both = h_both["cost"][0], h_both["cost"][-1]
     print(json.dumps({
@@ -103,6 +150,7 @@ def main():
         "basins_where_search_then_calibrate_ends_lower": int((c_both < c_lm).sum()),
         "basins_where_calibrate_alone_ends_lower": int((c_lm < c_both).sum()),
         "population_search_history_summed": [float(v) for v in h_ps["cost"].sum(1)],
+        **joint,
     }))
 
 

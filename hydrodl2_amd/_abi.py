@@ -140,6 +140,17 @@ class PopStats(C.Structure):
                 ("s1", _fp), ("s2", _fp), ("s3", _fp)]
 
 
+# the series hbvx_population_joint can score beside streamflow: enum hbvx_flux indices of the module's output keys
+POP_AUX_SERIES = {"srflow_no_rout": 1, "ssflow_no_rout": 2, "gwflow_no_rout": 3, "AET_hydro": 4, "SWE": 5}
+
+
+class PopJoint(C.Structure):
+    """hbvx_pop_joint: hbvx_pop_stats for the flow term, and the aux term -- which flux, its target / weights / shift and
+    its four sums, optionally its series (include/hbvx.h)."""
+    _fields_ = [("flow", PopStats), ("aux_series", C.c_int32), ("aux_target", _fp), ("aux_w", _fp), ("aux_shift", _fp),
+                ("aux_sse", _fp), ("aux_s1", _fp), ("aux_s2", _fp), ("aux_s3", _fp), ("aux_sim", _fp)]
+
+
 class LstmDesc(C.Structure):
     """include/hbvx_lstm.h"""
     _fields_ = [("abi_version", C.c_int32), ("T", C.c_int32), ("B", C.c_int32), ("H", C.c_int32)]
@@ -164,7 +175,7 @@ OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forwa
                     "hbvx_gage_route_tangent_workspace_bytes", "hbvx_adj_tangent_batch", "hbvx_gram",
                     "hbvx_gram_workspace_bytes", "hbvx_quadform", "hbvx_quadform_workspace_bytes",
                     "hbvx_population_cost", "hbvx_population_stats",
-                    "hbvx_adj_population_cost", "hbvx_adj_population_stats"]
+                    "hbvx_adj_population_cost", "hbvx_adj_population_stats", "hbvx_population_joint"]
 
 
 class HbvxError(RuntimeError):
@@ -335,6 +346,11 @@ class Library:
             d.hbvx_adj_population_stats.argtypes = [C.POINTER(Desc), C.POINTER(PopStats), C.c_void_p]
             if d.hbvx_sizeof(11) != C.sizeof(PopStats):
                 raise HbvxError(f"{path}: layout mismatch for PopStats: {d.hbvx_sizeof(11)} != {C.sizeof(PopStats)}")
+        if "hbvx_population_joint" not in self.missing:
+            d.hbvx_population_joint.restype = C.c_int
+            d.hbvx_population_joint.argtypes = [C.POINTER(Desc), C.POINTER(PopJoint), C.c_void_p]
+            if d.hbvx_sizeof(12) != C.sizeof(PopJoint):
+                raise HbvxError(f"{path}: layout mismatch for PopJoint: {d.hbvx_sizeof(12)} != {C.sizeof(PopJoint)}")
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -531,6 +547,13 @@ class Library:
         self._check(self.dll.hbvx_population_stats(None if desc is None else C.byref(desc),
                                                    None if ps is None else C.byref(ps), C.c_void_p(stream)),
                     "hbvx_population_stats")
+
+    def population_joint(self, desc, pj, stream: int):
+        """hbvx_population_joint; `desc` / `pj` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_population_joint")
+        self._check(self.dll.hbvx_population_joint(None if desc is None else C.byref(desc),
+                                                   None if pj is None else C.byref(pj), stream),
+                    "hbvx_population_joint")
 
     def adj_population_cost(self, desc, pop, stream: int):
         """hbvx_adj_population_cost; `desc` / `pop` may be None (the ABI's own refusals are under test)."""

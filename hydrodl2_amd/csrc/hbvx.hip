@@ -70,6 +70,7 @@ extern "C" uint64_t hbvx_sizeof(int which)
     case 9: return sizeof(hbvx_gram_desc);
     case 10: return sizeof(hbvx_pop);
     case 11: return sizeof(hbvx_pop_stats);
+    case 12: return sizeof(hbvx_pop_joint);
     default: return 0;
     }
 }

@@ -1,5 +1,5 @@
-// launch_pop.hip -- the entry points of the population evaluation: hbvx_population_cost and hbvx_population_stats
-// (hbv_pop.h), and their twins for the implicit scheme, hbvx_adj_population_cost and hbvx_adj_population_stats
+// launch_pop.hip -- the entry points of the population evaluation: hbvx_population_cost, hbvx_population_stats and
+// hbvx_population_joint (hbv_pop.h), and the first two's twins for the implicit scheme, hbvx_adj_population_cost and hbvx_adj_population_stats
 // (hbv_adj_pop.h).
 #include "hbvx_host.h"
 #include "hbv_pop.h"
@@ -128,6 +128,54 @@ extern "C" int hbvx_population_stats(const hbvx_desc *d, const hbvx_pop_stats *p
     });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "hbvx_population_stats launch");
+    return HBVX_OK;
+}
+
+extern "C" int hbvx_population_joint(const hbvx_desc *d, const hbvx_pop_joint *pj, void *stream)
+{
+    const char *who = "hbvx_population_joint";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!pj) return fail_as(who, HBVX_E_NULL, "pj is NULL");
+    PopJointArgs j;
+    rc = prepare(who, d, &pj->flow.pop, j.s.a);
+    if (rc) return rc;
+    rc = prepare_stats(who, &pj->flow, j.s);
+    if (rc) return rc;
+    switch (pj->aux_series) {
+    case HBVX_F_Q0: case HBVX_F_Q1: case HBVX_F_Q2: case HBVX_F_AET: case HBVX_F_SWE: break;
+    default: return fail_as(who, HBVX_E_UNSUPPORTED, "aux_series must be HBVX_F_Q0, _Q1, _Q2, _AET or _SWE");
+    }
+    if (!pj->aux_target) return fail_as(who, HBVX_E_NULL, "aux_target is NULL");
+    if (!pj->aux_shift) return fail_as(who, HBVX_E_NULL, "aux_shift is NULL");
+    if (!pj->aux_sse || !pj->aux_s1 || !pj->aux_s2 || !pj->aux_s3)
+        return fail_as(who, HBVX_E_NULL, "aux_sse / aux_s1 / aux_s2 / aux_s3 is NULL");
+    j.aux_series = pj->aux_series;
+    j.aux_target = pj->aux_target;
+    j.aux_w = pj->aux_w;
+    j.aux_shift = pj->aux_shift;
+    j.aux_sse = pj->aux_sse;
+    j.aux_s1 = pj->aux_s1;
+    j.aux_s2 = pj->aux_s2;
+    j.aux_s3 = pj->aux_s3;
+    j.aux_sim = pj->aux_sim;
+    const dim3 grid = pop_grid(j.s.a);
+    with_model(d, [&](auto m, auto be) {
+        if constexpr (m != MODEL_HOURLY) {
+            switch (pj->flow.transform) {
+            case HBVX_POP_T_SQRT:
+                hipLaunchKernelGGL((k_pop_joint<m, be, hbvx_popk::T_SQRT>), grid, dim3(64), 0, (hipStream_t)stream, j);
+                break;
+            case HBVX_POP_T_LOG:
+                hipLaunchKernelGGL((k_pop_joint<m, be, hbvx_popk::T_LOG>), grid, dim3(64), 0, (hipStream_t)stream, j);
+                break;
+            default:
+                hipLaunchKernelGGL((k_pop_joint<m, be, hbvx_popk::T_NONE>), grid, dim3(64), 0, (hipStream_t)stream, j);
+            }
+        }
+    });
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "hbvx_population_joint launch");
     return HBVX_OK;
 }
 

@@ -1085,7 +1085,7 @@ def population_cost(rec: PathRecord, cand_sources: dict, route_cands, target: to
                   Ignored when the recorded call does not route.
     target, w     [T_out,B] float32; w may be None (ones).  The kernel multiplies what it is given: the caller masks.
     More than POP_MAX_CAND candidates go in several launches; a candidate's bits do not depend on the split."""
-    cost, _, sim = _population("population_cost", "hbvx_population_cost", lambda lib: lib.population_cost, rec,
+    cost, _, sim, _ = _population("population_cost", "hbvx_population_cost", lambda lib: lib.population_cost, rec,
                                cand_sources, route_cands, target, w, t_first, want_sim, None)
     return cost, sim
 
@@ -1104,10 +1104,37 @@ def population_stats(rec: PathRecord, cand_sources: dict, route_cands, target_t:
         raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
     if transform == "log" and eps is None:
         raise ValueError("population_stats: transform 'log' needs eps")
-    sse, moments, sim = _population("population_stats", "hbvx_population_stats", lambda lib: lib.population_stats, rec,
+    sse, moments, sim, _ = _population("population_stats", "hbvx_population_stats", lambda lib: lib.population_stats, rec,
                                     cand_sources, route_cands, target_t, w, t_first, want_sim,
                                     (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None))
     return (sse,) + moments + (sim,)
+
+
+def population_joint(rec: PathRecord, cand_sources: dict, route_cands, target_t: torch.Tensor, w: Optional[torch.Tensor],
+                     shift: torch.Tensor, eps: Optional[torch.Tensor], transform: str, aux_series: int,
+                     aux_target: torch.Tensor, aux_w: Optional[torch.Tensor], aux_shift: torch.Tensor, t_first: int = 0,
+                     want_sim: bool = False):
+    """`population_stats` with a second observed series scored in the same launch, through hbvx_population_joint
+    (include/hbvx.h): ((sse, s1, s2, s3, sim), (aux_sse, aux_s1, aux_s2, aux_s3, aux_sim)) -- the flow term with the bits
+    `population_stats` gives, the aux term the same four chains on the un-routed, un-transformed ensemble mean of flux
+    `aux_series` (an hbvx_flux index among _abi.POP_AUX_SERIES' values).
+
+    aux_target, aux_w  [T_out,B] float32, aux_w may be None (ones); aux_shift [B] float32.  want_sim asks for both series.
+    Everything else as `population_stats`: the same checks, the same split above POP_MAX_CAND."""
+    if transform not in _abi.POP_TRANSFORMS:
+        raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
+    if transform == "log" and eps is None:
+        raise ValueError("population_joint: transform 'log' needs eps")
+    if aux_series not in _abi.POP_AUX_SERIES.values():
+        raise ValueError(f"population_joint: aux_series must be one of {sorted(_abi.POP_AUX_SERIES.values())} "
+                         f"(hbvx_flux indices), got {aux_series!r}")
+    if aux_target is None or aux_shift is None:
+        raise ValueError("population_joint needs aux_target and aux_shift")
+    sse, moments, sim, aux = _population("population_joint", "hbvx_population_joint", lambda lib: lib.population_joint,
+                                         rec, cand_sources, route_cands, target_t, w, t_first, want_sim,
+                                         (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None),
+                                         (aux_series, aux_target, aux_w, aux_shift))
+    return (sse,) + moments + (sim,), aux
 
 
 def _require_adj_record(what: str, rec: PathRecord) -> None:
@@ -1124,7 +1151,7 @@ def adj_population_cost(rec: PathRecord, cand_sources: dict, route_cands, target
     """`population_cost` for a recorded call of HbvAdjPath, through hbvx_adj_population_cost (include/hbvx.h): every
     candidate's days are solved in registers under the record's Newton policy.  Same arguments, same results."""
     _require_adj_record("adj_population_cost", rec)
-    cost, _, sim = _population("adj_population_cost", "hbvx_adj_population_cost", lambda lib: lib.adj_population_cost,
+    cost, _, sim, _ = _population("adj_population_cost", "hbvx_adj_population_cost", lambda lib: lib.adj_population_cost,
                                rec, cand_sources, route_cands, target, w, t_first, want_sim, None)
     return cost, sim
 
@@ -1138,18 +1165,19 @@ def adj_population_stats(rec: PathRecord, cand_sources: dict, route_cands, targe
     if transform == "log" and eps is None:
         raise ValueError("adj_population_stats: transform 'log' needs eps")
     _require_adj_record("adj_population_stats", rec)
-    sse, moments, sim = _population("adj_population_stats", "hbvx_adj_population_stats",
-                                    lambda lib: lib.adj_population_stats, rec, cand_sources, route_cands, target_t, w,
-                                    t_first, want_sim,
+    sse, moments, sim, _ = _population("adj_population_stats", "hbvx_adj_population_stats",
+                                       lambda lib: lib.adj_population_stats, rec, cand_sources, route_cands, target_t, w,
+                                       t_first, want_sim,
                                     (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None))
     return (sse,) + moments + (sim,)
 
 
 def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: dict, route_cands, target, w, t_first,
-                want_sim, stats):
-    """What the four population calls share -- stats None: the cost, stats = (transform id, shift, eps): the cost and the
-    moment chains; `entry` the export's name and `call_of(lib)` its Library method -- the checks, the descriptors, the
-    NaN-poisoned outputs and the launches.  -> (cost, (s1, s2, s3) or None, sim)."""
+                want_sim, stats, aux=None):
+    """What the five population calls share -- stats None: the cost, stats = (transform id, shift, eps): the cost and the
+    moment chains, aux = (flux index, target, w, shift) with stats: the aux term's four chains beside them; `entry` the
+    export's name and `call_of(lib)` its Library method -- the checks, the descriptors, the NaN-poisoned outputs and the
+    launches.  -> (cost, (s1, s2, s3) or None, sim, (aux_sse, aux_s1, aux_s2, aux_s3, aux_sim) or None)."""
     lib = get_library()
     lib.require(entry)
     call = call_of(lib)
@@ -1179,14 +1207,15 @@ def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: d
     for s in (route_cands or ()):
         if s is not None and not 0 <= s[1] < Cn:
             raise ValueError(f"routing candidate column {s[1]} outside the {Cn} columns")
-    for name, t in (("target", target), ("w", w)):
+    aux_series, aux_target, aux_w, aux_shift = aux if aux is not None else (None, None, None, None)
+    for name, t in (("target", target), ("w", w), ("aux_target", aux_target), ("aux_w", aux_w)):
         if t is None:
             continue
         _check_tensor(lib, t, name)
         if tuple(t.shape) != (T_out, B) or t.device != dev:
             raise ValueError(f"{name} must be [{T_out},{B}] on {dev}, got {tuple(t.shape)} on {t.device}")
     transform, shift, eps = stats if stats is not None else (None, None, None)
-    for name, t in (("shift", shift), ("eps", eps)):
+    for name, t in (("shift", shift), ("eps", eps), ("aux_shift", aux_shift)):
         if t is None:
             continue
         _check_tensor(lib, t, name)
@@ -1196,6 +1225,7 @@ def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: d
     wc = None if w is None else w.contiguous()
     shc = None if shift is None else shift.contiguous()
     epc = None if eps is None else eps.contiguous()
+    atc, awc, ashc = (None if t is None else t.contiguous() for t in (aux_target, aux_w, aux_shift))
     stream = _stream_of(lib, x)
     desc = _fill_desc(cfg, x, rec.state_in, rec.muwts, rec.ac, rec.elev, ptensors)
     route = _route_desc(cfg, ptensors, S=1) if cfg.route is not None else None
@@ -1203,8 +1233,12 @@ def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: d
         cost = _out((P, B), dev)
         moments = tuple(_out((P, B), dev) for _ in range(3)) if stats is not None else None
         sim = _out((P, T_out, B), dev) if want_sim else None
+        aux_out = None
+        if aux is not None:
+            aux_out = tuple(_out((P, B), dev) for _ in range(4)) + ((_out((P, T_out, B), dev) if want_sim else None),)
         for c0 in range(0, P, POP_MAX_CAND):
-            ps = _abi.PopStats() if stats is not None else None
+            pj = _abi.PopJoint() if aux is not None else None
+            ps = pj.flow if aux is not None else _abi.PopStats() if stats is not None else None
             pop = ps.pop if stats is not None else _abi.Pop()
             pop.n_cand, pop.t_first = min(POP_MAX_CAND, P - c0), t_first
             for slot, (_, col) in cand_sources.items():
@@ -1226,8 +1260,14 @@ def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: d
             else:
                 ps.transform, ps.shift, ps.eps = transform, _ptr(shc), _ptr(epc)
                 ps.s1, ps.s2, ps.s3 = (_ptr(m, c0 * B) for m in moments)
-                _call(lib, entry, call, desc, ps, stream)
-    return cost, moments, sim
+                if aux is None:
+                    _call(lib, entry, call, desc, ps, stream)
+                else:
+                    pj.aux_series, pj.aux_target, pj.aux_w, pj.aux_shift = aux_series, _ptr(atc), _ptr(awc), _ptr(ashc)
+                    pj.aux_sse, pj.aux_s1, pj.aux_s2, pj.aux_s3 = (_ptr(m, c0 * B) for m in aux_out[:4])
+                    pj.aux_sim = _ptr(aux_out[4], c0 * T_out * B)
+                    _call(lib, entry, call, desc, pj, stream)
+    return cost, moments, sim, aux_out
 
 
 class PathOut(NamedTuple):

@@ -11,8 +11,14 @@ registers and writes [P,B] costs -- no flux series, no trajectory, no [P,B,ny] c
 `population_stats` is the same launch with three more sums per (candidate, basin), on the raw, the square-root or the
 log flow (hbvx_population_stats), from which `population_score` forms NSE, KGE, correlation, variability and bias in
 float64 -- so a search can run in the metric its result is reported in.
+`population_joint_stats` is that launch with a second observed series beside streamflow -- evapotranspiration, snow-water
+equivalent or one of the three un-routed runoff components (hbvx_population_joint): eight [P,B] numbers, still no
+series -- and `population_search(aux_target=...)` minimises a weighted sum of the two scores.
 
-Hbv, Hbv_1_1p and Hbv_2 only; the series scored is 'streamflow'.  HbvAdj has the same three calls in adj_population.py.
+Hbv, Hbv_1_1p and Hbv_2 only.  HbvAdj has the first three calls in adj_population.py; the joint call is not built for
+it (its kernel is a separate family), nor for the hourly and multi-timescale models.  The aux series is not transformed,
+there is one per launch, it is compared day by day (no 8-day or monthly sums), and there is no joint `calibrate`: two
+`normal_equations` calls can be summed by the caller.
 """
 from __future__ import annotations
 
@@ -243,6 +249,85 @@ def population_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, 
     return _stats(model, req, x_dict, parameters, candidates, names, ob, transform, return_series)
 
 
+AUX_KEYS = tuple(_abi.POP_AUX_SERIES)       # 'srflow_no_rout', 'ssflow_no_rout', 'gwflow_no_rout', 'AET_hydro', 'SWE'
+
+
+def _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what):
+    """What can be refused about the aux term without running the model."""
+    if aux_target is None or aux_key is None:
+        raise ValueError(f"{what}: aux_target and aux_key go together "
+                         f"({'aux_target' if aux_target is None else 'aux_key'} is missing)")
+    if aux_key not in _abi.POP_AUX_SERIES:
+        raise ValueError(f"{what}: aux_key must be one of {list(AUX_KEYS)}, got {aux_key!r}")
+    dev = x_dict['x_phy'].device
+    for name, t, shapes in (("aux_target", aux_target, ((req.T_out, req.B), (req.T_out, req.B, 1))),
+                            ("aux_weights", aux_weights, ((req.T_out, req.B),))):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) not in shapes:
+            raise ValueError(f"{what}: {name} must be {' or '.join(str(list(s)) for s in shapes)} (the days after the "
+                             f"warm-up), got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{what}: {name} must be float32 or float64, got {t.dtype}")
+        if t.device != dev:
+            raise ValueError(f"{what}: {name} lives on {t.device}, x_phy on {dev}")
+    if bool(torch.isinf(aux_target).any()):
+        raise ValueError(f"{what}: aux_target holds infinities (a missing observation is a NaN)")
+    if aux_weights is not None:
+        if not bool(torch.isfinite(aux_weights).all()):
+            raise ValueError(f"{what}: aux_weights must be finite")
+        if bool((aux_weights < 0).any()):
+            raise ValueError(f"{what}: aux_weights must not be negative")
+
+
+def _joint(model, req, x_dict, parameters, candidates, names, ob, transform, aux_key, aux_ob, return_series):
+    outputs, main, t_first = _primal(model, req, x_dict, parameters)
+    sources, route = _candidate_sources(model, names, candidates)
+    flow, aux = ops.population_joint(main, sources, route, ob['target'], ob['w'], ob['shift'], ob['eps'], transform,
+                                     _abi.POP_AUX_SERIES[aux_key], aux_ob['target'], aux_ob['w'], aux_ob['shift'], t_first,
+                                     return_series)
+    out = {'columns': list(req.cols), 'outputs': outputs}
+    for name, got, o, tr in (('flow', flow, ob, transform), ('aux', aux, aux_ob, 'none')):
+        sub = dict(zip(('sse', 's1', 's2', 's3'), got[:4]))
+        sub.update(shift=o['shift'], obs=o['obs'], transform=tr, eps=o['eps'], n_obs=o['n_obs'], columns=list(req.cols),
+                   outputs=outputs)
+        if return_series:
+            sub['series'] = got[4]
+        out[name] = sub
+    out['aux']['key'] = aux_key
+    return out
+
+
+def population_joint_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, target, aux_target, aux_key: str,
+                           names: Optional[Sequence[str]] = None, weights=None, aux_weights=None,
+                           transform: str = 'none', eps=None, return_series: bool = False) -> dict:
+    """`population_stats` for streamflow and, from the same launch, the same four sums for a second observed series:
+    outputs[aux_key] with aux_key one of 'AET_hydro', 'SWE', 'srflow_no_rout', 'ssflow_no_rout', 'gwflow_no_rout' -- the
+    day's ensemble mean of that flux as the module returns it, never routed and never transformed.
+
+    candidates, target, names, weights, transform, eps: as `population_stats`; they shape the flow term only.
+    aux_target   [T_out,B] or [T_out,B,1], float32 or float64 on the device of x_phy; a NaN is a missing observation.
+                 Sparse records -- an 8-day product given as NaN on the other days -- are the normal case.
+    aux_weights  [T_out,B] >= 0 or None (ones).
+    Returns {'flow': what `population_stats` returns, bit for bit, 'aux': the same layout for the aux series (transform
+    'none', 'shift' the float32 weighted mean of aux_target, 'key': aux_key), 'columns', 'outputs'}; with return_series
+    each of the two carries its 'series' [P,T_out,B].  `population_score(result['flow'], m)` and
+    `population_score(result['aux'], m)` work as on `population_stats`' result.  include/hbvx.h states the aux chains
+    line by line; the guarantees are `population_stats`' for all eight numbers.
+
+    Refused before the model runs: everything `population_stats` refuses; an unknown aux_key; aux_key without aux_target
+    or the reverse; a wrong shape, dtype or device of aux_target / aux_weights, infinite aux targets, negative or
+    non-finite aux weights (ValueError); a library without hbvx_population_joint (HbvxError)."""
+    what = "population_joint_stats"
+    req = _check(model, x_dict, parameters, target, names, weights, what)
+    _check_candidates(req, x_dict, candidates)
+    _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what)
+    ob = _observations(req, x_dict, target, weights, transform, eps, what)
+    aux_ob = _observations(req, x_dict, aux_target, aux_weights, 'none', None, what)
+    get_library().require("hbvx_population_joint")
+    return _joint(model, req, x_dict, parameters, candidates, names, ob, transform, aux_key, aux_ob, return_series)
+
+
 def population_score(stats: dict, metric: str) -> torch.Tensor:
     """[P,B] float64 score of every candidate from what `population_stats` returned.  Weighted population moments in the
     transformed space, W = sum w:
@@ -322,7 +407,8 @@ def _to_input_space(u: torch.Tensor, raw: bool) -> torch.Tensor:
 def population_search(model, x_dict: dict, parameters, target, names: Optional[Sequence[str]] = None,
                       n_candidates: int = 256, n_rounds: int = 1, shrink: float = 0.5, weights=None,
                       generator: Optional[torch.Generator] = None, objective: str = 'sse', transform: str = 'none',
-                      eps=None):
+                      eps=None, aux_target=None, aux_key: Optional[str] = None, aux_weights=None,
+                      aux_objective: str = 'nse', aux_share: float = 0.5):
     """Per-basin shrinking random search over the static row, for a start that `calibrate` can refine.
 
     Round 0 evaluates the current row as candidate 0 and n_candidates - 1 uniform draws in the unit interval per
@@ -341,16 +427,42 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
     'kge12', or a transform 'sqrt' / 'log' (eps as `population_stats` takes it), makes every round one
     `population_stats` call: the quantity minimised, and what history['cost'] holds, is then 1 - score (the squared error
     of the transformed flow for 'sse'), +inf where `population_score` gives NaN, and history['score'] [n_rounds+1,B]
-    holds the score itself ('nse', 'kge', 'kge12' only).  A basin whose observations admit no score keeps its row."""
-    _check_search(model, n_candidates, n_rounds, shrink, objective, "population_search")
-    req = _check(model, x_dict, parameters, target, names, weights, "population_search")
-    by_stats = objective != 'sse' or transform != 'none'
+    holds the score itself ('nse', 'kge', 'kge12' only).  A basin whose observations admit no score keeps its row.
+
+    aux_target / aux_key (both or neither; aux_weights as `population_joint_stats` takes them) add a second observed
+    series: every round is then one `population_joint_stats` call, and the quantity minimised, and what history['cost']
+    holds, is (1 - aux_share) * cost_flow + aux_share * cost_aux, each term 1 - score (the squared error for 'sse') of
+    its own series under `objective` / `aux_objective`, +inf where either score is NaN; history['score'] (flow) and
+    history['score_aux'] hold the two scores (for 'sse' the squared error itself).  aux_share in [0, 1]; aux_objective
+    'sse' goes with objective 'sse' only -- a squared error and 1 - score are two scales in one sum.  Without aux_target
+    the function is the one above, bit for bit."""
+    what = "population_search"
+    _check_search(model, n_candidates, n_rounds, shrink, objective, what)
+    req = _check(model, x_dict, parameters, target, names, weights, what)
+    joint = aux_target is not None or aux_key is not None or aux_weights is not None
+    if joint:
+        _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what)
+        if aux_objective not in OBJECTIVES:
+            raise ValueError(f"{what}: aux_objective must be one of {list(OBJECTIVES)}, got {aux_objective!r}")
+        if not 0.0 <= float(aux_share) <= 1.0:          # (a NaN fails both comparisons)
+            raise ValueError(f"{what}: aux_share must lie in [0, 1], got {aux_share!r}")
+        if aux_objective == 'sse' and objective != 'sse':
+            raise ValueError(f"{what}: aux_objective 'sse' with objective {objective!r} would add a squared error to "
+                             "1 - score: two scales in one sum")
+    by_stats = joint or objective != 'sse' or transform != 'none'
     if by_stats:
-        ob = _observations(req, x_dict, target, weights, transform, eps, "population_search")
-        get_library().require("hbvx_population_stats")
+        ob = _observations(req, x_dict, target, weights, transform, eps, what)
+        if joint:
+            aux_ob = _observations(req, x_dict, aux_target, aux_weights, 'none', None, what)
+        get_library().require("hbvx_population_joint" if joint else "hbvx_population_stats")
 
     def evaluate(cands):
-        """(cost, score or None) [P,B] of one round's candidates."""
+        """(cost, score or None) [P,B] of one round's candidates; with the aux term the score is the pair."""
+        if joint:
+            st = _joint(model, req, x_dict, parameters, cands, names, ob, transform, aux_key, aux_ob, False)
+            score, score_aux = population_score(st['flow'], objective), population_score(st['aux'], aux_objective)
+            return _mixed_cost(_objective_cost(score, objective), _objective_cost(score_aux, aux_objective),
+                               float(aux_share)), (score, score_aux)
         if not by_stats:
             return population_cost(model, x_dict, parameters, cands, target, names, weights)['cost'], None
         st = _stats(model, req, x_dict, parameters, cands, names, ob, transform, False)
@@ -358,7 +470,15 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
         return _objective_cost(score, objective), score
 
     return _search(req, x_dict, parameters, evaluate, req.tname != 'p_sta', n_candidates, n_rounds, shrink, generator,
-                   objective != 'sse')
+                   joint or objective != 'sse', joint)
+
+
+def _mixed_cost(cost_flow: torch.Tensor, cost_aux: torch.Tensor, aux_share: float) -> torch.Tensor:
+    """(1 - aux_share) * cost_flow + aux_share * cost_aux, +inf where either is +inf (a share of 0 does not hide a
+    series that admits no score: 0 * inf would be NaN)."""
+    mixed = (1.0 - aux_share) * torch.where(torch.isinf(cost_flow), torch.zeros_like(cost_flow), cost_flow) \
+        + aux_share * torch.where(torch.isinf(cost_aux), torch.zeros_like(cost_aux), cost_aux)
+    return torch.where(torch.isinf(cost_flow) | torch.isinf(cost_aux), torch.full_like(mixed, float('inf')), mixed)
 
 
 def _check_search(model, n_candidates, n_rounds, shrink, objective, what):
@@ -375,9 +495,11 @@ def _check_search(model, n_candidates, n_rounds, shrink, objective, what):
         raise ValueError(f"{what}: objective must be one of {list(OBJECTIVES)}, got {objective!r}")
 
 
-def _search(req, x_dict, parameters, evaluate, raw, n_candidates, n_rounds, shrink, generator, keep_score):
+def _search(req, x_dict, parameters, evaluate, raw, n_candidates, n_rounds, shrink, generator, keep_score,
+            two_scores=False):
     """The search loop of `population_search` and `adj_population_search`: `evaluate(cands)` -> (cost, score or None)
-    [P,B] is the front end's route to one round's numbers; raw: the module applies a sigmoid to the row."""
+    [P,B] is the front end's route to one round's numbers; raw: the module applies a sigmoid to the row.  two_scores:
+    `evaluate` returns the pair (score, score_aux), kept as history['score'] and history['score_aux']."""
     two = req.tname == 'p_sta'
     cur = _static_tensor(two, parameters).detach().clone()
     row = cur if two else cur[-1]           # [B,width] view of the row that moves
@@ -391,28 +513,38 @@ def _search(req, x_dict, parameters, evaluate, raw, n_candidates, n_rounds, shri
     hist = {'cost': [], 'best_index': [], 'columns': list(req.cols)}
     if keep_score:
         hist['score'] = []
+    if two_scores:
+        hist['score_aux'] = []
     for k in range(n_rounds):
         draws = torch.rand((n_candidates - 1, req.B, C), generator=generator, device=gdev).to(dev)
         if k > 0:
             draws = best_u.unsqueeze(0) + (draws - 0.5) * float(shrink) ** k
         cands = torch.cat([best.unsqueeze(0), _to_input_space(draws, raw)]).contiguous()
         cost, score = evaluate(cands)
+        if two_scores:
+            score, score_aux = score
         low, idx = cost.min(0)
         idx = torch.where(cost[0] <= low, torch.zeros_like(idx), idx)          # a tie keeps the row that is held
         if k == 0:
             hist['cost'].append(cost[0].double().cpu())
             if keep_score:
                 hist['score'].append(score[0].cpu())
+            if two_scores:
+                hist['score_aux'].append(score_aux[0].cpu())
         pick = idx.view(1, req.B, 1).expand(1, req.B, C)
         best = cands.gather(0, pick)[0]
         best_u = torch.sigmoid(best) if raw else best.clone()
         hist['cost'].append(cost.gather(0, idx.unsqueeze(0))[0].double().cpu())
         if keep_score:
             hist['score'].append(score.gather(0, idx.unsqueeze(0))[0].cpu())
+        if two_scores:
+            hist['score_aux'].append(score_aux.gather(0, idx.unsqueeze(0))[0].cpu())
         hist['best_index'].append(idx.cpu())
     row[:, cols] = best.to(cur.device)
     hist['cost'] = torch.stack(hist['cost'])
     hist['best_index'] = torch.stack(hist['best_index'])
     if keep_score:
         hist['score'] = torch.stack(hist['score'])
+    if two_scores:
+        hist['score_aux'] = torch.stack(hist['score_aux'])
     return ((parameters[0], cur) if two else cur), hist

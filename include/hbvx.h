@@ -253,7 +253,7 @@ const char *hbvx_last_error(void);
 const char *hbvx_backend(void);         /* "hip:gfx950" or "cpu-oracle" */
 uint64_t hbvx_sizeof(int which);        /* 0 desc, 1 fwd_out, 2 bwd_io, 3 route_desc,
                                            4 param_src, 5 param_grad, 6 gage_desc, 7 tan_io, 8 tan_batch,
-                                           9 gram_desc, 10 pop, 11 pop_stats: layout check */
+                                           9 gram_desc, 10 pop, 11 pop_stats, 12 pop_joint: layout check */
 /* Diagnostic: the kernel family that took the process's last hbvx_forward (direction 0) / hbvx_backward (1) call --
  * "pipe", "stream2", "stream", "tiled", "simple", "chunked", "ckpt-block:<family>", "ckpt-lds"; "oracle" in the CPU
  * restatement.  The parity tests assert that the family they mean to pin against the reference is the one that ran. */
@@ -593,6 +593,41 @@ typedef struct hbvx_pop_stats {
     float *s1, *s2, *s3;           /* [P,B] each, overwritten completely */
 } hbvx_pop_stats;                  /* hbvx_sizeof(11) */
 int hbvx_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void *stream);
+
+/* Population scores for a second observed series beside streamflow (optional export; a library may lack it):
+ * hbvx_population_stats -- the flow term, `flow`, with exactly that call's meaning -- and in the same launch the same four
+ * sums of an aux term on one un-routed flux: evapotranspiration, snow-water equivalent or a runoff component.  The aux
+ * value of a day is what hbvx_forward writes for series `aux_series` of that day:
+ *   v = (sum over the members of x * act) * (1 / M),   x = Q0 | Q1 | Q2 | AET | SWE of the lane's day step
+ * (the plain ensemble mean: these series take 1 / M even when muwts is given), never routed and never transformed.  Per
+ * counted day (t >= flow.pop.t_first), days ascending, one chain each per (c, b), no atomics, every product written here
+ * rounded once:
+ *   r = v - o2      d = v - m2      e = o2 - m2           o2 = aux_target[t,b], m2 = aux_shift[b]
+ *   sse = fmaf(w * r, r, sse)                             -> aux_sse
+ *   s1  = fmaf(w,     d, s1)                              -> aux_s1
+ *   s2  = fmaf(w * d, d, s2)                              -> aux_s2
+ *   s3  = fmaf(w * d, e, s3)                              -> aux_s3      (w = aux_w[t,b], 1 when aux_w is NULL)
+ * aux_shift is meant to be the weighted mean of aux_target, as `shift` is of the flow target; masking is the caller's
+ * job here too (w = 0 does not neutralise a NaN in aux_target).  csrc/hbv_pop.h has the kernel and the arithmetic
+ * (hbvx_popk::AuxStats).
+ * Guarantees: (1) two calls on the same inputs give the same bits; (2) a candidate's eight numbers and both series do not
+ * depend on n_cand or on the other candidates; (3) flow.pop.sim == NULL or aux_sim == NULL changes no bit of anything
+ * else; (4) flow.pop.cost, flow.s1..s3 and flow.pop.sim have the bits hbvx_population_stats gives for the same candidate
+ * and transform; (5) argument errors are reported before anything is launched: hbvx_population_stats', and HBVX_E_NULL
+ * (pj, aux_target, aux_shift, aux_sse, aux_s1, aux_s2, aux_s3), HBVX_E_UNSUPPORTED (an aux_series other than
+ * HBVX_F_Q0, _Q1, _Q2, _AET, _SWE: HBVX_F_QSIM is the flow term, HBVX_F_RECHARGE .. HBVX_F_CAPILLARY are not offered).
+ * Not built: HBVX_MODEL_HBVADJ (its population kernel is a separate family) and HBVX_MODEL_HOURLY (HBVX_E_UNSUPPORTED),
+ * a transform of the aux value, more than one aux series per launch, sums over several days before the comparison. */
+typedef struct hbvx_pop_joint {
+    hbvx_pop_stats flow;           /* the flow term: hbvx_population_stats' argument, unchanged in meaning */
+    int32_t aux_series;            /* HBVX_F_Q0, HBVX_F_Q1, HBVX_F_Q2, HBVX_F_AET or HBVX_F_SWE */
+    const float *aux_target;       /* [T - t_first, B], required */
+    const float *aux_w;            /* [T - t_first, B] or NULL (= 1) */
+    const float *aux_shift;        /* [B], required */
+    float *aux_sse, *aux_s1, *aux_s2, *aux_s3;     /* [P,B] each, overwritten completely */
+    float *aux_sim;                /* optional [P, T - t_first, B]: each candidate's aux series */
+} hbvx_pop_joint;                  /* hbvx_sizeof(12) */
+int hbvx_population_joint(const hbvx_desc *d, const hbvx_pop_joint *pj, void *stream);
 
 /* Population evaluation of the implicit scheme (optional exports; a library may lack them): hbvx_population_cost and
  * hbvx_population_stats for HBVX_MODEL_HBVADJ, on the same structs.  For every candidate c and basin b the day loop of
