@@ -12,6 +12,7 @@ wide).  Two routes from that start, both per basin:
     python examples/calibrate_global.py [--basins 32] [--days 730] [--nmul 4] [--candidates 256] [--rounds 3] [--lm-iters 8]
                                         [--objective sse|nse|kge|kge12] [--transform none|sqrt|log] [--model Hbv|HbvAdj]
                                         [--aux-key AET_hydro|SWE|srflow_no_rout|ssflow_no_rout|gwflow_no_rout] [--aux-share 0.5]
+                                        [--aux-period N]
 
 --model HbvAdj runs the same experiment on the implicit scheme: adj_population_search (hbvx_adj_population_cost: every
 candidate's days solved in registers) in front of calibrate, scored on 'flow_sim', from the module's own start (empty
@@ -24,6 +25,9 @@ key every 8th day, and adds a third route: the search on (1 - share) * flow cost
 line then carries, for the search with and without the aux term, the basin means of the flow and the aux scores at the
 start and at the search's pick, and the distance of the picked row from the hidden one in unit space (the root mean
 square over the searched columns of sigmoid(raw) differences, mean over the basins).
+--aux-period N (with --aux-key) observes the aux series as what an N-day composite is: the MEANS of the hidden row's
+series over blocks of N days, compared with the candidates' means over the same blocks (hbvx_population_period), instead
+of one day's value in eight.  The flow stays daily.
 Prints one JSON line: per route the summed cost and the number of basins in which it ended lower, with the cost of
 the start and of the search's pick beside them, and -- whichever objective was searched -- the basin means of SSE, NSE
 and KGE on the raw flow at the start and at the end of every route.  Synthetic forcings (tests/synth.py), a fixed seed.
@@ -60,7 +64,11 @@ def main():
     ap.add_argument("--aux-key", default=None, choices=["AET_hydro", "SWE", "srflow_no_rout", "ssflow_no_rout", "gwflow_no_rout"],
                     help="also observe this series of the hidden row every 8th day and search on both scores")
     ap.add_argument("--aux-share", type=float, default=0.5, help="the aux term's share of the searched cost")
+    ap.add_argument("--aux-period", type=int, default=None,
+                    help="observe the aux series as N-day means of the hidden row instead of every 8th day")
     args = ap.parse_args()
+    if args.aux_period is not None and (not args.aux_key or args.aux_period < 1):
+        ap.error("--aux-period N >= 1 goes with --aux-key")
     if args.aux_key and (args.model != "Hbv" or args.objective == "sse"):
         ap.error("--aux-key goes with --model Hbv and --objective nse, kge or kge12")
     assert torch.cuda.is_available(), "the example runs on the GPU; there is no CPU fallback"
@@ -102,17 +110,25 @@ def main():
 
     joint = {}
     if args.aux_key:
-        aux_obs = torch.full_like(obs, float("nan"))
-        aux_obs[::8] = hidden[args.aux_key][..., 0][::8]
+        n = args.aux_period
+        if n:
+            K = obs.shape[0] // n                   # an incomplete last block is not observed
+            aux_obs = hidden[args.aux_key][..., 0][:K * n].double().unflatten(0, (K, n)).mean(1).float().contiguous()
+        else:
+            aux_obs = torch.full_like(obs, float("nan"))
+            aux_obs[::8] = hidden[args.aux_key][..., 0][::8]
         picked_aux, h_aux = search(model, x, start, obs, names=names, n_candidates=args.candidates, n_rounds=args.rounds,
                                    generator=torch.Generator().manual_seed(74), objective=args.objective,
                                    transform=args.transform, aux_target=aux_obs, aux_key=args.aux_key,
-                                   aux_share=args.aux_share)
+                                   aux_share=args.aux_share, aux_periods=n)
         both_aux, h_both_aux = hydrodl2_amd.calibrate(model, x, picked_aux, obs, names=names, n_iter=args.lm_iters)
 
         def both_scores(row):
             cand = row[-1][:, cols].unsqueeze(0).contiguous()
-            st = hydrodl2_amd.population_joint_stats(model, x, row, cand, obs, aux_obs, args.aux_key, names=names)
+            if n:
+                st = hydrodl2_amd.population_period_stats(model, x, row, cand, obs, None, aux_obs, args.aux_key, n, names=names)
+            else:
+                st = hydrodl2_amd.population_joint_stats(model, x, row, cand, obs, aux_obs, args.aux_key, names=names)
             return {f"{term}_{m}": float(hydrodl2_amd.population_score(st[term], m).nanmean())
                     for term in ("flow", "aux") for m in ("nse", "kge")}
 
@@ -121,7 +137,8 @@ def main():
             return float(d.pow(2).mean(1).sqrt().mean())
 
         joint = {
-            "aux_key": args.aux_key, "aux_share": args.aux_share, "aux_days_observed": int((~torch.isnan(aux_obs[:, 0])).sum()),
+            "aux_key": args.aux_key, "aux_share": args.aux_share, **({"aux_period_days": n, "aux_periods_observed": int(aux_obs.shape[0])} if n else
+               {"aux_days_observed": int((~torch.isnan(aux_obs[:, 0])).sum())}),
             "both_scores_start": both_scores(start),
             "both_scores_after_search_flow_only": both_scores(picked),
             "both_scores_after_search_with_aux": both_scores(picked_aux),

@@ -12,8 +12,8 @@ from hydrodl2_amd.hourly_jvp import hourly_jvp_batch
 from hydrodl2_amd.adj_jvp import adj_jvp_batch, adj_parameter_jacobian
 from hydrodl2_amd.calibrate import calibrate, lm_step, normal_equations
 from hydrodl2_amd.uncertainty import covariance_factor, parameter_covariance, predictive_variance
-from hydrodl2_amd.population import (population_cost, population_joint_stats, population_score, population_search,
-                                     population_stats)
+from hydrodl2_amd.population import (population_cost, population_joint_stats, population_period_stats, population_score,
+                                     population_search, population_stats)
 from hydrodl2_amd.adj_population import adj_population_cost, adj_population_search, adj_population_stats
 
 __version__ = "0.1.0"
@@ -22,4 +22,5 @@ __all__ = ["__version__", "available_models", "available_modules", "load_model",
            "parameter_jacobian", "lstm_jvp_batch", "hourly_jvp_batch", "adj_jvp_batch", "adj_parameter_jacobian",
            "normal_equations", "lm_step", "calibrate", "parameter_covariance", "covariance_factor", "predictive_variance",
            "population_cost", "population_search", "population_stats", "population_score", "population_joint_stats",
+           "population_period_stats",
            "adj_population_cost", "adj_population_stats", "adj_population_search"]

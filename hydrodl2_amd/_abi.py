@@ -151,6 +151,16 @@ class PopJoint(C.Structure):
                 ("aux_sse", _fp), ("aux_s1", _fp), ("aux_s2", _fp), ("aux_s3", _fp), ("aux_sim", _fp)]
 
 
+POP_NO_AUX = -1     # HBVX_POP_NO_AUX: hbvx_population_period without an aux term
+
+
+class PopPeriod(C.Structure):
+    """hbvx_pop_period: hbvx_pop_joint with targets, weights and series per period, and the two calendars -- counts and
+    device arrays of int32 closing days relative to t_first (include/hbvx.h)."""
+    _fields_ = [("joint", PopJoint), ("n_flow_periods", C.c_int32), ("flow_end", _fp),
+                ("n_aux_periods", C.c_int32), ("aux_end", _fp)]
+
+
 class LstmDesc(C.Structure):
     """include/hbvx_lstm.h"""
     _fields_ = [("abi_version", C.c_int32), ("T", C.c_int32), ("B", C.c_int32), ("H", C.c_int32)]
@@ -175,7 +185,8 @@ OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forwa
                     "hbvx_gage_route_tangent_workspace_bytes", "hbvx_adj_tangent_batch", "hbvx_gram",
                     "hbvx_gram_workspace_bytes", "hbvx_quadform", "hbvx_quadform_workspace_bytes",
                     "hbvx_population_cost", "hbvx_population_stats",
-                    "hbvx_adj_population_cost", "hbvx_adj_population_stats", "hbvx_population_joint"]
+                    "hbvx_adj_population_cost", "hbvx_adj_population_stats", "hbvx_population_joint",
+                    "hbvx_population_period"]
 
 
 class HbvxError(RuntimeError):
@@ -351,6 +362,11 @@ class Library:
             d.hbvx_population_joint.argtypes = [C.POINTER(Desc), C.POINTER(PopJoint), C.c_void_p]
             if d.hbvx_sizeof(12) != C.sizeof(PopJoint):
                 raise HbvxError(f"{path}: layout mismatch for PopJoint: {d.hbvx_sizeof(12)} != {C.sizeof(PopJoint)}")
+        if "hbvx_population_period" not in self.missing:
+            d.hbvx_population_period.restype = C.c_int
+            d.hbvx_population_period.argtypes = [C.POINTER(Desc), C.POINTER(PopPeriod), C.c_void_p]
+            if d.hbvx_sizeof(13) != C.sizeof(PopPeriod):
+                raise HbvxError(f"{path}: layout mismatch for PopPeriod: {d.hbvx_sizeof(13)} != {C.sizeof(PopPeriod)}")
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -554,6 +570,13 @@ class Library:
         self._check(self.dll.hbvx_population_joint(None if desc is None else C.byref(desc),
                                                    None if pj is None else C.byref(pj), stream),
                     "hbvx_population_joint")
+
+    def population_period(self, desc, pq, stream: int):
+        """hbvx_population_period; `desc` / `pq` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_population_period")
+        self._check(self.dll.hbvx_population_period(None if desc is None else C.byref(desc),
+                                                    None if pq is None else C.byref(pq), C.c_void_p(stream)),
+                    "hbvx_population_period")
 
     def adj_population_cost(self, desc, pop, stream: int):
         """hbvx_adj_population_cost; `desc` / `pop` may be None (the ABI's own refusals are under test)."""

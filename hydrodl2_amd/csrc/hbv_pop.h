@@ -12,6 +12,8 @@
 // hbvx_popk::BasinStats is Basin plus the transform and the three moment chains (tests/hosttest/popstats_host.cpp).
 // hbvx_popk::AuxStats is the aux term's four chains (tests/hosttest/popjoint_host.cpp).
 // k_pop maps lanes onto the one struct, k_pop_stats<TR> onto the other, k_pop_joint<TR> onto a BasinStats and an AuxStats.
+// hbvx_popk::PeriodMean is the mean over a period that hbvx_population_period (hbv_pop_period.h) puts between each of the
+// two values and its chains (tests/hosttest/popperiod_host.cpp).
 #pragma once
 
 #include <math.h>
@@ -132,6 +134,33 @@ struct BasinStats : Basin {
         }
         return y;
     }
+
+    // The lines of a counted day of push() on a value that is already there -- hbvx_population_period's period mean of
+    // y: v' = transform(v), then r, d, e and the four chains against `target` (already transformed) and w.  A
+    // restatement: push() keeps its text (k_pop_stats and k_pop_joint are pinned).  A change belongs in both.
+    template <int TR>
+    HBVX_POP_HD void score(float v, float target, float w)
+    {
+        const float yt = transform<TR>(v);
+        const float r = yt - target;
+        cost = __builtin_fmaf(w * r, r, cost);
+        const float dd = yt - m, e = target - m;
+        s1 = __builtin_fmaf(w, dd, s1);
+        s2 = __builtin_fmaf(w * dd, dd, s2);
+        s3 = __builtin_fmaf(w * dd, e, s3);
+    }
+};
+
+// The mean of a series over one period of hbvx_population_period: add() takes the period's days in ascending order, the
+// first one ASSIGNS (so a one-day period is y / 1.0f = y bit for bit, negative zero included, and nothing of the period
+// before is left), close(n) is the one division by the period's day count:
+//   acc = y (first day) | acc + y (later days)        mean = acc / (float)n
+struct PeriodMean {
+    float acc;
+
+    HBVX_POP_HD void add(float y, bool first) { acc = first ? y : acc + y; }
+
+    HBVX_POP_HD float close(int n) const { return acc / (float)n; }
 };
 
 // The aux term of hbvx_population_joint: the four chains of BasinStats on a value that is neither routed nor

@@ -71,6 +71,7 @@ extern "C" uint64_t hbvx_sizeof(int which)
     case 10: return sizeof(hbvx_pop);
     case 11: return sizeof(hbvx_pop_stats);
     case 12: return sizeof(hbvx_pop_joint);
+    case 13: return sizeof(hbvx_pop_period);
     default: return 0;
     }
 }

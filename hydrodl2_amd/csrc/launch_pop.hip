@@ -1,8 +1,9 @@
 // launch_pop.hip -- the entry points of the population evaluation: hbvx_population_cost, hbvx_population_stats and
-// hbvx_population_joint (hbv_pop.h), and the first two's twins for the implicit scheme, hbvx_adj_population_cost and hbvx_adj_population_stats
+// hbvx_population_joint (hbv_pop.h), hbvx_population_period (hbv_pop_period.h), and the first two's twins for the implicit scheme, hbvx_adj_population_cost and hbvx_adj_population_stats
 // (hbv_adj_pop.h).
 #include "hbvx_host.h"
 #include "hbv_pop.h"
+#include "hbv_pop_period.h"
 #define HBVX_CHUNK_NO_SHARED_KERNELS
 #include "hbv_chunked.h"        // (first: hbv_adj_kernels.h uses its XCD-aware block map)
 #include "hbv_adj_pop.h"
@@ -176,6 +177,73 @@ extern "C" int hbvx_population_joint(const hbvx_desc *d, const hbvx_pop_joint *p
     });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "hbvx_population_joint launch");
+    return HBVX_OK;
+}
+
+extern "C" int hbvx_population_period(const hbvx_desc *d, const hbvx_pop_period *pq, void *stream)
+{
+    const char *who = "hbvx_population_period";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!pq) return fail_as(who, HBVX_E_NULL, "pq is NULL");
+    const hbvx_pop_joint *pj = &pq->joint;
+    PopPeriodArgs q;
+    PopJointArgs &j = q.j;
+    rc = prepare(who, d, &pj->flow.pop, j.s.a);
+    if (rc) return rc;
+    rc = prepare_stats(who, &pj->flow, j.s);
+    if (rc) return rc;
+    const int t_out = d->T - pj->flow.pop.t_first;
+    if (!pq->flow_end) return fail_as(who, HBVX_E_NULL, "flow_end is NULL");
+    if (pq->n_flow_periods < 1 || pq->n_flow_periods > t_out)
+        return fail_as(who, HBVX_E_SHAPE, "n_flow_periods must be in 1..T - t_first");
+    q.has_aux = pj->aux_series != HBVX_POP_NO_AUX;
+    j = PopJointArgs{j.s, pj->aux_series, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    q.n_flow = pq->n_flow_periods;
+    q.flow_end = pq->flow_end;
+    q.n_aux = 0;
+    q.aux_end = nullptr;
+    if (q.has_aux) {
+        switch (pj->aux_series) {
+        case HBVX_F_Q0: case HBVX_F_Q1: case HBVX_F_Q2: case HBVX_F_AET: case HBVX_F_SWE: break;
+        default:
+            return fail_as(who, HBVX_E_UNSUPPORTED, "aux_series must be HBVX_POP_NO_AUX or HBVX_F_Q0, _Q1, _Q2, _AET or _SWE");
+        }
+        if (!pj->aux_target) return fail_as(who, HBVX_E_NULL, "aux_target is NULL");
+        if (!pj->aux_shift) return fail_as(who, HBVX_E_NULL, "aux_shift is NULL");
+        if (!pj->aux_sse || !pj->aux_s1 || !pj->aux_s2 || !pj->aux_s3)
+            return fail_as(who, HBVX_E_NULL, "aux_sse / aux_s1 / aux_s2 / aux_s3 is NULL");
+        if (!pq->aux_end) return fail_as(who, HBVX_E_NULL, "aux_end is NULL");
+        if (pq->n_aux_periods < 1 || pq->n_aux_periods > t_out)
+            return fail_as(who, HBVX_E_SHAPE, "n_aux_periods must be in 1..T - t_first");
+        j.aux_target = pj->aux_target;
+        j.aux_w = pj->aux_w;
+        j.aux_shift = pj->aux_shift;
+        j.aux_sse = pj->aux_sse;
+        j.aux_s1 = pj->aux_s1;
+        j.aux_s2 = pj->aux_s2;
+        j.aux_s3 = pj->aux_s3;
+        j.aux_sim = pj->aux_sim;
+        q.n_aux = pq->n_aux_periods;
+        q.aux_end = pq->aux_end;
+    }
+    const dim3 grid = pop_grid(j.s.a);
+    with_model(d, [&](auto m, auto be) {
+        if constexpr (m != MODEL_HOURLY) {
+            switch (pj->flow.transform) {
+            case HBVX_POP_T_SQRT:
+                hipLaunchKernelGGL((k_pop_period<m, be, hbvx_popk::T_SQRT>), grid, dim3(64), 0, (hipStream_t)stream, q);
+                break;
+            case HBVX_POP_T_LOG:
+                hipLaunchKernelGGL((k_pop_period<m, be, hbvx_popk::T_LOG>), grid, dim3(64), 0, (hipStream_t)stream, q);
+                break;
+            default:
+                hipLaunchKernelGGL((k_pop_period<m, be, hbvx_popk::T_NONE>), grid, dim3(64), 0, (hipStream_t)stream, q);
+            }
+        }
+    });
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "hbvx_population_period launch");
     return HBVX_OK;
 }
 

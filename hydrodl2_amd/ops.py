@@ -1137,6 +1137,43 @@ def population_joint(rec: PathRecord, cand_sources: dict, route_cands, target_t:
     return (sse,) + moments + (sim,), aux
 
 
+def population_period(rec: PathRecord, cand_sources: dict, route_cands, target_t: torch.Tensor, w: Optional[torch.Tensor],
+                      shift: torch.Tensor, eps: Optional[torch.Tensor], transform: str, flow_end: torch.Tensor,
+                      aux_series: Optional[int] = None, aux_target: Optional[torch.Tensor] = None,
+                      aux_w: Optional[torch.Tensor] = None, aux_shift: Optional[torch.Tensor] = None,
+                      aux_end: Optional[torch.Tensor] = None, t_first: int = 0, want_sim: bool = False):
+    """`population_joint` on period means, through hbvx_population_period (include/hbvx.h): each series is averaged over
+    the periods of its calendar before it meets its target.  ((sse, s1, s2, s3, sim), (aux_sse, aux_s1, aux_s2, aux_s3,
+    aux_sim) or None).
+
+    flow_end, aux_end  1-D int32 tensors on the device of the record: the closing days of the periods, 0-based in the
+                  scored days, ascending (the caller checks that; the kernel is safe either way).
+    target_t, w   [KF,B] float32 per period, KF = len(flow_end); aux_target, aux_w [KA,B]; sim / aux_sim [P,KF,B] /
+                  [P,KA,B] period means.  aux_series None: no aux term (then no aux argument may be given).
+    Everything else as `population_joint`: the same checks, the same split above POP_MAX_CAND."""
+    if transform not in _abi.POP_TRANSFORMS:
+        raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
+    if transform == "log" and eps is None:
+        raise ValueError("population_period: transform 'log' needs eps")
+    aux = None
+    if aux_series is None:
+        if any(t is not None for t in (aux_target, aux_w, aux_shift, aux_end)):
+            raise ValueError("population_period: aux arguments without aux_series")
+    else:
+        if aux_series not in _abi.POP_AUX_SERIES.values():
+            raise ValueError(f"population_period: aux_series must be one of {sorted(_abi.POP_AUX_SERIES.values())} "
+                             f"(hbvx_flux indices), got {aux_series!r}")
+        if aux_target is None or aux_shift is None or aux_end is None:
+            raise ValueError("population_period needs aux_target, aux_shift and aux_end with aux_series")
+        aux = (aux_series, aux_target, aux_w, aux_shift)
+    sse, moments, sim, aux_out = _population("population_period", "hbvx_population_period",
+                                             lambda lib: lib.population_period, rec, cand_sources, route_cands, target_t,
+                                             w, t_first, want_sim,
+                                             (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None),
+                                             aux, (flow_end, aux_end))
+    return (sse,) + moments + (sim,), aux_out
+
+
 def _require_adj_record(what: str, rec: PathRecord) -> None:
     cfg = rec.cfg
     if cfg.model != _abi.MODEL_HBVADJ:
@@ -1173,11 +1210,13 @@ def adj_population_stats(rec: PathRecord, cand_sources: dict, route_cands, targe
 
 
 def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: dict, route_cands, target, w, t_first,
-                want_sim, stats, aux=None):
-    """What the five population calls share -- stats None: the cost, stats = (transform id, shift, eps): the cost and the
-    moment chains, aux = (flux index, target, w, shift) with stats: the aux term's four chains beside them; `entry` the
-    export's name and `call_of(lib)` its Library method -- the checks, the descriptors, the NaN-poisoned outputs and the
-    launches.  -> (cost, (s1, s2, s3) or None, sim, (aux_sse, aux_s1, aux_s2, aux_s3, aux_sim) or None)."""
+                want_sim, stats, aux=None, periods=None):
+    """What the six population calls share -- stats None: the cost, stats = (transform id, shift, eps): the cost and the
+    moment chains, aux = (flux index, target, w, shift) with stats: the aux term's four chains beside them, periods =
+    (flow_end, aux_end or None) with stats: hbvx_population_period's calendars, with targets, weights and series per
+    period and aux optional; `entry` the export's name and `call_of(lib)` its Library method -- the checks, the
+    descriptors, the NaN-poisoned outputs and the launches.
+    -> (cost, (s1, s2, s3) or None, sim, (aux_sse, aux_s1, aux_s2, aux_s3, aux_sim) or None)."""
     lib = get_library()
     lib.require(entry)
     call = call_of(lib)
@@ -1208,12 +1247,27 @@ def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: d
         if s is not None and not 0 <= s[1] < Cn:
             raise ValueError(f"routing candidate column {s[1]} outside the {Cn} columns")
     aux_series, aux_target, aux_w, aux_shift = aux if aux is not None else (None, None, None, None)
-    for name, t in (("target", target), ("w", w), ("aux_target", aux_target), ("aux_w", aux_w)):
+    rows_f = rows_a = T_out         # rows of the flow's and the aux term's targets, weights and series
+    ends = [None, None]
+    if periods is not None:
+        if (periods[1] is None) != (aux is None):
+            raise ValueError(f"{what}: the aux calendar and the aux term go together")
+        for i, (name, e) in enumerate((("flow_end", periods[0]), ("aux_end", periods[1]))):
+            if e is None:
+                continue
+            if e.dtype != torch.int32 or e.dim() != 1 or e.device != dev or not 1 <= e.numel() <= T_out:
+                raise ValueError(f"{name} must be a 1-D int32 tensor of 1..{T_out} closing days on {dev}, got "
+                                 f"{e.dtype} {tuple(e.shape)} on {e.device}")
+            ends[i] = e.contiguous()
+        rows_f = int(ends[0].numel())
+        rows_a = int(ends[1].numel()) if ends[1] is not None else 0
+    for name, t, rows in (("target", target, rows_f), ("w", w, rows_f), ("aux_target", aux_target, rows_a),
+                          ("aux_w", aux_w, rows_a)):
         if t is None:
             continue
         _check_tensor(lib, t, name)
-        if tuple(t.shape) != (T_out, B) or t.device != dev:
-            raise ValueError(f"{name} must be [{T_out},{B}] on {dev}, got {tuple(t.shape)} on {t.device}")
+        if tuple(t.shape) != (rows, B) or t.device != dev:
+            raise ValueError(f"{name} must be [{rows},{B}] on {dev}, got {tuple(t.shape)} on {t.device}")
     transform, shift, eps = stats if stats is not None else (None, None, None)
     for name, t in (("shift", shift), ("eps", eps), ("aux_shift", aux_shift)):
         if t is None:
@@ -1232,13 +1286,14 @@ def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: d
     with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
         cost = _out((P, B), dev)
         moments = tuple(_out((P, B), dev) for _ in range(3)) if stats is not None else None
-        sim = _out((P, T_out, B), dev) if want_sim else None
+        sim = _out((P, rows_f, B), dev) if want_sim else None
         aux_out = None
         if aux is not None:
-            aux_out = tuple(_out((P, B), dev) for _ in range(4)) + ((_out((P, T_out, B), dev) if want_sim else None),)
+            aux_out = tuple(_out((P, B), dev) for _ in range(4)) + ((_out((P, rows_a, B), dev) if want_sim else None),)
         for c0 in range(0, P, POP_MAX_CAND):
-            pj = _abi.PopJoint() if aux is not None else None
-            ps = pj.flow if aux is not None else _abi.PopStats() if stats is not None else None
+            pq = _abi.PopPeriod() if periods is not None else None
+            pj = pq.joint if periods is not None else _abi.PopJoint() if aux is not None else None
+            ps = pj.flow if pj is not None else _abi.PopStats() if stats is not None else None
             pop = ps.pop if stats is not None else _abi.Pop()
             pop.n_cand, pop.t_first = min(POP_MAX_CAND, P - c0), t_first
             for slot, (_, col) in cand_sources.items():
@@ -1254,19 +1309,28 @@ def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: d
                 pop.r_c_stride, pop.r_b_stride = B * Cn, Cn
             pop.target, pop.w = _ptr(tc), _ptr(wc)
             pop.cost = _ptr(cost, c0 * B)
-            pop.sim = _ptr(sim, c0 * T_out * B)
+            pop.sim = _ptr(sim, c0 * rows_f * B)
             if stats is None:
                 _call(lib, entry, call, desc, pop, stream)
             else:
                 ps.transform, ps.shift, ps.eps = transform, _ptr(shc), _ptr(epc)
                 ps.s1, ps.s2, ps.s3 = (_ptr(m, c0 * B) for m in moments)
-                if aux is None:
+                if pj is None:
                     _call(lib, entry, call, desc, ps, stream)
+                    continue
+                if aux is None:
+                    pj.aux_series = _abi.POP_NO_AUX
                 else:
                     pj.aux_series, pj.aux_target, pj.aux_w, pj.aux_shift = aux_series, _ptr(atc), _ptr(awc), _ptr(ashc)
                     pj.aux_sse, pj.aux_s1, pj.aux_s2, pj.aux_s3 = (_ptr(m, c0 * B) for m in aux_out[:4])
-                    pj.aux_sim = _ptr(aux_out[4], c0 * T_out * B)
+                    pj.aux_sim = _ptr(aux_out[4], c0 * rows_a * B)
+                if pq is None:
                     _call(lib, entry, call, desc, pj, stream)
+                else:
+                    pq.n_flow_periods, pq.flow_end = rows_f, ends[0].data_ptr()
+                    if ends[1] is not None:
+                        pq.n_aux_periods, pq.aux_end = rows_a, ends[1].data_ptr()
+                    _call(lib, entry, call, desc, pq, stream)
     return cost, moments, sim, aux_out
 
 

@@ -14,10 +14,13 @@ float64 -- so a search can run in the metric its result is reported in.
 `population_joint_stats` is that launch with a second observed series beside streamflow -- evapotranspiration, snow-water
 equivalent or one of the three un-routed runoff components (hbvx_population_joint): eight [P,B] numbers, still no
 series -- and `population_search(aux_target=...)` minimises a weighted sum of the two scores.
+`population_period_stats` is the joint launch against period MEANS -- 8-day composites, months -- on a calendar per
+series (hbvx_population_period): each series is averaged over its periods inside the kernel, the chains take one step
+per period, and `population_search(periods=..., aux_periods=...)` searches on those scores.
 
-Hbv, Hbv_1_1p and Hbv_2 only.  HbvAdj has the first three calls in adj_population.py; the joint call is not built for
-it (its kernel is a separate family), nor for the hourly and multi-timescale models.  The aux series is not transformed,
-there is one per launch, it is compared day by day (no 8-day or monthly sums), and there is no joint `calibrate`: two
+Hbv, Hbv_1_1p and Hbv_2 only.  HbvAdj has the first three calls in adj_population.py; the joint and the period call are
+not built for it (its kernel is a separate family), nor for the hourly and multi-timescale models.  The aux series is not
+transformed, there is one per launch, calendars are shared by all basins, and there is no joint `calibrate`: two
 `normal_equations` calls can be summed by the caller.
 """
 from __future__ import annotations
@@ -28,7 +31,7 @@ import torch
 
 from . import _abi, ops
 from ._lib import get_library
-from .calibrate import _check_request, _static_tensor
+from .calibrate import _NO_TARGET, _check_request, _static_tensor
 from .sensitivity import jacobian_columns
 
 _EDGE = 1e-4        # unit-space draws are kept in [_EDGE, 1 - _EDGE] where the module applies a sigmoid (finite logits)
@@ -158,14 +161,16 @@ OBJECTIVES = ('sse', 'nse', 'kge', 'kge12')
 _VAR_FLOOR = 1e-6
 
 
-def _observations(req, x_dict, target, weights, transform, eps, what):
+def _observations(req, x_dict, target, weights, transform, eps, what, rows=None):
     """The observation side of `population_stats`, everything that can be refused about it, before the model runs.
     float64 on the device of x_phy -> {'target' [T_out,B] float32 transformed (0 where missing), 'w' [T_out,B] float32
-    or None, 'shift' [B] float32, 'eps' [B] float32 or None, 'obs': {'W','e1','e2'} [B] float64, 'n_obs' [B] int64}."""
+    or None, 'shift' [B] float32, 'eps' [B] float32 or None, 'obs': {'W','e1','e2'} [B] float64, 'n_obs' [B] int64}.
+    rows: the leading size of target and weights where it is not T_out -- the K periods of `population_period_stats`,
+    whose observations are one value per period; everything above then reads K for T_out."""
     if transform not in _abi.POP_TRANSFORMS:
         raise ValueError(f"{what}: transform must be one of {list(TRANSFORMS)}, got {transform!r}")
     dev = x_dict['x_phy'].device
-    tgt = target.to(device=dev, dtype=torch.float32).reshape(req.T_out, req.B)
+    tgt = target.to(device=dev, dtype=torch.float32).reshape(req.T_out if rows is None else rows, req.B)
     miss = torch.isnan(tgt)
     plain = weights is None and not bool(miss.any())
     w = torch.ones_like(tgt) if weights is None else weights.to(device=dev, dtype=torch.float32)
@@ -252,21 +257,23 @@ def population_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, 
 AUX_KEYS = tuple(_abi.POP_AUX_SERIES)       # 'srflow_no_rout', 'ssflow_no_rout', 'gwflow_no_rout', 'AET_hydro', 'SWE'
 
 
-def _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what):
-    """What can be refused about the aux term without running the model."""
+def _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what, rows=None):
+    """What can be refused about the aux term without running the model.  rows: the leading size of aux_target and
+    aux_weights where it is not T_out (the periods of `population_period_stats`)."""
     if aux_target is None or aux_key is None:
         raise ValueError(f"{what}: aux_target and aux_key go together "
                          f"({'aux_target' if aux_target is None else 'aux_key'} is missing)")
     if aux_key not in _abi.POP_AUX_SERIES:
         raise ValueError(f"{what}: aux_key must be one of {list(AUX_KEYS)}, got {aux_key!r}")
     dev = x_dict['x_phy'].device
-    for name, t, shapes in (("aux_target", aux_target, ((req.T_out, req.B), (req.T_out, req.B, 1))),
-                            ("aux_weights", aux_weights, ((req.T_out, req.B),))):
+    n, of = (req.T_out, "days after the warm-up") if rows is None else (rows, "periods of its calendar")
+    for name, t, shapes in (("aux_target", aux_target, ((n, req.B), (n, req.B, 1))),
+                            ("aux_weights", aux_weights, ((n, req.B),))):
         if t is None:
             continue
         if not torch.is_tensor(t) or tuple(t.shape) not in shapes:
-            raise ValueError(f"{what}: {name} must be {' or '.join(str(list(s)) for s in shapes)} (the days after the "
-                             f"warm-up), got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            raise ValueError(f"{what}: {name} must be {' or '.join(str(list(s)) for s in shapes)} (the {of}), "
+                             f"got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
         if t.dtype not in (torch.float32, torch.float64):
             raise ValueError(f"{what}: {name} must be float32 or float64, got {t.dtype}")
         if t.device != dev:
@@ -326,6 +333,148 @@ def population_joint_stats(model, x_dict: dict, parameters, candidates: torch.Te
     aux_ob = _observations(req, x_dict, aux_target, aux_weights, 'none', None, what)
     get_library().require("hbvx_population_joint")
     return _joint(model, req, x_dict, parameters, candidates, names, ob, transform, aux_key, aux_ob, return_series)
+
+
+def _calendar(periods, T_out: int, name: str, what: str) -> torch.Tensor:
+    """The closing days of a calendar, 0-based in the scored days: a 1-D int64 CPU tensor.  periods None: every day its
+    own period; an int n: blocks of n days from the first scored day, an incomplete last block dropped; a 1-D integer
+    sequence or tensor: the closing days themselves, strictly ascending in 0..T_out-1."""
+    if periods is None:
+        return torch.arange(T_out, dtype=torch.int64)
+    if isinstance(periods, bool):
+        raise ValueError(f"{what}: {name} must be None, an int or a 1-D sequence of closing days, got a bool")
+    if isinstance(periods, int):
+        if not 1 <= periods <= T_out:
+            raise ValueError(f"{what}: {name} = {periods} days per period, with {T_out} scored days it must be in 1..{T_out}")
+        return torch.arange(periods - 1, T_out, periods, dtype=torch.int64)
+    try:
+        ends = periods.detach().cpu() if torch.is_tensor(periods) else torch.as_tensor(list(periods))
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"{what}: {name} must be None, an int or a 1-D sequence of closing days") from e
+    if ends.dim() != 1 or ends.numel() < 1:
+        raise ValueError(f"{what}: {name} must hold at least one closing day in one dimension, got shape {tuple(ends.shape)}")
+    if ends.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError(f"{what}: {name} must hold integers (closing days), got {ends.dtype}")
+    ends = ends.to(torch.int64)
+    if int(ends[0]) < 0 or int(ends[-1]) >= T_out or bool((ends[1:] <= ends[:-1]).any()):
+        raise ValueError(f"{what}: {name} must be strictly ascending closing days in 0..{T_out - 1} (0-based in the "
+                         "scored days)")
+    return ends
+
+
+def _period_days(ends: torch.Tensor) -> torch.Tensor:
+    """The day count of each period of a calendar: period 0 starts at the first scored day."""
+    return ends - torch.cat([ends.new_full((1,), -1), ends[:-1]])
+
+
+def _check_period_target(req, x_dict, target, weights, K, what):
+    """calibrate's checks of target and weights, with the K periods of the calendar in place of the days."""
+    dev = x_dict['x_phy'].device
+    for name, t, shapes in (("target", target, ((K, req.B), (K, req.B, 1))), ("weights", weights, ((K, req.B),))):
+        if t is None and name == "weights":
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) not in shapes:
+            raise ValueError(f"{what}: {name} must be {' or '.join(str(list(s)) for s in shapes)} (the {K} periods of its "
+                             f"calendar), got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{what}: {name} must be float32 or float64, got {t.dtype}")
+        if t.device != dev:
+            raise ValueError(f"{what}: {name} lives on {t.device}, x_phy on {dev}")
+    if bool(torch.isinf(target).any()):
+        raise ValueError(f"{what}: target holds infinities (a missing observation is a NaN)")
+    if weights is not None:
+        if not bool(torch.isfinite(weights).all()):
+            raise ValueError(f"{what}: weights must be finite")
+        if bool((weights < 0).any()):
+            raise ValueError(f"{what}: weights must not be negative")
+
+
+def _period_request(model, x_dict, parameters, candidates, target, periods, aux_target, aux_key, aux_periods, names,
+                    weights, aux_weights, transform, eps, what):
+    """Everything `population_period_stats` can refuse before the model runs, and what it works on: (req, ob, aux_ob or
+    None, (flow closing days, aux closing days or None) as int64 CPU tensors)."""
+    req = _check(model, x_dict, parameters, _NO_TARGET, names, None, what)
+    if candidates is not None:
+        _check_candidates(req, x_dict, candidates)
+    ends_f = _calendar(periods, req.T_out, "periods", what)
+    _check_period_target(req, x_dict, target, weights, int(ends_f.numel()), what)
+    ends_a = aux_ob = None
+    if aux_key is None and aux_target is None:
+        if aux_periods is not None or aux_weights is not None:
+            raise ValueError(f"{what}: {'aux_periods' if aux_periods is not None else 'aux_weights'} without aux_key")
+    else:
+        ends_a = _calendar(aux_periods, req.T_out, "aux_periods", what)
+        _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what, rows=int(ends_a.numel()))
+    ob = _observations(req, x_dict, target, weights, transform, eps, what, rows=int(ends_f.numel()))
+    if ends_a is not None:
+        aux_ob = _observations(req, x_dict, aux_target, aux_weights, 'none', None, what, rows=int(ends_a.numel()))
+    get_library().require("hbvx_population_period")
+    return req, ob, aux_ob, (ends_f, ends_a)
+
+
+def _period(model, req, x_dict, parameters, candidates, names, ob, transform, aux_key, aux_ob, ends, return_series):
+    outputs, main, t_first = _primal(model, req, x_dict, parameters)
+    sources, route = _candidate_sources(model, names, candidates)
+    dev = main.x.device
+    end_f, end_a = (None if e is None else e.to(device=dev, dtype=torch.int32) for e in ends)
+    if aux_ob is None:
+        flow, aux = ops.population_period(main, sources, route, ob['target'], ob['w'], ob['shift'], ob['eps'], transform,
+                                          end_f, t_first=t_first, want_sim=return_series)
+    else:
+        flow, aux = ops.population_period(main, sources, route, ob['target'], ob['w'], ob['shift'], ob['eps'], transform,
+                                          end_f, _abi.POP_AUX_SERIES[aux_key], aux_ob['target'], aux_ob['w'],
+                                          aux_ob['shift'], end_a, t_first, return_series)
+    out = {'columns': list(req.cols), 'outputs': outputs}
+    for name, got, o, tr, e in (('flow', flow, ob, transform, ends[0]), ('aux', aux, aux_ob, 'none', ends[1])):
+        if got is None:
+            continue
+        sub = dict(zip(('sse', 's1', 's2', 's3'), got[:4]))
+        sub.update(shift=o['shift'], obs=o['obs'], transform=tr, eps=o['eps'], n_obs=o['n_obs'], columns=list(req.cols),
+                   outputs=outputs, period_ends=e.clone(), period_days=_period_days(e))
+        if return_series:
+            sub['series'] = got[4]
+        out[name] = sub
+    if aux is not None:
+        out['aux']['key'] = aux_key
+    return out
+
+
+def population_period_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, target, periods=None,
+                            aux_target=None, aux_key: Optional[str] = None, aux_periods=None,
+                            names: Optional[Sequence[str]] = None, weights=None, aux_weights=None,
+                            transform: str = 'none', eps=None, return_series: bool = False) -> dict:
+    """`population_joint_stats` against period MEANS: each candidate's streamflow, and optionally one second series, is
+    averaged over the periods of a calendar -- 8-day composites, months -- inside the kernel, and the period means are
+    what meets the targets (hbvx_population_period).  Still nothing but [P,B] numbers; no daily series exists anywhere.
+
+    periods, aux_periods   the calendar of the flow and of the aux series, each one of
+                 None: every scored day is its own period (with both None the numbers are `population_joint_stats`' bit
+                       for bit);
+                 an int n >= 1: blocks of n days from the first scored day, an incomplete last block is not scored;
+                 a 1-D integer sequence or tensor of closing days: 0-based in the scored days, strictly ascending, all
+                       below T_out.  Period k covers the days after closing day k - 1 up to and including closing day k;
+                       days after the last closing day are simulated and not scored.
+    target       [K,B] or [K,B,1], K the number of periods of `periods`: the period MEAN in the module's units (a caller
+                 with sums divides by the lengths); a NaN is a missing period.  aux_target likewise on `aux_periods`.
+    weights, aux_weights   [K,B] >= 0 per period, or None (ones).
+    transform, eps   as `population_stats`, applied to the period mean of the flow; the default eps under 'log' is a
+                 hundredth of the weighted mean of the period targets.  The aux series is never transformed.
+    aux_key None (with aux_target None): there is no aux term; the flow numbers have the same bits either way.
+    Returns `population_joint_stats`' layout, {'flow', 'aux' (only with aux_key), 'columns', 'outputs'}; each of the two
+    also carries 'period_ends' and 'period_days' ([K] int64, CPU), 'n_obs' counts observed periods, and with
+    return_series 'series' is [P,K,B]: the period means (the flow's before its transform).  `population_score` works on
+    either unchanged.  include/hbvx.h states the arithmetic line by line: float32, the days of a period added in
+    ascending order and divided once, fused multiply-add chains over ascending periods, no atomics; two calls agree bit
+    for bit and a candidate's bits depend on nothing but its own values.
+
+    Refused before the model runs: everything `population_joint_stats` refuses (its aux rules only with an aux term); a
+    calendar that is empty, not integer, not strictly ascending, negative or >= T_out; n < 1 or n > T_out; a target or
+    weights whose leading size is not K; aux_periods or aux_weights without aux_key (ValueError); HbvAdj, the hourly and
+    multi-timescale models (NotImplementedError); a library without hbvx_population_period (HbvxError)."""
+    what = "population_period_stats"
+    req, ob, aux_ob, ends = _period_request(model, x_dict, parameters, candidates, target, periods, aux_target, aux_key,
+                                            aux_periods, names, weights, aux_weights, transform, eps, what)
+    return _period(model, req, x_dict, parameters, candidates, names, ob, transform, aux_key, aux_ob, ends, return_series)
 
 
 def population_score(stats: dict, metric: str) -> torch.Tensor:
@@ -408,7 +557,7 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
                       n_candidates: int = 256, n_rounds: int = 1, shrink: float = 0.5, weights=None,
                       generator: Optional[torch.Generator] = None, objective: str = 'sse', transform: str = 'none',
                       eps=None, aux_target=None, aux_key: Optional[str] = None, aux_weights=None,
-                      aux_objective: str = 'nse', aux_share: float = 0.5):
+                      aux_objective: str = 'nse', aux_share: float = 0.5, periods=None, aux_periods=None):
     """Per-basin shrinking random search over the static row, for a start that `calibrate` can refine.
 
     Round 0 evaluates the current row as candidate 0 and n_candidates - 1 uniform draws in the unit interval per
@@ -435,11 +584,39 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
     its own series under `objective` / `aux_objective`, +inf where either score is NaN; history['score'] (flow) and
     history['score_aux'] hold the two scores (for 'sse' the squared error itself).  aux_share in [0, 1]; aux_objective
     'sse' goes with objective 'sse' only -- a squared error and 1 - score are two scales in one sum.  Without aux_target
+    the function is the one above, bit for bit.
+
+    periods / aux_periods (as `population_period_stats` takes them; either may be given alone, the other is then daily)
+    score period means: target, weights, aux_target and aux_weights then hold one row per period, and every round is one
+    `population_period_stats` call, with or without an aux term; cost and history are formed as above.  With both None
     the function is the one above, bit for bit."""
     what = "population_search"
     _check_search(model, n_candidates, n_rounds, shrink, objective, what)
-    req = _check(model, x_dict, parameters, target, names, weights, what)
     joint = aux_target is not None or aux_key is not None or aux_weights is not None
+    if periods is not None or aux_periods is not None:
+        if joint:
+            if aux_objective not in OBJECTIVES:
+                raise ValueError(f"{what}: aux_objective must be one of {list(OBJECTIVES)}, got {aux_objective!r}")
+            if not 0.0 <= float(aux_share) <= 1.0:
+                raise ValueError(f"{what}: aux_share must lie in [0, 1], got {aux_share!r}")
+            if aux_objective == 'sse' and objective != 'sse':
+                raise ValueError(f"{what}: aux_objective 'sse' with objective {objective!r} would add a squared error to "
+                                 "1 - score: two scales in one sum")
+        req, ob, aux_ob, ends = _period_request(model, x_dict, parameters, None, target, periods, aux_target, aux_key,
+                                                aux_periods, names, weights, aux_weights, transform, eps, what)
+
+        def evaluate_periods(cands):
+            st = _period(model, req, x_dict, parameters, cands, names, ob, transform, aux_key, aux_ob, ends, False)
+            score = population_score(st['flow'], objective)
+            if not joint:
+                return _objective_cost(score, objective), score
+            score_aux = population_score(st['aux'], aux_objective)
+            return _mixed_cost(_objective_cost(score, objective), _objective_cost(score_aux, aux_objective),
+                               float(aux_share)), (score, score_aux)
+
+        return _search(req, x_dict, parameters, evaluate_periods, req.tname != 'p_sta', n_candidates, n_rounds, shrink,
+                       generator, joint or objective != 'sse', joint)
+    req = _check(model, x_dict, parameters, target, names, weights, what)
     if joint:
         _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what)
         if aux_objective not in OBJECTIVES:

@@ -253,7 +253,8 @@ const char *hbvx_last_error(void);
 const char *hbvx_backend(void);         /* "hip:gfx950" or "cpu-oracle" */
 uint64_t hbvx_sizeof(int which);        /* 0 desc, 1 fwd_out, 2 bwd_io, 3 route_desc,
                                            4 param_src, 5 param_grad, 6 gage_desc, 7 tan_io, 8 tan_batch,
-                                           9 gram_desc, 10 pop, 11 pop_stats, 12 pop_joint: layout check */
+                                           9 gram_desc, 10 pop, 11 pop_stats, 12 pop_joint,
+                                           13 pop_period: layout check */
 /* Diagnostic: the kernel family that took the process's last hbvx_forward (direction 0) / hbvx_backward (1) call --
  * "pipe", "stream2", "stream", "tiled", "simple", "chunked", "ckpt-block:<family>", "ckpt-lds"; "oracle" in the CPU
  * restatement.  The parity tests assert that the family they mean to pin against the reference is the one that ran. */
@@ -628,6 +629,46 @@ typedef struct hbvx_pop_joint {
     float *aux_sim;                /* optional [P, T - t_first, B]: each candidate's aux series */
 } hbvx_pop_joint;                  /* hbvx_sizeof(12) */
 int hbvx_population_joint(const hbvx_desc *d, const hbvx_pop_joint *pj, void *stream);
+
+/* Population scores against period means (optional export; a library may lack it): hbvx_population_joint with each of
+ * the two series averaged over the periods of a calendar of its own -- 8-day composites, months -- before it meets its
+ * target.  The model, the candidates, the ensemble means y (routed flow) and v (aux flux), the routing and t_first are
+ * hbvx_population_joint's; the routing runs on every day.  A calendar is an ascending array of closing days relative to
+ * t_first: period k covers the scored days after end[k-1] (period 0: from day 0) up to and including end[k]; days after
+ * the last closing day are simulated and scored nowhere.  Per series, days ascending, with n the period's day count:
+ *   acc = x                      (the period's first day: assigned)           x = y | v
+ *   acc = acc + x                (its later days)
+ *   mean = acc / (float)n        (the day that closes period k: one division; a one-day period gives x bit for bit)
+ * and on that day one step of the four chains, periods ascending, every product written here rounded once:
+ *   flow:  y' = mean | sqrtf(mean) | logf(mean + eps[b])     (the transform of the period MEAN)
+ *          r = y' - o'      d = y' - m      e = o' - m       o' = flow.pop.target[k,b], m = flow.shift[b]
+ *          sse = fmaf(w * r, r, sse)   s1 = fmaf(w, d, s1)   s2 = fmaf(w * d, d, s2)   s3 = fmaf(w * d, e, s3)
+ *                                                            (w = flow.pop.w[k,b], 1 when NULL)
+ *   aux:   the same four lines on mean itself against aux_target[k,b], aux_shift[b], aux_w[k,b]: never transformed.
+ * Targets, weights and the optional series are indexed by PERIOD: flow.pop.target / w [KF,B], flow.pop.sim [P,KF,B],
+ * aux_target / aux_w [KA,B], aux_sim [P,KA,B]; the series hold the period means (the flow's before its transform).
+ * Rows of a series whose period never closes are not written.  joint.aux_series == HBVX_POP_NO_AUX: there is no aux
+ * term; the aux pointers, n_aux_periods and aux_end are then not read and nothing aux is written, and the flow numbers
+ * have the bits they have with an aux term.
+ * Guarantees: those of hbvx_population_joint (1)-(3), for all eight outputs and both series; (4) with both calendars
+ * daily (end[k] = k, K = T - t_first) every output has hbvx_population_joint's bits; (5) the kernel is memory-safe for
+ * any calendar content: no closing day and no target row beyond its count is read, and a calendar that does not ascend
+ * only leaves periods unclosed; (6) argument errors are reported before anything is launched: hbvx_population_joint's
+ * (its aux rules only when there is an aux term), and HBVX_E_NULL (pq, flow_end; aux_end with an aux term),
+ * HBVX_E_SHAPE (n_flow_periods, or n_aux_periods with an aux term, outside 1..T - t_first), HBVX_E_UNSUPPORTED (an
+ * aux_series that is neither HBVX_POP_NO_AUX nor one of the five).  csrc/hbv_pop_period.h has the kernel,
+ * csrc/hbv_pop.h the arithmetic (hbvx_popk::PeriodMean, BasinStats::score, AuxStats::push).
+ * Not built: period sums as an input form (divide by the lengths), per-basin calendars, HBVX_MODEL_HBVADJ / _HOURLY. */
+#define HBVX_POP_NO_AUX (-1)
+
+typedef struct hbvx_pop_period {
+    hbvx_pop_joint joint;          /* both terms as above, targets / weights / series per period */
+    int32_t n_flow_periods;        /* KF, 1..T - t_first */
+    const int32_t *flow_end;       /* [KF] device array: closing days relative to t_first, ascending */
+    int32_t n_aux_periods;         /* KA, 1..T - t_first; not read without an aux term */
+    const int32_t *aux_end;        /* [KA] device array; not read without an aux term */
+} hbvx_pop_period;                 /* hbvx_sizeof(13) */
+int hbvx_population_period(const hbvx_desc *d, const hbvx_pop_period *pq, void *stream);
 
 /* Population evaluation of the implicit scheme (optional exports; a library may lack them): hbvx_population_cost and
  * hbvx_population_stats for HBVX_MODEL_HBVADJ, on the same structs.  For every candidate c and basin b the day loop of
