@@ -11,7 +11,8 @@ wide).  Two routes from that start, both per basin:
 
     python examples/calibrate_global.py [--basins 32] [--days 730] [--nmul 4] [--candidates 256] [--rounds 3] [--lm-iters 8]
                                         [--objective sse|nse|kge|kge12] [--transform none|sqrt|log] [--model Hbv|HbvAdj]
-                                        [--aux-key AET_hydro|SWE|srflow_no_rout|ssflow_no_rout|gwflow_no_rout] [--aux-share 0.5]
+                                        [--aux-key AET_hydro|SWE|srflow_no_rout|ssflow_no_rout|gwflow_no_rout |
+                                                   SNOWPACK|MELTWATER|SM|SUZ|SLZ (HbvAdj)] [--aux-share 0.5]
                                         [--aux-period N]
 
 --model HbvAdj runs the same experiment on the implicit scheme: adj_population_search (hbvx_adj_population_cost: every
@@ -28,6 +29,9 @@ square over the searched columns of sigmoid(raw) differences, mean over the basi
 --aux-period N (with --aux-key) observes the aux series as what an N-day composite is: the MEANS of the hidden row's
 series over blocks of N days, compared with the candidates' means over the same blocks (hbvx_population_period), instead
 of one day's value in eight.  The flow stays daily.
+--model HbvAdj takes --aux-key SNOWPACK, MELTWATER, SM, SUZ or SLZ: the second series is then the ensemble mean of that
+storage at the end of each day (the hidden row's comes from the module's trajectory), and both forms of the aux
+observation go through hbvx_adj_population_period.
 Prints one JSON line: per route the summed cost and the number of basins in which it ended lower, with the cost of
 the start and of the search's pick beside them, and -- whichever objective was searched -- the basin means of SSE, NSE
 and KGE on the raw flow at the start and at the end of every route.  Synthetic forcings (tests/synth.py), a fixed seed.
@@ -61,16 +65,20 @@ def main():
     ap.add_argument("--names", default=None,
                     help="default: parBETA,parFC,parK0,parK1,parK2,parLP,parPERC,parUZL and the two routing parameters")
     ap.add_argument("--model", default="Hbv", choices=["Hbv", "HbvAdj"])
-    ap.add_argument("--aux-key", default=None, choices=["AET_hydro", "SWE", "srflow_no_rout", "ssflow_no_rout", "gwflow_no_rout"],
-                    help="also observe this series of the hidden row every 8th day and search on both scores")
+    fluxes, storages = list(hydrodl2_amd.population.AUX_KEYS), list(hydrodl2_amd.adj_population.AUX_KEYS)
+    ap.add_argument("--aux-key", default=None, choices=fluxes + storages,
+                    help="also observe this series of the hidden row every 8th day and search on both scores "
+                         "(a flux of Hbv, a storage of HbvAdj)")
     ap.add_argument("--aux-share", type=float, default=0.5, help="the aux term's share of the searched cost")
     ap.add_argument("--aux-period", type=int, default=None,
                     help="observe the aux series as N-day means of the hidden row instead of every 8th day")
     args = ap.parse_args()
     if args.aux_period is not None and (not args.aux_key or args.aux_period < 1):
         ap.error("--aux-period N >= 1 goes with --aux-key")
-    if args.aux_key and (args.model != "Hbv" or args.objective == "sse"):
-        ap.error("--aux-key goes with --model Hbv and --objective nse, kge or kge12")
+    if args.aux_key and args.objective == "sse":
+        ap.error("--aux-key goes with --objective nse, kge or kge12")
+    if args.aux_key and args.aux_key not in (storages if args.model == "HbvAdj" else fluxes):
+        ap.error(f"--aux-key of --model {args.model} is one of {storages if args.model == 'HbvAdj' else fluxes}")
     assert torch.cuda.is_available(), "the example runs on the GPU; there is no CPU fallback"
     dev = torch.device("cuda:0")
     T, B, M = args.days, args.basins, args.nmul
@@ -87,9 +95,14 @@ def main():
     x = {"x_phy": torch.from_numpy(synth.forcing(T, B, seed=71)).to(dev)}
     ny = model.learnable_param_count
     truth = torch.from_numpy(synth.raw_parameters(T, B, ny, seed=72)).to(dev)
-    with torch.no_grad():
+    with torch.no_grad(), hydrodl2_amd.ops.record_paths(want_traj=True) as records:
         hidden = model(x, truth)
     obs = hidden[key][..., 0].clone()
+    if adj and args.aux_key:
+        # the storage at the end of each day, ensemble mean: rows 1..T of the trajectory [5, T + 1, B * M]
+        k = storages.index(args.aux_key)
+        hidden = dict(hidden)
+        hidden[args.aux_key] = records[-1].traj.view(5, T + 1, B, M)[k, 1:].mean(-1, keepdim=True)
     # the poor start: the named columns of the static row drawn anew, three times as wide; everything else is the truth's
     _, cols = hydrodl2_amd.sensitivity.jacobian_columns(model, names)
     start = truth.clone()
@@ -125,7 +138,10 @@ def main():
 
         def both_scores(row):
             cand = row[-1][:, cols].unsqueeze(0).contiguous()
-            if n:
+            if adj:
+                st = hydrodl2_amd.adj_population_period_stats(model, x, row, cand, obs, None, aux_obs, args.aux_key, n,
+                                                              names=names)
+            elif n:
                 st = hydrodl2_amd.population_period_stats(model, x, row, cand, obs, None, aux_obs, args.aux_key, n, names=names)
             else:
                 st = hydrodl2_amd.population_joint_stats(model, x, row, cand, obs, aux_obs, args.aux_key, names=names)

@@ -14,7 +14,8 @@ from hydrodl2_amd.calibrate import calibrate, lm_step, normal_equations
 from hydrodl2_amd.uncertainty import covariance_factor, parameter_covariance, predictive_variance
 from hydrodl2_amd.population import (population_cost, population_joint_stats, population_period_stats, population_score,
                                      population_search, population_stats)
-from hydrodl2_amd.adj_population import adj_population_cost, adj_population_search, adj_population_stats
+from hydrodl2_amd.adj_population import (adj_population_cost, adj_population_period_stats, adj_population_search,
+                                         adj_population_stats)
 
 __version__ = "0.1.0"
 
@@ -23,4 +24,4 @@ __all__ = ["__version__", "available_models", "available_modules", "load_model",
            "normal_equations", "lm_step", "calibrate", "parameter_covariance", "covariance_factor", "predictive_variance",
            "population_cost", "population_search", "population_stats", "population_score", "population_joint_stats",
            "population_period_stats",
-           "adj_population_cost", "adj_population_stats", "adj_population_search"]
+           "adj_population_cost", "adj_population_stats", "adj_population_period_stats", "adj_population_search"]

@@ -152,6 +152,8 @@ class PopJoint(C.Structure):
 
 
 POP_NO_AUX = -1     # HBVX_POP_NO_AUX: hbvx_population_period without an aux term
+# the storages hbvx_adj_population_period can score beside streamflow: HBVX_ADJ_AUX_*, the index of the solved state
+ADJ_POP_AUX_SERIES = {"SNOWPACK": 0, "MELTWATER": 1, "SM": 2, "SUZ": 3, "SLZ": 4}
 
 
 class PopPeriod(C.Structure):
@@ -186,7 +188,7 @@ OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forwa
                     "hbvx_gram_workspace_bytes", "hbvx_quadform", "hbvx_quadform_workspace_bytes",
                     "hbvx_population_cost", "hbvx_population_stats",
                     "hbvx_adj_population_cost", "hbvx_adj_population_stats", "hbvx_population_joint",
-                    "hbvx_population_period"]
+                    "hbvx_population_period", "hbvx_adj_population_period"]
 
 
 class HbvxError(RuntimeError):
@@ -365,6 +367,11 @@ class Library:
         if "hbvx_population_period" not in self.missing:
             d.hbvx_population_period.restype = C.c_int
             d.hbvx_population_period.argtypes = [C.POINTER(Desc), C.POINTER(PopPeriod), C.c_void_p]
+            if d.hbvx_sizeof(13) != C.sizeof(PopPeriod):
+                raise HbvxError(f"{path}: layout mismatch for PopPeriod: {d.hbvx_sizeof(13)} != {C.sizeof(PopPeriod)}")
+        if "hbvx_adj_population_period" not in self.missing:    # the struct of the one above
+            d.hbvx_adj_population_period.restype = C.c_int
+            d.hbvx_adj_population_period.argtypes = [C.POINTER(Desc), C.POINTER(PopPeriod), C.c_void_p]
             if d.hbvx_sizeof(13) != C.sizeof(PopPeriod):
                 raise HbvxError(f"{path}: layout mismatch for PopPeriod: {d.hbvx_sizeof(13)} != {C.sizeof(PopPeriod)}")
         if d.hbvx_version() != ABI_VERSION:
@@ -577,6 +584,13 @@ class Library:
         self._check(self.dll.hbvx_population_period(None if desc is None else C.byref(desc),
                                                     None if pq is None else C.byref(pq), C.c_void_p(stream)),
                     "hbvx_population_period")
+
+    def adj_population_period(self, desc, pq, stream: int):
+        """hbvx_adj_population_period; `desc` / `pq` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_adj_population_period")
+        self._check(self.dll.hbvx_adj_population_period(None if desc is None else C.byref(desc),
+                                                        None if pq is None else C.byref(pq), C.c_void_p(stream)),
+                    "hbvx_adj_population_period")
 
     def adj_population_cost(self, desc, pop, stream: int):
         """hbvx_adj_population_cost; `desc` / `pop` may be None (the ABI's own refusals are under test)."""

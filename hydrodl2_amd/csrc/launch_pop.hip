@@ -1,12 +1,13 @@
 // launch_pop.hip -- the entry points of the population evaluation: hbvx_population_cost, hbvx_population_stats and
 // hbvx_population_joint (hbv_pop.h), hbvx_population_period (hbv_pop_period.h), and the first two's twins for the implicit scheme, hbvx_adj_population_cost and hbvx_adj_population_stats
-// (hbv_adj_pop.h).
+// (hbv_adj_pop.h), and hbvx_adj_population_period (hbv_adj_pop_period.h).
 #include "hbvx_host.h"
 #include "hbv_pop.h"
 #include "hbv_pop_period.h"
 #define HBVX_CHUNK_NO_SHARED_KERNELS
 #include "hbv_chunked.h"        // (first: hbv_adj_kernels.h uses its XCD-aware block map)
 #include "hbv_adj_pop.h"
+#include "hbv_adj_pop_period.h"
 
 using namespace hbvx;
 using namespace hbvx_host;
@@ -303,6 +304,80 @@ extern "C" int hbvx_adj_population_stats(const hbvx_desc *d, const hbvx_pop_stat
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "hbvx_adj_population_stats launch");
+    return HBVX_OK;
+}
+
+template <int TR, bool AUX>
+static void launch_adj_pop_period(const PopPeriodArgs &q, void *stream)
+{
+    const PopArgs &a = q.j.s.a;
+    AdjFew few;
+    const bool is_few = adj_pop_few(&a.d, few);
+    const dim3 grid = pop_grid(a);
+    with_adj(&a.d, is_few, [&](auto be, auto fw) {
+        hipLaunchKernelGGL((k_adj_pop_period<be, fw, TR, AUX>), grid, dim3(64), 0, (hipStream_t)stream, q, few);
+    });
+}
+
+template <int TR>
+static void launch_adj_pop_period(const PopPeriodArgs &q, void *stream)
+{
+    if (q.has_aux) launch_adj_pop_period<TR, true>(q, stream);
+    else launch_adj_pop_period<TR, false>(q, stream);
+}
+
+extern "C" int hbvx_adj_population_period(const hbvx_desc *d, const hbvx_pop_period *pq, void *stream)
+{
+    const char *who = "hbvx_adj_population_period";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!pq) return fail_as(who, HBVX_E_NULL, "pq is NULL");
+    const hbvx_pop_joint *pj = &pq->joint;
+    PopPeriodArgs q;
+    PopJointArgs &j = q.j;
+    rc = prepare(who, d, &pj->flow.pop, j.s.a, true);
+    if (rc) return rc;
+    rc = prepare_stats(who, &pj->flow, j.s);
+    if (rc) return rc;
+    const int t_out = d->T - pj->flow.pop.t_first;
+    if (!pq->flow_end) return fail_as(who, HBVX_E_NULL, "flow_end is NULL");
+    if (pq->n_flow_periods < 1 || pq->n_flow_periods > t_out)
+        return fail_as(who, HBVX_E_SHAPE, "n_flow_periods must be in 1..T - t_first");
+    q.has_aux = pj->aux_series != HBVX_POP_NO_AUX;
+    j = PopJointArgs{j.s, pj->aux_series, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    q.n_flow = pq->n_flow_periods;
+    q.flow_end = pq->flow_end;
+    q.n_aux = 0;
+    q.aux_end = nullptr;
+    if (q.has_aux) {
+        if (pj->aux_series < HBVX_ADJ_AUX_SNOWPACK || pj->aux_series > HBVX_ADJ_AUX_SLZ)
+            return fail_as(who, HBVX_E_UNSUPPORTED, "aux_series must be HBVX_POP_NO_AUX or HBVX_ADJ_AUX_SNOWPACK .. _SLZ "
+                                                    "(a storage index 0..4)");
+        if (!pj->aux_target) return fail_as(who, HBVX_E_NULL, "aux_target is NULL");
+        if (!pj->aux_shift) return fail_as(who, HBVX_E_NULL, "aux_shift is NULL");
+        if (!pj->aux_sse || !pj->aux_s1 || !pj->aux_s2 || !pj->aux_s3)
+            return fail_as(who, HBVX_E_NULL, "aux_sse / aux_s1 / aux_s2 / aux_s3 is NULL");
+        if (!pq->aux_end) return fail_as(who, HBVX_E_NULL, "aux_end is NULL");
+        if (pq->n_aux_periods < 1 || pq->n_aux_periods > t_out)
+            return fail_as(who, HBVX_E_SHAPE, "n_aux_periods must be in 1..T - t_first");
+        j.aux_target = pj->aux_target;
+        j.aux_w = pj->aux_w;
+        j.aux_shift = pj->aux_shift;
+        j.aux_sse = pj->aux_sse;
+        j.aux_s1 = pj->aux_s1;
+        j.aux_s2 = pj->aux_s2;
+        j.aux_s3 = pj->aux_s3;
+        j.aux_sim = pj->aux_sim;
+        q.n_aux = pq->n_aux_periods;
+        q.aux_end = pq->aux_end;
+    }
+    switch (pj->flow.transform) {
+    case HBVX_POP_T_SQRT: launch_adj_pop_period<hbvx_popk::T_SQRT>(q, stream); break;
+    case HBVX_POP_T_LOG: launch_adj_pop_period<hbvx_popk::T_LOG>(q, stream); break;
+    default: launch_adj_pop_period<hbvx_popk::T_NONE>(q, stream);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "hbvx_adj_population_period launch");
     return HBVX_OK;
 }
 

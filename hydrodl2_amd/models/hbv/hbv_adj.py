@@ -190,6 +190,16 @@ class HbvAdj(torch.nn.Module):
         return adj_population_stats(self, x_dict, parameters, candidates, target, names, weights, transform, eps,
                                     return_series)
 
+    def population_period_stats(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor,
+                                candidates: torch.Tensor, target, periods=None, aux_target=None, aux_key=None,
+                                aux_periods=None, names=None, weights=None, aux_weights=None, transform: str = 'none',
+                                eps=None, return_series: bool = False) -> dict:
+        """Scores against period means of 'flow_sim' and, optionally, of one storage ('SNOWPACK', 'MELTWATER', 'SM',
+        'SUZ', 'SLZ'), per candidate: hydrodl2_amd.adj_population_period_stats(self, ...), see there."""
+        from hydrodl2_amd.adj_population import adj_population_period_stats
+        return adj_population_period_stats(self, x_dict, parameters, candidates, target, periods, aux_target, aux_key,
+                                           aux_periods, names, weights, aux_weights, transform, eps, return_series)
+
     def population_search(self, x_dict: dict[str, torch.Tensor], parameters: torch.Tensor, target, **kwargs):
         """Per-basin shrinking random search over the static row: hydrodl2_amd.adj_population_search(self, ...)."""
         from hydrodl2_amd.adj_population import adj_population_search

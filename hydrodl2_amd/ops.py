@@ -1209,9 +1209,42 @@ def adj_population_stats(rec: PathRecord, cand_sources: dict, route_cands, targe
     return (sse,) + moments + (sim,)
 
 
+def adj_population_period(rec: PathRecord, cand_sources: dict, route_cands, target_t: torch.Tensor,
+                          w: Optional[torch.Tensor], shift: torch.Tensor, eps: Optional[torch.Tensor], transform: str,
+                          flow_end: torch.Tensor, aux_series: Optional[int] = None,
+                          aux_target: Optional[torch.Tensor] = None, aux_w: Optional[torch.Tensor] = None,
+                          aux_shift: Optional[torch.Tensor] = None, aux_end: Optional[torch.Tensor] = None,
+                          t_first: int = 0, want_sim: bool = False):
+    """`population_period` for a recorded call of HbvAdjPath, through hbvx_adj_population_period (include/hbvx.h): the
+    same arguments and results, except that aux_series is the index of one of the five solved storages (among
+    _abi.ADJ_POP_AUX_SERIES' values), whose ensemble mean at the end of each day is the aux value."""
+    what = "adj_population_period"
+    if transform not in _abi.POP_TRANSFORMS:
+        raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
+    if transform == "log" and eps is None:
+        raise ValueError(f"{what}: transform 'log' needs eps")
+    _require_adj_record(what, rec)
+    aux = None
+    if aux_series is None:
+        if any(t is not None for t in (aux_target, aux_w, aux_shift, aux_end)):
+            raise ValueError(f"{what}: aux arguments without aux_series")
+    else:
+        if aux_series not in _abi.ADJ_POP_AUX_SERIES.values():
+            raise ValueError(f"{what}: aux_series must be one of {sorted(_abi.ADJ_POP_AUX_SERIES.values())} "
+                             f"(storage indices), got {aux_series!r}")
+        if aux_target is None or aux_shift is None or aux_end is None:
+            raise ValueError(f"{what} needs aux_target, aux_shift and aux_end with aux_series")
+        aux = (aux_series, aux_target, aux_w, aux_shift)
+    sse, moments, sim, aux_out = _population(what, "hbvx_adj_population_period", lambda lib: lib.adj_population_period,
+                                             rec, cand_sources, route_cands, target_t, w, t_first, want_sim,
+                                             (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None),
+                                             aux, (flow_end, aux_end))
+    return (sse,) + moments + (sim,), aux_out
+
+
 def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: dict, route_cands, target, w, t_first,
                 want_sim, stats, aux=None, periods=None):
-    """What the six population calls share -- stats None: the cost, stats = (transform id, shift, eps): the cost and the
+    """What the seven population calls share -- stats None: the cost, stats = (transform id, shift, eps): the cost and the
     moment chains, aux = (flux index, target, w, shift) with stats: the aux term's four chains beside them, periods =
     (flow_end, aux_end or None) with stats: hbvx_population_period's calendars, with targets, weights and series per
     period and aux optional; `entry` the export's name and `call_of(lib)` its Library method -- the checks, the

@@ -18,8 +18,9 @@ series -- and `population_search(aux_target=...)` minimises a weighted sum of th
 series (hbvx_population_period): each series is averaged over its periods inside the kernel, the chains take one step
 per period, and `population_search(periods=..., aux_periods=...)` searches on those scores.
 
-Hbv, Hbv_1_1p and Hbv_2 only.  HbvAdj has the first three calls in adj_population.py; the joint and the period call are
-not built for it (its kernel is a separate family), nor for the hourly and multi-timescale models.  The aux series is not
+Hbv, Hbv_1_1p and Hbv_2 only.  HbvAdj has the first three calls and a period call of its own in adj_population.py
+(`adj_population_period_stats`: its second series is one of its five storages); nothing here is built for the hourly and
+multi-timescale models.  The aux series is not
 transformed, there is one per launch, calendars are shared by all basins, and there is no joint `calibrate`: two
 `normal_equations` calls can be summed by the caller.
 """
@@ -257,14 +258,15 @@ def population_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, 
 AUX_KEYS = tuple(_abi.POP_AUX_SERIES)       # 'srflow_no_rout', 'ssflow_no_rout', 'gwflow_no_rout', 'AET_hydro', 'SWE'
 
 
-def _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what, rows=None):
+def _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what, rows=None, keys=AUX_KEYS):
     """What can be refused about the aux term without running the model.  rows: the leading size of aux_target and
-    aux_weights where it is not T_out (the periods of `population_period_stats`)."""
+    aux_weights where it is not T_out (the periods of `population_period_stats`).  keys: the aux keys the caller's
+    kernel offers (`adj_population_period_stats`: the five storages)."""
     if aux_target is None or aux_key is None:
         raise ValueError(f"{what}: aux_target and aux_key go together "
                          f"({'aux_target' if aux_target is None else 'aux_key'} is missing)")
-    if aux_key not in _abi.POP_AUX_SERIES:
-        raise ValueError(f"{what}: aux_key must be one of {list(AUX_KEYS)}, got {aux_key!r}")
+    if aux_key not in keys:
+        raise ValueError(f"{what}: aux_key must be one of {list(keys)}, got {aux_key!r}")
     dev = x_dict['x_phy'].device
     n, of = (req.T_out, "days after the warm-up") if rows is None else (rows, "periods of its calendar")
     for name, t, shapes in (("aux_target", aux_target, ((n, req.B), (n, req.B, 1))),

@@ -617,7 +617,8 @@ int hbvx_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void *st
  * and transform; (5) argument errors are reported before anything is launched: hbvx_population_stats', and HBVX_E_NULL
  * (pj, aux_target, aux_shift, aux_sse, aux_s1, aux_s2, aux_s3), HBVX_E_UNSUPPORTED (an aux_series other than
  * HBVX_F_Q0, _Q1, _Q2, _AET, _SWE: HBVX_F_QSIM is the flow term, HBVX_F_RECHARGE .. HBVX_F_CAPILLARY are not offered).
- * Not built: HBVX_MODEL_HBVADJ (its population kernel is a separate family) and HBVX_MODEL_HOURLY (HBVX_E_UNSUPPORTED),
+ * Not built: HBVX_MODEL_HBVADJ (its population kernel is a separate family: hbvx_adj_population_period scores one of
+ * its storages) and HBVX_MODEL_HOURLY (HBVX_E_UNSUPPORTED),
  * a transform of the aux value, more than one aux series per launch, sums over several days before the comparison. */
 typedef struct hbvx_pop_joint {
     hbvx_pop_stats flow;           /* the flow term: hbvx_population_stats' argument, unchanged in meaning */
@@ -658,7 +659,8 @@ int hbvx_population_joint(const hbvx_desc *d, const hbvx_pop_joint *pj, void *st
  * HBVX_E_SHAPE (n_flow_periods, or n_aux_periods with an aux term, outside 1..T - t_first), HBVX_E_UNSUPPORTED (an
  * aux_series that is neither HBVX_POP_NO_AUX nor one of the five).  csrc/hbv_pop_period.h has the kernel,
  * csrc/hbv_pop.h the arithmetic (hbvx_popk::PeriodMean, BasinStats::score, AuxStats::push).
- * Not built: period sums as an input form (divide by the lengths), per-basin calendars, HBVX_MODEL_HBVADJ / _HOURLY. */
+ * Not built: period sums as an input form (divide by the lengths), per-basin calendars, HBVX_MODEL_HOURLY;
+ * HBVX_MODEL_HBVADJ has hbvx_adj_population_period below. */
 #define HBVX_POP_NO_AUX (-1)
 
 typedef struct hbvx_pop_period {
@@ -694,6 +696,31 @@ int hbvx_population_period(const hbvx_desc *d, const hbvx_pop_period *pq, void *
  * family (the tiled stepper, the staged pipeline). */
 int hbvx_adj_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream);
 int hbvx_adj_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void *stream);
+
+/* Population scores of the implicit scheme against period means, with an optional observed STORAGE beside streamflow
+ * (optional export; a library may lack it): hbvx_population_period for HBVX_MODEL_HBVADJ, on the same struct.  The day
+ * loop, the candidates, the Newton policy, Q and its ensemble mean q are hbvx_adj_population_stats'; the routing runs on
+ * every day; the calendars, the period means, the transform of the flow's period mean, the eight chains, the per-PERIOD
+ * targets / weights / series and HBVX_POP_NO_AUX are hbvx_population_period's, line by line.  What differs is the aux
+ * value: the implicit scheme solves for its five storages every day, and the aux value of a day is the ensemble mean
+ * of one of them at the day's solved state,
+ *   v = (sum over the members of x[k]) * (1 / M),   k = joint.aux_series = HBVX_ADJ_AUX_SNOWPACK .. HBVX_ADJ_AUX_SLZ,
+ * the RAW x[k] -- what hbvx_adj_forward writes to row t + 1 of its trajectory, not the value clamped at zero that
+ * enters Q -- never routed and never transformed.  Fluxes (evapotranspiration, the runoff components) are not offered:
+ * the staged solve does not keep them.
+ * Guarantees: hbvx_population_period's (1)-(3) and (5); (4) with both calendars daily and no aux term, pop.cost,
+ * s1..s3 and pop.sim have hbvx_adj_population_stats' bits; with an aux term the flow outputs keep theirs; (6) argument
+ * errors are reported before anything is launched: hbvx_adj_population_stats' (the model, the Newton policy,
+ * adj_stop == 1, muwts) and hbvx_population_period's, with HBVX_E_UNSUPPORTED for an aux_series that is neither
+ * HBVX_POP_NO_AUX nor a storage index 0..4.  csrc/hbv_adj_pop_period.h has the kernel.
+ * Not built: fluxes as the aux series, a transform of the aux value, more than one aux series per launch, period sums,
+ * per-basin calendars. */
+#define HBVX_ADJ_AUX_SNOWPACK 0
+#define HBVX_ADJ_AUX_MELTWATER 1
+#define HBVX_ADJ_AUX_SM 2
+#define HBVX_ADJ_AUX_SUZ 3
+#define HBVX_ADJ_AUX_SLZ 4
+int hbvx_adj_population_period(const hbvx_desc *d, const hbvx_pop_period *pq, void *stream);
 
 /* Zero `bytes` bytes at `ptr` (streaming non-temporal stores).  The autograd contract of the plug-in wants
  * gradient tensors shaped like the raw parameter tensor [T,B,ny] (hbv.py:211-246: static parameters read
