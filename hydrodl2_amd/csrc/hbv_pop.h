@@ -1,19 +1,22 @@
-// hbv_pop.h -- population evaluation (hbvx_population_cost, include/hbvx.h): the weighted squared error of the routed
-// ensemble-mean streamflow of P candidate static-parameter sets per basin, one number per (candidate, basin), from one
-// launch that writes nothing else -- and (hbvx_population_stats) the same launch with three more chains per (candidate,
-// basin), on the raw, the square-root or the log flow, from which NSE, KGE, correlation, variability and bias follow on
-// the host: four [P,B] numbers instead of one, still no series -- and (hbvx_population_joint) that launch with the same
-// four chains on a second series beside streamflow, the day's ensemble mean of one un-routed flux (AET, SWE, Q0, Q1, Q2):
-// eight [P,B] numbers.
+// hbv_pop.h -- population evaluation of the explicit models (include/hbvx.h): for P candidate static-parameter sets per
+// basin, from one launch that writes no series it is not asked for,
+//   hbvx_population_cost    the weighted squared error of the routed ensemble-mean streamflow: one [P,B] number;
+//   hbvx_population_stats   that and three more chains per (candidate, basin), on the raw, the square-root or the log
+//                           flow, from which NSE, KGE, correlation, variability and bias follow on the host: four;
+//   hbvx_population_joint   the same four chains on a second series beside streamflow, the day's ensemble mean of one
+//                           un-routed flux (AET, SWE, Q0, Q1, Q2): eight;
+//   hbvx_population_period  the eight with the routed flow and the aux flux averaged over the periods of two calendars
+//                           -- 8-day composites, months -- before they meet their targets: the sums run once per period
+//                           instead of once per day, and the optional series are [P,K,B] period means.
+// One kernel template, k_pop below, is the day loop of all four; launch_pop.hip has the entry points.
 //
 // What happens to a basin's ensemble mean after the day step -- the normalised gamma unit hydrograph, the 15-day
 // window, the causal convolution and the residual chain -- is hbvx_popk::Basin below and compiles for the host as
 // well (tests/hosttest/pop_host.cpp), so the CPU tier checks it without a GPU; the kernel maps lanes onto it.
 // hbvx_popk::BasinStats is Basin plus the transform and the three moment chains (tests/hosttest/popstats_host.cpp).
 // hbvx_popk::AuxStats is the aux term's four chains (tests/hosttest/popjoint_host.cpp).
-// k_pop maps lanes onto the one struct, k_pop_stats<TR> onto the other, k_pop_joint<TR> onto a BasinStats and an AuxStats.
-// hbvx_popk::PeriodMean is the mean over a period that hbvx_population_period (hbv_pop_period.h) puts between each of the
-// two values and its chains (tests/hosttest/popperiod_host.cpp).
+// hbvx_popk::PeriodMean is the mean over a period that hbvx_population_period puts between each of the two values and
+// its chains (tests/hosttest/popperiod_host.cpp).
 #pragma once
 
 #include <math.h>
@@ -123,21 +126,12 @@ struct BasinStats : Basin {
     HBVX_POP_HD float push(float q, float target, float w, bool counted)
     {
         const float y = Basin::push(q, 0.0f, 0.0f, false);
-        if (counted) {
-            const float yt = transform<TR>(y);
-            const float r = yt - target;
-            cost = __builtin_fmaf(w * r, r, cost);
-            const float dd = yt - m, e = target - m;
-            s1 = __builtin_fmaf(w, dd, s1);
-            s2 = __builtin_fmaf(w * dd, dd, s2);
-            s3 = __builtin_fmaf(w * dd, e, s3);
-        }
+        if (counted) score<TR>(y, target, w);
         return y;
     }
 
-    // The lines of a counted day of push() on a value that is already there -- hbvx_population_period's period mean of
-    // y: v' = transform(v), then r, d, e and the four chains against `target` (already transformed) and w.  A
-    // restatement: push() keeps its text (k_pop_stats and k_pop_joint are pinned).  A change belongs in both.
+    // A counted day of push() on a value that is already there -- also hbvx_population_period's period mean of y:
+    // v' = transform(v), then r, d, e and the four chains against `target` (already transformed) and w.
     template <int TR>
     HBVX_POP_HD void score(float v, float target, float w)
     {
@@ -194,6 +188,8 @@ struct AuxStats {
 
 #if defined(__HIPCC__)
 
+#include <type_traits>
+
 #include "hbv_lane.h"
 
 namespace hbvx {
@@ -220,25 +216,95 @@ struct PopJointArgs {
     float *aux_sim;             // [P, T - t_first, B] or NULL
 };
 
+struct PopPeriodArgs {
+    PopJointArgs j;             // the two terms: hbvx_population_joint's arguments, targets / weights / series per PERIOD
+    int has_aux;                // 0: aux_series == HBVX_POP_NO_AUX, nothing of j's aux part is read or written
+    int n_flow, n_aux;          // KF, KA
+    const int *flow_end, *aux_end;      // [KF], [KA]: closing days relative to t_first, ascending
+};
+
+// each struct's view of the ones nested in it
+__host__ __device__ __forceinline__ const PopArgs &pop_args(const PopArgs &A) { return A; }
+__host__ __device__ __forceinline__ const PopArgs &pop_args(const PopStatsArgs &A) { return A.a; }
+__host__ __device__ __forceinline__ const PopArgs &pop_args(const PopJointArgs &A) { return A.s.a; }
+__host__ __device__ __forceinline__ const PopArgs &pop_args(const PopPeriodArgs &A) { return A.j.s.a; }
+__host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopStatsArgs &A) { return A; }
+__host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopJointArgs &A) { return A.s; }
+__host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopPeriodArgs &A) { return A.j.s; }
+__host__ __device__ __forceinline__ const PopJointArgs &joint_args(const PopJointArgs &A) { return A; }
+__host__ __device__ __forceinline__ const PopJointArgs &joint_args(const PopPeriodArgs &A) { return A.j; }
+
+constexpr int T_COST = -1;      // TR of the cost-only instances (the others are hbvx_popk::T_*)
+
+template <int TR> struct PopBasin { using type = hbvx_popk::BasinStats; };
+template <> struct PopBasin<T_COST> { using type = hbvx_popk::Basin; };
+
 // ---------------------------------------------------------------------------
-// k_pop<MODEL, BETAET>: k_fwd's day loop (the same Step::fwd instance, the same one-day-ahead register prefetch of the
-// forcings and the dynamic rows, the same ensemble sum and weights) with the lane mapping of k_tan's several-direction
-// form: one wave per workgroup, blockIdx.x the wave's group of basins, blockIdx.y the CANDIDATE, one lane per (basin,
-// member).  A candidate is a wave of its own that reads the forcings itself -- they come out of the L2 / Infinity
-// Cache after the first candidate's pass -- and nothing is shared between candidates inside the kernel: what many
-// candidates in one launch gain over a forward each is that their waves fill the SIMDs one forward leaves idle, and
-// that nothing but [P,B] costs is written.  The candidate index is uniform over the wave, so a candidate's base
-// address is scalar.  Several candidates per lane are not tried: k_tan measured that form and lost at every size
-// (hbv_tan.h), for a reason that holds here too (the loop is bound by instruction issue, registers cost resident waves).
+// k_pop<MODEL, BETAET, TR, Args>: the one day loop of the explicit models' population entry points.  It is k_fwd's day
+// loop (the same Step::fwd instance, the same one-day-ahead register prefetch of the forcings and the dynamic rows, the
+// same ensemble sum and weights) with the lane mapping of k_tan's several-direction form: one wave per workgroup,
+// blockIdx.x the wave's group of basins, blockIdx.y the CANDIDATE, one lane per (basin, member).  A candidate is a wave
+// of its own that reads the forcings itself -- they come out of the L2 / Infinity Cache after the first candidate's
+// pass -- and nothing is shared between candidates inside the kernel: what many candidates in one launch gain over a
+// forward each is that their waves fill the SIMDs one forward leaves idle, and that nothing but [P,B] sums is written.
+// The candidate index is uniform over the wave, so a candidate's base address is scalar.  Several candidates per lane
+// are not tried: k_tan measured that form and lost at every size (hbv_tan.h), for a reason that holds here too (the
+// loop is bound by instruction issue, registers cost resident waves).
 //
-// After ens_sum every lane of a basin holds the mean, so every lane carries the basin's window and cost chain (the
-// same values: no shuffle, no divergence) and the leader stores.  The bits of cost[c,b] and sim[c,:,b] depend on
-// candidate c's values alone: c enters addresses only.
+// After the ensemble sum every lane of a basin holds the mean, so every lane carries the basin's window and chains (the
+// same values: no shuffle, no divergence) and the leader stores.  The bits of what candidate c gets depend on c's values
+// alone: c enters addresses only.
+//
+// Args is the form, each one the form before it and something more:
+//   PopArgs        TR = T_COST; lanes map onto hbvx_popk::Basin: the squared error of the routed mean flow.
+//   PopStatsArgs   TR = T_NONE / T_SQRT / T_LOG; lanes map onto BasinStats: the shift and eps of the lane's basin are two
+//                  more registers, the three moment chains three more, the leader stores four numbers.  TR is a template
+//                  parameter: a wave-uniform switch inside the day loop would keep the log's registers live in every
+//                  transform.
+//   PopJointArgs   an AuxStats beside the BasinStats: per day one more ensemble sum, of the flux the aux term scores, and
+//                  four more chains on it.  The aux target and weight join the one-day-ahead prefetch.  Which flux is
+//                  taken is a run-time select on aux_series, uniform over the launch, not a template parameter: the five
+//                  values are all live at the end of Step::fwd anyway (Q is their sum, SP3 is the next state, ET has just
+//                  closed the soil balance), so the select keeps little alive that a fixed choice would free -- built
+//                  both ways, a fixed AET or SWE came out one VGPR below the select (three in one HBV 1.1p instance;
+//                  DESIGN.md has the table), never across an occupancy step, at five times the instantiations.
+//   PopPeriodArgs  (PERIOD) a PeriodMean between each of the two values and its chains.  Each calendar has a cursor k, the
+//                  day its period opened and the day it closes, all relative to t_first and uniform over the wave (they
+//                  come from kernel arguments and scalar loads).  A scored day adds to the period's accumulator; a day
+//                  that closes a period divides once, runs the four chains against row k of the target, lets the leader
+//                  store the mean, moves the cursor and loads the next closing day and the next period's target row and
+//                  weight -- at the OPENING of the period that needs them, so that its close does not wait on memory;
+//                  they are not in the per-day prefetch.  A cursor stops at its count: no closing day and no target row
+//                  beyond K is read, whatever the calendar holds.  A closing day that is not ahead of the cursor's day (a
+//                  calendar that does not ascend) is never met: the periods from there on stay open, nothing else
+//                  happens.  Days after the last closing day are simulated and scored nowhere.  Without an aux term
+//                  (has_aux == 0, uniform over the launch; a run-time flag in this form only) the aux value is zero
+//                  through the butterfly and nothing aux is accumulated, loaded or stored.
+// The flow's operations are the same ones on the same values in every form, and the aux term's in both of its forms:
+// tests/test_population_stats_gpu.py, test_population_joint_gpu.py and test_population_period_gpu.py (daily calendars)
+// hold each form to the bits of the one before it.
+//
+// Every instance is instruction for instruction the kernel it had when the four forms were four texts (profiles/
+// r21_population_one_source.md), so what was measured on those holds for these.  The compiler's schedule follows the
+// order and shape of the statements, and four things keep it:
+//   - the day's observations are loop-local constants (`obs = nxo` at the top of the iteration) in the daily forms; the
+//     period form's are variables of their own that live across days (`pobs`), not the prefetched ones reused;
+//   - the day count in the base address of `sim` / `aux_sim` is the inline expression `(T - t_first)` in the daily
+//     forms, not a variable shared with the period form's KF / KA;
+//   - `has_aux` is the constant true in the joint form;
+//   - the cost form's one store indexes `pp.cost[c * d.B + L.b]` in place; the other forms share `at` between their
+//     stores (the cost form through `at` computes the index before it loads the pointer).
+// A fix to the day's arithmetic belongs in Step::fwd, a fix to the loop around it here, once.
 // ---------------------------------------------------------------------------
-template <int MODEL, bool BETAET>
-__global__ void __launch_bounds__(64) k_pop(const PopArgs A)
+template <int MODEL, bool BETAET, int TR, typename Args>
+__global__ void __launch_bounds__(64) k_pop(const Args Q)
 {
+    constexpr bool STATS = !std::is_same<Args, PopArgs>::value;
+    constexpr bool PERIOD = std::is_same<Args, PopPeriodArgs>::value;
+    constexpr bool JOINT = PERIOD || std::is_same<Args, PopJointArgs>::value;      // the forms with an aux term
+    static_assert(STATS == (TR != T_COST), "TR = T_COST is the cost form's, and its alone");
     constexpr int NP = NParam<MODEL, BETAET>::value;
+    const PopArgs &A = pop_args(Q);
     const hbvx_desc &d = A.d;
     const hbvx_pop &pp = A.pop;
     const int lgMp = A.lgMp;
@@ -275,8 +341,10 @@ __global__ void __launch_bounds__(64) k_pop(const PopArgs A)
 #pragma unroll
     for (int k = 0; k < 5; k++) st[k] = d.state_in ? d.state_in[k * N + L.n] : 0.001f;
 
-    hbvx_popk::Basin bs;
-    bs.start(A.has_route != 0);
+    typename PopBasin<TR>::type bs;
+    if constexpr (STATS)
+        bs.start(A.has_route != 0, stats_args(Q).shift[L.b], TR == hbvx_popk::T_LOG ? stats_args(Q).eps[L.b] : 0.0f);
+    else bs.start(A.has_route != 0);
     if (A.has_route) {      // route_ab's lines (hbvx.hip) on the candidate's routing inputs
         const hbvx_route_desc &r = A.r;
         const float va = pp.ra ? pp.ra[c * pp.r_c_stride + (int64_t)L.b * pp.r_b_stride] : r.ra[(int64_t)L.b * r.r_stride];
@@ -286,299 +354,77 @@ __global__ void __launch_bounds__(64) k_pop(const PopArgs A)
         hbvx_popk::gamma_taps(descale_(ua, r.a_lo, r.a_hi), descale_(ub, r.b_lo, r.b_hi), r.L, bs.uh);
     }
 
-    const float *xb = d.x + (int64_t)L.b * d.x_b_stride;
-    const float *mu = d.muwts ? d.muwts + (int64_t)L.b * d.mu_b_stride + L.j : nullptr;
-    const float invM = 1.0f / (float)d.M;
-    const float act = L.active ? 1.0f : 0.0f;
-    const float *tg = pp.target + L.b;              // row t - t_first of [T - t_first, B]
-    const float *wt = pp.w ? pp.w + L.b : nullptr;
-    float *sim = pp.sim ? pp.sim + c * (int64_t)(T - t_first) * d.B + L.b : nullptr;
-
-    // one-step-ahead register prefetch of the per-step inputs (k_fwd's), the observation and its weight with them
-    float nxf[3], nxd[NP], nxo = 0.0f, nxw = 1.0f;
-    {
-        const float *xr = xb;
-        nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
-#pragma unroll
-        for (int i = 0; i < NP; i++) nxd[i] = ((dmask >> i) & 1) ? dynp[i][0] : 0.f;
-        if (t_first == 0) {
-            nxo = tg[0];
-            if (wt) nxw = wt[0];
-        }
-    }
-
-    for (int t = 0; t < T; t++) {
-        Step<MODEL, BETAET> s;
-        s.P = nxf[0]; s.Tf = nxf[1]; s.PET = nxf[2];
-        float cur[NP];
-#pragma unroll
-        for (int i = 0; i < NP; i++) cur[i] = nxd[i];
-        const float obs = nxo, wobs = nxw;
-        {
-            const int tn = t + 1 < T ? t + 1 : t;
-            const float *xr = xb + (int64_t)tn * d.x_t_stride;
-            nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
-#pragma unroll
-            for (int i = 0; i < NP; i++)
-                if ((dmask >> i) & 1) nxd[i] = dynp[i][(int64_t)tn * d.p[i].dyn_t_stride];
-            if (tn >= t_first) {
-                const int64_t row = (int64_t)(tn - t_first) * d.B;
-                nxo = tg[row];
-                if (wt) nxw = wt[row];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NP; i++)
-            if ((dmask >> i) & 1) {
-                float v = raw ? sigmoid_dyn_(cur[i]) : cur[i];
-                float pv = descale_(v, d.p[i].lo, d.p[i].hi);
-                if (use_dyn[i]) p[i] = pv;
-            }
-        s.SP = st[0]; s.MW = st[1]; s.SM = st[2]; s.SUZ = st[3]; s.SLZ = st[4];
-        s.template fwd<false, true>(p, nz, ac, elev, 0.f, 0.f);
-        st[0] = s.SP3; st[1] = s.MW3; st[2] = s.SM4; st[3] = s.SUZ4; st[4] = s.SLZ2;
-
-        // the ensemble mean of Q as k_fwd forms series HBVX_F_QSIM
-        const float wq = mu ? mu[(int64_t)t * d.mu_t_stride] : 1.0f;
-        float q = ens_sum((mu ? s.Q * wq : s.Q) * act, lgMp);
-        if (!mu) q = q * invM;
-        const bool counted = t >= t_first;
-        const float y = bs.push(q, obs, wobs, counted);
-        if (counted && sim && L.leader) sim[(int64_t)(t - t_first) * d.B] = y;
-    }
-    if (L.leader) pp.cost[c * d.B + L.b] = bs.cost;
-}
-
-// ---------------------------------------------------------------------------
-// k_pop_stats<MODEL, BETAET, TR>: k_pop on a BasinStats -- the same lanes, the same day loop, the same y; the shift
-// and eps of the lane's basin are two more registers, the three chains three more, and the leader stores four numbers.
-// TR is a template parameter: a wave-uniform switch inside the day loop would keep the log's registers live in every
-// transform.
-//
-// A restatement of k_pop's lines, not a shared body: one body for both (an inlined function template on the struct,
-// with overloads or `if constexpr` at the three places that differ) was built, and every form of it changed k_pop's
-// registers (138 -> 140 for HBV 1.0) and schedule (tools/compare_code.py), which are pinned; so k_pop keeps its text, as
-// k_uh_gamma does above.  A change to either belongs in both: tests/test_population_stats_gpu.py holds the two to the
-// same bits of the squared error and of the series.
-// ---------------------------------------------------------------------------
-template <int MODEL, bool BETAET, int TR>
-__global__ void __launch_bounds__(64) k_pop_stats(const PopStatsArgs S)
-{
-    constexpr int NP = NParam<MODEL, BETAET>::value;
-    const PopArgs &A = S.a;
-    const hbvx_desc &d = A.d;
-    const hbvx_pop &pp = A.pop;
-    const int lgMp = A.lgMp;
-    const LaneId L = lane_id(d, lgMp);
-    const int T = d.T;
-    const int t_first = pp.t_first;
-    const int64_t N = (int64_t)d.B * d.M;
-    const int64_t c = blockIdx.y;
-    const bool raw = d.raw_sigmoid != 0;
-    const float nz = d.nearzero;
-    const float ac = (MODEL == MODEL_HBV20) ? d.ac[L.b] : 0.0f;
-    const float elev = (MODEL == MODEL_HBV20) ? d.elev[L.b] : 0.0f;
-
-    float p[NPARAM_MAX];
-    const float *dynp[NP];
-    bool use_dyn[NP];
-    unsigned dmask = 0;
-#pragma unroll
-    for (int i = 0; i < NP; i++) {
-        const hbvx_param_src &s = d.p[i];
-        const hbvx_pop_src &cs = pp.p[i];
-        float v = cs.sta ? cs.sta[c * cs.c_stride + (int64_t)L.b * cs.b_stride + L.j]
-                         : s.sta[(int64_t)L.b * s.sta_b_stride + L.j];
-        v = raw ? sigmoid_(v) : v;
-        p[i] = descale_(v, s.lo, s.hi);
-        dynp[i] = s.dyn ? s.dyn + (int64_t)L.b * s.dyn_b_stride + L.j : s.sta;
-        use_dyn[i] = s.dyn && !(s.drop && s.drop[L.b]);
-        if (s.dyn) dmask |= 1u << i;
-    }
-#pragma unroll
-    for (int i = NP; i < NPARAM_MAX; i++) p[i] = 0.0f;
-
-    float st[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) st[k] = d.state_in ? d.state_in[k * N + L.n] : 0.001f;
-
-    hbvx_popk::BasinStats bs;
-    bs.start(A.has_route != 0, S.shift[L.b], TR == hbvx_popk::T_LOG ? S.eps[L.b] : 0.0f);
-    if (A.has_route) {      // route_ab's lines (hbvx.hip) on the candidate's routing inputs
-        const hbvx_route_desc &r = A.r;
-        const float va = pp.ra ? pp.ra[c * pp.r_c_stride + (int64_t)L.b * pp.r_b_stride] : r.ra[(int64_t)L.b * r.r_stride];
-        const float vb = pp.rb ? pp.rb[c * pp.r_c_stride + (int64_t)L.b * pp.r_b_stride] : r.rb[(int64_t)L.b * r.r_stride];
-        const float ua = r.raw_sigmoid ? sigmoid_(va) : va;
-        const float ub = r.raw_sigmoid ? sigmoid_(vb) : vb;
-        hbvx_popk::gamma_taps(descale_(ua, r.a_lo, r.a_hi), descale_(ub, r.b_lo, r.b_hi), r.L, bs.uh);
-    }
-
-    const float *xb = d.x + (int64_t)L.b * d.x_b_stride;
-    const float *mu = d.muwts ? d.muwts + (int64_t)L.b * d.mu_b_stride + L.j : nullptr;
-    const float invM = 1.0f / (float)d.M;
-    const float act = L.active ? 1.0f : 0.0f;
-    const float *tg = pp.target + L.b;              // row t - t_first of [T - t_first, B]: the TRANSFORMED target
-    const float *wt = pp.w ? pp.w + L.b : nullptr;
-    float *sim = pp.sim ? pp.sim + c * (int64_t)(T - t_first) * d.B + L.b : nullptr;
-
-    // one-step-ahead register prefetch of the per-step inputs (k_fwd's), the observation and its weight with them
-    float nxf[3], nxd[NP], nxo = 0.0f, nxw = 1.0f;
-    {
-        const float *xr = xb;
-        nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
-#pragma unroll
-        for (int i = 0; i < NP; i++) nxd[i] = ((dmask >> i) & 1) ? dynp[i][0] : 0.f;
-        if (t_first == 0) {
-            nxo = tg[0];
-            if (wt) nxw = wt[0];
-        }
-    }
-
-    for (int t = 0; t < T; t++) {
-        Step<MODEL, BETAET> s;
-        s.P = nxf[0]; s.Tf = nxf[1]; s.PET = nxf[2];
-        float cur[NP];
-#pragma unroll
-        for (int i = 0; i < NP; i++) cur[i] = nxd[i];
-        const float obs = nxo, wobs = nxw;
-        {
-            const int tn = t + 1 < T ? t + 1 : t;
-            const float *xr = xb + (int64_t)tn * d.x_t_stride;
-            nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
-#pragma unroll
-            for (int i = 0; i < NP; i++)
-                if ((dmask >> i) & 1) nxd[i] = dynp[i][(int64_t)tn * d.p[i].dyn_t_stride];
-            if (tn >= t_first) {
-                const int64_t row = (int64_t)(tn - t_first) * d.B;
-                nxo = tg[row];
-                if (wt) nxw = wt[row];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NP; i++)
-            if ((dmask >> i) & 1) {
-                float v = raw ? sigmoid_dyn_(cur[i]) : cur[i];
-                float pv = descale_(v, d.p[i].lo, d.p[i].hi);
-                if (use_dyn[i]) p[i] = pv;
-            }
-        s.SP = st[0]; s.MW = st[1]; s.SM = st[2]; s.SUZ = st[3]; s.SLZ = st[4];
-        s.template fwd<false, true>(p, nz, ac, elev, 0.f, 0.f);
-        st[0] = s.SP3; st[1] = s.MW3; st[2] = s.SM4; st[3] = s.SUZ4; st[4] = s.SLZ2;
-
-        // the ensemble mean of Q as k_fwd forms series HBVX_F_QSIM
-        const float wq = mu ? mu[(int64_t)t * d.mu_t_stride] : 1.0f;
-        float q = ens_sum((mu ? s.Q * wq : s.Q) * act, lgMp);
-        if (!mu) q = q * invM;
-        const bool counted = t >= t_first;
-        const float y = bs.template push<TR>(q, obs, wobs, counted);
-        if (counted && sim && L.leader) sim[(int64_t)(t - t_first) * d.B] = y;      // y, not y'
-    }
-    if (L.leader) {
-        const int64_t at = c * d.B + L.b;
-        pp.cost[at] = bs.cost;
-        S.s1[at] = bs.s1;
-        S.s2[at] = bs.s2;
-        S.s3[at] = bs.s3;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// k_pop_joint<MODEL, BETAET, TR>: k_pop_stats with an AuxStats beside the BasinStats -- the same lanes, grid, candidate
-// axis and day loop, the same y and the same four flow chains (tests/test_population_joint_gpu.py holds them to
-// k_pop_stats' bits); per day one more ensemble sum, of the flux the aux term scores -- in the same butterfly loop as the
-// flow's --, and four more chains on it.  The aux target and weight join the one-day-ahead prefetch.
-//
-// Again a restatement, for the reason given above k_pop_stats: k_pop and k_pop_stats keep their text, registers and
-// schedule.  A change to the day loop belongs in all three.
-//
-// Which flux is taken is a run-time select on J.aux_series, uniform over the launch, not a template parameter: the five
-// values are all live at the end of Step::fwd anyway (Q is their sum, SP3 is the next state, ET has just closed the soil
-// balance), so the select keeps little alive that a fixed choice would free -- built both ways, a fixed AET or SWE came
-// out one VGPR below the select (three in one HBV 1.1p instance; DESIGN.md has the table), never across an occupancy
-// step of the final kernel, at five times the instantiations.
-// ---------------------------------------------------------------------------
-template <int MODEL, bool BETAET, int TR>
-__global__ void __launch_bounds__(64) k_pop_joint(const PopJointArgs J)
-{
-    constexpr int NP = NParam<MODEL, BETAET>::value;
-    const PopStatsArgs &S = J.s;
-    const PopArgs &A = S.a;
-    const hbvx_desc &d = A.d;
-    const hbvx_pop &pp = A.pop;
-    const int lgMp = A.lgMp;
-    const LaneId L = lane_id(d, lgMp);
-    const int T = d.T;
-    const int t_first = pp.t_first;
-    const int64_t N = (int64_t)d.B * d.M;
-    const int64_t c = blockIdx.y;
-    const bool raw = d.raw_sigmoid != 0;
-    const float nz = d.nearzero;
-    const float ac = (MODEL == MODEL_HBV20) ? d.ac[L.b] : 0.0f;
-    const float elev = (MODEL == MODEL_HBV20) ? d.elev[L.b] : 0.0f;
-
-    float p[NPARAM_MAX];
-    const float *dynp[NP];
-    bool use_dyn[NP];
-    unsigned dmask = 0;
-#pragma unroll
-    for (int i = 0; i < NP; i++) {
-        const hbvx_param_src &s = d.p[i];
-        const hbvx_pop_src &cs = pp.p[i];
-        float v = cs.sta ? cs.sta[c * cs.c_stride + (int64_t)L.b * cs.b_stride + L.j]
-                         : s.sta[(int64_t)L.b * s.sta_b_stride + L.j];
-        v = raw ? sigmoid_(v) : v;
-        p[i] = descale_(v, s.lo, s.hi);
-        dynp[i] = s.dyn ? s.dyn + (int64_t)L.b * s.dyn_b_stride + L.j : s.sta;
-        use_dyn[i] = s.dyn && !(s.drop && s.drop[L.b]);
-        if (s.dyn) dmask |= 1u << i;
-    }
-#pragma unroll
-    for (int i = NP; i < NPARAM_MAX; i++) p[i] = 0.0f;
-
-    float st[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) st[k] = d.state_in ? d.state_in[k * N + L.n] : 0.001f;
-
-    hbvx_popk::BasinStats bs;
-    bs.start(A.has_route != 0, S.shift[L.b], TR == hbvx_popk::T_LOG ? S.eps[L.b] : 0.0f);
-    if (A.has_route) {      // route_ab's lines (hbvx.hip) on the candidate's routing inputs
-        const hbvx_route_desc &r = A.r;
-        const float va = pp.ra ? pp.ra[c * pp.r_c_stride + (int64_t)L.b * pp.r_b_stride] : r.ra[(int64_t)L.b * r.r_stride];
-        const float vb = pp.rb ? pp.rb[c * pp.r_c_stride + (int64_t)L.b * pp.r_b_stride] : r.rb[(int64_t)L.b * r.r_stride];
-        const float ua = r.raw_sigmoid ? sigmoid_(va) : va;
-        const float ub = r.raw_sigmoid ? sigmoid_(vb) : vb;
-        hbvx_popk::gamma_taps(descale_(ua, r.a_lo, r.a_hi), descale_(ub, r.b_lo, r.b_hi), r.L, bs.uh);
-    }
-
+    bool has_aux = JOINT;       // uniform over the launch
     hbvx_popk::AuxStats ax;
-    ax.start(J.aux_shift[L.b]);
-    const int aux_series = J.aux_series;        // uniform over the launch
+    int aux_series = 0;
+    if constexpr (PERIOD) has_aux = Q.has_aux != 0;
+    if constexpr (JOINT) {
+        ax.start(has_aux ? joint_args(Q).aux_shift[L.b] : 0.0f);
+        aux_series = joint_args(Q).aux_series;
+    }
 
     const float *xb = d.x + (int64_t)L.b * d.x_b_stride;
     const float *mu = d.muwts ? d.muwts + (int64_t)L.b * d.mu_b_stride + L.j : nullptr;
     const float invM = 1.0f / (float)d.M;
     const float act = L.active ? 1.0f : 0.0f;
-    const float *tg = pp.target + L.b;              // row t - t_first of [T - t_first, B]: the TRANSFORMED target
+    int KF = 0, KA = 0;                             // PERIOD: the calendars' lengths and closing days
+    const int *fend = nullptr, *aend = nullptr;
+    if constexpr (PERIOD) {
+        KF = Q.n_flow, KA = has_aux ? Q.n_aux : 0;
+        fend = Q.flow_end, aend = Q.aux_end;
+    }
+    // row t - t_first of [T - t_first, B], PERIOD: row k of [KF, B]; with STATS the TRANSFORMED target
+    const float *tg = pp.target + L.b;
     const float *wt = pp.w ? pp.w + L.b : nullptr;
-    float *sim = pp.sim ? pp.sim + c * (int64_t)(T - t_first) * d.B + L.b : nullptr;
+    float *sim;
+    if constexpr (PERIOD) sim = pp.sim ? pp.sim + c * (int64_t)KF * d.B + L.b : nullptr;
+    else sim = pp.sim ? pp.sim + c * (int64_t)(T - t_first) * d.B + L.b : nullptr;
     // the same rows of the aux target and its weights, addressed from the (scalar) bases with the lane's basin added per
     // load: three per-lane pointers less, which is what keeps HBV 1.1p at three waves (DESIGN.md has the table)
-    const float *atg = J.aux_target;
-    const float *awt = J.aux_w;
-    float *asim = J.aux_sim ? J.aux_sim + c * (int64_t)(T - t_first) * d.B : nullptr;
+    const float *atg = nullptr, *awt = nullptr;
+    float *asim = nullptr;
+    if constexpr (JOINT) {
+        atg = joint_args(Q).aux_target;
+        awt = joint_args(Q).aux_w;
+        if constexpr (PERIOD) asim = has_aux && joint_args(Q).aux_sim ? joint_args(Q).aux_sim + c * (int64_t)KA * d.B : nullptr;
+        else asim = joint_args(Q).aux_sim ? joint_args(Q).aux_sim + c * (int64_t)(T - t_first) * d.B : nullptr;
+    }
 
-    // one-step-ahead register prefetch of the per-step inputs (k_fwd's), both observations and their weights with them
+    // PERIOD: the calendars' cursors (uniform): period kf of the flow runs from day sf to day ef of the scored days, ka /
+    // sa / ea the same for the aux series; and the open periods' target rows and weights
+    int kf = 0, sf = 0, ef = KF > 0 ? fend[0] : -1;
+    int ka = 0, sa = 0, ea = KA > 0 ? aend[0] : -1;
+    float pobs = 0.0f, pwobs = 1.0f, paobs = 0.0f, pawobs = 1.0f;
+    hbvx_popk::PeriodMean pf, pa;
+    if constexpr (PERIOD) {
+        if (KF > 0) {
+            pobs = tg[0];
+            if (wt) pwobs = wt[0];
+        }
+        if (KA > 0) {
+            paobs = atg[L.b];
+            if (awt) pawobs = awt[L.b];
+        }
+        pf.acc = pa.acc = 0.0f;
+    }
+
+    // one-step-ahead register prefetch of the per-step inputs (k_fwd's); in the daily forms the observations and their
+    // weights with them
     float nxf[3], nxd[NP], nxo = 0.0f, nxw = 1.0f, nxa = 0.0f, nxaw = 1.0f;
     {
         const float *xr = xb;
         nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
 #pragma unroll
         for (int i = 0; i < NP; i++) nxd[i] = ((dmask >> i) & 1) ? dynp[i][0] : 0.f;
-        if (t_first == 0) {
-            nxo = tg[0];
-            if (wt) nxw = wt[0];
-            nxa = atg[L.b];
-            if (awt) nxaw = awt[L.b];
+        if constexpr (!PERIOD) {
+            if (t_first == 0) {
+                nxo = tg[0];
+                if (wt) nxw = wt[0];
+                if constexpr (JOINT) {
+                    nxa = atg[L.b];
+                    if (awt) nxaw = awt[L.b];
+                }
+            }
         }
     }
 
@@ -596,12 +442,16 @@ __global__ void __launch_bounds__(64) k_pop_joint(const PopJointArgs J)
 #pragma unroll
             for (int i = 0; i < NP; i++)
                 if ((dmask >> i) & 1) nxd[i] = dynp[i][(int64_t)tn * d.p[i].dyn_t_stride];
-            if (tn >= t_first) {
-                const int64_t row = (int64_t)(tn - t_first) * d.B;
-                nxo = tg[row];
-                if (wt) nxw = wt[row];
-                nxa = atg[row + L.b];
-                if (awt) nxaw = awt[row + L.b];
+            if constexpr (!PERIOD) {
+                if (tn >= t_first) {
+                    const int64_t row = (int64_t)(tn - t_first) * d.B;
+                    nxo = tg[row];
+                    if (wt) nxw = wt[row];
+                    if constexpr (JOINT) {
+                        nxa = atg[row + L.b];
+                        if (awt) nxaw = awt[row + L.b];
+                    }
+                }
             }
         }
 #pragma unroll
@@ -617,40 +467,95 @@ __global__ void __launch_bounds__(64) k_pop_joint(const PopJointArgs J)
 
         // the ensemble mean of Q as k_fwd forms series HBVX_F_QSIM, and the aux value as it forms that flux series: the
         // plain ensemble mean (invM with muwts too), never routed.  The two xor butterflies run in ONE loop, each value's
-        // additions in ens_sum's order (so q has k_pop_stats' bits): as two loops the second waits out the first's
-        // cross-lane latency on every day of a serial loop.
+        // additions in ens_sum's order (so q has the bits of the forms without an aux term): as two loops the second
+        // waits out the first's cross-lane latency on every day of a serial loop.
         const float wq = mu ? mu[(int64_t)t * d.mu_t_stride] : 1.0f;
-        const float av = aux_series == HBVX_F_AET ? s.ET : aux_series == HBVX_F_SWE ? s.SP3
-                       : aux_series == HBVX_F_Q0 ? s.Q0 : aux_series == HBVX_F_Q1 ? s.Q1 : s.Q2;
-        float q = (mu ? s.Q * wq : s.Q) * act, v = av * act;
-        for (int k = 0; k < lgMp; k++) {
-            const float qo = __shfl_xor(q, 1 << k, 64), vo = __shfl_xor(v, 1 << k, 64);
-            q += qo;
-            v += vo;
+        float q, v = 0.0f;
+        if constexpr (JOINT) {
+            const float av = !has_aux ? 0.0f
+                           : aux_series == HBVX_F_AET ? s.ET : aux_series == HBVX_F_SWE ? s.SP3
+                           : aux_series == HBVX_F_Q0 ? s.Q0 : aux_series == HBVX_F_Q1 ? s.Q1 : s.Q2;
+            q = (mu ? s.Q * wq : s.Q) * act, v = av * act;
+            for (int k = 0; k < lgMp; k++) {
+                const float qo = __shfl_xor(q, 1 << k, 64), vo = __shfl_xor(v, 1 << k, 64);
+                q += qo;
+                v += vo;
+            }
+            if (!mu) q = q * invM;
+            v = v * invM;
+        } else {
+            q = ens_sum((mu ? s.Q * wq : s.Q) * act, lgMp);
+            if (!mu) q = q * invM;
         }
-        if (!mu) q = q * invM;
-        v = v * invM;
-        const bool counted = t >= t_first;
-        const float y = bs.template push<TR>(q, obs, wobs, counted);
-        if (counted && sim && L.leader) sim[(int64_t)(t - t_first) * d.B] = y;      // y, not y'
-        if (counted) {
-            ax.push(v, aobs, awobs);
-            if (asim && L.leader) asim[(int64_t)(t - t_first) * d.B + L.b] = v;
+        if constexpr (PERIOD) {
+            const float y = bs.Basin::push(q, 0.0f, 0.0f, false);       // the routing runs every day
+            const int rel = t - t_first;                                // the day among the scored days
+            if (rel >= 0 && kf < KF) {
+                pf.add(y, rel == sf);
+                if (rel == ef) {
+                    const int n = ef - sf + 1;
+                    const float mean = n == 1 ? pf.acc : pf.close(n);       // (x / 1.0f is x: the same bits, no division)
+                    bs.template score<TR>(mean, pobs, pwobs);
+                    if (sim && L.leader) sim[(int64_t)kf * d.B] = mean;     // the mean, not its transform
+                    kf++;
+                    sf = rel + 1;
+                    if (kf < KF) {
+                        ef = fend[kf];
+                        pobs = tg[(int64_t)kf * d.B];
+                        if (wt) pwobs = wt[(int64_t)kf * d.B];
+                    }
+                }
+            }
+            if (rel >= 0 && ka < KA) {
+                pa.add(v, rel == sa);
+                if (rel == ea) {
+                    const int n = ea - sa + 1;
+                    const float mean = n == 1 ? pa.acc : pa.close(n);
+                    ax.push(mean, paobs, pawobs);
+                    if (asim && L.leader) asim[(int64_t)ka * d.B + L.b] = mean;
+                    ka++;
+                    sa = rel + 1;
+                    if (ka < KA) {
+                        ea = aend[ka];
+                        paobs = atg[(int64_t)ka * d.B + L.b];
+                        if (awt) pawobs = awt[(int64_t)ka * d.B + L.b];
+                    }
+                }
+            }
+        } else {
+            const bool counted = t >= t_first;
+            float y;
+            if constexpr (STATS) y = bs.template push<TR>(q, obs, wobs, counted);
+            else y = bs.push(q, obs, wobs, counted);
+            if (counted && sim && L.leader) sim[(int64_t)(t - t_first) * d.B] = y;      // y, not its transform
+            if constexpr (JOINT) {
+                if (counted) {
+                    ax.push(v, aobs, awobs);
+                    if (asim && L.leader) asim[(int64_t)(t - t_first) * d.B + L.b] = v;
+                }
+            }
         }
     }
     if (L.leader) {
-        const int64_t at = c * d.B + L.b;
-        pp.cost[at] = bs.cost;
-        S.s1[at] = bs.s1;
-        S.s2[at] = bs.s2;
-        S.s3[at] = bs.s3;
-        J.aux_sse[at] = ax.sse;
-        J.aux_s1[at] = ax.s1;
-        J.aux_s2[at] = ax.s2;
-        J.aux_s3[at] = ax.s3;
+        if constexpr (STATS) {
+            const int64_t at = c * d.B + L.b;
+            const PopStatsArgs &S = stats_args(Q);
+            pp.cost[at] = bs.cost;
+            S.s1[at] = bs.s1;
+            S.s2[at] = bs.s2;
+            S.s3[at] = bs.s3;
+            if constexpr (JOINT) {
+                if (has_aux) {
+                    const PopJointArgs &J = joint_args(Q);
+                    J.aux_sse[at] = ax.sse;
+                    J.aux_s1[at] = ax.s1;
+                    J.aux_s2[at] = ax.s2;
+                    J.aux_s3[at] = ax.s3;
+                }
+            }
+        } else pp.cost[c * d.B + L.b] = bs.cost;
     }
 }
-
 
 } // namespace hbvx
 

@@ -1,13 +1,11 @@
-// launch_pop.hip -- the entry points of the population evaluation: hbvx_population_cost, hbvx_population_stats and
-// hbvx_population_joint (hbv_pop.h), hbvx_population_period (hbv_pop_period.h), and the first two's twins for the implicit scheme, hbvx_adj_population_cost and hbvx_adj_population_stats
-// (hbv_adj_pop.h), and hbvx_adj_population_period (hbv_adj_pop_period.h).
+// launch_pop.hip -- the entry points of the population evaluation: hbvx_population_cost, hbvx_population_stats,
+// hbvx_population_joint and hbvx_population_period (hbv_pop.h), and the implicit scheme's hbvx_adj_population_cost,
+// hbvx_adj_population_stats and hbvx_adj_population_period (hbv_adj_pop.h).
 #include "hbvx_host.h"
 #include "hbv_pop.h"
-#include "hbv_pop_period.h"
 #define HBVX_CHUNK_NO_SHARED_KERNELS
 #include "hbv_chunked.h"        // (first: hbv_adj_kernels.h uses its XCD-aware block map)
 #include "hbv_adj_pop.h"
-#include "hbv_adj_pop_period.h"
 
 using namespace hbvx;
 using namespace hbvx_host;
@@ -76,78 +74,11 @@ int prepare_stats(const char *who, const hbvx_pop_stats *ps, PopStatsArgs &s)
     return HBVX_OK;
 }
 
-dim3 pop_grid(const PopArgs &a)
+// The aux term's checks and arguments, after prepare_stats.  series_ok: whether the entry point scores pj->aux_series
+// (the explicit models a flux, the implicit scheme a storage); series_msg: what it says when not.
+int prepare_aux(const char *who, const hbvx_pop_joint *pj, bool series_ok, const char *series_msg, PopJointArgs &j)
 {
-    const int bpw = 64 >> a.lgMp;
-    return dim3((a.d.B + bpw - 1) / bpw, a.pop.n_cand);
-}
-
-} // namespace
-
-extern "C" int hbvx_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream)
-{
-    int rc = check_desc(d);
-    if (rc) return rc;
-    if (!pop) return fail(HBVX_E_NULL, "hbvx_population_cost: pop is NULL");
-    PopArgs a;
-    rc = prepare("hbvx_population_cost", d, pop, a);
-    if (rc) return rc;
-    const dim3 grid = pop_grid(a);
-    with_model(d, [&](auto m, auto be) {
-        if constexpr (m != MODEL_HOURLY)
-            hipLaunchKernelGGL((k_pop<m, be>), grid, dim3(64), 0, (hipStream_t)stream, a);
-    });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "hbvx_population_cost launch");
-    return HBVX_OK;
-}
-
-extern "C" int hbvx_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void *stream)
-{
-    const char *who = "hbvx_population_stats";
-    int rc = check_desc(d);
-    if (rc) return rc;
-    if (!ps) return fail_as(who, HBVX_E_NULL, "ps is NULL");
-    PopStatsArgs s;
-    rc = prepare(who, d, &ps->pop, s.a);
-    if (rc) return rc;
-    rc = prepare_stats(who, ps, s);
-    if (rc) return rc;
-    const dim3 grid = pop_grid(s.a);
-    with_model(d, [&](auto m, auto be) {
-        if constexpr (m != MODEL_HOURLY) {
-            switch (ps->transform) {
-            case HBVX_POP_T_SQRT:
-                hipLaunchKernelGGL((k_pop_stats<m, be, hbvx_popk::T_SQRT>), grid, dim3(64), 0, (hipStream_t)stream, s);
-                break;
-            case HBVX_POP_T_LOG:
-                hipLaunchKernelGGL((k_pop_stats<m, be, hbvx_popk::T_LOG>), grid, dim3(64), 0, (hipStream_t)stream, s);
-                break;
-            default:
-                hipLaunchKernelGGL((k_pop_stats<m, be, hbvx_popk::T_NONE>), grid, dim3(64), 0, (hipStream_t)stream, s);
-            }
-        }
-    });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "hbvx_population_stats launch");
-    return HBVX_OK;
-}
-
-extern "C" int hbvx_population_joint(const hbvx_desc *d, const hbvx_pop_joint *pj, void *stream)
-{
-    const char *who = "hbvx_population_joint";
-    int rc = check_desc(d);
-    if (rc) return rc;
-    if (!pj) return fail_as(who, HBVX_E_NULL, "pj is NULL");
-    PopJointArgs j;
-    rc = prepare(who, d, &pj->flow.pop, j.s.a);
-    if (rc) return rc;
-    rc = prepare_stats(who, &pj->flow, j.s);
-    if (rc) return rc;
-    switch (pj->aux_series) {
-    case HBVX_F_Q0: case HBVX_F_Q1: case HBVX_F_Q2: case HBVX_F_AET: case HBVX_F_SWE: break;
-    default: return fail_as(who, HBVX_E_UNSUPPORTED, "aux_series must be HBVX_F_Q0, _Q1, _Q2, _AET or _SWE");
-    }
+    if (!series_ok) return fail_as(who, HBVX_E_UNSUPPORTED, series_msg);
     if (!pj->aux_target) return fail_as(who, HBVX_E_NULL, "aux_target is NULL");
     if (!pj->aux_shift) return fail_as(who, HBVX_E_NULL, "aux_shift is NULL");
     if (!pj->aux_sse || !pj->aux_s1 || !pj->aux_s2 || !pj->aux_s3)
@@ -161,36 +92,23 @@ extern "C" int hbvx_population_joint(const hbvx_desc *d, const hbvx_pop_joint *p
     j.aux_s2 = pj->aux_s2;
     j.aux_s3 = pj->aux_s3;
     j.aux_sim = pj->aux_sim;
-    const dim3 grid = pop_grid(j.s.a);
-    with_model(d, [&](auto m, auto be) {
-        if constexpr (m != MODEL_HOURLY) {
-            switch (pj->flow.transform) {
-            case HBVX_POP_T_SQRT:
-                hipLaunchKernelGGL((k_pop_joint<m, be, hbvx_popk::T_SQRT>), grid, dim3(64), 0, (hipStream_t)stream, j);
-                break;
-            case HBVX_POP_T_LOG:
-                hipLaunchKernelGGL((k_pop_joint<m, be, hbvx_popk::T_LOG>), grid, dim3(64), 0, (hipStream_t)stream, j);
-                break;
-            default:
-                hipLaunchKernelGGL((k_pop_joint<m, be, hbvx_popk::T_NONE>), grid, dim3(64), 0, (hipStream_t)stream, j);
-            }
-        }
-    });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "hbvx_population_joint launch");
     return HBVX_OK;
 }
 
-extern "C" int hbvx_population_period(const hbvx_desc *d, const hbvx_pop_period *pq, void *stream)
+bool is_aux_flux(int series)        // the fluxes the explicit models score as an aux term
 {
-    const char *who = "hbvx_population_period";
-    int rc = check_desc(d);
-    if (rc) return rc;
-    if (!pq) return fail_as(who, HBVX_E_NULL, "pq is NULL");
+    switch (series) {
+    case HBVX_F_Q0: case HBVX_F_Q1: case HBVX_F_Q2: case HBVX_F_AET: case HBVX_F_SWE: return true;
+    default: return false;
+    }
+}
+
+// Everything the period entry points check after `pq`, and the kernel's arguments.
+int prepare_period(const char *who, const hbvx_desc *d, const hbvx_pop_period *pq, PopPeriodArgs &q, bool adj)
+{
     const hbvx_pop_joint *pj = &pq->joint;
-    PopPeriodArgs q;
     PopJointArgs &j = q.j;
-    rc = prepare(who, d, &pj->flow.pop, j.s.a);
+    int rc = prepare(who, d, &pj->flow.pop, j.s.a, adj);
     if (rc) return rc;
     rc = prepare_stats(who, &pj->flow, j.s);
     if (rc) return rc;
@@ -205,68 +123,134 @@ extern "C" int hbvx_population_period(const hbvx_desc *d, const hbvx_pop_period 
     q.n_aux = 0;
     q.aux_end = nullptr;
     if (q.has_aux) {
-        switch (pj->aux_series) {
-        case HBVX_F_Q0: case HBVX_F_Q1: case HBVX_F_Q2: case HBVX_F_AET: case HBVX_F_SWE: break;
-        default:
-            return fail_as(who, HBVX_E_UNSUPPORTED, "aux_series must be HBVX_POP_NO_AUX or HBVX_F_Q0, _Q1, _Q2, _AET or _SWE");
-        }
-        if (!pj->aux_target) return fail_as(who, HBVX_E_NULL, "aux_target is NULL");
-        if (!pj->aux_shift) return fail_as(who, HBVX_E_NULL, "aux_shift is NULL");
-        if (!pj->aux_sse || !pj->aux_s1 || !pj->aux_s2 || !pj->aux_s3)
-            return fail_as(who, HBVX_E_NULL, "aux_sse / aux_s1 / aux_s2 / aux_s3 is NULL");
+        if (adj)
+            rc = prepare_aux(who, pj, pj->aux_series >= HBVX_ADJ_AUX_SNOWPACK && pj->aux_series <= HBVX_ADJ_AUX_SLZ,
+                             "aux_series must be HBVX_POP_NO_AUX or HBVX_ADJ_AUX_SNOWPACK .. _SLZ (a storage index 0..4)", j);
+        else
+            rc = prepare_aux(who, pj, is_aux_flux(pj->aux_series),
+                             "aux_series must be HBVX_POP_NO_AUX or HBVX_F_Q0, _Q1, _Q2, _AET or _SWE", j);
+        if (rc) return rc;
         if (!pq->aux_end) return fail_as(who, HBVX_E_NULL, "aux_end is NULL");
         if (pq->n_aux_periods < 1 || pq->n_aux_periods > t_out)
             return fail_as(who, HBVX_E_SHAPE, "n_aux_periods must be in 1..T - t_first");
-        j.aux_target = pj->aux_target;
-        j.aux_w = pj->aux_w;
-        j.aux_shift = pj->aux_shift;
-        j.aux_sse = pj->aux_sse;
-        j.aux_s1 = pj->aux_s1;
-        j.aux_s2 = pj->aux_s2;
-        j.aux_s3 = pj->aux_s3;
-        j.aux_sim = pj->aux_sim;
         q.n_aux = pq->n_aux_periods;
         q.aux_end = pq->aux_end;
     }
-    const dim3 grid = pop_grid(j.s.a);
-    with_model(d, [&](auto m, auto be) {
-        if constexpr (m != MODEL_HOURLY) {
-            switch (pj->flow.transform) {
-            case HBVX_POP_T_SQRT:
-                hipLaunchKernelGGL((k_pop_period<m, be, hbvx_popk::T_SQRT>), grid, dim3(64), 0, (hipStream_t)stream, q);
-                break;
-            case HBVX_POP_T_LOG:
-                hipLaunchKernelGGL((k_pop_period<m, be, hbvx_popk::T_LOG>), grid, dim3(64), 0, (hipStream_t)stream, q);
-                break;
-            default:
-                hipLaunchKernelGGL((k_pop_period<m, be, hbvx_popk::T_NONE>), grid, dim3(64), 0, (hipStream_t)stream, q);
-            }
-        }
-    });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "hbvx_population_period launch");
     return HBVX_OK;
 }
 
-// "Few" mode (hbv_adj_kernels.h): whether the call has at most ADJ_FEW dynamic parameters, and then their slot list
-static bool adj_pop_few(const hbvx_desc *d, AdjFew &few)
+// The template instance of a transform: f(TR) with TR one of hbvx_popk::T_* as std::integral_constant, as with_model
+// (hbvx_host.h).  prepare_stats has checked the value.
+template <typename F>
+auto with_transform(int transform, F &&f)
 {
-    few = AdjFew{};
-    if (count_dyn(d) > ADJ_FEW) return false;
-    for (int i = 0; i < d->n_param; i++)
-        if (d->p[i].dyn) few.slot[few.nd++] = i;
-    return true;
+    switch (transform) {
+    case HBVX_POP_T_SQRT: return f(std::integral_constant<int, hbvx_popk::T_SQRT>{});
+    case HBVX_POP_T_LOG: return f(std::integral_constant<int, hbvx_popk::T_LOG>{});
+    default: return f(std::integral_constant<int, hbvx_popk::T_NONE>{});
+    }
 }
 
-template <int TR>
-static void launch_adj_pop(const PopStatsArgs &s, void *stream)
+dim3 pop_grid(const PopArgs &a)
 {
-    AdjFew few;
-    const bool is_few = adj_pop_few(&s.a.d, few);
-    const dim3 grid = pop_grid(s.a);
-    with_adj(&s.a.d, is_few, [&](auto be, auto fw) {
-        hipLaunchKernelGGL((k_adj_pop<be, fw, TR>), grid, dim3(64), 0, (hipStream_t)stream, s, few);
+    const int bpw = 64 >> a.lgMp;
+    return dim3((a.d.B + bpw - 1) / bpw, a.pop.n_cand);
+}
+
+int launched(const char *who)
+{
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return HBVX_OK;
+    char what[64];
+    snprintf(what, sizeof what, "%s launch", who);
+    return hip_fail(e, what);
+}
+
+// The explicit models: k_pop's instance for the descriptor's model, TR (T_COST for PopArgs) and the form Args.
+template <int TR, typename Args>
+int launch_pop(const char *who, const Args &args, void *stream)
+{
+    const PopArgs &a = pop_args(args);
+    const dim3 grid = pop_grid(a);
+    with_model(&a.d, [&](auto m, auto be) {
+        if constexpr (m != MODEL_HOURLY)
+            hipLaunchKernelGGL((k_pop<m, be, TR, Args>), grid, dim3(64), 0, (hipStream_t)stream, args);
     });
+    return launched(who);
+}
+
+// The implicit scheme: k_adj_pop's instance for the descriptor's parameter count and "few" mode (hbv_adj_kernels.h:
+// whether the call has at most ADJ_FEW dynamic parameters, and then their slot list), TR, AUX and the form Args.
+template <int TR, bool AUX, typename Args>
+int launch_adj_pop(const char *who, const Args &args, void *stream)
+{
+    const PopArgs &a = pop_args(args);
+    AdjFew few{};
+    const bool is_few = count_dyn(&a.d) <= ADJ_FEW;
+    if (is_few)
+        for (int i = 0; i < a.d.n_param; i++)
+            if (a.d.p[i].dyn) few.slot[few.nd++] = i;
+    const dim3 grid = pop_grid(a);
+    with_adj(&a.d, is_few, [&](auto be, auto fw) {
+        hipLaunchKernelGGL((k_adj_pop<be, fw, TR, AUX, Args>), grid, dim3(64), 0, (hipStream_t)stream, args, few);
+    });
+    return launched(who);
+}
+
+} // namespace
+
+extern "C" int hbvx_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream)
+{
+    const char *who = "hbvx_population_cost";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!pop) return fail_as(who, HBVX_E_NULL, "pop is NULL");
+    PopArgs a;
+    rc = prepare(who, d, pop, a);
+    if (rc) return rc;
+    return launch_pop<T_COST>(who, a, stream);
+}
+
+extern "C" int hbvx_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void *stream)
+{
+    const char *who = "hbvx_population_stats";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!ps) return fail_as(who, HBVX_E_NULL, "ps is NULL");
+    PopStatsArgs s;
+    rc = prepare(who, d, &ps->pop, s.a);
+    if (rc) return rc;
+    rc = prepare_stats(who, ps, s);
+    if (rc) return rc;
+    return with_transform(ps->transform, [&](auto tr) { return launch_pop<tr>(who, s, stream); });
+}
+
+extern "C" int hbvx_population_joint(const hbvx_desc *d, const hbvx_pop_joint *pj, void *stream)
+{
+    const char *who = "hbvx_population_joint";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!pj) return fail_as(who, HBVX_E_NULL, "pj is NULL");
+    PopJointArgs j;
+    rc = prepare(who, d, &pj->flow.pop, j.s.a);
+    if (rc) return rc;
+    rc = prepare_stats(who, &pj->flow, j.s);
+    if (rc) return rc;
+    rc = prepare_aux(who, pj, is_aux_flux(pj->aux_series), "aux_series must be HBVX_F_Q0, _Q1, _Q2, _AET or _SWE", j);
+    if (rc) return rc;
+    return with_transform(pj->flow.transform, [&](auto tr) { return launch_pop<tr>(who, j, stream); });
+}
+
+extern "C" int hbvx_population_period(const hbvx_desc *d, const hbvx_pop_period *pq, void *stream)
+{
+    const char *who = "hbvx_population_period";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!pq) return fail_as(who, HBVX_E_NULL, "pq is NULL");
+    PopPeriodArgs q;
+    rc = prepare_period(who, d, pq, q, false);
+    if (rc) return rc;
+    return with_transform(pq->joint.flow.transform, [&](auto tr) { return launch_pop<tr>(who, q, stream); });
 }
 
 extern "C" int hbvx_adj_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream)
@@ -280,10 +264,7 @@ extern "C" int hbvx_adj_population_cost(const hbvx_desc *d, const hbvx_pop *pop,
     if (rc) return rc;
     s.shift = s.eps = nullptr;
     s.s1 = s.s2 = s.s3 = nullptr;
-    launch_adj_pop<T_COST>(s, stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "hbvx_adj_population_cost launch");
-    return HBVX_OK;
+    return launch_adj_pop<T_COST, false>(who, s, stream);
 }
 
 extern "C" int hbvx_adj_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void *stream)
@@ -297,33 +278,7 @@ extern "C" int hbvx_adj_population_stats(const hbvx_desc *d, const hbvx_pop_stat
     if (rc) return rc;
     rc = prepare_stats(who, ps, s);
     if (rc) return rc;
-    switch (ps->transform) {
-    case HBVX_POP_T_SQRT: launch_adj_pop<hbvx_popk::T_SQRT>(s, stream); break;
-    case HBVX_POP_T_LOG: launch_adj_pop<hbvx_popk::T_LOG>(s, stream); break;
-    default: launch_adj_pop<hbvx_popk::T_NONE>(s, stream);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "hbvx_adj_population_stats launch");
-    return HBVX_OK;
-}
-
-template <int TR, bool AUX>
-static void launch_adj_pop_period(const PopPeriodArgs &q, void *stream)
-{
-    const PopArgs &a = q.j.s.a;
-    AdjFew few;
-    const bool is_few = adj_pop_few(&a.d, few);
-    const dim3 grid = pop_grid(a);
-    with_adj(&a.d, is_few, [&](auto be, auto fw) {
-        hipLaunchKernelGGL((k_adj_pop_period<be, fw, TR, AUX>), grid, dim3(64), 0, (hipStream_t)stream, q, few);
-    });
-}
-
-template <int TR>
-static void launch_adj_pop_period(const PopPeriodArgs &q, void *stream)
-{
-    if (q.has_aux) launch_adj_pop_period<TR, true>(q, stream);
-    else launch_adj_pop_period<TR, false>(q, stream);
+    return with_transform(ps->transform, [&](auto tr) { return launch_adj_pop<tr, false>(who, s, stream); });
 }
 
 extern "C" int hbvx_adj_population_period(const hbvx_desc *d, const hbvx_pop_period *pq, void *stream)
@@ -332,53 +287,12 @@ extern "C" int hbvx_adj_population_period(const hbvx_desc *d, const hbvx_pop_per
     int rc = check_desc(d);
     if (rc) return rc;
     if (!pq) return fail_as(who, HBVX_E_NULL, "pq is NULL");
-    const hbvx_pop_joint *pj = &pq->joint;
     PopPeriodArgs q;
-    PopJointArgs &j = q.j;
-    rc = prepare(who, d, &pj->flow.pop, j.s.a, true);
+    rc = prepare_period(who, d, pq, q, true);
     if (rc) return rc;
-    rc = prepare_stats(who, &pj->flow, j.s);
-    if (rc) return rc;
-    const int t_out = d->T - pj->flow.pop.t_first;
-    if (!pq->flow_end) return fail_as(who, HBVX_E_NULL, "flow_end is NULL");
-    if (pq->n_flow_periods < 1 || pq->n_flow_periods > t_out)
-        return fail_as(who, HBVX_E_SHAPE, "n_flow_periods must be in 1..T - t_first");
-    q.has_aux = pj->aux_series != HBVX_POP_NO_AUX;
-    j = PopJointArgs{j.s, pj->aux_series, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    q.n_flow = pq->n_flow_periods;
-    q.flow_end = pq->flow_end;
-    q.n_aux = 0;
-    q.aux_end = nullptr;
-    if (q.has_aux) {
-        if (pj->aux_series < HBVX_ADJ_AUX_SNOWPACK || pj->aux_series > HBVX_ADJ_AUX_SLZ)
-            return fail_as(who, HBVX_E_UNSUPPORTED, "aux_series must be HBVX_POP_NO_AUX or HBVX_ADJ_AUX_SNOWPACK .. _SLZ "
-                                                    "(a storage index 0..4)");
-        if (!pj->aux_target) return fail_as(who, HBVX_E_NULL, "aux_target is NULL");
-        if (!pj->aux_shift) return fail_as(who, HBVX_E_NULL, "aux_shift is NULL");
-        if (!pj->aux_sse || !pj->aux_s1 || !pj->aux_s2 || !pj->aux_s3)
-            return fail_as(who, HBVX_E_NULL, "aux_sse / aux_s1 / aux_s2 / aux_s3 is NULL");
-        if (!pq->aux_end) return fail_as(who, HBVX_E_NULL, "aux_end is NULL");
-        if (pq->n_aux_periods < 1 || pq->n_aux_periods > t_out)
-            return fail_as(who, HBVX_E_SHAPE, "n_aux_periods must be in 1..T - t_first");
-        j.aux_target = pj->aux_target;
-        j.aux_w = pj->aux_w;
-        j.aux_shift = pj->aux_shift;
-        j.aux_sse = pj->aux_sse;
-        j.aux_s1 = pj->aux_s1;
-        j.aux_s2 = pj->aux_s2;
-        j.aux_s3 = pj->aux_s3;
-        j.aux_sim = pj->aux_sim;
-        q.n_aux = pq->n_aux_periods;
-        q.aux_end = pq->aux_end;
-    }
-    switch (pj->flow.transform) {
-    case HBVX_POP_T_SQRT: launch_adj_pop_period<hbvx_popk::T_SQRT>(q, stream); break;
-    case HBVX_POP_T_LOG: launch_adj_pop_period<hbvx_popk::T_LOG>(q, stream); break;
-    default: launch_adj_pop_period<hbvx_popk::T_NONE>(q, stream);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "hbvx_adj_population_period launch");
-    return HBVX_OK;
+    return with_transform(pq->joint.flow.transform, [&](auto tr) {
+        return q.has_aux ? launch_adj_pop<tr, true>(who, q, stream) : launch_adj_pop<tr, false>(who, q, stream);
+    });
 }
 
 // Diagnostics (tests only): the transform as the kernel applies it -- BasinStats::transform on the device.
@@ -397,13 +311,8 @@ extern "C" int hbvx_selftest_pop_transform(const float *y, const float *eps, flo
     if (!y || !out || n <= 0 || transform < HBVX_POP_T_NONE || transform > HBVX_POP_T_LOG || (transform == HBVX_POP_T_LOG && !eps))
         return fail(HBVX_E_NULL, "selftest_pop_transform: bad arguments");
     const dim3 grid((n + 255) / 256), block(256);
-    if (transform == HBVX_POP_T_SQRT)
-        hipLaunchKernelGGL(k_selftest_pop_transform<hbvx_popk::T_SQRT>, grid, block, 0, (hipStream_t)stream, y, eps, out, n);
-    else if (transform == HBVX_POP_T_LOG)
-        hipLaunchKernelGGL(k_selftest_pop_transform<hbvx_popk::T_LOG>, grid, block, 0, (hipStream_t)stream, y, eps, out, n);
-    else
-        hipLaunchKernelGGL(k_selftest_pop_transform<hbvx_popk::T_NONE>, grid, block, 0, (hipStream_t)stream, y, eps, out, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "selftest_pop_transform launch");
-    return HBVX_OK;
+    with_transform(transform, [&](auto tr) {
+        hipLaunchKernelGGL(k_selftest_pop_transform<tr>, grid, block, 0, (hipStream_t)stream, y, eps, out, n);
+    });
+    return launched("selftest_pop_transform");
 }

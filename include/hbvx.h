@@ -657,8 +657,8 @@ int hbvx_population_joint(const hbvx_desc *d, const hbvx_pop_joint *pj, void *st
  * only leaves periods unclosed; (6) argument errors are reported before anything is launched: hbvx_population_joint's
  * (its aux rules only when there is an aux term), and HBVX_E_NULL (pq, flow_end; aux_end with an aux term),
  * HBVX_E_SHAPE (n_flow_periods, or n_aux_periods with an aux term, outside 1..T - t_first), HBVX_E_UNSUPPORTED (an
- * aux_series that is neither HBVX_POP_NO_AUX nor one of the five).  csrc/hbv_pop_period.h has the kernel,
- * csrc/hbv_pop.h the arithmetic (hbvx_popk::PeriodMean, BasinStats::score, AuxStats::push).
+ * aux_series that is neither HBVX_POP_NO_AUX nor one of the five).  csrc/hbv_pop.h has the kernel and
+ * the arithmetic (hbvx_popk::PeriodMean, BasinStats::score, AuxStats::push).
  * Not built: period sums as an input form (divide by the lengths), per-basin calendars, HBVX_MODEL_HOURLY;
  * HBVX_MODEL_HBVADJ has hbvx_adj_population_period below. */
 #define HBVX_POP_NO_AUX (-1)
@@ -712,7 +712,7 @@ int hbvx_adj_population_stats(const hbvx_desc *d, const hbvx_pop_stats *ps, void
  * s1..s3 and pop.sim have hbvx_adj_population_stats' bits; with an aux term the flow outputs keep theirs; (6) argument
  * errors are reported before anything is launched: hbvx_adj_population_stats' (the model, the Newton policy,
  * adj_stop == 1, muwts) and hbvx_population_period's, with HBVX_E_UNSUPPORTED for an aux_series that is neither
- * HBVX_POP_NO_AUX nor a storage index 0..4.  csrc/hbv_adj_pop_period.h has the kernel.
+ * HBVX_POP_NO_AUX nor a storage index 0..4.  csrc/hbv_adj_pop.h has the kernel.
  * Not built: fluxes as the aux series, a transform of the aux value, more than one aux series per launch, period sums,
  * per-basin calendars. */
 #define HBVX_ADJ_AUX_SNOWPACK 0

@@ -1,5 +1,5 @@
 // popjoint_host.cpp -- the per-basin part of hbvx_population_joint (hydrodl2_amd/csrc/hbv_pop.h: a BasinStats for the
-// flow term and an AuxStats for the aux term) compiled for the host, one pair per basin fed day by day as k_pop_joint
+// flow term and an AuxStats for the aux term) compiled for the host, one pair per basin fed day by day as k_pop's joint form
 // feeds it (tests/test_popjoint_host.py).  Built together with popstats_host.cpp and pop_host.cpp, whose popstats_host
 // (the BasinStats alone) the test holds the flow term to.
 #include <cstdint>

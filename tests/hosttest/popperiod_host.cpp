@@ -1,6 +1,6 @@
 // popperiod_host.cpp -- the per-basin part of hbvx_population_period (hydrodl2_amd/csrc/hbv_pop.h: a BasinStats and an
 // AuxStats fed from two PeriodMeans) compiled for the host, one set per basin fed day by day with the cursors of
-// k_pop_period (hydrodl2_amd/csrc/hbv_pop_period.h): tests/test_popperiod_host.py.  Built together with
+// k_pop's period form (the same header): tests/test_popperiod_host.py.  Built together with
 // popjoint_host.cpp, popstats_host.cpp and pop_host.cpp, whose popjoint_host the test holds the daily calendars to.
 #include <cstdint>
 

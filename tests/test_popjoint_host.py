@@ -1,6 +1,6 @@
 """CPU tier: the per-basin arithmetic of hbvx_population_joint (hydrodl2_amd/csrc/hbv_pop.h: a BasinStats for the flow
 term and an AuxStats for the aux term), compiled for the host (tests/hosttest/popjoint_host.cpp feeds one pair per basin
-day by day, as k_pop_joint does) and checked on the random float32 series of tests/test_popstats_host.py.
+day by day, as k_pop's joint form does) and checked on the random float32 series of tests/test_popstats_host.py.
 
 The aux term: the four chains on a value v that is neither routed nor transformed, against float64 sums over the
 float32 v, o, m the code was given, d = v - m, e = o - m, r = v - o formed in float64 -- the bounds of

@@ -1,6 +1,6 @@
 """CPU tier: the per-basin arithmetic of hbvx_population_period (hydrodl2_amd/csrc/hbv_pop.h: two PeriodMeans feeding a
 BasinStats and an AuxStats), compiled for the host (tests/hosttest/popperiod_host.cpp feeds one set per basin day by day
-with the cursors of k_pop_period) and checked on the random float32 series of tests/test_pop_host.py.
+with the cursors of k_pop's period form) and checked on the random float32 series of tests/test_pop_host.py.
 
 With gamma(n) = n u / (1 - n u), u = 2^-24:
   a period value   the mean of n float32 daily values, n - 1 additions in ascending order and one division: against the

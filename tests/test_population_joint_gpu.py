@@ -7,7 +7,8 @@ candidate times exp(0.2 noise): on the cases in SPARSE it is NaN except every 8t
 carries the case's own NaN mask and weights.
 
   flow term   for every case and transform, sse, s1, s2, s3 and the series equal `population_stats`' bit for bit:
-              k_pop_joint restates k_pop_stats' day loop, and this is what holds the two texts together.
+              the two are forms of one kernel template (k_pop, csrc/hbv_pop.h), and this holds the joint form to the
+              stats form.
   aux series  aux.series[c] against outputs[aux_key] of a module call at candidate c, the project's flux tolerance
               (tests/abi_util.py: rtol 1e-4, atol 1e-5), every element, no outlier allowance.
   aux sums    each of sse, s1, s2, s3 against the float64 sum over the kernel's OWN float32 aux series, the bounds of

@@ -7,8 +7,8 @@ records, thirteen months on the wet 400-day record (four days dropped); MIXED is
 blocks of 8 and the aux series in blocks of 5 in the same launch.
 
   daily calendars  for every case and transform, with key AET_hydro, all eight sums and both series equal
-                   `population_joint_stats`' bit for bit: k_pop_period restates k_pop_joint's day loop, and this is what
-                   holds the two texts together.  With the flow daily and the aux series in periods the flow numbers are
+                   `population_joint_stats`' bit for bit: the two are forms of one kernel template (k_pop, csrc/
+                   hbv_pop.h), and this holds the period form to the joint form.  With the flow daily and the aux series in periods the flow numbers are
                    `population_stats`'; without an aux term they are those of the call with one.
   period series    against float64 period means of the module route's daily series, the project's flux tolerance
                    (tests/abi_util.py) on every element -- a mean of values that are each inside it is inside it, and the

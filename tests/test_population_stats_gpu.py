@@ -7,8 +7,8 @@ masks and weights, so that the scores lie where calibration works and no basin's
 zero (asserted first: no comparison below is empty, and no score of the yardstick is NaN).
 
   same model  under 'none' the squared error has the bits of `population_cost`'s cost, and under every transform the
-              series has the bits of its series: k_pop_stats restates k_pop's day loop, and this is what holds the two
-              texts together.
+              series has the bits of its series: the two are forms of one kernel template (k_pop, csrc/hbv_pop.h), and
+              this holds the stats form to the cost form.
   the sums    each of sse, s1, s2, s3 against the float64 sum over the kernel's OWN float32 series, transformed in
               float64.  'none': the bounds of tests/test_popstats_host.py.  'sqrt' / 'log': widened by the device
               function's own error, |y'_device - y'| <= k u (1 + |y'|) per value, propagated to first order:

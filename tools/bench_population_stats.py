@@ -12,8 +12,8 @@ timed repetition is one whole call between two HIP events, the variants alternat
 [min, max] over the repetitions.  Per (model, shape, P) one JSON line per variant with its peak memory (torch's
 allocator, above what the inputs hold) and the kernel by itself (the library call timed by events of its own), and one
 with the worst difference of the KGE of the two routes, |new - route| / (1 + |1 - route|).
---cost-only --lib <a library of the parent commit> times `population_cost` alone on that library (its k_pop instances
-are the same instructions as this tree's by tools/compare_code.py, so the figure on this tree is the parent's)."""
+--cost-only --lib <another build of the library> times `population_cost` alone on that library (when its cost-form
+k_pop instances are the same instructions as this tree's by tools/compare_code.py, the figure on this tree is its own)."""
 import argparse
 import json
 import os
