@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple, Optional
 
 ABI_VERSION = 10
 MAX_PARAM = 20
@@ -171,24 +172,95 @@ class LstmDesc(C.Structure):
 LSTM_ABI_VERSION = 1
 LSTM_HIDDEN_SIZES = (64, 128, 256)     # what the HIP library instantiates
 
-EXPORTS = ["hbvx_zero", "hbvx_zero_except", "hbvx_preferred_traj_layout", "hbvx_lstm_workspace_bytes", "hbvx_lstm_forward", "hbvx_lstm_backward", "hbvx_lstm_check",
-           "hbvx_version", "hbvx_last_error", "hbvx_backend", "hbvx_sizeof", "hbvx_forward",
-           "hbvx_backward", "hbvx_backward_workspace_bytes", "hbvx_ckpt_workspace_bytes", "hbvx_route_forward", "hbvx_route_workspace_bytes",
-           "hbvx_route_backward", "hbvx_adj_forward", "hbvx_adj_backward", "hbvx_bfi",
-           "hbvx_gage_route_forward", "hbvx_gage_route_backward",
-           "hbvx_gage_route_workspace_bytes"]
+class PopEntry(NamedTuple):
+    """What ops.population needs to know about one population export."""
+    struct: type                    # Pop, PopStats, PopJoint or PopPeriod: the export's second argument
+    implicit: bool                  # the export is HbvAdj's: it takes a record of the implicit scheme only
+    aux_series: Optional[dict]      # the aux series it can score beside the flow, None where it has no aux term
 
-# Exports a library may lack (the CPU restatement under oracle/ has only the calls above); a call that needs one raises
-# HbvxError naming it.
-OPTIONAL_EXPORTS = ["hbvx_lstm_forward_hx", "hbvx_lstm_backward_hx", "hbvx_forward_tangent", "hbvx_route_tangent",
-                    "hbvx_bfi_tangent", "hbvx_lstm_tangent", "hbvx_forward_tangent_batch", "hbvx_route_tangent_batch",
-                    "hbvx_bfi_tangent_batch", "hbvx_lstm_tangent_batch", "hbvx_lstm_tangent_batch_workspace_bytes",
-                    "hbvx_hourly_tangent_batch", "hbvx_gage_route_tangent_batch",
-                    "hbvx_gage_route_tangent_workspace_bytes", "hbvx_adj_tangent_batch", "hbvx_gram",
-                    "hbvx_gram_workspace_bytes", "hbvx_quadform", "hbvx_quadform_workspace_bytes",
-                    "hbvx_population_cost", "hbvx_population_stats",
-                    "hbvx_adj_population_cost", "hbvx_adj_population_stats", "hbvx_population_joint",
-                    "hbvx_population_period", "hbvx_adj_population_period"]
+
+POPULATION = {"hbvx_population_cost": PopEntry(Pop, False, None),
+              "hbvx_population_stats": PopEntry(PopStats, False, None),
+              "hbvx_adj_population_cost": PopEntry(Pop, True, None),
+              "hbvx_adj_population_stats": PopEntry(PopStats, True, None),
+              "hbvx_population_joint": PopEntry(PopJoint, False, POP_AUX_SERIES),
+              "hbvx_population_period": PopEntry(PopPeriod, False, POP_AUX_SERIES),
+              "hbvx_adj_population_period": PopEntry(PopPeriod, True, ADJ_POP_AUX_SERIES)}
+
+
+def pop_levels(args):
+    """(PopPeriod, PopJoint, PopStats, Pop) as they nest in `args` -- PopPeriod.joint.flow.pop, entered at the type of
+    `args` -- with None for the levels above it.  The inner ones are views of `args`' memory."""
+    levels = {type(args): args}
+    for field in ("joint", "flow", "pop"):
+        if hasattr(args, field):
+            args = getattr(args, field)
+            levels[type(args)] = args
+    return tuple(levels.get(st) for st in (PopPeriod, PopJoint, PopStats, Pop))
+
+
+_int, _u64, _str, _vp, _i32, _i64, _P = C.c_int, C.c_uint64, C.c_char_p, C.c_void_p, C.c_int32, C.c_int64, C.POINTER
+_POP_SIZEOF = {Pop: 10, PopStats: 11, PopJoint: 12, PopPeriod: 13}
+
+# Every export the binding calls, in the order it is looked up: (name, required, restype, argtypes, layout), layout None
+# or (hbvx_sizeof index, the struct that must have that size).  A library may lack a row that is not required (the CPU
+# restatement under oracle/ has the required ones only); a call that needs one raises HbvxError naming it.
+SIGNATURES = [
+    ("hbvx_zero", True, _int, [_vp, _u64, _vp], None),
+    ("hbvx_zero_except", True, _int, [_vp, _i64, _i32, _i64, _i64, _i32, C.c_uint32, _vp], None),
+    ("hbvx_preferred_traj_layout", True, _int, [_P(Desc)], None),
+    ("hbvx_lstm_workspace_bytes", True, _u64, [_P(LstmDesc)], None),
+    ("hbvx_lstm_forward", True, _int, [_P(LstmDesc), _fp, _fp, _fp, _fp, _fp, _vp, _u64, _vp], None),
+    ("hbvx_lstm_backward", True, _int, [_P(LstmDesc), _fp, _fp, _fp, _fp, _fp, _vp, _u64, _vp], None),
+    ("hbvx_lstm_check", True, _int, [_P(LstmDesc), _vp, _vp], None),
+    ("hbvx_version", True, _int, [], None),
+    ("hbvx_last_error", True, _str, [], None),
+    ("hbvx_backend", True, _str, [], None),
+    ("hbvx_sizeof", True, _u64, [_int], None),
+    ("hbvx_forward", True, _int, [_P(Desc), _P(FwdOut), _vp], None),
+    ("hbvx_backward", True, _int, [_P(Desc), _P(BwdIO), _vp], None),
+    ("hbvx_backward_workspace_bytes", True, _u64, [_P(Desc)], None),
+    ("hbvx_ckpt_workspace_bytes", True, _u64, [_P(Desc), _i32], None),
+    ("hbvx_route_forward", True, _int, [_P(RouteDesc), _fp, _fp, _fp, _vp], None),
+    ("hbvx_route_workspace_bytes", True, _u64, [_P(RouteDesc)], None),
+    ("hbvx_route_backward", True, _int, [_P(RouteDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _u64, _vp], None),
+    ("hbvx_adj_forward", True, _int, [_P(Desc), _P(FwdOut), _vp], None),
+    ("hbvx_adj_backward", True, _int, [_P(Desc), _P(BwdIO), _vp], None),
+    ("hbvx_bfi", True, _int, [_i32, _i32, _fp, _fp, C.c_float, _fp, _vp], None),
+    ("hbvx_gage_route_forward", True, _int, [_P(GageDesc), _fp, _fp, _fp, _vp, _u64, _vp], None),
+    ("hbvx_gage_route_backward", True, _int, [_P(GageDesc), _fp, _fp, _fp, _fp, _fp, _vp, _u64, _vp], None),
+    ("hbvx_gage_route_workspace_bytes", True, _u64, [_P(GageDesc)], None),
+    ("hbvx_zero_in_launch", True, _int, [], None),
+    ("hbvx_zero_rest", True, _int, [_vp, _u64, _vp, _vp], None),
+    ("hbvx_last_dispatch", True, _str, [_int], None),
+    ("hbvx_lstm_forward_hx", False, _int, [_P(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _u64, _vp], None),
+    ("hbvx_lstm_backward_hx", False, _int, [_P(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _u64, _vp], None),
+    ("hbvx_forward_tangent", False, _int, [_P(Desc), _P(TanIO), _vp], (7, TanIO)),
+    ("hbvx_route_tangent", False, _int, [_P(RouteDesc), _fp, _fp, _fp, _fp, _fp, _fp, _vp], None),
+    ("hbvx_bfi_tangent", False, _int, [_i32, _i32, _fp, _fp, _fp, _fp, C.c_float, _fp, _vp], None),
+    ("hbvx_lstm_tangent", False, _int,
+     [_P(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _u64, _vp], None),
+    ("hbvx_forward_tangent_batch", False, _int, [_P(Desc), _P(TanBatch), _vp], (8, TanBatch)),
+    ("hbvx_route_tangent_batch", False, _int,
+     [_P(RouteDesc), _i32, _fp, _fp, _fp, _i64, _fp, _fp, _i64, _fp, _vp], None),
+    ("hbvx_bfi_tangent_batch", False, _int, [_i32, _i32, _i32, _fp, _fp, _fp, _fp, _i64, C.c_float, _fp, _vp], None),
+    ("hbvx_lstm_tangent_batch", False, _int,
+     [_P(LstmDesc), _i32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _u64, _vp], None),
+    ("hbvx_lstm_tangent_batch_workspace_bytes", False, _u64, [_P(LstmDesc), _i32], None),
+    ("hbvx_hourly_tangent_batch", False, _int, [_P(Desc), _P(TanBatch), _vp], (8, TanBatch)),
+    ("hbvx_gage_route_tangent_batch", False, _int,
+     [_P(GageDesc), _i32, _fp, _fp, _fp, _i64, _fp, _i64, _fp, _vp, _u64, _vp], None),
+    ("hbvx_gage_route_tangent_workspace_bytes", False, _u64, [_P(GageDesc), _i32], None),
+    ("hbvx_adj_tangent_batch", False, _int, [_P(Desc), _P(TanBatch), _fp, _vp], (8, TanBatch)),
+    ("hbvx_gram", False, _int, [_P(GramDesc), _fp, _fp, _fp, _fp, _fp, _fp, _vp, _u64, _vp], (9, GramDesc)),
+    ("hbvx_gram_workspace_bytes", False, _u64, [_P(GramDesc)], None),
+    ("hbvx_quadform", False, _int, [_P(GramDesc), _fp, _fp, _fp, _vp, _u64, _vp], (9, GramDesc)),
+    ("hbvx_quadform_workspace_bytes", False, _u64, [_P(GramDesc)], None),
+] + [(_name, False, _int, [_P(Desc), _P(_e.struct), _vp], (_POP_SIZEOF[_e.struct], _e.struct))
+     for _name, _e in POPULATION.items()]
+
+EXPORTS = [row[0] for row in SIGNATURES if row[1]]
+OPTIONAL_EXPORTS = [row[0] for row in SIGNATURES if not row[1]]
 
 
 class HbvxError(RuntimeError):
@@ -207,173 +279,18 @@ class Library:
         for name in EXPORTS:
             if not hasattr(d, name):
                 raise HbvxError(f"{path}: missing export {name}")
-        d.hbvx_version.restype = C.c_int
-        d.hbvx_last_error.restype = C.c_char_p
-        d.hbvx_backend.restype = C.c_char_p
-        d.hbvx_sizeof.restype = C.c_uint64
-        d.hbvx_sizeof.argtypes = [C.c_int]
-        d.hbvx_forward.restype = C.c_int
-        d.hbvx_forward.argtypes = [C.POINTER(Desc), C.POINTER(FwdOut), C.c_void_p]
-        d.hbvx_backward.restype = C.c_int
-        d.hbvx_backward.argtypes = [C.POINTER(Desc), C.POINTER(BwdIO), C.c_void_p]
-        d.hbvx_backward_workspace_bytes.restype = C.c_uint64
-        d.hbvx_backward_workspace_bytes.argtypes = [C.POINTER(Desc)]
-        d.hbvx_route_forward.restype = C.c_int
-        d.hbvx_route_forward.argtypes = [C.POINTER(RouteDesc), _fp, _fp, _fp, C.c_void_p]
-        d.hbvx_route_backward.restype = C.c_int
-        d.hbvx_route_workspace_bytes.restype = C.c_uint64
-        d.hbvx_route_workspace_bytes.argtypes = [C.POINTER(RouteDesc)]
-        d.hbvx_route_backward.argtypes = [C.POINTER(RouteDesc), _fp, _fp, _fp, _fp, _fp, _fp,
-                                          _fp, C.c_uint64, C.c_void_p]
-        for fn in (d.hbvx_adj_forward, d.hbvx_adj_backward):
-            fn.restype = C.c_int
-        d.hbvx_adj_forward.argtypes = [C.POINTER(Desc), C.POINTER(FwdOut), C.c_void_p]
-        d.hbvx_adj_backward.argtypes = [C.POINTER(Desc), C.POINTER(BwdIO), C.c_void_p]
-        d.hbvx_gage_route_forward.restype = C.c_int
-        d.hbvx_gage_route_workspace_bytes.restype = C.c_uint64
-        d.hbvx_gage_route_workspace_bytes.argtypes = [C.POINTER(GageDesc)]
-        d.hbvx_gage_route_forward.argtypes = [C.POINTER(GageDesc), _fp, _fp, _fp, C.c_void_p, C.c_uint64, C.c_void_p]
-        d.hbvx_gage_route_backward.restype = C.c_int
-        d.hbvx_gage_route_backward.argtypes = [C.POINTER(GageDesc), _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_uint64,
-                                               C.c_void_p]
-        d.hbvx_bfi.restype = C.c_int
-        d.hbvx_bfi.argtypes = [C.c_int32, C.c_int32, _fp, _fp, C.c_float, _fp, C.c_void_p]
-        d.hbvx_ckpt_workspace_bytes.restype = C.c_uint64
-        d.hbvx_ckpt_workspace_bytes.argtypes = [C.POINTER(Desc), C.c_int32]
-        d.hbvx_preferred_traj_layout.restype = C.c_int
-        d.hbvx_preferred_traj_layout.argtypes = [C.POINTER(Desc)]
-        d.hbvx_zero_in_launch.restype = C.c_int
-        d.hbvx_zero_in_launch.argtypes = []
-        d.hbvx_zero_rest.restype = C.c_int
-        d.hbvx_zero_rest.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        d.hbvx_last_dispatch.restype = C.c_char_p
-        d.hbvx_last_dispatch.argtypes = [C.c_int]
-        d.hbvx_zero.restype = C.c_int
-        d.hbvx_zero.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-        d.hbvx_zero_except.restype = C.c_int
-        d.hbvx_zero_except.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
-                                       C.c_uint32, C.c_void_p]
-        d.hbvx_lstm_workspace_bytes.restype = C.c_uint64
-        d.hbvx_lstm_workspace_bytes.argtypes = [C.POINTER(LstmDesc)]
-        d.hbvx_lstm_forward.restype = C.c_int
-        d.hbvx_lstm_forward.argtypes = [C.POINTER(LstmDesc), _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_uint64,
-                                        C.c_void_p]
-        d.hbvx_lstm_backward.restype = C.c_int
-        d.hbvx_lstm_backward.argtypes = [C.POINTER(LstmDesc), _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_uint64,
-                                         C.c_void_p]
-        d.hbvx_lstm_check.restype = C.c_int
-        d.hbvx_lstm_check.argtypes = [C.POINTER(LstmDesc), C.c_void_p, C.c_void_p]
         self.missing = [name for name in OPTIONAL_EXPORTS if not hasattr(d, name)]
-        if "hbvx_lstm_forward_hx" not in self.missing:
-            d.hbvx_lstm_forward_hx.restype = C.c_int
-            d.hbvx_lstm_forward_hx.argtypes = [C.POINTER(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p,
-                                               C.c_uint64, C.c_void_p]
-        if "hbvx_lstm_backward_hx" not in self.missing:
-            d.hbvx_lstm_backward_hx.restype = C.c_int
-            d.hbvx_lstm_backward_hx.argtypes = [C.POINTER(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
-                                                C.c_void_p, C.c_uint64, C.c_void_p]
-        if "hbvx_lstm_tangent" not in self.missing:
-            d.hbvx_lstm_tangent.restype = C.c_int
-            d.hbvx_lstm_tangent.argtypes = [C.POINTER(LstmDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
-                                            C.c_void_p, C.c_uint64, C.c_void_p]
-        if "hbvx_lstm_tangent_batch" not in self.missing:
-            d.hbvx_lstm_tangent_batch.restype = C.c_int
-            d.hbvx_lstm_tangent_batch.argtypes = [C.POINTER(LstmDesc), C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
-                                                  _fp, _fp, C.c_void_p, C.c_uint64, C.c_void_p]
-        if "hbvx_lstm_tangent_batch_workspace_bytes" not in self.missing:
-            d.hbvx_lstm_tangent_batch_workspace_bytes.restype = C.c_uint64
-            d.hbvx_lstm_tangent_batch_workspace_bytes.argtypes = [C.POINTER(LstmDesc), C.c_int32]
-        if "hbvx_forward_tangent" not in self.missing:
-            d.hbvx_forward_tangent.restype = C.c_int
-            d.hbvx_forward_tangent.argtypes = [C.POINTER(Desc), C.POINTER(TanIO), C.c_void_p]
-            if d.hbvx_sizeof(7) != C.sizeof(TanIO):
-                raise HbvxError(f"{path}: layout mismatch for TanIO: {d.hbvx_sizeof(7)} != {C.sizeof(TanIO)}")
-        if "hbvx_route_tangent" not in self.missing:
-            d.hbvx_route_tangent.restype = C.c_int
-            d.hbvx_route_tangent.argtypes = [C.POINTER(RouteDesc), _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p]
-        if "hbvx_bfi_tangent" not in self.missing:
-            d.hbvx_bfi_tangent.restype = C.c_int
-            d.hbvx_bfi_tangent.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_float, _fp, C.c_void_p]
-        if "hbvx_forward_tangent_batch" not in self.missing:
-            d.hbvx_forward_tangent_batch.restype = C.c_int
-            d.hbvx_forward_tangent_batch.argtypes = [C.POINTER(Desc), C.POINTER(TanBatch), C.c_void_p]
-            if d.hbvx_sizeof(8) != C.sizeof(TanBatch):
-                raise HbvxError(f"{path}: layout mismatch for TanBatch: {d.hbvx_sizeof(8)} != {C.sizeof(TanBatch)}")
-        if "hbvx_route_tangent_batch" not in self.missing:
-            d.hbvx_route_tangent_batch.restype = C.c_int
-            d.hbvx_route_tangent_batch.argtypes = [C.POINTER(RouteDesc), C.c_int32, _fp, _fp, _fp, C.c_int64, _fp, _fp,
-                                                   C.c_int64, _fp, C.c_void_p]
-        if "hbvx_bfi_tangent_batch" not in self.missing:
-            d.hbvx_bfi_tangent_batch.restype = C.c_int
-            d.hbvx_bfi_tangent_batch.argtypes = [C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_int64,
-                                                 C.c_float, _fp, C.c_void_p]
-        if "hbvx_hourly_tangent_batch" not in self.missing:
-            d.hbvx_hourly_tangent_batch.restype = C.c_int
-            d.hbvx_hourly_tangent_batch.argtypes = [C.POINTER(Desc), C.POINTER(TanBatch), C.c_void_p]
-            if d.hbvx_sizeof(8) != C.sizeof(TanBatch):
-                raise HbvxError(f"{path}: layout mismatch for TanBatch: {d.hbvx_sizeof(8)} != {C.sizeof(TanBatch)}")
-        if "hbvx_gage_route_tangent_workspace_bytes" not in self.missing:
-            d.hbvx_gage_route_tangent_workspace_bytes.restype = C.c_uint64
-            d.hbvx_gage_route_tangent_workspace_bytes.argtypes = [C.POINTER(GageDesc), C.c_int32]
-        if "hbvx_gage_route_tangent_batch" not in self.missing:
-            d.hbvx_gage_route_tangent_batch.restype = C.c_int
-            d.hbvx_gage_route_tangent_batch.argtypes = [C.POINTER(GageDesc), C.c_int32, _fp, _fp, _fp, C.c_int64, _fp,
-                                                        C.c_int64, _fp, C.c_void_p, C.c_uint64, C.c_void_p]
-        if "hbvx_adj_tangent_batch" not in self.missing:
-            d.hbvx_adj_tangent_batch.restype = C.c_int
-            d.hbvx_adj_tangent_batch.argtypes = [C.POINTER(Desc), C.POINTER(TanBatch), _fp, C.c_void_p]
-            if d.hbvx_sizeof(8) != C.sizeof(TanBatch):
-                raise HbvxError(f"{path}: layout mismatch for TanBatch: {d.hbvx_sizeof(8)} != {C.sizeof(TanBatch)}")
-        if "hbvx_gram" not in self.missing:
-            d.hbvx_gram.restype = C.c_int
-            d.hbvx_gram.argtypes = [C.POINTER(GramDesc), _fp, _fp, _fp, _fp, _fp, _fp, C.c_void_p, C.c_uint64,
-                                    C.c_void_p]
-        if "hbvx_gram_workspace_bytes" not in self.missing:
-            d.hbvx_gram_workspace_bytes.restype = C.c_uint64
-            d.hbvx_gram_workspace_bytes.argtypes = [C.POINTER(GramDesc)]
-        if "hbvx_quadform" not in self.missing:
-            d.hbvx_quadform.restype = C.c_int
-            d.hbvx_quadform.argtypes = [C.POINTER(GramDesc), _fp, _fp, _fp, C.c_void_p, C.c_uint64, C.c_void_p]
-        if "hbvx_quadform_workspace_bytes" not in self.missing:
-            d.hbvx_quadform_workspace_bytes.restype = C.c_uint64
-            d.hbvx_quadform_workspace_bytes.argtypes = [C.POINTER(GramDesc)]
-        if not {"hbvx_gram", "hbvx_quadform"} <= set(self.missing) and d.hbvx_sizeof(9) != C.sizeof(GramDesc):
-            raise HbvxError(f"{path}: layout mismatch for GramDesc: {d.hbvx_sizeof(9)} != {C.sizeof(GramDesc)}")
-        if "hbvx_population_cost" not in self.missing:
-            d.hbvx_population_cost.restype = C.c_int
-            d.hbvx_population_cost.argtypes = [C.POINTER(Desc), C.POINTER(Pop), C.c_void_p]
-            if d.hbvx_sizeof(10) != C.sizeof(Pop):
-                raise HbvxError(f"{path}: layout mismatch for Pop: {d.hbvx_sizeof(10)} != {C.sizeof(Pop)}")
-        if "hbvx_population_stats" not in self.missing:
-            d.hbvx_population_stats.restype = C.c_int
-            d.hbvx_population_stats.argtypes = [C.POINTER(Desc), C.POINTER(PopStats), C.c_void_p]
-            if d.hbvx_sizeof(11) != C.sizeof(PopStats):
-                raise HbvxError(f"{path}: layout mismatch for PopStats: {d.hbvx_sizeof(11)} != {C.sizeof(PopStats)}")
-        if "hbvx_adj_population_cost" not in self.missing:      # the structs of the two above
-            d.hbvx_adj_population_cost.restype = C.c_int
-            d.hbvx_adj_population_cost.argtypes = [C.POINTER(Desc), C.POINTER(Pop), C.c_void_p]
-            if d.hbvx_sizeof(10) != C.sizeof(Pop):
-                raise HbvxError(f"{path}: layout mismatch for Pop: {d.hbvx_sizeof(10)} != {C.sizeof(Pop)}")
-        if "hbvx_adj_population_stats" not in self.missing:
-            d.hbvx_adj_population_stats.restype = C.c_int
-            d.hbvx_adj_population_stats.argtypes = [C.POINTER(Desc), C.POINTER(PopStats), C.c_void_p]
-            if d.hbvx_sizeof(11) != C.sizeof(PopStats):
-                raise HbvxError(f"{path}: layout mismatch for PopStats: {d.hbvx_sizeof(11)} != {C.sizeof(PopStats)}")
-        if "hbvx_population_joint" not in self.missing:
-            d.hbvx_population_joint.restype = C.c_int
-            d.hbvx_population_joint.argtypes = [C.POINTER(Desc), C.POINTER(PopJoint), C.c_void_p]
-            if d.hbvx_sizeof(12) != C.sizeof(PopJoint):
-                raise HbvxError(f"{path}: layout mismatch for PopJoint: {d.hbvx_sizeof(12)} != {C.sizeof(PopJoint)}")
-        if "hbvx_population_period" not in self.missing:
-            d.hbvx_population_period.restype = C.c_int
-            d.hbvx_population_period.argtypes = [C.POINTER(Desc), C.POINTER(PopPeriod), C.c_void_p]
-            if d.hbvx_sizeof(13) != C.sizeof(PopPeriod):
-                raise HbvxError(f"{path}: layout mismatch for PopPeriod: {d.hbvx_sizeof(13)} != {C.sizeof(PopPeriod)}")
-        if "hbvx_adj_population_period" not in self.missing:    # the struct of the one above
-            d.hbvx_adj_population_period.restype = C.c_int
-            d.hbvx_adj_population_period.argtypes = [C.POINTER(Desc), C.POINTER(PopPeriod), C.c_void_p]
-            if d.hbvx_sizeof(13) != C.sizeof(PopPeriod):
-                raise HbvxError(f"{path}: layout mismatch for PopPeriod: {d.hbvx_sizeof(13)} != {C.sizeof(PopPeriod)}")
+        checked = set()             # hbvx_sizeof indices: several exports share a struct
+        for name, _, restype, argtypes, layout in SIGNATURES:    # the required rows come first: hbvx_sizeof is bound by then
+            if name in self.missing:
+                continue
+            fn = getattr(d, name)
+            fn.restype, fn.argtypes = restype, argtypes
+            if layout is not None and layout[0] not in checked:
+                checked.add(layout[0])
+                which, st = layout
+                if d.hbvx_sizeof(which) != C.sizeof(st):
+                    raise HbvxError(f"{path}: layout mismatch for {st.__name__}: {d.hbvx_sizeof(which)} != {C.sizeof(st)}")
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -557,55 +474,6 @@ class Library:
         self._check(self.dll.hbvx_quadform(C.byref(g), s, m, q, ws, C.c_uint64(ws_bytes), C.c_void_p(stream)),
                     "hbvx_quadform")
 
-    def population_cost(self, desc, pop, stream: int):
-        """hbvx_population_cost; `desc` / `pop` may be None (the ABI's own refusals are under test)."""
-        self.require("hbvx_population_cost")
-        self._check(self.dll.hbvx_population_cost(None if desc is None else C.byref(desc),
-                                                  None if pop is None else C.byref(pop), C.c_void_p(stream)),
-                    "hbvx_population_cost")
-
-    def population_stats(self, desc, ps, stream: int):
-        """hbvx_population_stats; `desc` / `ps` may be None (the ABI's own refusals are under test)."""
-        self.require("hbvx_population_stats")
-        self._check(self.dll.hbvx_population_stats(None if desc is None else C.byref(desc),
-                                                   None if ps is None else C.byref(ps), C.c_void_p(stream)),
-                    "hbvx_population_stats")
-
-    def population_joint(self, desc, pj, stream: int):
-        """hbvx_population_joint; `desc` / `pj` may be None (the ABI's own refusals are under test)."""
-        self.require("hbvx_population_joint")
-        self._check(self.dll.hbvx_population_joint(None if desc is None else C.byref(desc),
-                                                   None if pj is None else C.byref(pj), stream),
-                    "hbvx_population_joint")
-
-    def population_period(self, desc, pq, stream: int):
-        """hbvx_population_period; `desc` / `pq` may be None (the ABI's own refusals are under test)."""
-        self.require("hbvx_population_period")
-        self._check(self.dll.hbvx_population_period(None if desc is None else C.byref(desc),
-                                                    None if pq is None else C.byref(pq), C.c_void_p(stream)),
-                    "hbvx_population_period")
-
-    def adj_population_period(self, desc, pq, stream: int):
-        """hbvx_adj_population_period; `desc` / `pq` may be None (the ABI's own refusals are under test)."""
-        self.require("hbvx_adj_population_period")
-        self._check(self.dll.hbvx_adj_population_period(None if desc is None else C.byref(desc),
-                                                        None if pq is None else C.byref(pq), C.c_void_p(stream)),
-                    "hbvx_adj_population_period")
-
-    def adj_population_cost(self, desc, pop, stream: int):
-        """hbvx_adj_population_cost; `desc` / `pop` may be None (the ABI's own refusals are under test)."""
-        self.require("hbvx_adj_population_cost")
-        self._check(self.dll.hbvx_adj_population_cost(None if desc is None else C.byref(desc),
-                                                      None if pop is None else C.byref(pop), C.c_void_p(stream)),
-                    "hbvx_adj_population_cost")
-
-    def adj_population_stats(self, desc, ps, stream: int):
-        """hbvx_adj_population_stats; `desc` / `ps` may be None (the ABI's own refusals are under test)."""
-        self.require("hbvx_adj_population_stats")
-        self._check(self.dll.hbvx_adj_population_stats(None if desc is None else C.byref(desc),
-                                                       None if ps is None else C.byref(ps), C.c_void_p(stream)),
-                    "hbvx_adj_population_stats")
-
     def gage_route_tangent_workspace_bytes(self, r: GageDesc, n_dir: int) -> int:
         self.require("hbvx_gage_route_tangent_workspace_bytes")
         return int(self.dll.hbvx_gage_route_tangent_workspace_bytes(C.byref(r), n_dir))
@@ -636,3 +504,18 @@ class Library:
         self._check(self.dll.hbvx_route_backward(C.byref(r), q, uh, gqr, gq, gra, grb, ws,
                                                  C.c_uint64(ws_bytes), C.c_void_p(stream)),
                     "hbvx_route_backward")
+
+
+def _population_method(entry: str):
+    def call(self, desc, args, stream: int):
+        self.require(entry)
+        self._check(getattr(self.dll, entry)(None if desc is None else C.byref(desc),
+                                             None if args is None else C.byref(args), C.c_void_p(stream)), entry)
+    call.__name__ = entry[len("hbvx_"):]
+    call.__doc__ = (f"{entry}; `desc` / `args` (its {POPULATION[entry].struct.__name__}) may be None (the ABI's own "
+                    "refusals are under test).")
+    return call
+
+
+for _name in POPULATION:        # Library.population_cost(desc, pop, stream) ... Library.adj_population_period(desc, pq, stream)
+    setattr(Library, _name[len("hbvx_"):], _population_method(_name))

@@ -30,39 +30,10 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _abi, ops
-from ._lib import get_library
-from .calibrate import _NO_TARGET, _check_request
-from .population import (OBJECTIVES, _calendar, _candidate_sources, _check_aux, _check_candidates, _check_period_target,
-                         _check_search, _mixed_cost, _objective_cost, _observations, _period_days, _search,
-                         population_score)
+from . import _abi
+from .population import IMPLICIT, _front, _search_call
 
 AUX_KEYS = tuple(_abi.ADJ_POP_AUX_SERIES)       # 'SNOWPACK', 'MELTWATER', 'SM', 'SUZ', 'SLZ'
-
-
-def _check(model, x_dict, parameters, target, names, weights, what):
-    """Everything that can be refused without running the model."""
-    if getattr(model, '_model_id', None) != _abi.MODEL_HBVADJ:
-        raise NotImplementedError(f"{what} is for HbvAdj, not {type(model).__name__}: Hbv, Hbv_1_1p and Hbv_2 go through "
-                                  f"hydrodl2_amd.{what[4:]}")
-    req = _check_request(model, x_dict, parameters, target, names, 'flow_sim', weights, 1, what=what)
-    if model.newton_stop == 'global':
-        raise ValueError(f"{what}: newton_stop='global' (one stopping vote over the lanes of a wave) would make a "
-                         "candidate's cost depend on the basins that share its wave; use newton_stop='lane'")
-    if model.comprout:
-        raise ValueError(f"{what}: comprout=True routes every member, not the ensemble mean; not supported")
-    return req
-
-
-def _primal(model, req, x_dict, parameters):
-    """The one run of the module at `parameters`: (outputs, the recorded call of its main pass)."""
-    with torch.no_grad(), ops.record_paths(want_traj=False) as records:     # the kernel solves every day itself
-        outputs = model(x_dict, parameters)
-    main = records[-1]
-    cfg = main.cfg
-    if cfg.T != req.T_out or cfg.B != req.B:
-        raise RuntimeError(f"{type(model).__name__} ran {cfg.T} days on {cfg.B} basins, expected {req.T_out} on {req.B}")
-    return outputs, main
 
 
 def adj_population_cost(model, x_dict: dict, parameters, candidates: torch.Tensor, target,
@@ -87,42 +58,8 @@ def adj_population_cost(model, x_dict: dict, parameters, candidates: torch.Tenso
     Refused before the model runs: any model but HbvAdj (NotImplementedError); graph=True, newton_stop='global',
     comprout=True, dynamic or unknown names, a wrong shape / dtype / device of candidates, target or weights, infinite
     targets, negative or non-finite weights (ValueError); a library without hbvx_adj_population_cost (HbvxError)."""
-    req = _check(model, x_dict, parameters, target, names, weights, "adj_population_cost")
-    _check_candidates(req, x_dict, candidates)
-    get_library().require("hbvx_adj_population_cost")
-
-    outputs, main = _primal(model, req, x_dict, parameters)
-    dev = main.x.device
-    tgt = target.to(device=dev, dtype=torch.float32).reshape(req.T_out, req.B)
-    miss = torch.isnan(tgt)
-    if weights is None and not bool(miss.any()):
-        w = None
-        n_obs = torch.full((req.B,), req.T_out, dtype=torch.int64, device=dev)
-    else:
-        w = torch.ones_like(tgt) if weights is None else weights.to(device=dev, dtype=torch.float32)
-        w = torch.where(miss, torch.zeros_like(w), w).contiguous()
-        tgt = torch.where(miss, torch.zeros_like(tgt), tgt)     # 0 * NaN would be NaN: the kernel multiplies what it gets
-        n_obs = (w > 0).sum(0, dtype=torch.int64)
-
-    sources, route = _candidate_sources(model, names, candidates)
-    cost, series = ops.adj_population_cost(main, sources, route, tgt.contiguous(), w, 0, return_series)
-    cost = torch.where(torch.isfinite(cost), cost, torch.full_like(cost, float('inf')))
-    out = {'cost': cost, 'n_obs': n_obs, 'columns': list(req.cols), 'outputs': outputs}
-    if return_series:
-        out['series'] = series
-    return out
-
-
-def _stats(model, req, x_dict, parameters, candidates, names, ob, transform, return_series):
-    outputs, main = _primal(model, req, x_dict, parameters)
-    sources, route = _candidate_sources(model, names, candidates)
-    sse, s1, s2, s3, series = ops.adj_population_stats(main, sources, route, ob['target'], ob['w'], ob['shift'],
-                                                       ob['eps'], transform, 0, return_series)
-    out = {'sse': sse, 's1': s1, 's2': s2, 's3': s3, 'shift': ob['shift'], 'obs': ob['obs'], 'transform': transform,
-           'eps': ob['eps'], 'n_obs': ob['n_obs'], 'columns': list(req.cols), 'outputs': outputs}
-    if return_series:
-        out['series'] = series
-    return out
+    return _front(IMPLICIT, "adj_population_cost", 'cost', model, x_dict, parameters, candidates, target, names, weights,
+                  return_series=return_series)
 
 
 def adj_population_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, target,
@@ -137,62 +74,8 @@ def adj_population_stats(model, x_dict: dict, parameters, candidates: torch.Tens
     Refused before the model runs: everything `adj_population_cost` refuses; an unknown transform; eps <= 0 or
     non-finite; a negative target under 'sqrt'; a target <= -eps under 'log' (ValueError); a library without
     hbvx_adj_population_stats (HbvxError)."""
-    req = _check(model, x_dict, parameters, target, names, weights, "adj_population_stats")
-    _check_candidates(req, x_dict, candidates)
-    ob = _observations(req, x_dict, target, weights, transform, eps, "adj_population_stats")
-    get_library().require("hbvx_adj_population_stats")
-    return _stats(model, req, x_dict, parameters, candidates, names, ob, transform, return_series)
-
-
-def _period_request(model, x_dict, parameters, candidates, target, periods, aux_target, aux_key, aux_periods, names,
-                    weights, aux_weights, transform, eps, what):
-    """Everything `adj_population_period_stats` can refuse before the model runs, and what it works on: population.py's
-    `_period_request` with this module's `_check` and the five storages as aux keys -> (req, ob, aux_ob or None, (flow
-    closing days, aux closing days or None) as int64 CPU tensors)."""
-    req = _check(model, x_dict, parameters, _NO_TARGET, names, None, what)
-    if candidates is not None:
-        _check_candidates(req, x_dict, candidates)
-    ends_f = _calendar(periods, req.T_out, "periods", what)
-    _check_period_target(req, x_dict, target, weights, int(ends_f.numel()), what)
-    ends_a = aux_ob = None
-    if aux_key is None and aux_target is None:
-        if aux_periods is not None or aux_weights is not None:
-            raise ValueError(f"{what}: {'aux_periods' if aux_periods is not None else 'aux_weights'} without aux_key")
-    else:
-        ends_a = _calendar(aux_periods, req.T_out, "aux_periods", what)
-        _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what, rows=int(ends_a.numel()), keys=AUX_KEYS)
-    ob = _observations(req, x_dict, target, weights, transform, eps, what, rows=int(ends_f.numel()))
-    if ends_a is not None:
-        aux_ob = _observations(req, x_dict, aux_target, aux_weights, 'none', None, what, rows=int(ends_a.numel()))
-    get_library().require("hbvx_adj_population_period")
-    return req, ob, aux_ob, (ends_f, ends_a)
-
-
-def _period(model, req, x_dict, parameters, candidates, names, ob, transform, aux_key, aux_ob, ends, return_series):
-    outputs, main = _primal(model, req, x_dict, parameters)
-    sources, route = _candidate_sources(model, names, candidates)
-    dev = main.x.device
-    end_f, end_a = (None if e is None else e.to(device=dev, dtype=torch.int32) for e in ends)
-    if aux_ob is None:
-        flow, aux = ops.adj_population_period(main, sources, route, ob['target'], ob['w'], ob['shift'], ob['eps'],
-                                              transform, end_f, t_first=0, want_sim=return_series)
-    else:
-        flow, aux = ops.adj_population_period(main, sources, route, ob['target'], ob['w'], ob['shift'], ob['eps'],
-                                              transform, end_f, _abi.ADJ_POP_AUX_SERIES[aux_key], aux_ob['target'],
-                                              aux_ob['w'], aux_ob['shift'], end_a, 0, return_series)
-    out = {'columns': list(req.cols), 'outputs': outputs}
-    for name, got, o, tr, e in (('flow', flow, ob, transform, ends[0]), ('aux', aux, aux_ob, 'none', ends[1])):
-        if got is None:
-            continue
-        sub = dict(zip(('sse', 's1', 's2', 's3'), got[:4]))
-        sub.update(shift=o['shift'], obs=o['obs'], transform=tr, eps=o['eps'], n_obs=o['n_obs'], columns=list(req.cols),
-                   outputs=outputs, period_ends=e.clone(), period_days=_period_days(e))
-        if return_series:
-            sub['series'] = got[4]
-        out[name] = sub
-    if aux is not None:
-        out['aux']['key'] = aux_key
-    return out
+    return _front(IMPLICIT, "adj_population_stats", 'stats', model, x_dict, parameters, candidates, target, names, weights,
+                  transform, eps, return_series=return_series)
 
 
 def adj_population_period_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, target, periods=None,
@@ -219,10 +102,8 @@ def adj_population_period_stats(model, x_dict: dict, parameters, candidates: tor
     refuses about calendars, period targets and aux arguments; an aux_key that is not one of the five storages
     (ValueError); any model but HbvAdj (NotImplementedError); a library without hbvx_adj_population_period
     (HbvxError)."""
-    what = "adj_population_period_stats"
-    req, ob, aux_ob, ends = _period_request(model, x_dict, parameters, candidates, target, periods, aux_target, aux_key,
-                                            aux_periods, names, weights, aux_weights, transform, eps, what)
-    return _period(model, req, x_dict, parameters, candidates, names, ob, transform, aux_key, aux_ob, ends, return_series)
+    return _front(IMPLICIT, "adj_population_period_stats", 'period', model, x_dict, parameters, candidates, target, periods,
+                  aux_target, aux_key, aux_periods, names, weights, aux_weights, transform, eps, return_series)
 
 
 def adj_population_search(model, x_dict: dict, parameters, target, names: Optional[Sequence[str]] = None,
@@ -244,47 +125,6 @@ def adj_population_search(model, x_dict: dict, parameters, target, names: Option
 
     Returns (best, history) as `population_search`; the inputs are not modified.  dy_drop > 0 makes the cost
     stochastic: ValueError."""
-    what = "adj_population_search"
-    _check_search(model, n_candidates, n_rounds, shrink, objective, what)
-    joint = aux_target is not None or aux_key is not None or aux_weights is not None
-    if joint or periods is not None or aux_periods is not None:
-        if joint:
-            if aux_objective not in OBJECTIVES:
-                raise ValueError(f"{what}: aux_objective must be one of {list(OBJECTIVES)}, got {aux_objective!r}")
-            if not 0.0 <= float(aux_share) <= 1.0:          # (a NaN fails both comparisons)
-                raise ValueError(f"{what}: aux_share must lie in [0, 1], got {aux_share!r}")
-            if aux_objective == 'sse' and objective != 'sse':
-                raise ValueError(f"{what}: aux_objective 'sse' with objective {objective!r} would add a squared error to "
-                                 "1 - score: two scales in one sum")
-        req, ob, aux_ob, ends = _period_request(model, x_dict, parameters, None, target, periods, aux_target, aux_key,
-                                                aux_periods, names, weights, aux_weights, transform, eps, what)
-
-        def evaluate_periods(cands):
-            st = _period(model, req, x_dict, parameters, cands, names, ob, transform, aux_key, aux_ob, ends, False)
-            score = population_score(st['flow'], objective)
-            if not joint:
-                return _objective_cost(score, objective), score
-            score_aux = population_score(st['aux'], aux_objective)
-            return _mixed_cost(_objective_cost(score, objective), _objective_cost(score_aux, aux_objective),
-                               float(aux_share)), (score, score_aux)
-
-        return _search(req, x_dict, parameters, evaluate_periods, True, n_candidates, n_rounds, shrink, generator,
-                       joint or objective != 'sse', joint)
-    req = _check(model, x_dict, parameters, target, names, weights, "adj_population_search")
-    by_stats = objective != 'sse' or transform != 'none'
-    if by_stats:
-        ob = _observations(req, x_dict, target, weights, transform, eps, "adj_population_search")
-        get_library().require("hbvx_adj_population_stats")
-    else:
-        get_library().require("hbvx_adj_population_cost")       # before the first draw is made
-
-    def evaluate(cands):
-        """(cost, score or None) [P,B] of one round's candidates."""
-        if not by_stats:
-            return adj_population_cost(model, x_dict, parameters, cands, target, names, weights)['cost'], None
-        st = _stats(model, req, x_dict, parameters, cands, names, ob, transform, False)
-        score = population_score(st, objective)
-        return _objective_cost(score, objective), score
-
-    return _search(req, x_dict, parameters, evaluate, True, n_candidates, n_rounds, shrink, generator,
-                   objective != 'sse')
+    return _search_call(IMPLICIT, "adj_population_search", model, x_dict, parameters, target, names, n_candidates,
+                        n_rounds, shrink, weights, generator, objective, transform, eps, aux_target, aux_key, aux_weights,
+                        aux_objective, aux_share, periods, aux_periods)

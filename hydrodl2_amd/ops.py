@@ -1069,191 +1069,79 @@ def quadform(series: torch.Tensor, factor: torch.Tensor) -> torch.Tensor:
     return out
 
 
-POP_MAX_CAND = 65535       # candidates of one hbvx_population_cost launch (a grid dimension)
+POP_MAX_CAND = 65535       # candidates of one launch of a population export (a grid dimension)
 
 
-def population_cost(rec: PathRecord, cand_sources: dict, route_cands, target: torch.Tensor, w: Optional[torch.Tensor],
-                    t_first: int = 0, want_sim: bool = False):
-    """The weighted squared error of the (routed) streamflow of P candidate static-parameter sets on one recorded call
-    of the path, through hbvx_population_cost (include/hbvx.h) on the current stream: (cost [P,B], sim [P,T_out,B] or
-    None), T_out = rec.cfg.T - t_first.
+class PopTerm(NamedTuple):
+    """One scored series of a population call, the flow or the aux term; what a form does not use stays None.
+    target, w   [rows,B] float32, rows = T_out, or the periods of `ends`; w may be None (ones).  The target is ALREADY
+                transformed, and the kernel multiplies what it is given: the caller masks.
+    shift       [B] float32, the point the moments are taken about (the weighted mean of target); not for the cost form.
+    eps         [B] float32, read under transform 'log' only.
+    transform   'none' | 'sqrt' | 'log', the flow's (the aux series is never transformed); not for the cost form.
+    ends        the period form: 1-D int32 tensor on the device of the record, the closing days of the periods, 0-based
+                in the scored days, ascending (the caller checks that; the kernel is safe either way).
+    series      the aux term: which series, a value of the entry's table in _abi.POPULATION."""
+    target: Optional[torch.Tensor]
+    w: Optional[torch.Tensor] = None
+    shift: Optional[torch.Tensor] = None
+    eps: Optional[torch.Tensor] = None
+    transform: Optional[str] = None
+    ends: Optional[torch.Tensor] = None
+    series: Optional[int] = None
+
+
+def population(rec: PathRecord, entry: str, cand_sources: dict, route_cands, flow: PopTerm,
+               aux: Optional[PopTerm] = None, t_first: int = 0, want_sim: bool = False):
+    """The scores of P candidate static-parameter sets on one recorded call of the path, through the population export
+    `entry` (a key of _abi.POPULATION; include/hbvx.h states each one's arithmetic) on the current stream:
+    (flow_out, aux_out), each (sse, s1, s2, s3, sim) -- [P,B] float32 sums and the series [P,rows,B] or None without
+    want_sim; rows = T_out = rec.cfg.T - t_first, under the period form the periods of the term's calendar.  The cost
+    form (hbvx_[adj_]population_cost) gives its cost as sse and None moments.  aux_out is None without an aux term.
 
     cand_sources  {parameter slot: (cands, column)}: candidate c's values of that slot for basin b are
                   cands[c, b, column : column + M] of the compact float32 [P,B,C] tensor `cands`; slots not named keep
                   the recorded call's static values.
     route_cands   (a, b), each None or (cands, column): the candidates' routing inputs; None keeps the recorded one.
                   Ignored when the recorded call does not route.
-    target, w     [T_out,B] float32; w may be None (ones).  The kernel multiplies what it is given: the caller masks.
+    flow, aux     `PopTerm`s.  The joint form needs `aux`, the period form takes it or not (aux None, or all of its
+                  fields None), the others refuse it.  The entries of the implicit scheme take a record of HbvAdjPath
+                  only, and their aux series is one of the five solved storages.
     More than POP_MAX_CAND candidates go in several launches; a candidate's bits do not depend on the split."""
-    cost, _, sim, _ = _population("population_cost", "hbvx_population_cost", lambda lib: lib.population_cost, rec,
-                               cand_sources, route_cands, target, w, t_first, want_sim, None)
-    return cost, sim
-
-
-def population_stats(rec: PathRecord, cand_sources: dict, route_cands, target_t: torch.Tensor, w: Optional[torch.Tensor],
-                     shift: torch.Tensor, eps: Optional[torch.Tensor], transform: str, t_first: int = 0,
-                     want_sim: bool = False):
-    """`population_cost` with the three moment chains of hbvx_population_stats (include/hbvx.h) beside the squared
-    error, on the transformed flow: (sse, s1, s2, s3 [P,B] each, sim [P,T_out,B] or None).
-
-    target_t      [T_out,B] float32, the target ALREADY transformed; shift [B] float32, the point the moments are taken
-                  about (the weighted mean of target_t); eps [B] float32, needed for transform 'log' only;
-                  transform 'none' | 'sqrt' | 'log'.  `sim` is the flow itself in every transform.
-    Everything else as `population_cost`: the same checks, the same split above POP_MAX_CAND."""
-    if transform not in _abi.POP_TRANSFORMS:
-        raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
-    if transform == "log" and eps is None:
-        raise ValueError("population_stats: transform 'log' needs eps")
-    sse, moments, sim, _ = _population("population_stats", "hbvx_population_stats", lambda lib: lib.population_stats, rec,
-                                    cand_sources, route_cands, target_t, w, t_first, want_sim,
-                                    (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None))
-    return (sse,) + moments + (sim,)
-
-
-def population_joint(rec: PathRecord, cand_sources: dict, route_cands, target_t: torch.Tensor, w: Optional[torch.Tensor],
-                     shift: torch.Tensor, eps: Optional[torch.Tensor], transform: str, aux_series: int,
-                     aux_target: torch.Tensor, aux_w: Optional[torch.Tensor], aux_shift: torch.Tensor, t_first: int = 0,
-                     want_sim: bool = False):
-    """`population_stats` with a second observed series scored in the same launch, through hbvx_population_joint
-    (include/hbvx.h): ((sse, s1, s2, s3, sim), (aux_sse, aux_s1, aux_s2, aux_s3, aux_sim)) -- the flow term with the bits
-    `population_stats` gives, the aux term the same four chains on the un-routed, un-transformed ensemble mean of flux
-    `aux_series` (an hbvx_flux index among _abi.POP_AUX_SERIES' values).
-
-    aux_target, aux_w  [T_out,B] float32, aux_w may be None (ones); aux_shift [B] float32.  want_sim asks for both series.
-    Everything else as `population_stats`: the same checks, the same split above POP_MAX_CAND."""
-    if transform not in _abi.POP_TRANSFORMS:
-        raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
-    if transform == "log" and eps is None:
-        raise ValueError("population_joint: transform 'log' needs eps")
-    if aux_series not in _abi.POP_AUX_SERIES.values():
-        raise ValueError(f"population_joint: aux_series must be one of {sorted(_abi.POP_AUX_SERIES.values())} "
-                         f"(hbvx_flux indices), got {aux_series!r}")
-    if aux_target is None or aux_shift is None:
-        raise ValueError("population_joint needs aux_target and aux_shift")
-    sse, moments, sim, aux = _population("population_joint", "hbvx_population_joint", lambda lib: lib.population_joint,
-                                         rec, cand_sources, route_cands, target_t, w, t_first, want_sim,
-                                         (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None),
-                                         (aux_series, aux_target, aux_w, aux_shift))
-    return (sse,) + moments + (sim,), aux
-
-
-def population_period(rec: PathRecord, cand_sources: dict, route_cands, target_t: torch.Tensor, w: Optional[torch.Tensor],
-                      shift: torch.Tensor, eps: Optional[torch.Tensor], transform: str, flow_end: torch.Tensor,
-                      aux_series: Optional[int] = None, aux_target: Optional[torch.Tensor] = None,
-                      aux_w: Optional[torch.Tensor] = None, aux_shift: Optional[torch.Tensor] = None,
-                      aux_end: Optional[torch.Tensor] = None, t_first: int = 0, want_sim: bool = False):
-    """`population_joint` on period means, through hbvx_population_period (include/hbvx.h): each series is averaged over
-    the periods of its calendar before it meets its target.  ((sse, s1, s2, s3, sim), (aux_sse, aux_s1, aux_s2, aux_s3,
-    aux_sim) or None).
-
-    flow_end, aux_end  1-D int32 tensors on the device of the record: the closing days of the periods, 0-based in the
-                  scored days, ascending (the caller checks that; the kernel is safe either way).
-    target_t, w   [KF,B] float32 per period, KF = len(flow_end); aux_target, aux_w [KA,B]; sim / aux_sim [P,KF,B] /
-                  [P,KA,B] period means.  aux_series None: no aux term (then no aux argument may be given).
-    Everything else as `population_joint`: the same checks, the same split above POP_MAX_CAND."""
-    if transform not in _abi.POP_TRANSFORMS:
-        raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
-    if transform == "log" and eps is None:
-        raise ValueError("population_period: transform 'log' needs eps")
-    aux = None
-    if aux_series is None:
-        if any(t is not None for t in (aux_target, aux_w, aux_shift, aux_end)):
-            raise ValueError("population_period: aux arguments without aux_series")
-    else:
-        if aux_series not in _abi.POP_AUX_SERIES.values():
-            raise ValueError(f"population_period: aux_series must be one of {sorted(_abi.POP_AUX_SERIES.values())} "
-                             f"(hbvx_flux indices), got {aux_series!r}")
-        if aux_target is None or aux_shift is None or aux_end is None:
-            raise ValueError("population_period needs aux_target, aux_shift and aux_end with aux_series")
-        aux = (aux_series, aux_target, aux_w, aux_shift)
-    sse, moments, sim, aux_out = _population("population_period", "hbvx_population_period",
-                                             lambda lib: lib.population_period, rec, cand_sources, route_cands, target_t,
-                                             w, t_first, want_sim,
-                                             (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None),
-                                             aux, (flow_end, aux_end))
-    return (sse,) + moments + (sim,), aux_out
-
-
-def _require_adj_record(what: str, rec: PathRecord) -> None:
+    info = _abi.POPULATION[entry]
+    what = entry[len("hbvx_"):]
+    cost_form, period_form = info.struct is _abi.Pop, info.struct is _abi.PopPeriod
+    if not cost_form:
+        if flow.transform not in _abi.POP_TRANSFORMS:
+            raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {flow.transform!r}")
+        if flow.transform == "log" and flow.eps is None:
+            raise ValueError(f"{what}: transform 'log' needs eps")
     cfg = rec.cfg
-    if cfg.model != _abi.MODEL_HBVADJ:
-        raise ValueError(f"{what}: the record is not a call of the implicit scheme (HbvAdjPath)")
-    if cfg.adj_stop == 1:
-        raise ValueError(f"{what}: the batch-wide Newton stopping rule (newton_stop='global') votes over the 64 lanes of a "
-                         "wave; a candidate's cost must not depend on that")
-
-
-def adj_population_cost(rec: PathRecord, cand_sources: dict, route_cands, target: torch.Tensor,
-                        w: Optional[torch.Tensor], t_first: int = 0, want_sim: bool = False):
-    """`population_cost` for a recorded call of HbvAdjPath, through hbvx_adj_population_cost (include/hbvx.h): every
-    candidate's days are solved in registers under the record's Newton policy.  Same arguments, same results."""
-    _require_adj_record("adj_population_cost", rec)
-    cost, _, sim, _ = _population("adj_population_cost", "hbvx_adj_population_cost", lambda lib: lib.adj_population_cost,
-                               rec, cand_sources, route_cands, target, w, t_first, want_sim, None)
-    return cost, sim
-
-
-def adj_population_stats(rec: PathRecord, cand_sources: dict, route_cands, target_t: torch.Tensor,
-                         w: Optional[torch.Tensor], shift: torch.Tensor, eps: Optional[torch.Tensor], transform: str,
-                         t_first: int = 0, want_sim: bool = False):
-    """`population_stats` for a recorded call of HbvAdjPath, through hbvx_adj_population_stats (include/hbvx.h)."""
-    if transform not in _abi.POP_TRANSFORMS:
-        raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
-    if transform == "log" and eps is None:
-        raise ValueError("adj_population_stats: transform 'log' needs eps")
-    _require_adj_record("adj_population_stats", rec)
-    sse, moments, sim, _ = _population("adj_population_stats", "hbvx_adj_population_stats",
-                                       lambda lib: lib.adj_population_stats, rec, cand_sources, route_cands, target_t, w,
-                                       t_first, want_sim,
-                                    (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None))
-    return (sse,) + moments + (sim,)
-
-
-def adj_population_period(rec: PathRecord, cand_sources: dict, route_cands, target_t: torch.Tensor,
-                          w: Optional[torch.Tensor], shift: torch.Tensor, eps: Optional[torch.Tensor], transform: str,
-                          flow_end: torch.Tensor, aux_series: Optional[int] = None,
-                          aux_target: Optional[torch.Tensor] = None, aux_w: Optional[torch.Tensor] = None,
-                          aux_shift: Optional[torch.Tensor] = None, aux_end: Optional[torch.Tensor] = None,
-                          t_first: int = 0, want_sim: bool = False):
-    """`population_period` for a recorded call of HbvAdjPath, through hbvx_adj_population_period (include/hbvx.h): the
-    same arguments and results, except that aux_series is the index of one of the five solved storages (among
-    _abi.ADJ_POP_AUX_SERIES' values), whose ensemble mean at the end of each day is the aux value."""
-    what = "adj_population_period"
-    if transform not in _abi.POP_TRANSFORMS:
-        raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {transform!r}")
-    if transform == "log" and eps is None:
-        raise ValueError(f"{what}: transform 'log' needs eps")
-    _require_adj_record(what, rec)
-    aux = None
-    if aux_series is None:
-        if any(t is not None for t in (aux_target, aux_w, aux_shift, aux_end)):
+    if info.implicit:
+        if cfg.model != _abi.MODEL_HBVADJ:
+            raise ValueError(f"{what}: the record is not a call of the implicit scheme (HbvAdjPath)")
+        if cfg.adj_stop == 1:
+            raise ValueError(f"{what}: the batch-wide Newton stopping rule (newton_stop='global') votes over the 64 lanes "
+                             "of a wave; a candidate's cost must not depend on that")
+    if info.aux_series is None:
+        if aux is not None:
+            raise ValueError(f"{what} has no aux term")
+    elif period_form and (aux is None or aux.series is None):
+        if aux is not None and any(t is not None for t in (aux.target, aux.w, aux.shift, aux.ends)):
             raise ValueError(f"{what}: aux arguments without aux_series")
+        aux = None
     else:
-        if aux_series not in _abi.ADJ_POP_AUX_SERIES.values():
-            raise ValueError(f"{what}: aux_series must be one of {sorted(_abi.ADJ_POP_AUX_SERIES.values())} "
-                             f"(storage indices), got {aux_series!r}")
-        if aux_target is None or aux_shift is None or aux_end is None:
+        if aux is None or aux.series not in info.aux_series.values():
+            raise ValueError(f"{what}: aux_series must be one of {sorted(info.aux_series.values())} "
+                             f"({'storage' if info.implicit else 'hbvx_flux'} indices), got "
+                             f"{None if aux is None else aux.series!r}")
+        if period_form and (aux.target is None or aux.shift is None or aux.ends is None):
             raise ValueError(f"{what} needs aux_target, aux_shift and aux_end with aux_series")
-        aux = (aux_series, aux_target, aux_w, aux_shift)
-    sse, moments, sim, aux_out = _population(what, "hbvx_adj_population_period", lambda lib: lib.adj_population_period,
-                                             rec, cand_sources, route_cands, target_t, w, t_first, want_sim,
-                                             (_abi.POP_TRANSFORMS[transform], shift, eps if transform == "log" else None),
-                                             aux, (flow_end, aux_end))
-    return (sse,) + moments + (sim,), aux_out
-
-
-def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: dict, route_cands, target, w, t_first,
-                want_sim, stats, aux=None, periods=None):
-    """What the seven population calls share -- stats None: the cost, stats = (transform id, shift, eps): the cost and the
-    moment chains, aux = (flux index, target, w, shift) with stats: the aux term's four chains beside them, periods =
-    (flow_end, aux_end or None) with stats: hbvx_population_period's calendars, with targets, weights and series per
-    period and aux optional; `entry` the export's name and `call_of(lib)` its Library method -- the checks, the
-    descriptors, the NaN-poisoned outputs and the launches.
-    -> (cost, (s1, s2, s3) or None, sim, (aux_sse, aux_s1, aux_s2, aux_s3, aux_sim) or None)."""
+        if aux.target is None or aux.shift is None:
+            raise ValueError(f"{what} needs aux_target and aux_shift")
     lib = get_library()
     lib.require(entry)
-    call = call_of(lib)
-    cfg = rec.cfg
+    call = getattr(lib, what)
     x, ptensors = rec.x, rec.ptensors
     dev = x.device
     T, B, M = cfg.T, cfg.B, cfg.M
@@ -1279,13 +1167,10 @@ def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: d
     for s in (route_cands or ()):
         if s is not None and not 0 <= s[1] < Cn:
             raise ValueError(f"routing candidate column {s[1]} outside the {Cn} columns")
-    aux_series, aux_target, aux_w, aux_shift = aux if aux is not None else (None, None, None, None)
     rows_f = rows_a = T_out         # rows of the flow's and the aux term's targets, weights and series
     ends = [None, None]
-    if periods is not None:
-        if (periods[1] is None) != (aux is None):
-            raise ValueError(f"{what}: the aux calendar and the aux term go together")
-        for i, (name, e) in enumerate((("flow_end", periods[0]), ("aux_end", periods[1]))):
+    if period_form:
+        for i, (name, e) in enumerate((("flow_end", flow.ends), ("aux_end", None if aux is None else aux.ends))):
             if e is None:
                 continue
             if e.dtype != torch.int32 or e.dim() != 1 or e.device != dev or not 1 <= e.numel() <= T_out:
@@ -1294,40 +1179,36 @@ def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: d
             ends[i] = e.contiguous()
         rows_f = int(ends[0].numel())
         rows_a = int(ends[1].numel()) if ends[1] is not None else 0
-    for name, t, rows in (("target", target, rows_f), ("w", w, rows_f), ("aux_target", aux_target, rows_a),
-                          ("aux_w", aux_w, rows_a)):
+    no_aux = PopTerm(None)
+    for name, t, rows in (("target", flow.target, rows_f), ("w", flow.w, rows_f),
+                          ("aux_target", (aux or no_aux).target, rows_a), ("aux_w", (aux or no_aux).w, rows_a)):
         if t is None:
             continue
         _check_tensor(lib, t, name)
         if tuple(t.shape) != (rows, B) or t.device != dev:
             raise ValueError(f"{name} must be [{rows},{B}] on {dev}, got {tuple(t.shape)} on {t.device}")
-    transform, shift, eps = stats if stats is not None else (None, None, None)
-    for name, t in (("shift", shift), ("eps", eps), ("aux_shift", aux_shift)):
+    shift, eps = (None, None) if cost_form else (flow.shift, flow.eps if flow.transform == "log" else None)
+    for name, t in (("shift", shift), ("eps", eps), ("aux_shift", (aux or no_aux).shift)):
         if t is None:
             continue
         _check_tensor(lib, t, name)
         if tuple(t.shape) != (B,) or t.device != dev:
             raise ValueError(f"{name} must be [{B}] on {dev}, got {tuple(t.shape)} on {t.device}")
-    tc = target.contiguous()
-    wc = None if w is None else w.contiguous()
-    shc = None if shift is None else shift.contiguous()
-    epc = None if eps is None else eps.contiguous()
-    atc, awc, ashc = (None if t is None else t.contiguous() for t in (aux_target, aux_w, aux_shift))
+    tc, wc, shc, epc = (None if t is None else t.contiguous() for t in (flow.target, flow.w, shift, eps))
+    atc, awc, ashc = (None if t is None else t.contiguous() for t in (aux or no_aux)[:3])
     stream = _stream_of(lib, x)
     desc = _fill_desc(cfg, x, rec.state_in, rec.muwts, rec.ac, rec.elev, ptensors)
     route = _route_desc(cfg, ptensors, S=1) if cfg.route is not None else None
     with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
         cost = _out((P, B), dev)
-        moments = tuple(_out((P, B), dev) for _ in range(3)) if stats is not None else None
+        moments = (None, None, None) if cost_form else tuple(_out((P, B), dev) for _ in range(3))
         sim = _out((P, rows_f, B), dev) if want_sim else None
         aux_out = None
         if aux is not None:
             aux_out = tuple(_out((P, B), dev) for _ in range(4)) + ((_out((P, rows_a, B), dev) if want_sim else None),)
         for c0 in range(0, P, POP_MAX_CAND):
-            pq = _abi.PopPeriod() if periods is not None else None
-            pj = pq.joint if periods is not None else _abi.PopJoint() if aux is not None else None
-            ps = pj.flow if pj is not None else _abi.PopStats() if stats is not None else None
-            pop = ps.pop if stats is not None else _abi.Pop()
+            args = info.struct()
+            pq, pj, ps, pop = _abi.pop_levels(args)
             pop.n_cand, pop.t_first = min(POP_MAX_CAND, P - c0), t_first
             for slot, (_, col) in cand_sources.items():
                 s = pop.p[slot]
@@ -1343,28 +1224,21 @@ def _population(what: str, entry: str, call_of, rec: PathRecord, cand_sources: d
             pop.target, pop.w = _ptr(tc), _ptr(wc)
             pop.cost = _ptr(cost, c0 * B)
             pop.sim = _ptr(sim, c0 * rows_f * B)
-            if stats is None:
-                _call(lib, entry, call, desc, pop, stream)
-            else:
-                ps.transform, ps.shift, ps.eps = transform, _ptr(shc), _ptr(epc)
+            if ps is not None:
+                ps.transform, ps.shift, ps.eps = _abi.POP_TRANSFORMS[flow.transform], _ptr(shc), _ptr(epc)
                 ps.s1, ps.s2, ps.s3 = (_ptr(m, c0 * B) for m in moments)
-                if pj is None:
-                    _call(lib, entry, call, desc, ps, stream)
-                    continue
-                if aux is None:
-                    pj.aux_series = _abi.POP_NO_AUX
-                else:
-                    pj.aux_series, pj.aux_target, pj.aux_w, pj.aux_shift = aux_series, _ptr(atc), _ptr(awc), _ptr(ashc)
-                    pj.aux_sse, pj.aux_s1, pj.aux_s2, pj.aux_s3 = (_ptr(m, c0 * B) for m in aux_out[:4])
-                    pj.aux_sim = _ptr(aux_out[4], c0 * rows_a * B)
-                if pq is None:
-                    _call(lib, entry, call, desc, pj, stream)
-                else:
-                    pq.n_flow_periods, pq.flow_end = rows_f, ends[0].data_ptr()
-                    if ends[1] is not None:
-                        pq.n_aux_periods, pq.aux_end = rows_a, ends[1].data_ptr()
-                    _call(lib, entry, call, desc, pq, stream)
-    return cost, moments, sim, aux_out
+            if pj is not None and aux is None:
+                pj.aux_series = _abi.POP_NO_AUX
+            elif pj is not None:
+                pj.aux_series, pj.aux_target, pj.aux_w, pj.aux_shift = aux.series, _ptr(atc), _ptr(awc), _ptr(ashc)
+                pj.aux_sse, pj.aux_s1, pj.aux_s2, pj.aux_s3 = (_ptr(m, c0 * B) for m in aux_out[:4])
+                pj.aux_sim = _ptr(aux_out[4], c0 * rows_a * B)
+            if pq is not None:
+                pq.n_flow_periods, pq.flow_end = rows_f, ends[0].data_ptr()
+                if ends[1] is not None:
+                    pq.n_aux_periods, pq.aux_end = rows_a, ends[1].data_ptr()
+            _call(lib, entry, call, desc, args, stream)
+    return (cost,) + moments + (sim,), aux_out
 
 
 class PathOut(NamedTuple):

@@ -20,33 +20,55 @@ per period, and `population_search(periods=..., aux_periods=...)` searches on th
 
 Hbv, Hbv_1_1p and Hbv_2 only.  HbvAdj has the first three calls and a period call of its own in adj_population.py
 (`adj_population_period_stats`: its second series is one of its five storages); nothing here is built for the hourly and
-multi-timescale models.  The aux series is not
-transformed, there is one per launch, calendars are shared by all basins, and there is no joint `calibrate`: two
-`normal_equations` calls can be summed by the caller.
+multi-timescale models.  The aux series is not transformed, there is one per launch, calendars are shared by all basins,
+and there is no joint `calibrate`: two `normal_equations` calls can be summed by the caller.
+
+Every call here and in adj_population.py is one front end over two `Family` records: checks, observations, requests and
+results are written once, and `_run` is the one function that runs the module and reaches ops.population.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
 from . import _abi, ops
 from ._lib import get_library
 from .calibrate import _NO_TARGET, _check_request, _static_tensor
-from .sensitivity import jacobian_columns
 
 _EDGE = 1e-4        # unit-space draws are kept in [_EDGE, 1 - _EDGE] where the module applies a sigmoid (finite logits)
 
 
-def _check(model, x_dict, parameters, target, names, weights, what):
-    """Everything that can be refused without running the model: calibrate's request checks for the key
-    'streamflow', and what this path adds to them."""
-    if getattr(model, '_model_id', None) == _abi.MODEL_HBVADJ:
+class Family(NamedTuple):
+    """What differs between the front ends of the explicit models (Hbv, Hbv_1_1p, Hbv_2: the functions of this file) and
+    those of the implicit scheme (HbvAdj: adj_population.py).  Everything else in this file is written once."""
+    implicit: bool      # which models `_check` admits and what it refuses; how `_primal` records the run and finds t_first
+    key: str            # the output that is scored
+    aux_keys: dict      # aux_key -> the series index the family's kernels take
+    prefix: str         # of the family's exports: prefix + 'cost' | 'stats' | 'joint' | 'period'
+    has_joint: bool     # False: there is no prefix + 'joint'; an aux term without a calendar goes to prefix + 'period'
+
+
+EXPLICIT = Family(False, 'streamflow', _abi.POP_AUX_SERIES, 'hbvx_population_', True)
+IMPLICIT = Family(True, 'flow_sim', _abi.ADJ_POP_AUX_SERIES, 'hbvx_adj_population_', False)
+
+
+def _check(family, model, x_dict, parameters, target, names, weights, what):
+    """Everything that can be refused without running the model: calibrate's request checks for the family's key, and
+    what this path adds to them."""
+    adj = getattr(model, '_model_id', None) == _abi.MODEL_HBVADJ
+    if adj and not family.implicit:
         raise NotImplementedError(f"{what} is not implemented for {type(model).__name__}: the implicit scheme needs its "
                                   "Newton solve inside the day loop, which is not this kernel; Hbv, Hbv_1_1p and Hbv_2 only "
                                   "-- HbvAdj goes through hydrodl2_amd.adj_population_cost / adj_population_stats / "
                                   "adj_population_search")
-    req = _check_request(model, x_dict, parameters, target, names, 'streamflow', weights, 1, what=what)
+    if family.implicit and not adj:
+        raise NotImplementedError(f"{what} is for HbvAdj, not {type(model).__name__}: Hbv, Hbv_1_1p and Hbv_2 go through "
+                                  f"hydrodl2_amd.{what[4:]}")
+    req = _check_request(model, x_dict, parameters, target, names, family.key, weights, 1, what=what)
+    if family.implicit and model.newton_stop == 'global':
+        raise ValueError(f"{what}: newton_stop='global' (one stopping vote over the lanes of a wave) would make a "
+                         "candidate's cost depend on the basins that share its wave; use newton_stop='lane'")
     if model.comprout:
         raise ValueError(f"{what}: comprout=True routes every member, not the ensemble mean; not supported")
     return req
@@ -80,21 +102,79 @@ def _check_candidates(req, x_dict, candidates):
         raise ValueError(f"candidates live on {candidates.device}, x_phy on {x.device}")
 
 
-def _primal(model, req, x_dict, parameters):
+def _primal(family, model, req, x_dict, parameters):
     """The one run of the module at `parameters`: (outputs, the recorded call of its main pass, t_first)."""
-    with torch.no_grad(), ops.record_paths() as records:
+    with torch.no_grad(), ops.record_paths(want_traj=not family.implicit) as records:   # HbvAdj's kernel solves every day itself
         outputs = model(x_dict, parameters)
     main = records[-1]
     cfg = main.cfg
-    t_first = cfg.T - req.T_out          # warm_up_states=False: the warm-up days are simulated, not scored
-    if t_first < 0 or cfg.B != req.B:
-        raise RuntimeError(f"{type(model).__name__} ran {cfg.T} days on {cfg.B} basins, expected at least {req.T_out} on {req.B}")
+    t_first = 0 if family.implicit else cfg.T - req.T_out       # warm_up_states=False: the warm-up days are simulated, not scored
+    if t_first < 0 or cfg.B != req.B or (family.implicit and cfg.T != req.T_out):
+        raise RuntimeError(f"{type(model).__name__} ran {cfg.T} days on {cfg.B} basins, expected "
+                           f"{'' if family.implicit else 'at least '}{req.T_out} on {req.B}")
     return outputs, main, t_first
 
 
+class Request(NamedTuple):
+    """A population call after its checks: what `_run` works on."""
+    model: object
+    x_dict: dict
+    parameters: object
+    names: Optional[Sequence[str]]
+    req: object                     # calibrate's request: columns, T_out, B
+    ob: dict                        # the flow's observations: `_cost_observations` (form 'cost') or `_observations`
+    transform: str = 'none'
+    aux_key: Optional[str] = None
+    aux_ob: Optional[dict] = None   # `_observations` of the aux term, None without one
+    ends: tuple = (None, None)      # form 'period': the closing days of the flow's and the aux calendar, int64 on the CPU
+    candidates: Optional[torch.Tensor] = None
+    return_series: bool = False
+
+
+def _sums(got, ob, transform, rq, outputs, ends=None):
+    """What `population_score` reads, for one scored series: the four chains `got[:4]` with the observation side `ob`."""
+    out = dict(zip(('sse', 's1', 's2', 's3'), got[:4]))
+    out.update(shift=ob['shift'], obs=ob['obs'], transform=transform, eps=ob['eps'], n_obs=ob['n_obs'],
+               columns=list(rq.req.cols), outputs=outputs)
+    if ends is not None:
+        out.update(period_ends=ends.clone(), period_days=_period_days(ends))
+    if rq.return_series:
+        out['series'] = got[4]
+    return out
+
+
+def _run(family, form, rq):
+    """The one route from every front end to the kernels: runs the module once at rq.parameters, then rq.candidates
+    through ops.population on the export family.prefix + form, and returns the call's result dictionary."""
+    outputs, main, t_first = _primal(family, rq.model, rq.req, rq.x_dict, rq.parameters)
+    sources, route = _candidate_sources(rq.model, rq.names, rq.candidates)
+    ob, aux_ob = rq.ob, rq.aux_ob
+    ends = rq.ends if form == 'period' else (None, None)
+    end_f, end_a = (None if e is None else e.to(device=main.x.device, dtype=torch.int32) for e in ends)
+    flow = ops.PopTerm(ob['target'], ob['w'], ob.get('shift'), ob.get('eps'), None if form == 'cost' else rq.transform,
+                       end_f)
+    aux = None if aux_ob is None else ops.PopTerm(aux_ob['target'], aux_ob['w'], aux_ob['shift'], ends=end_a,
+                                                  series=family.aux_keys[rq.aux_key])
+    flow_out, aux_out = ops.population(main, family.prefix + form, sources, route, flow, aux, t_first, rq.return_series)
+    if form == 'cost':
+        cost = flow_out[0]
+        out = {'cost': torch.where(torch.isfinite(cost), cost, torch.full_like(cost, float('inf'))), 'n_obs': ob['n_obs'],
+               'columns': list(rq.req.cols), 'outputs': outputs}
+        if rq.return_series:
+            out['series'] = flow_out[4]
+        return out
+    if form == 'stats':
+        return _sums(flow_out, ob, rq.transform, rq, outputs)
+    out = {'columns': list(rq.req.cols), 'outputs': outputs, 'flow': _sums(flow_out, ob, rq.transform, rq, outputs, ends[0])}
+    if aux_out is not None:
+        out['aux'] = _sums(aux_out, aux_ob, 'none', rq, outputs, ends[1])
+        out['aux']['key'] = rq.aux_key
+    return out
+
+
 def _candidate_sources(model, names, candidates):
-    """({parameter slot: (cands, column)}, (route_a, route_b) each None or (cands, column)) as ops.population_cost
-    takes them."""
+    """({parameter slot: (cands, column)}, (route_a, route_b) each None or (cands, column)) as ops.population takes
+    them."""
     cands = candidates.detach().contiguous()
     sources, route = {}, [None, None]
     for name, col, _ in _column_groups(model, names):
@@ -128,12 +208,14 @@ def population_cost(model, x_dict: dict, parameters, candidates: torch.Tensor, t
     initialize mode, comprout=True, dynamic or unknown names, a wrong shape / dtype / device of candidates, target or
     weights, infinite targets, negative or non-finite weights (ValueError); a library without hbvx_population_cost
     (HbvxError)."""
-    req = _check(model, x_dict, parameters, target, names, weights, "population_cost")
-    _check_candidates(req, x_dict, candidates)
-    get_library().require("hbvx_population_cost")
+    return _front(EXPLICIT, "population_cost", 'cost', model, x_dict, parameters, candidates, target, names, weights,
+                  return_series=return_series)
 
-    outputs, main, t_first = _primal(model, req, x_dict, parameters)
-    dev = main.x.device
+
+def _cost_observations(req, x_dict, target, weights):
+    """The observation side of the cost form: {'target' [T_out,B] float32 (0 where missing), 'w' [T_out,B] float32 or
+    None, 'n_obs' [B] int64} on the device of x_phy."""
+    dev = x_dict['x_phy'].device
     tgt = target.to(device=dev, dtype=torch.float32).reshape(req.T_out, req.B)
     miss = torch.isnan(tgt)
     if weights is None and not bool(miss.any()):
@@ -144,14 +226,36 @@ def population_cost(model, x_dict: dict, parameters, candidates: torch.Tensor, t
         w = torch.where(miss, torch.zeros_like(w), w).contiguous()
         tgt = torch.where(miss, torch.zeros_like(tgt), tgt)     # 0 * NaN would be NaN: the kernel multiplies what it gets
         n_obs = (w > 0).sum(0, dtype=torch.int64)
+    return {'target': tgt.contiguous(), 'w': w, 'n_obs': n_obs}
 
-    sources, route = _candidate_sources(model, names, candidates)
-    cost, series = ops.population_cost(main, sources, route, tgt.contiguous(), w, t_first, return_series)
-    cost = torch.where(torch.isfinite(cost), cost, torch.full_like(cost, float('inf')))
-    out = {'cost': cost, 'n_obs': n_obs, 'columns': list(req.cols), 'outputs': outputs}
-    if return_series:
-        out['series'] = series
-    return out
+
+def _daily_request(family, what, form, model, x_dict, parameters, candidates, target, names, weights, transform='none',
+                   eps=None, aux_target=None, aux_key=None, aux_weights=None, return_series=False, mix=None) -> Request:
+    """Everything the forms 'cost', 'stats' and 'joint' can refuse before the model runs, and what they work on.
+    candidates None: the search, which fills them in round by round; mix: its (objective, aux_objective, aux_share)."""
+    req = _check(family, model, x_dict, parameters, target, names, weights, what)
+    if candidates is not None:
+        _check_candidates(req, x_dict, candidates)
+    aux_ob = None
+    if form == 'joint':
+        _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what, keys=tuple(family.aux_keys))
+        if mix is not None:
+            _check_mix(*mix, what)
+    if form == 'cost':
+        ob = _cost_observations(req, x_dict, target, weights)
+    else:
+        ob = _observations(req, x_dict, target, weights, transform, eps, what)
+    if form == 'joint':
+        aux_ob = _observations(req, x_dict, aux_target, aux_weights, 'none', None, what)
+    get_library().require(family.prefix + form)
+    return Request(model, x_dict, parameters, names, req, ob, transform, aux_key, aux_ob, candidates=candidates,
+                   return_series=return_series)
+
+
+def _front(family, what, form, *args, **kw):
+    """A public call: the request of its form (`_period_request` / `_daily_request` take the arguments), then `_run`."""
+    rq = _period_request(family, what, *args, **kw) if form == 'period' else _daily_request(family, what, form, *args, **kw)
+    return _run(family, form, rq)
 
 
 TRANSFORMS = tuple(_abi.POP_TRANSFORMS)                 # 'none', 'sqrt', 'log'
@@ -214,18 +318,6 @@ def _observations(req, x_dict, target, weights, transform, eps, what, rows=None)
             'n_obs': (w > 0).sum(0, dtype=torch.int64)}
 
 
-def _stats(model, req, x_dict, parameters, candidates, names, ob, transform, return_series):
-    outputs, main, t_first = _primal(model, req, x_dict, parameters)
-    sources, route = _candidate_sources(model, names, candidates)
-    sse, s1, s2, s3, series = ops.population_stats(main, sources, route, ob['target'], ob['w'], ob['shift'], ob['eps'],
-                                                   transform, t_first, return_series)
-    out = {'sse': sse, 's1': s1, 's2': s2, 's3': s3, 'shift': ob['shift'], 'obs': ob['obs'], 'transform': transform,
-           'eps': ob['eps'], 'n_obs': ob['n_obs'], 'columns': list(req.cols), 'outputs': outputs}
-    if return_series:
-        out['series'] = series
-    return out
-
-
 def population_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, target,
                      names: Optional[Sequence[str]] = None, weights=None, transform: str = 'none', eps=None,
                      return_series: bool = False) -> dict:
@@ -248,11 +340,8 @@ def population_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, 
     Refused before the model runs: everything `population_cost` refuses; an unknown transform; eps <= 0 or non-finite;
     a negative target under 'sqrt'; a target <= -eps under 'log' (ValueError); a library without hbvx_population_stats
     (HbvxError)."""
-    req = _check(model, x_dict, parameters, target, names, weights, "population_stats")
-    _check_candidates(req, x_dict, candidates)
-    ob = _observations(req, x_dict, target, weights, transform, eps, "population_stats")
-    get_library().require("hbvx_population_stats")
-    return _stats(model, req, x_dict, parameters, candidates, names, ob, transform, return_series)
+    return _front(EXPLICIT, "population_stats", 'stats', model, x_dict, parameters, candidates, target, names, weights,
+                  transform, eps, return_series=return_series)
 
 
 AUX_KEYS = tuple(_abi.POP_AUX_SERIES)       # 'srflow_no_rout', 'ssflow_no_rout', 'gwflow_no_rout', 'AET_hydro', 'SWE'
@@ -260,18 +349,23 @@ AUX_KEYS = tuple(_abi.POP_AUX_SERIES)       # 'srflow_no_rout', 'ssflow_no_rout'
 
 def _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what, rows=None, keys=AUX_KEYS):
     """What can be refused about the aux term without running the model.  rows: the leading size of aux_target and
-    aux_weights where it is not T_out (the periods of `population_period_stats`).  keys: the aux keys the caller's
-    kernel offers (`adj_population_period_stats`: the five storages)."""
+    aux_weights where it is not T_out (the periods of its calendar).  keys: the aux keys the family's kernels offer."""
     if aux_target is None or aux_key is None:
         raise ValueError(f"{what}: aux_target and aux_key go together "
                          f"({'aux_target' if aux_target is None else 'aux_key'} is missing)")
     if aux_key not in keys:
         raise ValueError(f"{what}: aux_key must be one of {list(keys)}, got {aux_key!r}")
-    dev = x_dict['x_phy'].device
     n, of = (req.T_out, "days after the warm-up") if rows is None else (rows, "periods of its calendar")
-    for name, t, shapes in (("aux_target", aux_target, ((n, req.B), (n, req.B, 1))),
-                            ("aux_weights", aux_weights, ((n, req.B),))):
-        if t is None:
+    _check_rows(req, x_dict, aux_target, aux_weights, n, of, what, "aux_")
+
+
+def _check_rows(req, x_dict, target, weights, rows, of, what, aux=""):
+    """calibrate's checks of a target and its weights where their leading size is `rows` -- the `of` of the message --
+    and not necessarily T_out; aux: 'aux_' for the aux term's pair, which the messages then name so."""
+    dev = x_dict['x_phy'].device
+    for name, t, shapes in ((aux + "target", target, ((rows, req.B), (rows, req.B, 1))),
+                            (aux + "weights", weights, ((rows, req.B),))):
+        if t is None and name.endswith("weights"):
             continue
         if not torch.is_tensor(t) or tuple(t.shape) not in shapes:
             raise ValueError(f"{what}: {name} must be {' or '.join(str(list(s)) for s in shapes)} (the {of}), "
@@ -280,31 +374,13 @@ def _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what, rows=None, k
             raise ValueError(f"{what}: {name} must be float32 or float64, got {t.dtype}")
         if t.device != dev:
             raise ValueError(f"{what}: {name} lives on {t.device}, x_phy on {dev}")
-    if bool(torch.isinf(aux_target).any()):
-        raise ValueError(f"{what}: aux_target holds infinities (a missing observation is a NaN)")
-    if aux_weights is not None:
-        if not bool(torch.isfinite(aux_weights).all()):
-            raise ValueError(f"{what}: aux_weights must be finite")
-        if bool((aux_weights < 0).any()):
-            raise ValueError(f"{what}: aux_weights must not be negative")
-
-
-def _joint(model, req, x_dict, parameters, candidates, names, ob, transform, aux_key, aux_ob, return_series):
-    outputs, main, t_first = _primal(model, req, x_dict, parameters)
-    sources, route = _candidate_sources(model, names, candidates)
-    flow, aux = ops.population_joint(main, sources, route, ob['target'], ob['w'], ob['shift'], ob['eps'], transform,
-                                     _abi.POP_AUX_SERIES[aux_key], aux_ob['target'], aux_ob['w'], aux_ob['shift'], t_first,
-                                     return_series)
-    out = {'columns': list(req.cols), 'outputs': outputs}
-    for name, got, o, tr in (('flow', flow, ob, transform), ('aux', aux, aux_ob, 'none')):
-        sub = dict(zip(('sse', 's1', 's2', 's3'), got[:4]))
-        sub.update(shift=o['shift'], obs=o['obs'], transform=tr, eps=o['eps'], n_obs=o['n_obs'], columns=list(req.cols),
-                   outputs=outputs)
-        if return_series:
-            sub['series'] = got[4]
-        out[name] = sub
-    out['aux']['key'] = aux_key
-    return out
+    if bool(torch.isinf(target).any()):
+        raise ValueError(f"{what}: {aux}target holds infinities (a missing observation is a NaN)")
+    if weights is not None:
+        if not bool(torch.isfinite(weights).all()):
+            raise ValueError(f"{what}: {aux}weights must be finite")
+        if bool((weights < 0).any()):
+            raise ValueError(f"{what}: {aux}weights must not be negative")
 
 
 def population_joint_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, target, aux_target, aux_key: str,
@@ -327,14 +403,8 @@ def population_joint_stats(model, x_dict: dict, parameters, candidates: torch.Te
     Refused before the model runs: everything `population_stats` refuses; an unknown aux_key; aux_key without aux_target
     or the reverse; a wrong shape, dtype or device of aux_target / aux_weights, infinite aux targets, negative or
     non-finite aux weights (ValueError); a library without hbvx_population_joint (HbvxError)."""
-    what = "population_joint_stats"
-    req = _check(model, x_dict, parameters, target, names, weights, what)
-    _check_candidates(req, x_dict, candidates)
-    _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what)
-    ob = _observations(req, x_dict, target, weights, transform, eps, what)
-    aux_ob = _observations(req, x_dict, aux_target, aux_weights, 'none', None, what)
-    get_library().require("hbvx_population_joint")
-    return _joint(model, req, x_dict, parameters, candidates, names, ob, transform, aux_key, aux_ob, return_series)
+    return _front(EXPLICIT, "population_joint_stats", 'joint', model, x_dict, parameters, candidates, target, names, weights,
+                  transform, eps, aux_target, aux_key, aux_weights, return_series)
 
 
 def _calendar(periods, T_out: int, name: str, what: str) -> torch.Tensor:
@@ -369,76 +439,29 @@ def _period_days(ends: torch.Tensor) -> torch.Tensor:
     return ends - torch.cat([ends.new_full((1,), -1), ends[:-1]])
 
 
-def _check_period_target(req, x_dict, target, weights, K, what):
-    """calibrate's checks of target and weights, with the K periods of the calendar in place of the days."""
-    dev = x_dict['x_phy'].device
-    for name, t, shapes in (("target", target, ((K, req.B), (K, req.B, 1))), ("weights", weights, ((K, req.B),))):
-        if t is None and name == "weights":
-            continue
-        if not torch.is_tensor(t) or tuple(t.shape) not in shapes:
-            raise ValueError(f"{what}: {name} must be {' or '.join(str(list(s)) for s in shapes)} (the {K} periods of its "
-                             f"calendar), got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
-        if t.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"{what}: {name} must be float32 or float64, got {t.dtype}")
-        if t.device != dev:
-            raise ValueError(f"{what}: {name} lives on {t.device}, x_phy on {dev}")
-    if bool(torch.isinf(target).any()):
-        raise ValueError(f"{what}: target holds infinities (a missing observation is a NaN)")
-    if weights is not None:
-        if not bool(torch.isfinite(weights).all()):
-            raise ValueError(f"{what}: weights must be finite")
-        if bool((weights < 0).any()):
-            raise ValueError(f"{what}: weights must not be negative")
-
-
-def _period_request(model, x_dict, parameters, candidates, target, periods, aux_target, aux_key, aux_periods, names,
-                    weights, aux_weights, transform, eps, what):
-    """Everything `population_period_stats` can refuse before the model runs, and what it works on: (req, ob, aux_ob or
-    None, (flow closing days, aux closing days or None) as int64 CPU tensors)."""
-    req = _check(model, x_dict, parameters, _NO_TARGET, names, None, what)
+def _period_request(family, what, model, x_dict, parameters, candidates, target, periods, aux_target, aux_key,
+                    aux_periods, names, weights, aux_weights, transform, eps, return_series=False) -> Request:
+    """Everything the period form can refuse before the model runs, and what it works on.  candidates None: the search,
+    which fills them in round by round."""
+    req = _check(family, model, x_dict, parameters, _NO_TARGET, names, None, what)
     if candidates is not None:
         _check_candidates(req, x_dict, candidates)
     ends_f = _calendar(periods, req.T_out, "periods", what)
-    _check_period_target(req, x_dict, target, weights, int(ends_f.numel()), what)
+    K = int(ends_f.numel())
+    _check_rows(req, x_dict, target, weights, K, f"{K} periods of its calendar", what)
     ends_a = aux_ob = None
     if aux_key is None and aux_target is None:
         if aux_periods is not None or aux_weights is not None:
             raise ValueError(f"{what}: {'aux_periods' if aux_periods is not None else 'aux_weights'} without aux_key")
     else:
         ends_a = _calendar(aux_periods, req.T_out, "aux_periods", what)
-        _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what, rows=int(ends_a.numel()))
-    ob = _observations(req, x_dict, target, weights, transform, eps, what, rows=int(ends_f.numel()))
+        _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what, rows=int(ends_a.numel()), keys=tuple(family.aux_keys))
+    ob = _observations(req, x_dict, target, weights, transform, eps, what, rows=K)
     if ends_a is not None:
         aux_ob = _observations(req, x_dict, aux_target, aux_weights, 'none', None, what, rows=int(ends_a.numel()))
-    get_library().require("hbvx_population_period")
-    return req, ob, aux_ob, (ends_f, ends_a)
-
-
-def _period(model, req, x_dict, parameters, candidates, names, ob, transform, aux_key, aux_ob, ends, return_series):
-    outputs, main, t_first = _primal(model, req, x_dict, parameters)
-    sources, route = _candidate_sources(model, names, candidates)
-    dev = main.x.device
-    end_f, end_a = (None if e is None else e.to(device=dev, dtype=torch.int32) for e in ends)
-    if aux_ob is None:
-        flow, aux = ops.population_period(main, sources, route, ob['target'], ob['w'], ob['shift'], ob['eps'], transform,
-                                          end_f, t_first=t_first, want_sim=return_series)
-    else:
-        flow, aux = ops.population_period(main, sources, route, ob['target'], ob['w'], ob['shift'], ob['eps'], transform,
-                                          end_f, _abi.POP_AUX_SERIES[aux_key], aux_ob['target'], aux_ob['w'],
-                                          aux_ob['shift'], end_a, t_first, return_series)
-    out = {'columns': list(req.cols), 'outputs': outputs}
-    for name, got, o, tr, e in (('flow', flow, ob, transform, ends[0]), ('aux', aux, aux_ob, 'none', ends[1])):
-        if got is None:
-            continue
-        sub = dict(zip(('sse', 's1', 's2', 's3'), got[:4]))
-        sub.update(shift=o['shift'], obs=o['obs'], transform=tr, eps=o['eps'], n_obs=o['n_obs'], columns=list(req.cols),
-                   outputs=outputs, period_ends=e.clone(), period_days=_period_days(e))
-        if return_series:
-            sub['series'] = got[4]
-        out[name] = sub
-    if aux is not None:
-        out['aux']['key'] = aux_key
-    return out
+    get_library().require(family.prefix + 'period')
+    return Request(model, x_dict, parameters, names, req, ob, transform, aux_key, aux_ob, (ends_f, ends_a), candidates,
+                   return_series)
 
 
 def population_period_stats(model, x_dict: dict, parameters, candidates: torch.Tensor, target, periods=None,
@@ -473,10 +496,8 @@ def population_period_stats(model, x_dict: dict, parameters, candidates: torch.T
     calendar that is empty, not integer, not strictly ascending, negative or >= T_out; n < 1 or n > T_out; a target or
     weights whose leading size is not K; aux_periods or aux_weights without aux_key (ValueError); HbvAdj, the hourly and
     multi-timescale models (NotImplementedError); a library without hbvx_population_period (HbvxError)."""
-    what = "population_period_stats"
-    req, ob, aux_ob, ends = _period_request(model, x_dict, parameters, candidates, target, periods, aux_target, aux_key,
-                                            aux_periods, names, weights, aux_weights, transform, eps, what)
-    return _period(model, req, x_dict, parameters, candidates, names, ob, transform, aux_key, aux_ob, ends, return_series)
+    return _front(EXPLICIT, "population_period_stats", 'period', model, x_dict, parameters, candidates, target, periods,
+                  aux_target, aux_key, aux_periods, names, weights, aux_weights, transform, eps, return_series)
 
 
 def population_score(stats: dict, metric: str) -> torch.Tensor:
@@ -592,63 +613,53 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
     score period means: target, weights, aux_target and aux_weights then hold one row per period, and every round is one
     `population_period_stats` call, with or without an aux term; cost and history are formed as above.  With both None
     the function is the one above, bit for bit."""
-    what = "population_search"
+    return _search_call(EXPLICIT, "population_search", model, x_dict, parameters, target, names, n_candidates, n_rounds,
+                        shrink, weights, generator, objective, transform, eps, aux_target, aux_key, aux_weights,
+                        aux_objective, aux_share, periods, aux_periods)
+
+
+def _check_mix(objective, aux_objective, aux_share, what):
+    """What the search refuses about the weighted sum of the two terms' costs."""
+    if aux_objective not in OBJECTIVES:
+        raise ValueError(f"{what}: aux_objective must be one of {list(OBJECTIVES)}, got {aux_objective!r}")
+    if not 0.0 <= float(aux_share) <= 1.0:          # (a NaN fails both comparisons)
+        raise ValueError(f"{what}: aux_share must lie in [0, 1], got {aux_share!r}")
+    if aux_objective == 'sse' and objective != 'sse':
+        raise ValueError(f"{what}: aux_objective 'sse' with objective {objective!r} would add a squared error to "
+                         "1 - score: two scales in one sum")
+
+
+def _search_call(family, what, model, x_dict, parameters, target, names, n_candidates, n_rounds, shrink, weights,
+                 generator, objective, transform, eps, aux_target, aux_key, aux_weights, aux_objective, aux_share, periods,
+                 aux_periods):
+    """`population_search` / `adj_population_search`: the checks, the form every round is scored in ('period' with a
+    calendar, or an aux term where there is no joint export) and the loop.  The export is required before the first draw."""
     _check_search(model, n_candidates, n_rounds, shrink, objective, what)
     joint = aux_target is not None or aux_key is not None or aux_weights is not None
-    if periods is not None or aux_periods is not None:
+    if periods is not None or aux_periods is not None or (joint and not family.has_joint):
+        form = 'period'
         if joint:
-            if aux_objective not in OBJECTIVES:
-                raise ValueError(f"{what}: aux_objective must be one of {list(OBJECTIVES)}, got {aux_objective!r}")
-            if not 0.0 <= float(aux_share) <= 1.0:
-                raise ValueError(f"{what}: aux_share must lie in [0, 1], got {aux_share!r}")
-            if aux_objective == 'sse' and objective != 'sse':
-                raise ValueError(f"{what}: aux_objective 'sse' with objective {objective!r} would add a squared error to "
-                                 "1 - score: two scales in one sum")
-        req, ob, aux_ob, ends = _period_request(model, x_dict, parameters, None, target, periods, aux_target, aux_key,
-                                                aux_periods, names, weights, aux_weights, transform, eps, what)
-
-        def evaluate_periods(cands):
-            st = _period(model, req, x_dict, parameters, cands, names, ob, transform, aux_key, aux_ob, ends, False)
-            score = population_score(st['flow'], objective)
-            if not joint:
-                return _objective_cost(score, objective), score
-            score_aux = population_score(st['aux'], aux_objective)
-            return _mixed_cost(_objective_cost(score, objective), _objective_cost(score_aux, aux_objective),
-                               float(aux_share)), (score, score_aux)
-
-        return _search(req, x_dict, parameters, evaluate_periods, req.tname != 'p_sta', n_candidates, n_rounds, shrink,
-                       generator, joint or objective != 'sse', joint)
-    req = _check(model, x_dict, parameters, target, names, weights, what)
-    if joint:
-        _check_aux(req, x_dict, aux_target, aux_key, aux_weights, what)
-        if aux_objective not in OBJECTIVES:
-            raise ValueError(f"{what}: aux_objective must be one of {list(OBJECTIVES)}, got {aux_objective!r}")
-        if not 0.0 <= float(aux_share) <= 1.0:          # (a NaN fails both comparisons)
-            raise ValueError(f"{what}: aux_share must lie in [0, 1], got {aux_share!r}")
-        if aux_objective == 'sse' and objective != 'sse':
-            raise ValueError(f"{what}: aux_objective 'sse' with objective {objective!r} would add a squared error to "
-                             "1 - score: two scales in one sum")
-    by_stats = joint or objective != 'sse' or transform != 'none'
-    if by_stats:
-        ob = _observations(req, x_dict, target, weights, transform, eps, what)
-        if joint:
-            aux_ob = _observations(req, x_dict, aux_target, aux_weights, 'none', None, what)
-        get_library().require("hbvx_population_joint" if joint else "hbvx_population_stats")
+            _check_mix(objective, aux_objective, aux_share, what)
+        rq = _period_request(family, what, model, x_dict, parameters, None, target, periods, aux_target, aux_key,
+                             aux_periods, names, weights, aux_weights, transform, eps)
+    else:
+        form = 'joint' if joint else 'stats' if objective != 'sse' or transform != 'none' else 'cost'
+        rq = _daily_request(family, what, form, model, x_dict, parameters, None, target, names, weights, transform, eps,
+                            aux_target, aux_key, aux_weights, mix=(objective, aux_objective, aux_share))
 
     def evaluate(cands):
         """(cost, score or None) [P,B] of one round's candidates; with the aux term the score is the pair."""
-        if joint:
-            st = _joint(model, req, x_dict, parameters, cands, names, ob, transform, aux_key, aux_ob, False)
-            score, score_aux = population_score(st['flow'], objective), population_score(st['aux'], aux_objective)
-            return _mixed_cost(_objective_cost(score, objective), _objective_cost(score_aux, aux_objective),
-                               float(aux_share)), (score, score_aux)
-        if not by_stats:
-            return population_cost(model, x_dict, parameters, cands, target, names, weights)['cost'], None
-        st = _stats(model, req, x_dict, parameters, cands, names, ob, transform, False)
-        score = population_score(st, objective)
-        return _objective_cost(score, objective), score
+        st = _run(family, form, rq._replace(candidates=cands))
+        if form == 'cost':
+            return st['cost'], None
+        score = population_score(st if form == 'stats' else st['flow'], objective)
+        if not joint:
+            return _objective_cost(score, objective), score
+        score_aux = population_score(st['aux'], aux_objective)
+        return _mixed_cost(_objective_cost(score, objective), _objective_cost(score_aux, aux_objective),
+                           float(aux_share)), (score, score_aux)
 
-    return _search(req, x_dict, parameters, evaluate, req.tname != 'p_sta', n_candidates, n_rounds, shrink, generator,
+    return _search(rq.req, x_dict, parameters, evaluate, rq.req.tname != 'p_sta', n_candidates, n_rounds, shrink, generator,
                    joint or objective != 'sse', joint)
 
 
@@ -689,41 +700,29 @@ def _search(req, x_dict, parameters, evaluate, raw, n_candidates, n_rounds, shri
 
     best = row[:, cols].to(device=dev, dtype=torch.float32)                     # [B,C], input space
     best_u = torch.sigmoid(best) if raw else best.clone()
-    hist = {'cost': [], 'best_index': [], 'columns': list(req.cols)}
-    if keep_score:
-        hist['score'] = []
-    if two_scores:
-        hist['score_aux'] = []
+    kept = ['score'] * bool(keep_score) + ['score_aux'] * bool(two_scores)
+    hist = {'cost': [], 'best_index': [], 'columns': list(req.cols), **{name: [] for name in kept}}
     for k in range(n_rounds):
         draws = torch.rand((n_candidates - 1, req.B, C), generator=generator, device=gdev).to(dev)
         if k > 0:
             draws = best_u.unsqueeze(0) + (draws - 0.5) * float(shrink) ** k
         cands = torch.cat([best.unsqueeze(0), _to_input_space(draws, raw)]).contiguous()
         cost, score = evaluate(cands)
-        if two_scores:
-            score, score_aux = score
+        scores = dict(zip(kept, score if two_scores else (score,)))
         low, idx = cost.min(0)
         idx = torch.where(cost[0] <= low, torch.zeros_like(idx), idx)          # a tie keeps the row that is held
         if k == 0:
             hist['cost'].append(cost[0].double().cpu())
-            if keep_score:
-                hist['score'].append(score[0].cpu())
-            if two_scores:
-                hist['score_aux'].append(score_aux[0].cpu())
+            for name, sc in scores.items():
+                hist[name].append(sc[0].cpu())
         pick = idx.view(1, req.B, 1).expand(1, req.B, C)
         best = cands.gather(0, pick)[0]
         best_u = torch.sigmoid(best) if raw else best.clone()
         hist['cost'].append(cost.gather(0, idx.unsqueeze(0))[0].double().cpu())
-        if keep_score:
-            hist['score'].append(score.gather(0, idx.unsqueeze(0))[0].cpu())
-        if two_scores:
-            hist['score_aux'].append(score_aux.gather(0, idx.unsqueeze(0))[0].cpu())
+        for name, sc in scores.items():
+            hist[name].append(sc.gather(0, idx.unsqueeze(0))[0].cpu())
         hist['best_index'].append(idx.cpu())
     row[:, cols] = best.to(cur.device)
-    hist['cost'] = torch.stack(hist['cost'])
-    hist['best_index'] = torch.stack(hist['best_index'])
-    if keep_score:
-        hist['score'] = torch.stack(hist['score'])
-    if two_scores:
-        hist['score_aux'] = torch.stack(hist['score_aux'])
+    for name in ['cost', 'best_index'] + kept:
+        hist[name] = torch.stack(hist[name])
     return ((parameters[0], cur) if two else cur), hist

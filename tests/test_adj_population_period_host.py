@@ -11,6 +11,7 @@ import torch
 import hydrodl2_amd
 from hydrodl2_amd import _abi
 from hydrodl2_amd import adj_population as ap
+from hydrodl2_amd import population as pop
 from hydrodl2_amd.adj_population import adj_population_period_stats, adj_population_search
 from hydrodl2_amd.population import (_calendar, _period_days, population_joint_stats, population_period_stats,
                                      population_search)
@@ -215,12 +216,24 @@ def test_the_refusals_happen_before_the_model_runs():
     assert torch.equal(torch.get_rng_state(), state)            # nothing ran: no draw was made
 
 
-def test_the_calendar_forms_resolve_as_the_explicit_call_s(monkeypatch):
+def _hbv():
+    return hydrodl2_amd.load_model("hbv", "Hbv")({"nmul": 2, "dynamic_params": {"Hbv": []}}, torch.device("cpu"))
+
+
+# (the model, the period call, the search, an aux key, the family's export prefix)
+FAMILIES = {"implicit": (_adj, adj_population_period_stats, adj_population_search, "SLZ", "hbvx_adj_population_"),
+            "explicit": (_hbv, population_period_stats, population_search, "SWE", "hbvx_population_")}
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+def test_the_calendar_forms_resolve_as_the_explicit_call_s(monkeypatch, family):
     """None, an int and a sequence of closing days reach the kernel call as the closing days `_calendar` gives, and come
-    back as 'period_ends' / 'period_days': the library is stubbed at `_period`, nothing runs."""
+    back as 'period_ends' / 'period_days': the library is stubbed at `_run`, the one route from every front end to the
+    kernels, so nothing runs."""
     T, B, P = 20, 3, 2
-    adj = _adj()
-    ny = adj.learnable_param_count
+    make, period_stats, _, aux_key, prefix = FAMILIES[family]
+    model = make()
+    ny = model.learnable_param_count
     x, p, cand = {"x_phy": torch.zeros(T, B, 3)}, torch.zeros(T, B, ny), torch.zeros(P, B, ny)
     seen = []
 
@@ -228,20 +241,24 @@ def test_the_calendar_forms_resolve_as_the_explicit_call_s(monkeypatch):
         def require(self, name):
             seen.append(name)
 
-    monkeypatch.setattr(ap, "get_library", lambda: Lib())
-    monkeypatch.setattr(ap, "_period", lambda model, req, xd, pp, c, names, ob, tr, key, aux_ob, ends, rs: (ob, aux_ob, ends))
+    def run(fam, form, rq):
+        assert (fam.prefix, form) == (prefix, "period") and rq.candidates is cand
+        return rq.ob, rq.aux_ob, rq.ends
+
+    monkeypatch.setattr(pop, "get_library", lambda: Lib())
+    monkeypatch.setattr(pop, "_run", run)
     for periods, aux_periods in ((None, None), (8, None), (None, 8), (8, 5), ([0, 3, 17], [1, 2, 3, 4]),
                                  (torch.tensor([4, 9], dtype=torch.int32), range(0, 20, 7)), ([0], 20)):
         want_f, want_a = _calendar(periods, T, "periods", "t"), _calendar(aux_periods, T, "aux_periods", "t")
         KF, KA = int(want_f.numel()), int(want_a.numel())
-        ob, aux_ob, ends = adj_population_period_stats(adj, x, p, cand, torch.ones(KF, B), periods, torch.ones(KA, B, 1),
-                                                       "SLZ", aux_periods)
+        ob, aux_ob, ends = period_stats(model, x, p, cand, torch.ones(KF, B), periods, torch.ones(KA, B, 1), aux_key,
+                                        aux_periods)
         assert torch.equal(ends[0], want_f) and torch.equal(ends[1], want_a) and ends[0].dtype == torch.int64
         assert tuple(ob["target"].shape) == (KF, B) and tuple(aux_ob["target"].shape) == (KA, B)
         assert int(_period_days(ends[0]).sum()) == int(want_f[-1]) + 1
-        ob, aux_ob, ends = adj_population_period_stats(adj, x, p, cand, torch.ones(KF, B), periods)
+        ob, aux_ob, ends = period_stats(model, x, p, cand, torch.ones(KF, B), periods)
         assert torch.equal(ends[0], want_f) and ends[1] is None and aux_ob is None
-    assert set(seen) == {EXPORT}
+    assert set(seen) == {prefix + "period"}
 
 
 def test_a_library_without_the_export_is_named_before_any_draw_or_run(host_math_backend):  # noqa: F811
@@ -264,11 +281,14 @@ def test_a_library_without_the_export_is_named_before_any_draw_or_run(host_math_
     assert torch.equal(torch.get_rng_state(), state)
 
 
-def test_the_search_with_default_arguments_never_reaches_the_new_entry(monkeypatch):
-    """periods, aux_periods, aux_target, aux_key and aux_weights left at None: every round is one adj_population_cost
-    call (objective 'sse', transform 'none') or one `_stats` call (anything else), as before."""
+@pytest.mark.parametrize("family", FAMILIES)
+def test_the_search_with_default_arguments_never_reaches_the_new_entry(monkeypatch, family):
+    """periods, aux_periods, aux_target, aux_key and aux_weights left at None: every round is one launch of the cost
+    export (objective 'sse', transform 'none') or of the stats export (anything else), as before; neither the period nor
+    the joint export is reached.  The library is stubbed at `_run`."""
     T, B = 6, 3
-    model = _adj()
+    make, _, search, _, prefix = FAMILIES[family]
+    model = make()
     ny = model.learnable_param_count
     x, p, tgt = {"x_phy": torch.rand(T, B, 3)}, torch.randn(T, B, ny), torch.rand(T, B) + 0.5
     calls = []
@@ -277,32 +297,25 @@ def test_the_search_with_default_arguments_never_reaches_the_new_entry(monkeypat
         def require(self, name):
             calls.append(name)
 
-    def never(*a, **k):
-        raise AssertionError("the period entry was reached")
-
-    def cost(m, xd, pp, cands, target, names, weights):
-        calls.append("cost")
-        return {"cost": torch.arange(cands.shape[0] * B, dtype=torch.float32).view(-1, B)}
-
-    def stats(m, req, xd, pp, cands, names, ob, transform, rs):
-        calls.append("stats")
-        n = cands.shape[0]
+    def run(fam, form, rq):
+        assert fam.prefix == prefix and form in ("cost", "stats"), "the period or the joint entry was reached"
+        assert rq.aux_ob is None and rq.ends == (None, None) and not rq.return_series
+        calls.append(form)
+        n, ob = rq.candidates.shape[0], rq.ob
+        if form == "cost":
+            return {"cost": torch.arange(n * B, dtype=torch.float32).view(-1, B)}
         z = torch.ones(n, B)
         return {"sse": z * torch.arange(1, n + 1).view(-1, 1), "s1": z * 0, "s2": z, "s3": z, "shift": ob["shift"],
                 "obs": ob["obs"], "n_obs": ob["n_obs"]}
 
-    monkeypatch.setattr(ap, "get_library", lambda: Lib())
-    monkeypatch.setattr(ap, "_period", never)
-    monkeypatch.setattr(ap, "_period_request", never)
-    monkeypatch.setattr(ap, "adj_population_period_stats", never)
-    monkeypatch.setattr(ap, "adj_population_cost", cost)
-    monkeypatch.setattr(ap, "_stats", stats)
+    monkeypatch.setattr(pop, "get_library", lambda: Lib())
+    monkeypatch.setattr(pop, "_run", run)
     g = torch.Generator().manual_seed(1)
-    _, hist = adj_population_search(model, x, p, tgt, n_candidates=4, n_rounds=2, generator=g)
-    assert calls == ["hbvx_adj_population_cost", "cost", "cost"] and set(hist) == {"cost", "best_index", "columns"}
+    _, hist = search(model, x, p, tgt, n_candidates=4, n_rounds=2, generator=g)
+    assert calls == [prefix + "cost", "cost", "cost"] and set(hist) == {"cost", "best_index", "columns"}
     calls.clear()
-    _, hist = adj_population_search(model, x, p, tgt, n_candidates=4, n_rounds=2, generator=g, objective="nse")
-    assert calls == ["hbvx_adj_population_stats", "stats", "stats"] and "score_aux" not in hist
+    _, hist = search(model, x, p, tgt, n_candidates=4, n_rounds=2, generator=g, objective="nse")
+    assert calls == [prefix + "stats", "stats", "stats"] and "score_aux" not in hist
 
 
 def test_the_abi_refuses_bad_arguments_before_any_launch():
