@@ -17,6 +17,8 @@ from hydrodl2_amd.population import (population_cost, population_joint_stats, po
 from hydrodl2_amd.adj_population import (adj_population_cost, adj_population_period_stats, adj_population_search,
                                          adj_population_stats)
 
+from hydrodl2_amd.hourly_population import hourly_population_columns, hourly_population_stats
+
 __version__ = "0.1.0"
 
 __all__ = ["__version__", "available_models", "available_modules", "load_model", "load_module", "jvp_batch",
@@ -24,4 +26,5 @@ __all__ = ["__version__", "available_models", "available_modules", "load_model",
            "normal_equations", "lm_step", "calibrate", "parameter_covariance", "covariance_factor", "predictive_variance",
            "population_cost", "population_search", "population_stats", "population_score", "population_joint_stats",
            "population_period_stats",
-           "adj_population_cost", "adj_population_stats", "adj_population_period_stats", "adj_population_search"]
+           "adj_population_cost", "adj_population_stats", "adj_population_period_stats", "adj_population_search",
+           "hourly_population_stats", "hourly_population_columns"]

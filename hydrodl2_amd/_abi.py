@@ -262,6 +262,33 @@ SIGNATURES = [
 EXPORTS = [row[0] for row in SIGNATURES if row[1]]
 OPTIONAL_EXPORTS = [row[0] for row in SIGNATURES if not row[1]]
 
+GAGE_POP_ABI_VERSION = 1    # HBVX_GAGE_POP_ABI_VERSION
+
+
+class PopRunoff(C.Structure):
+    """hbvx_pop_runoff: the candidates' static values and the [P,T,B] runoff they give (include/hbvx_gage_pop.h)."""
+    _fields_ = [("abi_version", C.c_int32), ("n_cand", C.c_int32), ("p", PopSrc * MAX_PARAM), ("runoff", _fp)]
+
+
+class GagePop(C.Structure):
+    """hbvx_gage_pop: the candidates' runoff and routing parameters, the calendar, the observations per gage and the
+    [P,G] outputs of hbvx_gage_population_stats (include/hbvx_gage_pop.h)."""
+    _fields_ = [("abi_version", C.c_int32), ("n_cand", C.c_int32), ("runoff", _fp), ("runoff_c_stride", C.c_int64),
+                ("dp", _fp), ("uh", _fp), ("transform", C.c_int32), ("n_periods", C.c_int32),
+                ("period_end", C.c_void_p),     # const int32_t *: an address like the float pointers, of another type
+                ("target", _fp), ("w", _fp), ("shift", _fp), ("eps", _fp),
+                ("sse", _fp), ("s1", _fp), ("s2", _fp), ("s3", _fp), ("sim", _fp), ("series", _fp)]
+
+
+# The exports of include/hbvx_gage_pop.h, rows as in SIGNATURES (all optional); the layout index is
+# hbvx_gage_pop_sizeof's, not hbvx_sizeof's.
+GAGE_POP_SIGNATURES = [
+    ("hbvx_gage_pop_sizeof", False, _u64, [_int], None),
+    ("hbvx_hourly_population_runoff", False, _int, [_P(Desc), _P(PopRunoff), _vp], (0, PopRunoff)),
+    ("hbvx_gage_population_workspace_bytes", False, _u64, [_P(GageDesc), _P(GagePop)], (1, GagePop)),
+    ("hbvx_gage_population_stats", False, _int, [_P(GageDesc), _P(GagePop), _vp, _u64, _vp], (1, GagePop)),
+]
+
 
 class HbvxError(RuntimeError):
     pass
@@ -279,18 +306,21 @@ class Library:
         for name in EXPORTS:
             if not hasattr(d, name):
                 raise HbvxError(f"{path}: missing export {name}")
-        self.missing = [name for name in OPTIONAL_EXPORTS if not hasattr(d, name)]
-        checked = set()             # hbvx_sizeof indices: several exports share a struct
-        for name, _, restype, argtypes, layout in SIGNATURES:    # the required rows come first: hbvx_sizeof is bound by then
+        self.missing = [name for name in OPTIONAL_EXPORTS + [row[0] for row in GAGE_POP_SIGNATURES] if not hasattr(d, name)]
+        checked = set()             # (sizeof export, index): several exports share a struct
+        # the required rows come first, and each table's sizeof export before the rows that name a layout: it is bound by then
+        for name, _, restype, argtypes, layout, sizeof in [row + ("hbvx_sizeof",) for row in SIGNATURES] + \
+                [row + ("hbvx_gage_pop_sizeof",) for row in GAGE_POP_SIGNATURES]:
             if name in self.missing:
                 continue
             fn = getattr(d, name)
             fn.restype, fn.argtypes = restype, argtypes
-            if layout is not None and layout[0] not in checked:
-                checked.add(layout[0])
+            if layout is not None and (sizeof, layout[0]) not in checked and sizeof not in self.missing:
+                checked.add((sizeof, layout[0]))
                 which, st = layout
-                if d.hbvx_sizeof(which) != C.sizeof(st):
-                    raise HbvxError(f"{path}: layout mismatch for {st.__name__}: {d.hbvx_sizeof(which)} != {C.sizeof(st)}")
+                got = getattr(d, sizeof)(which)
+                if got != C.sizeof(st):
+                    raise HbvxError(f"{path}: layout mismatch for {st.__name__}: {got} != {C.sizeof(st)}")
         if d.hbvx_version() != ABI_VERSION:
             raise HbvxError(f"{path}: ABI version {d.hbvx_version()} != {ABI_VERSION}")
         for which, st in enumerate([Desc, FwdOut, BwdIO, RouteDesc, ParamSrc, ParamGrad, GageDesc]):
@@ -484,6 +514,25 @@ class Library:
         self._check(self.dll.hbvx_gage_route_tangent_batch(C.byref(r), n_dir, qs, uh, qs_dot, qs_dot_ds, dp_dot,
                                                            dp_dot_ds, out_dot, ws, C.c_uint64(ws_bytes),
                                                            C.c_void_p(stream)), "hbvx_gage_route_tangent_batch")
+
+    def hourly_population_runoff(self, desc, pr, stream: int):
+        """hbvx_hourly_population_runoff; `desc` / `pr` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_hourly_population_runoff")
+        self._check(self.dll.hbvx_hourly_population_runoff(None if desc is None else C.byref(desc),
+                                                           None if pr is None else C.byref(pr), C.c_void_p(stream)),
+                    "hbvx_hourly_population_runoff")
+
+    def gage_population_workspace_bytes(self, r, gp) -> int:
+        self.require("hbvx_gage_population_workspace_bytes")
+        return int(self.dll.hbvx_gage_population_workspace_bytes(None if r is None else C.byref(r),
+                                                                 None if gp is None else C.byref(gp)))
+
+    def gage_population_stats(self, r, gp, ws, ws_bytes: int, stream: int):
+        """hbvx_gage_population_stats; `r` / `gp` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_gage_population_stats")
+        self._check(self.dll.hbvx_gage_population_stats(None if r is None else C.byref(r),
+                                                        None if gp is None else C.byref(gp), ws, C.c_uint64(ws_bytes),
+                                                        C.c_void_p(stream)), "hbvx_gage_population_stats")
 
     def lstm_check(self, r: LstmDesc, ws, stream: int):
         self._check(self.dll.hbvx_lstm_check(C.byref(r), ws, C.c_void_p(stream)), "hbvx_lstm_check")

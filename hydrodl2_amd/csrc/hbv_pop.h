@@ -8,7 +8,9 @@
 //   hbvx_population_period  the eight with the routed flow and the aux flux averaged over the periods of two calendars
 //                           -- 8-day composites, months -- before they meet their targets: the sums run once per period
 //                           instead of once per day, and the optional series are [P,K,B] period means.
-// One kernel template, k_pop below, is the day loop of all four; launch_pop.hip has the entry points.
+// One kernel template, k_pop below, is the day loop of all four; launch_pop.hip has the entry points.  A fifth form of
+// it, the runoff form, is stage 1 of the hourly model's population evaluation (hbvx_hourly_population_runoff,
+// include/hbvx_gage_pop.h; launch_gage_pop.hip): the candidate loop alone, storing each candidate's unit runoff.
 //
 // What happens to a basin's ensemble mean after the day step -- the normalised gamma unit hydrograph, the 15-day
 // window, the causal convolution and the residual chain -- is hbvx_popk::Basin below and compiles for the host as
@@ -216,6 +218,13 @@ struct PopJointArgs {
     float *aux_sim;             // [P, T - t_first, B] or NULL
 };
 
+// hbvx_hourly_population_runoff (include/hbvx_gage_pop.h): the candidate loop alone.  `a` carries the descriptor and the
+// candidates' sources (a.pop.p); nothing else of a.pop is read.
+struct PopRunoffArgs {
+    PopArgs a;
+    float *runoff;              // [P,T,B]: each candidate's hourly unit runoff, the module's Qs
+};
+
 struct PopPeriodArgs {
     PopJointArgs j;             // the two terms: hbvx_population_joint's arguments, targets / weights / series per PERIOD
     int has_aux;                // 0: aux_series == HBVX_POP_NO_AUX, nothing of j's aux part is read or written
@@ -228,6 +237,7 @@ __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopArgs &A) { 
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopStatsArgs &A) { return A.a; }
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopJointArgs &A) { return A.s.a; }
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopPeriodArgs &A) { return A.j.s.a; }
+__host__ __device__ __forceinline__ const PopArgs &pop_args(const PopRunoffArgs &A) { return A.a; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopStatsArgs &A) { return A; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopJointArgs &A) { return A.s; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopPeriodArgs &A) { return A.j.s; }
@@ -280,6 +290,9 @@ template <> struct PopBasin<T_COST> { using type = hbvx_popk::Basin; };
 //                  happens.  Days after the last closing day are simulated and scored nowhere.  Without an aux term
 //                  (has_aux == 0, uniform over the launch; a run-time flag in this form only) the aux value is zero
 //                  through the butterfly and nothing aux is accumulated, loaded or stored.
+//   PopRunoffArgs  (RUNOFF) TR = T_COST; Step<MODEL_HOURLY> only: the candidate loop with none of the window or chains.  The
+//                  hour's ensemble mean times 1/24 is the module's Qs, and the unit's leader stores it to [P,T,B]: the score
+//                  of the hourly model lives at the gages, after a sum over units (hbv_gage_pop.h takes it from there).
 // The flow's operations are the same ones on the same values in every form, and the aux term's in both of its forms:
 // tests/test_population_stats_gpu.py, test_population_joint_gpu.py and test_population_period_gpu.py (daily calendars)
 // hold each form to the bits of the one before it.
@@ -299,7 +312,8 @@ template <> struct PopBasin<T_COST> { using type = hbvx_popk::Basin; };
 template <int MODEL, bool BETAET, int TR, typename Args>
 __global__ void __launch_bounds__(64) k_pop(const Args Q)
 {
-    constexpr bool STATS = !std::is_same<Args, PopArgs>::value;
+    constexpr bool RUNOFF = std::is_same<Args, PopRunoffArgs>::value;
+    constexpr bool STATS = !RUNOFF && !std::is_same<Args, PopArgs>::value;
     constexpr bool PERIOD = std::is_same<Args, PopPeriodArgs>::value;
     constexpr bool JOINT = PERIOD || std::is_same<Args, PopJointArgs>::value;      // the forms with an aux term
     static_assert(STATS == (TR != T_COST), "TR = T_COST is the cost form's, and its alone");
@@ -315,8 +329,8 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
     const int64_t c = blockIdx.y;
     const bool raw = d.raw_sigmoid != 0;
     const float nz = d.nearzero;
-    const float ac = (MODEL == MODEL_HBV20) ? d.ac[L.b] : 0.0f;
-    const float elev = (MODEL == MODEL_HBV20) ? d.elev[L.b] : 0.0f;
+    const float ac = (MODEL == MODEL_HBV20 || MODEL == MODEL_HOURLY) ? d.ac[L.b] : 0.0f;
+    const float elev = (MODEL == MODEL_HBV20 || MODEL == MODEL_HOURLY) ? d.elev[L.b] : 0.0f;
 
     float p[NPARAM_MAX];
     const float *dynp[NP];
@@ -342,10 +356,11 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
     for (int k = 0; k < 5; k++) st[k] = d.state_in ? d.state_in[k * N + L.n] : 0.001f;
 
     typename PopBasin<TR>::type bs;
-    if constexpr (STATS)
+    if constexpr (RUNOFF) ;     // no window, no chains: the runoff form scores nothing
+    else if constexpr (STATS)
         bs.start(A.has_route != 0, stats_args(Q).shift[L.b], TR == hbvx_popk::T_LOG ? stats_args(Q).eps[L.b] : 0.0f);
     else bs.start(A.has_route != 0);
-    if (A.has_route) {      // route_ab's lines (hbvx.hip) on the candidate's routing inputs
+    if (!RUNOFF && A.has_route) {      // route_ab's lines (hbvx.hip) on the candidate's routing inputs
         const hbvx_route_desc &r = A.r;
         const float va = pp.ra ? pp.ra[c * pp.r_c_stride + (int64_t)L.b * pp.r_b_stride] : r.ra[(int64_t)L.b * r.r_stride];
         const float vb = pp.rb ? pp.rb[c * pp.r_c_stride + (int64_t)L.b * pp.r_b_stride] : r.rb[(int64_t)L.b * r.r_stride];
@@ -416,7 +431,7 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
         nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
 #pragma unroll
         for (int i = 0; i < NP; i++) nxd[i] = ((dmask >> i) & 1) ? dynp[i][0] : 0.f;
-        if constexpr (!PERIOD) {
+        if constexpr (!PERIOD && !RUNOFF) {
             if (t_first == 0) {
                 nxo = tg[0];
                 if (wt) nxw = wt[0];
@@ -442,7 +457,7 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
 #pragma unroll
             for (int i = 0; i < NP; i++)
                 if ((dmask >> i) & 1) nxd[i] = dynp[i][(int64_t)tn * d.p[i].dyn_t_stride];
-            if constexpr (!PERIOD) {
+            if constexpr (!PERIOD && !RUNOFF) {
                 if (tn >= t_first) {
                     const int64_t row = (int64_t)(tn - t_first) * d.B;
                     nxo = tg[row];
@@ -487,7 +502,10 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
             q = ens_sum((mu ? s.Q * wq : s.Q) * act, lgMp);
             if (!mu) q = q * invM;
         }
-        if constexpr (PERIOD) {
+        if constexpr (RUNOFF) {
+            // the module's Qs: the ensemble mean times dt = 1/24, one float32 multiply (hbv_2_hourly.py:741)
+            if (L.leader) Q.runoff[(c * T + t) * d.B + L.b] = q * (float)(1.0 / 24.0);
+        } else if constexpr (PERIOD) {
             const float y = bs.Basin::push(q, 0.0f, 0.0f, false);       // the routing runs every day
             const int rel = t - t_first;                                // the day among the scored days
             if (rel >= 0 && kf < KF) {
@@ -536,6 +554,7 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
             }
         }
     }
+    if constexpr (RUNOFF) return;
     if (L.leader) {
         if constexpr (STATS) {
             const int64_t at = c * d.B + L.b;

@@ -1,0 +1,152 @@
+// launch_gage_pop.hip -- the entry points of the hourly model's population evaluation (include/hbvx_gage_pop.h):
+// hbvx_hourly_population_runoff (k_pop's runoff form, hbv_pop.h) and hbvx_gage_population_stats (hbv_gage_pop.h).
+#include "hbvx_host.h"
+#include "hbv_gage_pop.h"
+
+using namespace hbvx;
+using namespace hbvx_host;
+
+namespace {
+
+int fail_as(const char *who, int code, const char *msg)
+{
+    char text[160];
+    snprintf(text, sizeof text, "%s: %s", who, msg);
+    return fail(code, text);
+}
+
+int launched(const char *who)
+{
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return HBVX_OK;
+    char what[64];
+    snprintf(what, sizeof what, "%s launch", who);
+    return hip_fail(e, what);
+}
+
+// What hbvx_gage_route_forward checks of its descriptor (hbvx.hip), without r->dp: the candidates bring their own.
+int check_gage(const char *who, const hbvx_gage_desc *r)
+{
+    if (!r) return fail_as(who, HBVX_E_NULL, "gage desc is NULL");
+    if (r->abi_version != HBVX_ABI_VERSION) return fail_as(who, HBVX_E_ABI, "abi_version mismatch");
+    if (r->T <= 0 || r->U <= 0 || r->G <= 0 || r->NPAIR < 0) return fail_as(who, HBVX_E_SHAPE, "bad T/U/G/NPAIR");
+    const int L = r->T < HBVX_GAGE_MAXLEN ? r->T : HBVX_GAGE_MAXLEN;
+    if (r->L != L) return fail_as(who, HBVX_E_SHAPE, "L must be min(T, 72)");
+    if (r->U > 65535 || r->G > 65535) return fail_as(who, HBVX_E_SHAPE, "more than 65535 units or gages per call");
+    if (!r->pair_unit || !r->gage_ptr || !r->areas || !r->denom)
+        return fail_as(who, HBVX_E_NULL, "gage routing pointer is NULL");
+    return HBVX_OK;
+}
+
+int check_gage_pop(const char *who, const hbvx_gage_desc *r, const hbvx_gage_pop *gp)
+{
+    int rc = check_gage(who, r);
+    if (rc) return rc;
+    if (!gp) return fail_as(who, HBVX_E_NULL, "gp is NULL");
+    if (gp->abi_version != HBVX_GAGE_POP_ABI_VERSION) return fail_as(who, HBVX_E_ABI, "gp abi_version mismatch");
+    if (gp->n_cand < 1 || gp->n_cand > 65535) return fail_as(who, HBVX_E_SHAPE, "n_cand must be in 1..65535");
+    if (!gp->runoff) return fail_as(who, HBVX_E_NULL, "runoff is NULL");
+    if (gp->runoff_c_stride < 0) return fail_as(who, HBVX_E_SHAPE, "runoff_c_stride is negative");
+    if (!gp->dp && !gp->uh && r->NPAIR > 0) return fail_as(who, HBVX_E_NULL, "neither dp nor uh is given");
+    if (gp->transform != HBVX_POP_T_NONE && gp->transform != HBVX_POP_T_SQRT && gp->transform != HBVX_POP_T_LOG)
+        return fail_as(who, HBVX_E_UNSUPPORTED, "transform must be HBVX_POP_T_NONE, _SQRT or _LOG");
+    if (gp->n_periods < 1 || gp->n_periods > r->T) return fail_as(who, HBVX_E_SHAPE, "n_periods must be in 1..T");
+    if (!gp->period_end) return fail_as(who, HBVX_E_NULL, "period_end is NULL");
+    if (!gp->target) return fail_as(who, HBVX_E_NULL, "target is NULL");
+    if (!gp->shift) return fail_as(who, HBVX_E_NULL, "shift is NULL");
+    if (gp->transform == HBVX_POP_T_LOG && !gp->eps) return fail_as(who, HBVX_E_NULL, "eps is NULL under HBVX_POP_T_LOG");
+    if (!gp->sse || !gp->s1 || !gp->s2 || !gp->s3) return fail_as(who, HBVX_E_NULL, "sse / s1 / s2 / s3 is NULL");
+    return HBVX_OK;
+}
+
+// the workspace's three parts, in floats
+struct Plan {
+    uint64_t qsT, uh, series;
+};
+
+Plan plan(const hbvx_gage_desc *r, const hbvx_gage_pop *gp)
+{
+    const uint64_t P = (uint64_t)gp->n_cand;
+    Plan pl;
+    pl.qsT = (gp->runoff_c_stride ? P : 1) * (uint64_t)r->U * r->T;
+    pl.uh = gp->dp ? P * (uint64_t)r->NPAIR * r->L : 0;
+    pl.series = gp->series ? 0 : P * (uint64_t)r->T * r->G;
+    return pl;
+}
+
+} // namespace
+
+extern "C" uint64_t hbvx_gage_pop_sizeof(int which)
+{
+    switch (which) {
+    case 0: return sizeof(hbvx_pop_runoff);
+    case 1: return sizeof(hbvx_gage_pop);
+    default: return 0;
+    }
+}
+
+extern "C" int hbvx_hourly_population_runoff(const hbvx_desc *d, const hbvx_pop_runoff *pr, void *stream)
+{
+    const char *who = "hbvx_hourly_population_runoff";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (d->model != HBVX_MODEL_HOURLY) return fail_as(who, HBVX_E_UNSUPPORTED, "the hourly model (HBVX_MODEL_HOURLY) only");
+    if (!pr) return fail_as(who, HBVX_E_NULL, "pr is NULL");
+    if (pr->abi_version != HBVX_GAGE_POP_ABI_VERSION) return fail_as(who, HBVX_E_ABI, "pr abi_version mismatch");
+    if (pr->n_cand < 1 || pr->n_cand > 65535) return fail_as(who, HBVX_E_SHAPE, "n_cand must be in 1..65535");
+    if (!pr->runoff) return fail_as(who, HBVX_E_NULL, "runoff is NULL");
+    for (int i = d->n_param; i < HBVX_MAX_PARAM; i++)
+        if (pr->p[i].sta) return fail_as(who, HBVX_E_SHAPE, "candidate values for a parameter slot the model lacks");
+    PopRunoffArgs q;
+    memset(&q, 0, sizeof q);
+    q.a.d = *d;
+    q.a.pop.n_cand = pr->n_cand;
+    for (int i = 0; i < HBVX_MAX_PARAM; i++) q.a.pop.p[i] = pr->p[i];
+    q.a.lgMp = lg_members(d->M);
+    q.runoff = pr->runoff;
+    const int bpw = 64 >> q.a.lgMp;
+    const dim3 grid((d->B + bpw - 1) / bpw, pr->n_cand);
+    hipLaunchKernelGGL((k_pop<MODEL_HOURLY, true, T_COST, PopRunoffArgs>), grid, dim3(64), 0, (hipStream_t)stream, q);
+    return launched(who);
+}
+
+extern "C" uint64_t hbvx_gage_population_workspace_bytes(const hbvx_gage_desc *r, const hbvx_gage_pop *gp)
+{
+    if (!r || !gp || r->T <= 0 || r->U <= 0 || r->G <= 0 || r->NPAIR < 0 || r->L <= 0 || gp->n_cand < 1 || gp->n_cand > 65535)
+        return 0;
+    const Plan pl = plan(r, gp);
+    return (pl.qsT + pl.uh + pl.series) * sizeof(float);
+}
+
+extern "C" int hbvx_gage_population_stats(const hbvx_gage_desc *r, const hbvx_gage_pop *gp, void *workspace,
+                                          uint64_t workspace_bytes, void *stream)
+{
+    const char *who = "hbvx_gage_population_stats";
+    int rc = check_gage_pop(who, r, gp);
+    if (rc) return rc;
+    if (!workspace || workspace_bytes < hbvx_gage_population_workspace_bytes(r, gp))
+        return fail_as(who, HBVX_E_NULL, "workspace missing or too small");
+    const Plan pl = plan(r, gp);
+    hipStream_t st = (hipStream_t)stream;
+    const int P = gp->n_cand;
+    gagepop::Args a;
+    a.r = *r;
+    a.gp = *gp;
+    a.qsT = (float *)workspace;
+    a.qsT_c_stride = gp->runoff_c_stride ? (int64_t)r->U * r->T : 0;
+    a.uh = gp->dp ? a.qsT + pl.qsT : const_cast<float *>(gp->uh);
+    a.uh_c_stride = gp->dp ? (int64_t)r->NPAIR * r->L : 0;
+    a.series = gp->series ? gp->series : a.qsT + pl.qsT + pl.uh;
+    hipLaunchKernelGGL(gagepop::k_gp_transpose, dim3((r->U + 31) / 32, (r->T + 31) / 32, gp->runoff_c_stride ? P : 1),
+                       dim3(256), 0, st, r->T, r->U, gp->runoff, gp->runoff_c_stride, a.qsT);
+    if (gp->dp && r->NPAIR > 0) hipLaunchKernelGGL(gagepop::k_gp_uh, dim3(r->NPAIR, P), dim3(128), 0, st, a);
+    hipLaunchKernelGGL(gagepop::k_gp_route, dim3((r->T + gagepop::TILE4 - 1) / gagepop::TILE4, r->G, P),
+                       dim3(gagepop::TILE), 0, st, a);
+    const dim3 sgrid((r->G + 63) / 64, P);
+    switch (gp->transform) {
+    case HBVX_POP_T_SQRT: hipLaunchKernelGGL(gagepop::k_gp_score<hbvx_popk::T_SQRT>, sgrid, dim3(64), 0, st, a); break;
+    case HBVX_POP_T_LOG: hipLaunchKernelGGL(gagepop::k_gp_score<hbvx_popk::T_LOG>, sgrid, dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL(gagepop::k_gp_score<hbvx_popk::T_NONE>, sgrid, dim3(64), 0, st, a); break;
+    }
+    return launched(who);
+}

@@ -117,6 +117,15 @@ class Hbv_2_hourly(HbvModule):
         from hydrodl2_amd.hourly_jvp import hourly_jvp_batch
         return hourly_jvp_batch(self, x_dict, parameters, tangents, keys, max_directions)
 
+    def population_stats(self, x_dict: dict[str, torch.Tensor], parameters, target, candidates=None,
+                         distr_candidates=None, names=None, weights=None, periods=None, transform: str = 'none',
+                         eps=None, return_series: bool = False, max_candidates: Optional[int] = None):
+        """The score sums of many candidate parameter sets at the gages on one run of the module:
+        hydrodl2_amd.hourly_population_stats(self, ...), see there."""
+        from hydrodl2_amd.hourly_population import hourly_population_stats
+        return hourly_population_stats(self, x_dict, parameters, target, candidates, distr_candidates, names, weights,
+                                       periods, transform, eps, return_series, max_candidates)
+
     def _topology(self, tag, outlet_topo, areas, T, lag, bounds):
         """GageTopology of (outlet_topo, areas), built once per pair of tensor objects + versions: building it
         costs a `nonzero` (a host synchronisation) and a handful of small kernels per call, and cannot be captured

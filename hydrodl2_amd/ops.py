@@ -1507,6 +1507,122 @@ def gage_route_tangent_batch(rec: GageRecord, D: int, qs_t=None, dp_t=None) -> t
     return out
 
 
+# How often each stage of the hourly model's population evaluation has been launched in this process: a routing-only
+# call must leave 'runoff' alone (tests read it; nothing else does).
+HOURLY_POP_LAUNCHES = {'runoff': 0, 'gage': 0}
+
+
+def hourly_population_runoff(rec: PathRecord, cand_sources: dict, P: int) -> torch.Tensor:
+    """Stage 1 of the hourly model's population evaluation (include/hbvx_gage_pop.h): the unit runoff [P,T,U] of P
+    candidate static-parameter sets on one recorded call of the path, the module's Qs (ensemble mean times 1/24), through
+    hbvx_hourly_population_runoff on the current stream.  cand_sources as `population` takes them: {parameter slot:
+    (cands, column)} into one compact contiguous float32 [P,U,C] tensor; at least one."""
+    lib = get_library()
+    lib.require('hbvx_hourly_population_runoff')
+    cfg, x = rec.cfg, rec.x
+    if cfg.model != _abi.MODEL_HOURLY:
+        raise ValueError("hourly_population_runoff: the record is not a call of the hourly model")
+    if not cand_sources:
+        raise ValueError("hourly_population_runoff needs at least one candidate column")
+    dev = x.device
+    B, M = cfg.B, cfg.M
+    cands = next(iter(cand_sources.values()))[0]
+    _check_tensor(lib, cands, "candidates")
+    if cands.dim() != 3 or tuple(cands.shape[:2]) != (P, B) or not cands.is_contiguous() or cands.device != dev or P < 1:
+        raise ValueError(f"candidates must be a contiguous [{P},{B},C] tensor on {dev}, got {tuple(cands.shape)} on {cands.device}")
+    Cn = int(cands.shape[2])
+    for slot, (t, col) in cand_sources.items():
+        if t is not cands:
+            raise ValueError("all candidate columns must lie in one compact tensor")
+        if not 0 <= col <= Cn - M:
+            raise ValueError(f"candidate column {col} of slot {slot} does not hold {M} members in {Cn} columns")
+    desc = _fill_desc(cfg, x, rec.state_in, rec.muwts, rec.ac, rec.elev, rec.ptensors)
+    stream = _stream_of(lib, x)
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        runoff = _out((P, cfg.T, B), dev)
+        for c0 in range(0, P, POP_MAX_CAND):
+            pr = _abi.PopRunoff(abi_version=_abi.GAGE_POP_ABI_VERSION, n_cand=min(POP_MAX_CAND, P - c0))
+            for slot, (_, col) in cand_sources.items():
+                s = pr.p[slot]
+                s.sta, s.c_stride, s.b_stride = _ptr(cands, c0 * B * Cn + col), B * Cn, Cn
+            pr.runoff = _ptr(runoff, c0 * cfg.T * B)
+            _call(lib, 'hbvx_hourly_population_runoff', lib.hourly_population_runoff, desc, pr, stream)
+            HOURLY_POP_LAUNCHES['runoff'] += 1
+    return runoff
+
+
+def gage_population(grec: GageRecord, runoff: torch.Tensor, distr_cands: Optional[torch.Tensor], term: PopTerm,
+                    ends: torch.Tensor, return_series: bool = False, want_gage: bool = False):
+    """Stage 2 (include/hbvx_gage_pop.h): routes P candidates' unit runoff to the gages of one recorded GageRoute call and
+    scores the period means there, through hbvx_gage_population_stats on the current stream.
+    runoff       [P,T,U] float32 contiguous, or [T,U]: one runoff for every candidate (P then comes from distr_cands).
+    distr_cands  [P,n_pair,3] float32 unit-interval route_a / route_b / route_tau, or None: the record's taps serve all.
+    term         PopTerm per GAGE: target / w [K,G], shift / eps [G], transform.
+    ends         [K] int32 on the device: the closing hours, ascending.
+    Returns (sse, s1, s2, s3, sim, gage): [P,G] float32 chains, sim [P,K,G] the period means with return_series (else
+    None), gage [P,T,G] the hourly gage series with want_gage (else None; it then lives in scratch only)."""
+    lib = get_library()
+    lib.require('hbvx_gage_population_stats')
+    topo = grec.topo
+    dev = grec.qs.device
+    T, U, G = topo.T, topo.U, topo.G
+    if term.transform not in _abi.POP_TRANSFORMS:
+        raise ValueError(f"transform must be one of {sorted(_abi.POP_TRANSFORMS)}, got {term.transform!r}")
+    if term.transform == "log" and term.eps is None:
+        raise ValueError("gage_population: transform 'log' needs eps")
+    _check_tensor(lib, runoff, "runoff")
+    shared = runoff.dim() == 2
+    if tuple(runoff.shape[-2:]) != (T, U) or runoff.dim() not in (2, 3) or not runoff.is_contiguous() or runoff.device != dev:
+        raise ValueError(f"runoff must be a contiguous [P,{T},{U}] or [{T},{U}] tensor on {dev}, got {tuple(runoff.shape)}")
+    if distr_cands is not None:
+        _check_tensor(lib, distr_cands, "distr_candidates")
+        if distr_cands.dim() != 3 or tuple(distr_cands.shape[1:]) != (topo.n_pair, 3) or not distr_cands.is_contiguous() \
+                or distr_cands.device != dev:
+            raise ValueError(f"distr_candidates must be a contiguous [P,{topo.n_pair},3] tensor on {dev}, got "
+                             f"{tuple(distr_cands.shape)}")
+    if shared and distr_cands is None:
+        raise ValueError("gage_population: one runoff and no routing candidates leaves nothing to evaluate")
+    P = int(distr_cands.shape[0]) if shared else int(runoff.shape[0])
+    if P < 1 or (distr_cands is not None and int(distr_cands.shape[0]) != P):
+        raise ValueError(f"gage_population: {P} runoff candidates, "
+                         f"{None if distr_cands is None else int(distr_cands.shape[0])} routing candidates")
+    if ends.dtype != torch.int32 or ends.dim() != 1 or ends.device != dev or not 1 <= ends.numel() <= T:
+        raise ValueError(f"ends must be a 1-D int32 tensor of 1..{T} closing hours on {dev}")
+    ends = ends.contiguous()
+    K = int(ends.numel())
+    for name, t, shape in (("target", term.target, (K, G)), ("w", term.w, (K, G)), ("shift", term.shift, (G,)),
+                           ("eps", term.eps if term.transform == "log" else None, (G,))):
+        if t is None and name in ("w", "eps"):
+            continue
+        if t is None:
+            raise ValueError(f"gage_population needs {name}")
+        _check_tensor(lib, t, name)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise ValueError(f"{name} must be {list(shape)} on {dev}, got {tuple(t.shape)} on {t.device}")
+    tc, wc, shc = (None if t is None else t.contiguous() for t in (term.target, term.w, term.shift))
+    epc = term.eps.contiguous() if term.transform == "log" else None
+    stream = _stream_of(lib, grec.qs)
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        r = topo.desc(grec.dp)
+        sums = tuple(_out((P, G), dev) for _ in range(4))
+        sim = _out((P, K, G), dev) if return_series else None
+        gage = _out((P, T, G), dev) if want_gage else None
+        for c0 in range(0, P, POP_MAX_CAND):
+            n = min(POP_MAX_CAND, P - c0)
+            gp = _abi.GagePop(abi_version=_abi.GAGE_POP_ABI_VERSION, n_cand=n,
+                              runoff=_ptr(runoff, 0 if shared else c0 * T * U), runoff_c_stride=0 if shared else T * U,
+                              dp=_ptr(distr_cands, c0 * topo.n_pair * 3), uh=_ptr(grec.uh),
+                              transform=_abi.POP_TRANSFORMS[term.transform], n_periods=K, period_end=ends.data_ptr(),
+                              target=_ptr(tc), w=_ptr(wc), shift=_ptr(shc), eps=_ptr(epc),
+                              sim=_ptr(sim, c0 * K * G), series=_ptr(gage, c0 * T * G))
+            gp.sse, gp.s1, gp.s2, gp.s3 = (_ptr(m, c0 * G) for m in sums)
+            ws_bytes = lib.gage_population_workspace_bytes(r, gp)
+            ws = _out(((max(ws_bytes, 4) + 3) // 4,), dev)      # poisoned with the outputs: the call must not need it cleared
+            _call(lib, 'hbvx_gage_population_stats', lib.gage_population_stats, r, gp, _ptr(ws), ws_bytes, stream)
+            HOURLY_POP_LAUNCHES['gage'] += 1
+    return sums + (sim, gage)
+
+
 @dataclass
 class GageTopology:
     """Index arrays of the (gage, unit) pairs of `outlet_topo == 1` (hbv_2_hourly.py:813-817), in

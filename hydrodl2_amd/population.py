@@ -19,8 +19,10 @@ series (hbvx_population_period): each series is averaged over its periods inside
 per period, and `population_search(periods=..., aux_periods=...)` searches on those scores.
 
 Hbv, Hbv_1_1p and Hbv_2 only.  HbvAdj has the first three calls and a period call of its own in adj_population.py
-(`adj_population_period_stats`: its second series is one of its five storages); nothing here is built for the hourly and
-multi-timescale models.  The aux series is not transformed, there is one per launch, calendars are shared by all basins,
+(`adj_population_period_stats`: its second series is one of its five storages).  Hbv_2_hourly, whose scores live at
+the gages, has `hourly_population_stats` in hourly_population.py (two stages: every candidate's unit runoff, then its
+routing to the gages and the same four chains per gage); the calls here keep refusing it, and nothing is built for the
+multi-timescale model.  The aux series is not transformed, there is one per launch, calendars are shared by all basins,
 and there is no joint `calibrate`: two `normal_equations` calls can be summed by the caller.
 
 Every call here and in adj_population.py is one front end over two `Family` records: checks, observations, requests and
