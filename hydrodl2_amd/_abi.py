@@ -290,6 +290,12 @@ GAGE_POP_SIGNATURES = [
 ]
 
 
+# The export of include/hbvx_route_rows.h, a row as in SIGNATURES (optional, no struct of its own).
+ROUTE_ROWS_SIGNATURES = [
+    ("hbvx_route_backward_rows", False, _int, [_P(RouteDesc), _fp, _fp, _fp, _fp, _i32, _fp, _fp, _fp, _u64, _vp], None),
+]
+
+
 class HbvxError(RuntimeError):
     pass
 
@@ -306,11 +312,13 @@ class Library:
         for name in EXPORTS:
             if not hasattr(d, name):
                 raise HbvxError(f"{path}: missing export {name}")
-        self.missing = [name for name in OPTIONAL_EXPORTS + [row[0] for row in GAGE_POP_SIGNATURES] if not hasattr(d, name)]
+        self.missing = [name for name in OPTIONAL_EXPORTS + [row[0] for row in GAGE_POP_SIGNATURES + ROUTE_ROWS_SIGNATURES]
+                        if not hasattr(d, name)]
         checked = set()             # (sizeof export, index): several exports share a struct
         # the required rows come first, and each table's sizeof export before the rows that name a layout: it is bound by then
         for name, _, restype, argtypes, layout, sizeof in [row + ("hbvx_sizeof",) for row in SIGNATURES] + \
-                [row + ("hbvx_gage_pop_sizeof",) for row in GAGE_POP_SIGNATURES]:
+                [row + ("hbvx_gage_pop_sizeof",) for row in GAGE_POP_SIGNATURES] + \
+                [row + ("hbvx_sizeof",) for row in ROUTE_ROWS_SIGNATURES]:
             if name in self.missing:
                 continue
             fn = getattr(d, name)
@@ -553,6 +561,14 @@ class Library:
         self._check(self.dll.hbvx_route_backward(C.byref(r), q, uh, gqr, gq, gra, grb, ws,
                                                  C.c_uint64(ws_bytes), C.c_void_p(stream)),
                     "hbvx_route_backward")
+
+    def route_backward_rows(self, r: RouteDesc, q: int, uh: int, gqr: int, gq: int, gq_rows: int, gra, grb,
+                            ws, ws_bytes: int, stream: int):
+        """hbvx_route_backward into a grad_q of gq_rows >= r.S rows: the launch zeroes the rows from r.S on."""
+        self.require("hbvx_route_backward_rows")
+        self._check(self.dll.hbvx_route_backward_rows(C.byref(r), q, uh, gqr, gq, gq_rows, gra, grb, ws,
+                                                      C.c_uint64(ws_bytes), C.c_void_p(stream)),
+                    "hbvx_route_backward_rows")
 
 
 def _population_method(entry: str):

@@ -34,11 +34,24 @@ namespace hbvx_popk {
 
 constexpr int UH = 15;      // HBVX_UH_MAXLEN
 
-// The normalised gamma unit hydrograph (uh_routing.py:5-22) of physical route_a = a, route_b = bb: taps 0..L-1 as
-// k_uh_gamma stores them and k_route_fwd loads them back, zero from L on.  A restatement of k_uh_gamma's lines
-// (hbvx.hip), operation for operation -- the sum runs over all 15 values, zeros included.  k_uh_gamma keeps its own
-// text: calling this from it changed that kernel's instruction schedule (tools/compare_code.py), and the forward's
-// kernels are pinned.  A change to either belongs in both.
+// The gamma unit hydrograph's arithmetic per tap (uh_routing.py:5-22), aa = relu(route_a) + 0.1, theta = relu(route_b)
+// + 0.5: tap k before normalisation is 1 / denom * mid * right, in that order.  k_uh_gamma (hbvx.hip) runs one thread
+// per (basin, tap) on these two, sums the 15 values of a basin in ascending k, zeros from L on included, and divides
+// each by the sum.
+HBVX_POP_HD float gamma_denom(float aa, float theta) { return expf(lgammaf(aa)) * powf(theta, aa); }
+HBVX_POP_HD float gamma_tap(float denom, float aa, float theta, int k)
+{
+    float t = (float)k + 0.5f;
+    float mid = powf(t, aa - 1.0f);
+    float right = expf(-t / theta);
+    return 1.0f / denom * mid * right;
+}
+
+// The normalised gamma unit hydrograph of physical route_a = a, route_b = bb: taps 0..L-1 as k_uh_gamma stores them and
+// k_route_fwd loads them back, zero from L on.  A restatement of gamma_denom / gamma_tap and of k_uh_gamma's sum and
+// divide, operation for operation (tests/test_uh_tap_host.py holds the two texts to each other).  It keeps its own
+// text: calling the two helpers from it changed the instruction schedule of the population kernels
+// (tools/compare_code.py), and those are pinned.  A change to either belongs in both.
 HBVX_POP_HD void gamma_taps(float a, float bb, int L, float (&w)[UH])
 {
     float aa = fmaxf(a, 0.0f) + 0.1f;

@@ -8,9 +8,11 @@
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared
 #include "hbvx_host.h"
+#include "../../include/hbvx_route_rows.h"
 #include "hbv_step.h"
 #include "hbv_lane.h"
 #include "hbv_gage.h"
+#include "hbv_pop.h"      // hbvx_popk::gamma_denom / gamma_tap: the unit hydrograph's per-tap arithmetic
 
 using namespace hbvx;
 using namespace hbvx_host;
@@ -370,42 +372,67 @@ __device__ __forceinline__ void route_ab(const hbvx_route_desc &r, int b, float 
     bb = descale_(ub, r.b_lo, r.b_hi);
 }
 
-// uh_gamma (uh_routing.py:5-22): one thread per basin
-__global__ void k_uh_gamma(const hbvx_route_desc r, float *__restrict__ uh)
+// uh_gamma (uh_routing.py:5-22): one thread per (basin, tap), 16 basins x 16 tap slots per workgroup.  Every thread
+// forms its tap's 1 / denom * mid * right (hbvx_popk::gamma_denom / gamma_tap, hbv_pop.h: the text gamma_taps runs); the
+// 15 values of a basin meet in LDS, every thread sums them k = 0..14 in that order, zeros from L on included, and
+// divides its own.  One thread per basin walked 15 powf + 15 expf + lgammaf in series on 11 workgroups of 64
+// (10-14 us at 671 basins).
+#define UH_PB 16        // basins per block of k_uh_gamma
+__global__ void __launch_bounds__(16 * UH_PB) k_uh_gamma(const hbvx_route_desc r, float *__restrict__ uh)
 {
-    int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= r.B) return;
-    float ua, ub, a, bb;
-    route_ab(r, b, ua, ub, a, bb);
-    float aa = fmaxf(a, 0.0f) + 0.1f;
-    float theta = fmaxf(bb, 0.0f) + 0.5f;
-    float denom = expf(lgammaf(aa)) * powf(theta, aa);
-    float w[HBVX_UH_MAXLEN];
+    static_assert(HBVX_UH_MAXLEN <= 16, "k_uh_gamma: 16 tap slots");
+    __shared__ float sw[16][UH_PB];
+    const int bl = threadIdx.x % UH_PB, k = threadIdx.x / UH_PB;
+    const int b = blockIdx.x * UH_PB + bl;
+    const bool mine = b < r.B && k < r.L;
+    float v = 0.0f;
+    if (mine) {
+        float ua, ub, a, bb;
+        route_ab(r, b, ua, ub, a, bb);
+        float aa = fmaxf(a, 0.0f) + 0.1f;
+        float theta = fmaxf(bb, 0.0f) + 0.5f;
+        v = hbvx_popk::gamma_tap(hbvx_popk::gamma_denom(aa, theta), aa, theta, k);
+    }
+    sw[k][bl] = v;
+    __syncthreads();
+    if (!mine) return;
     float sum = 0.0f;
 #pragma unroll
-    for (int k = 0; k < HBVX_UH_MAXLEN; k++) {
-        float t = (float)k + 0.5f;
-        float mid = powf(t, aa - 1.0f);
-        float right = expf(-t / theta);
-        w[k] = (k < r.L) ? 1.0f / denom * mid * right : 0.0f;
-        sum += w[k];
-    }
-#pragma unroll
-    for (int k = 0; k < HBVX_UH_MAXLEN; k++)
-        if (k < r.L) uh[(int64_t)b * r.L + k] = w[k] / sum;
+    for (int j = 0; j < HBVX_UH_MAXLEN; j++) sum += sw[j][bl];
+    uh[(int64_t)b * r.L + k] = v / sum;
 }
 
-// Routing kernels: thread = (basin, chunk of ROUTE_CHUNK days); the 64 lanes of a wave are 64
-// consecutive basins (256-byte coalesced accesses), the 15-tap window slides through registers,
-// so every input element is read once (plus a 14-day halo per chunk).
+// Routing kernels: the 64 lanes of a wave are 64 consecutive basins (256-byte coalesced accesses); a workgroup stages
+// its days' rows in LDS, so every input element is read from memory once (plus a 14-day halo per workgroup), and the
+// 15-tap window slides through registers.  ROUTE_CHUNK: the days of a wave in k_route_fwd, of a thread in
+// k_route_tan_batch.
 #ifndef ROUTE_CHUNK
 #define ROUTE_CHUNK 32
 #endif
-// The adjoint's chunk: its tap-gradient partials are per chunk, so longer chunks halve the second stage's input; measured at
-// the headline shape (round 5, whole-library variants): forward 32 / 16 / 64 days: 81 / 78 / 82 us; adjoint: 68 / 84 / 57 us.
+// The adjoint's chunk: its tap-gradient partials are per chunk (their sums are part of the gradient's bits), so longer
+// chunks halve the second stage's input.  Measured at the headline shape with one thread per (basin, chunk) and the
+// hydrograph in a launch of its own (round 5, whole-library variants): forward 32 / 16 / 64 days: 81 / 78 / 82 us; adjoint:
+// 68 / 84 / 57 us.  The workgroup forms below, kernel trace at config 2 (profiles/r20_route_bfi_fold.md): k_uh_gamma
+// 13.7 -> 6 us, k_route_fwd 58.6 -> 47 us (four series), k_route_bwd 37.6 -> 35.5 us with the zeros of three more rows
+// (a 10 us fill before), k_route_bwd_params 15.7 -> 12 us.
 #ifndef ROUTE_CHUNK_BWD
 #define ROUTE_CHUNK_BWD 64
 #endif
+
+// Block map of the routing and BFI kernels.  Workgroups are dealt round-robin over the 8 XCDs (block i runs on XCD
+// i % 8: observed, not guaranteed -- it only matters for speed; hbv_chunked.h), each with its own L2.  A [T,B] row is
+// 4-byte aligned only, so the 256-byte (64-byte) piece a workgroup takes of it shares its first and last 128-byte line
+// with the neighbouring basins' workgroups; on the plain grid those run on other XCDs and the shared lines are
+// fetched once per L2: 1.5 x the bytes (a micro-benchmark of k_route_fwd's loads and stores alone at config 2: 36 us on
+// the plain grid, 25 us on this map, 23 us for a flat copy of the same bytes).  Here XCD c takes the contiguous run
+// [c * per, (c + 1) * per) of the n logical blocks, basins fastest, so neighbours meet in one L2.
+// The launch has xcd_grid(n) workgroups; -1: none for this one (uniform over the workgroup).
+static inline unsigned xcd_grid(int64_t n) { return (unsigned)((n + 7) / 8 * 8); }
+__device__ __forceinline__ int xcd_block()
+{
+    const int per = gridDim.x / 8;
+    return (blockIdx.x % 8) * per + blockIdx.x / 8;
+}
 
 __device__ __forceinline__ void load_uh(const float *__restrict__ uh, int b, int L, float *w)
 {
@@ -414,110 +441,162 @@ __device__ __forceinline__ void load_uh(const float *__restrict__ uh, int b, int
 }
 
 // uh_conv (uh_routing.py:25-57): y[s,t,b] = sum_k UH[b,k] * q[s,t-k,b], zero history.
-// grid.z = series; the chunk is consumed in groups of ROUTE_GROUP days whose loads are all issued
-// before the first is used (a thread would otherwise have one load in flight at a time).
-#ifndef ROUTE_GROUP
-#define ROUTE_GROUP 8
-#endif
+// Workgroup (xcd_block: basins, then days, then series) = 64 basins x 4 * ROUTE_CHUNK days, wave p the days ROUTE_CHUNK p .. of them.  The tile's
+// rows (with the 14 days before it) go to LDS with every thread's share of the loads issued at once: one round trip to
+// memory per workgroup and a halo of 14 rows in 142 (a thread per (basin, chunk) loading for itself made five
+// dependent round trips and re-read 14 rows in 46).
+#define ROUTE_FWD_TILE (4 * ROUTE_CHUNK)
+#define ROUTE_FWD_ROWS (ROUTE_FWD_TILE + HBVX_UH_MAXLEN - 1)
 __global__ void __launch_bounds__(256) k_route_fwd(int T, int B, int S, int L,
                                                    const float *__restrict__ q,
                                                    const float *__restrict__ uh,
                                                    float *__restrict__ y)
 {
-    const int b = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int chunk = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int t0 = chunk * ROUTE_CHUNK;
-    if (b >= B || t0 >= T) return;
-    const int t1 = min(T, t0 + ROUTE_CHUNK);
-    const int s = blockIdx.z;
+    __shared__ float sq[ROUTE_FWD_ROWS][64];      // q[t0 - 14 + r], zero before the record and from T on
+    constexpr int NLOAD = (ROUTE_FWD_ROWS + 3) / 4;
+    const int lane = threadIdx.x & 63, part = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (a scalar: row addresses are)
+    const int nx = (B + 63) / 64, ny = (T + ROUTE_FWD_TILE - 1) / ROUTE_FWD_TILE;
+    const int blk = xcd_block();
+    if (blk >= nx * ny * S) return;       // (the whole workgroup)
+    const int b = (blk % nx) * 64 + lane;
+    const int t0 = (blk / nx) % ny * ROUTE_FWD_TILE;
+    const bool live = b < B;        // (no early return before the barrier)
+    const int s = blk / (nx * ny);
+    const float *qs = q + (int64_t)s * T * B;      // rows are addressed as (uniform row pointer)[b]
+    float *ys = y + (int64_t)s * T * B;
+    float v[NLOAD];
+#pragma unroll
+    for (int i = 0; i < NLOAD; i++) {
+        const int r = part + 4 * i, t = t0 - (HBVX_UH_MAXLEN - 1) + r;
+        v[i] = (live && r < ROUTE_FWD_ROWS && t >= 0 && t < T) ? (qs + (int64_t)t * B)[b] : 0.0f;
+    }
     float w[HBVX_UH_MAXLEN];
-    load_uh(uh, b, L, w);
-    const float *qs = q + (int64_t)s * T * B + b;
-    float *ys = y + (int64_t)s * T * B + b;
+    load_uh(uh, live ? b : B - 1, L, w);
+#pragma unroll
+    for (int i = 0; i < NLOAD; i++) {
+        const int r = part + 4 * i;
+        if (r < ROUTE_FWD_ROWS) sq[r][lane] = v[i];
+    }
+    __syncthreads();
+    const int c0 = part * ROUTE_CHUNK;
+    if (!live || t0 + c0 >= T) return;
     float win[HBVX_UH_MAXLEN];
 #pragma unroll
-    for (int k = 1; k < HBVX_UH_MAXLEN; k++) win[k] = (t0 - k >= 0) ? qs[(int64_t)(t0 - k) * B] : 0.0f;
-    for (int tg = t0; tg < t1; tg += ROUTE_GROUP) {
-        float v[ROUTE_GROUP];
+    for (int k = 1; k < HBVX_UH_MAXLEN; k++) win[k] = sq[c0 + HBVX_UH_MAXLEN - 1 - k][lane];
+#pragma unroll 8
+    for (int d = 0; d < ROUTE_CHUNK; d++) {
+        win[0] = sq[c0 + HBVX_UH_MAXLEN - 1 + d][lane];
+        float acc = 0.0f;
 #pragma unroll
-        for (int j = 0; j < ROUTE_GROUP; j++) v[j] = (tg + j < t1) ? qs[(int64_t)(tg + j) * B] : 0.0f;
+        for (int k = 0; k < HBVX_UH_MAXLEN; k++) acc += w[k] * win[k];
+        if (t0 + c0 + d < T) (ys + (int64_t)(t0 + c0 + d) * B)[b] = acc;
 #pragma unroll
-        for (int j = 0; j < ROUTE_GROUP; j++) {
-            win[0] = v[j];
-            float acc = 0.0f;
-#pragma unroll
-            for (int k = 0; k < HBVX_UH_MAXLEN; k++) acc += w[k] * win[k];
-            if (tg + j < t1) ys[(int64_t)(tg + j) * B] = acc;
-#pragma unroll
-            for (int k = HBVX_UH_MAXLEN - 1; k > 0; k--) win[k] = win[k - 1];
-        }
+        for (int k = HBVX_UH_MAXLEN - 1; k > 0; k--) win[k] = win[k - 1];
     }
 }
 
 // conv1d backward in one pass over the chunk:
 //   gq[s,t,b] = sum_k UH[b,k] * gy[s,t+k,b]                      (w.r.t. the input)
 //   ws[(chunk*L+k)*B + b] = sum_{s, t in chunk} gy[s,t,b] * q[s,t-k,b]   (partial tap gradients)
-__global__ void __launch_bounds__(256) k_route_bwd(int T, int B, int S, int L,
+// Workgroup (xcd_block: basins, then chunks) = 64 basins x one chunk of ROUTE_CHUNK_BWD days, four waves.  The chunk's rows of q (with the 14 days
+// before it) and of gy (with the 14 days after it) are staged in LDS, every thread's share of the loads issued at
+// once -- one round trip to memory per series instead of one per 8 days -- and each row is read from memory
+// once.  The sums are independent of each other, so the four waves share them without changing one: wave p forms
+// gq of the days 16 p .. 16 p + 15 of the chunk (all 15 taps each, ascending k) and the tap gradients 4 p .. 4 p + 3
+// (all days of the chunk, series by series, ascending t; fma in double).  One thread per (basin, chunk) walked
+// 64 days x 15 taps x (fp32 multiply-add + fp64 fma) on 1.2 waves per SIMD.
+// gq has n_rows >= S rows of [T,B]: the rows S .. n_rows - 1 get zeros for the workgroup's own days and basins.
+#define ROUTE_BWD_ROWS (ROUTE_CHUNK_BWD + HBVX_UH_MAXLEN - 1)
+#define ROUTE_BWD_DAYS (ROUTE_CHUNK_BWD / 4)     // days of gq per wave
+#define ROUTE_BWD_TAPS 4                         // tap gradients per wave (the last wave: 3)
+static_assert(ROUTE_CHUNK_BWD % 4 == 0 && 4 * ROUTE_BWD_TAPS >= HBVX_UH_MAXLEN, "k_route_bwd: four waves share a chunk");
+__global__ void __launch_bounds__(256) k_route_bwd(int T, int B, int S, int L, int n_rows,
                                                    const float *__restrict__ q,
                                                    const float *__restrict__ uh,
                                                    const float *__restrict__ gy,
                                                    float *__restrict__ gq, double *__restrict__ ws)
 {
-    const int b = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int chunk = blockIdx.y * 4 + (threadIdx.x >> 6);
+    __shared__ float sq[ROUTE_BWD_ROWS][64], sg[ROUTE_BWD_ROWS][64];   // q[t0 - 14 + r], gy[t0 + r]
+    constexpr int NLOAD = (ROUTE_BWD_ROWS + 3) / 4;
+    const int lane = threadIdx.x & 63, part = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (a scalar: row addresses are)
+    const int nx = (B + 63) / 64;
+    const int blk = xcd_block();
+    if (blk >= nx * ((T + ROUTE_CHUNK_BWD - 1) / ROUTE_CHUNK_BWD)) return;      // (the whole workgroup)
+    const int b = (blk % nx) * 64 + lane;
+    const int chunk = blk / nx;
     const int t0 = chunk * ROUTE_CHUNK_BWD;
-    if (b >= B || t0 >= T) return;
     const int t1 = min(T, t0 + ROUTE_CHUNK_BWD);
+    const bool live = b < B;        // (no early return: the workgroup meets at barriers)
+    const int d0 = part * ROUTE_BWD_DAYS, k0 = part * ROUTE_BWD_TAPS;
     // The tap gradients are summed in DOUBLE: what leaves this path is sum_k gw[k] w_k (ln t_k - <ln t>), whose weights
     // sum to zero (the hydrograph is normalised), so the common part of the gw[k] -- nearly all of them when the
     // inflow is smooth -- cancels and float32 sums (eps x ~1e+2) left 1e-6 where the result is 1e-4: 0.7 % off the
     // float64 value on hbv_ties' route_b, twenty times the reference's own error (round 5).
     float w[HBVX_UH_MAXLEN];
-    double gw[HBVX_UH_MAXLEN];
-    load_uh(uh, b, L, w);
+    double gw[ROUTE_BWD_TAPS];
+    load_uh(uh, live ? b : B - 1, L, w);
 #pragma unroll
-    for (int k = 0; k < HBVX_UH_MAXLEN; k++) gw[k] = 0.0;
+    for (int j = 0; j < ROUTE_BWD_TAPS; j++) gw[j] = 0.0;
     for (int s = 0; s < S; s++) {
-    const float *qs = q + (int64_t)s * T * B + b;
-    const float *gs = gy + (int64_t)s * T * B + b;
-    float *gqs = gq + (int64_t)s * T * B + b;
-    float qwin[HBVX_UH_MAXLEN], gwin[HBVX_UH_MAXLEN]; // q[t-k], gy[t+k]
+        const float *qs = q + (int64_t)s * T * B;      // rows are addressed as (uniform row pointer)[b]
+        const float *gs = gy + (int64_t)s * T * B;
+        float *gqs = gq + (int64_t)s * T * B;
+        float vq[NLOAD], vg[NLOAD];
 #pragma unroll
-    for (int k = 1; k < HBVX_UH_MAXLEN; k++) qwin[k] = (t0 - k >= 0) ? qs[(int64_t)(t0 - k) * B] : 0.0f;
-#pragma unroll
-    for (int k = 0; k < HBVX_UH_MAXLEN - 1; k++) gwin[k + 1] = (t0 + k < T) ? gs[(int64_t)(t0 + k) * B] : 0.0f;
-    for (int tg = t0; tg < t1; tg += ROUTE_GROUP) {
-        float vq[ROUTE_GROUP], vg[ROUTE_GROUP];
-#pragma unroll
-        for (int j = 0; j < ROUTE_GROUP; j++) {
-            const int t = tg + j;
-            vq[j] = (t < t1) ? qs[(int64_t)t * B] : 0.0f;
-            vg[j] = (t + HBVX_UH_MAXLEN - 1 < T) ? gs[(int64_t)(t + HBVX_UH_MAXLEN - 1) * B] : 0.0f;
+        for (int i = 0; i < NLOAD; i++) {
+            const int r = part + 4 * i, tq = t0 - (HBVX_UH_MAXLEN - 1) + r, tg = t0 + r;
+            const bool in = live && r < ROUTE_BWD_ROWS;
+            vq[i] = (in && tq >= 0 && tq < t1) ? (qs + (int64_t)tq * B)[b] : 0.0f;
+            vg[i] = (in && tg < T) ? (gs + (int64_t)tg * B)[b] : 0.0f;
         }
+        if (s) __syncthreads();     // the previous series' tile has been read
 #pragma unroll
-        for (int j = 0; j < ROUTE_GROUP; j++) {
-            const bool on = tg + j < t1;
-#pragma unroll
-            for (int k = 0; k < HBVX_UH_MAXLEN - 1; k++) gwin[k] = gwin[k + 1];
-            gwin[HBVX_UH_MAXLEN - 1] = vg[j];
-            qwin[0] = vq[j];
-            float acc = 0.0f;
-            const double g0 = on ? (double)gwin[0] : 0.0;
-#pragma unroll
-            for (int k = 0; k < HBVX_UH_MAXLEN; k++) {
-                acc += w[k] * gwin[k];
-                gw[k] = fma(g0, (double)qwin[k], gw[k]);
+        for (int i = 0; i < NLOAD; i++) {
+            const int r = part + 4 * i;
+            if (r < ROUTE_BWD_ROWS) {
+                sq[r][lane] = vq[i];
+                sg[r][lane] = vg[i];
             }
-            if (on) gqs[(int64_t)(tg + j) * B] = acc;
+        }
+        __syncthreads();
+        if (s == 0 && live) {
+            for (int z = S; z < n_rows; z++) {
+                float *gz = gq + (int64_t)z * T * B;
 #pragma unroll
-            for (int k = HBVX_UH_MAXLEN - 1; k > 0; k--) qwin[k] = qwin[k - 1];
+                for (int d = 0; d < ROUTE_BWD_DAYS; d++)
+                    if (t0 + d0 + d < t1) (gz + (int64_t)(t0 + d0 + d) * B)[b] = 0.0f;
+            }
+        }
+        float g[ROUTE_BWD_DAYS + HBVX_UH_MAXLEN - 1];     // gy[t0 + d0 + i], zero from T on
+#pragma unroll
+        for (int i = 0; i < ROUTE_BWD_DAYS + HBVX_UH_MAXLEN - 1; i++) g[i] = sg[d0 + i][lane];
+#pragma unroll
+        for (int d = 0; d < ROUTE_BWD_DAYS; d++) {
+            float acc = 0.0f;
+#pragma unroll
+            for (int k = 0; k < HBVX_UH_MAXLEN; k++) acc += w[k] * g[d + k];
+            if (live && t0 + d0 + d < t1) (gqs + (int64_t)(t0 + d0 + d) * B)[b] = acc;
+        }
+        // tap k0 + j of day t0 + i reads q[t0 + i - k0 - j] = sq[i + 14 - k0 - j]; the window slides through qw.  (The
+        // last wave's fourth value is tap 15, which does not exist: its row index is kept in range and its sum dropped.)
+        double qw[ROUTE_BWD_TAPS];
+#pragma unroll
+        for (int j = 1; j < ROUTE_BWD_TAPS; j++) qw[j] = (double)sq[max(HBVX_UH_MAXLEN - 1 - k0 - j, 0)][lane];
+        const int nd = t1 - t0;
+#pragma unroll 8
+        for (int i = 0; i < nd; i++) {
+            qw[0] = (double)sq[i + HBVX_UH_MAXLEN - 1 - k0][lane];
+            const double g0 = (double)sg[i][lane];
+#pragma unroll
+            for (int j = 0; j < ROUTE_BWD_TAPS; j++) gw[j] = fma(g0, qw[j], gw[j]);
+#pragma unroll
+            for (int j = ROUTE_BWD_TAPS - 1; j > 0; j--) qw[j] = qw[j - 1];
         }
     }
-    }
-    if (ws) {
+    if (ws && live) {
 #pragma unroll
-        for (int k = 0; k < HBVX_UH_MAXLEN; k++)
-            if (k < L) ws[((int64_t)chunk * L + k) * B + b] = gw[k];
+        for (int j = 0; j < ROUTE_BWD_TAPS; j++)
+            if (k0 + j < L) ws[((int64_t)chunk * L + k0 + j) * B + b] = gw[j];
     }
 }
 
@@ -596,7 +675,8 @@ __global__ void __launch_bounds__(256) k_route_tan_batch(const hbvx_route_desc r
 // gamma UH to the routing inputs.  Block = 16 basins x 16 tap-threads x 4 parts: thread (bl, k, part) sums tap k over
 // the chunks c = part (mod 4) in ascending order (part 0 also the last nchunk mod 4 ones), the parts are combined as
 // (p0 + p1) + (p2 + p3) -- the association the one-thread-per-tap version used, on four times the threads and blocks
-// (11 blocks of 1 024 at config 2 were a 35 us latency chain of 229 dependent loads) -- then the k == 0 threads finish
+// (11 blocks of 1 024 at config 2 were a 35 us latency chain of 229 dependent loads; with one load in flight per thread
+// the four parts took 15.7 us, with eight 12 us) -- then the k == 0 threads finish
 // per basin.
 // d w_k / d aa    = w_k (ln t_k - sum_j w_j ln t_j)      (Gamma(aa) and theta^aa cancel
 // d w_k / d theta = w_k (t_k - sum_j w_j t_j) / theta^2    in the normalisation)
@@ -616,7 +696,17 @@ __global__ void __launch_bounds__(1024) k_route_bwd_params(const hbvx_route_desc
         const double *src = ws + (int64_t)k * B + b;
         const int64_t cs = (int64_t)L * B;
         const int n4 = nchunk & ~3;
-        for (int c = part; c < n4; c += 4) acc += src[(int64_t)c * cs];
+        int c = part;
+        // eight chunks' loads issued before the first add (one in flight made nchunk / 4 dependent round trips); the
+        // adds keep their ascending order
+        for (; c + 4 * 7 < n4; c += 4 * 8) {
+            double v[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) v[j] = src[(int64_t)(c + 4 * j) * cs];
+#pragma unroll
+            for (int j = 0; j < 8; j++) acc += v[j];
+        }
+        for (; c < n4; c += 4) acc += src[(int64_t)c * cs];
         if (part == 0)
             for (int c = n4; c < nchunk; c++) acc += src[(int64_t)c * cs];
     }
@@ -894,10 +984,10 @@ extern "C" int hbvx_route_forward(const hbvx_route_desc *r, const float *q, floa
     if (rc) return rc;
     if (!q || !uh || !q_rout) return fail(HBVX_E_NULL, "route buffer is NULL");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_uh_gamma, dim3((r->B + 63) / 64), dim3(64), 0, st, *r, uh);
-    const int nchunk = (r->T + ROUTE_CHUNK - 1) / ROUTE_CHUNK;
-    hipLaunchKernelGGL(k_route_fwd, dim3((r->B + 63) / 64, (nchunk + 3) / 4, r->S), dim3(256), 0, st, r->T,
-                       r->B, r->S, r->L, q, uh, q_rout);
+    hipLaunchKernelGGL(k_uh_gamma, dim3((r->B + UH_PB - 1) / UH_PB), dim3(16 * UH_PB), 0, st, *r, uh);
+    const int64_t nblk = (int64_t)((r->B + 63) / 64) * ((r->T + ROUTE_FWD_TILE - 1) / ROUTE_FWD_TILE) * r->S;
+    if (nblk > INT32_MAX - 8) return fail(HBVX_E_SHAPE, "routing: too many (basin, day, series) tiles for one launch");
+    hipLaunchKernelGGL(k_route_fwd, dim3(xcd_grid(nblk)), dim3(256), 0, st, r->T, r->B, r->S, r->L, q, uh, q_rout);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "hbvx_route_forward launch");
     return HBVX_OK;
@@ -911,27 +1001,46 @@ extern "C" uint64_t hbvx_route_workspace_bytes(const hbvx_route_desc *r)
     return (uint64_t)route_chunks(r) * (uint64_t)r->L * (uint64_t)r->B * sizeof(double);    // (8-byte aligned: torch's allocations are)
 }
 
-extern "C" int hbvx_route_backward(const hbvx_route_desc *r, const float *q, const float *uh,
-                                   const float *grad_q_rout, float *grad_q, float *grad_ra,
-                                   float *grad_rb, void *workspace, uint64_t workspace_bytes,
-                                   void *stream)
+static int launch_route_bwd(const hbvx_route_desc *r, const float *q, const float *uh, const float *grad_q_rout,
+                            float *grad_q, int n_rows, float *grad_ra, float *grad_rb, void *workspace,
+                            uint64_t workspace_bytes, void *stream, const char *what)
 {
     int rc = check_route(r);
     if (rc) return rc;
     if (!q || !uh || !grad_q_rout || !grad_q) return fail(HBVX_E_NULL, "route buffer is NULL");
+    if (n_rows < r->S) return fail(HBVX_E_SHAPE, "grad_q has fewer rows than series");
     hipStream_t st = (hipStream_t)stream;
     const bool want_p = grad_ra || grad_rb;
     if (want_p && (!workspace || workspace_bytes < hbvx_route_workspace_bytes(r)))
         return fail(HBVX_E_NULL, "route workspace missing or too small");
     const int nchunk = route_chunks(r);
-    hipLaunchKernelGGL(k_route_bwd, dim3((r->B + 63) / 64, (nchunk + 3) / 4), dim3(256), 0, st, r->T,
-                       r->B, r->S, r->L, q, uh, grad_q_rout, grad_q, want_p ? (double *)workspace : nullptr);
+    const int64_t nblk = (int64_t)((r->B + 63) / 64) * nchunk;
+    if (nblk > INT32_MAX - 8) return fail(HBVX_E_SHAPE, "routing adjoint: too many (basin, chunk) tiles for one launch");
+    hipLaunchKernelGGL(k_route_bwd, dim3(xcd_grid(nblk)), dim3(256), 0, st, r->T, r->B, r->S, r->L, n_rows, q, uh,
+                       grad_q_rout, grad_q, want_p ? (double *)workspace : nullptr);
     if (want_p)
         hipLaunchKernelGGL(k_route_bwd_params, dim3((r->B + ROUTE_PB - 1) / ROUTE_PB), dim3(1024), 0, st, *r, nchunk,
                            uh, (const double *)workspace, grad_ra, grad_rb);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "hbvx_route_backward launch");
+    if (e != hipSuccess) return hip_fail(e, what);
     return HBVX_OK;
+}
+
+extern "C" int hbvx_route_backward(const hbvx_route_desc *r, const float *q, const float *uh,
+                                   const float *grad_q_rout, float *grad_q, float *grad_ra,
+                                   float *grad_rb, void *workspace, uint64_t workspace_bytes,
+                                   void *stream)
+{
+    return launch_route_bwd(r, q, uh, grad_q_rout, grad_q, r ? r->S : 0, grad_ra, grad_rb, workspace, workspace_bytes,
+                            stream, "hbvx_route_backward launch");
+}
+
+extern "C" int hbvx_route_backward_rows(const hbvx_route_desc *r, const float *q, const float *uh,
+                                        const float *grad_q_rout, float *grad_q, int32_t grad_q_rows, float *grad_ra,
+                                        float *grad_rb, void *workspace, uint64_t workspace_bytes, void *stream)
+{
+    return launch_route_bwd(r, q, uh, grad_q_rout, grad_q, grad_q_rows, grad_ra, grad_rb, workspace, workspace_bytes,
+                            stream, "hbvx_route_backward_rows launch");
 }
 
 // ---------------------------------------------------------------------------
@@ -970,56 +1079,96 @@ extern "C" int hbvx_selftest_div(const float *x, const float *y, float *out, int
 }
 
 // ---------------------------------------------------------------------------
-// baseflow index (hbv.py:562-567): block = 16 basins x 64 time slices (64-byte row segments; four
-// times the blocks of a 64-basin tile: B / 16 instead of B / 64 CUs busy), fixed-order sums
+// baseflow index (hbv.py:562-567), fixed-order sums.  Per basin and series, 64 time slices sl with two chains each,
+//   a over t = sl, sl + 128, ..   and   c over t = sl + 64, sl + 192, ..      (ascending, from 0)
+// then a + c per slice, then the slices sl = 0..63 in sequence.  Block = PB basins x 64 slices (x the two chains
+// where a thread owns one chain of both series), BFI_ROWS rows in flight before the first add; the blocks on the map
+// of xcd_block.  Measured alone at config 2 (39 MB, 6 us at the copy rate): 16 basins x 64 slices with both chains
+// on one thread, 42 blocks: 30 us, with or without eight rows in flight (not a latency chain); 8 basins on 84 blocks
+// 30 us; the 16-basin form on the XCD map 28 us; 8 / 4 basins with a chain per thread on the XCD map 24 / 22 us; without
+// the map 4 / 2 / 1 basins 44 / 58 / 66 us, 64-basin rows on 11 blocks 147 us.  What binds is the 128-byte lines a
+// narrow piece of a 4-byte-aligned row shares with its neighbours, fetched by every L2 that holds one of them.
+// k_bfi_tan_batch below keeps the 16 x 64 layout and its own order.
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(1024) k_bfi(int T, int B, const float *__restrict__ qs,
-                                              const float *__restrict__ q2, float nz,
-                                              float *__restrict__ bfi)
+#define BFI_ROWS 8      // rows in flight per series and thread
+// NH = 2: a chain per thread (narrow blocks for few basins); NH = 1: both chains of a slice on one thread
+template <int PB, int NH>
+__global__ void __launch_bounds__(PB * 64 * NH) k_bfi(int T, int B, const float *__restrict__ qs,
+                                                      const float *__restrict__ q2, float nz,
+                                                      float *__restrict__ bfi)
 {
-    __shared__ float r0[64][16], r2[64][16];
-    const int bl = threadIdx.x & 15, sl = threadIdx.x >> 4;
-    const int b = blockIdx.x * 16 + bl;
-    float a0 = 0.0f, a2 = 0.0f, c0 = 0.0f, c2 = 0.0f;
+    constexpr int NC = 2 / NH, NR = BFI_ROWS / NC;      // chains per thread, rows of a chain in flight
+    __shared__ float r0[2][64][PB], r2[2][64][PB];
+    const int bl = threadIdx.x % PB, sl = (threadIdx.x / PB) & 63, half = threadIdx.x / (PB * 64);
+    const int b = xcd_block() * PB + bl;        // (past B: the lanes idle, the barrier is still met)
+    float a0[NC], a2[NC];
+#pragma unroll
+    for (int i = 0; i < NC; i++) a0[i] = a2[i] = 0.0f;
     if (b < B) {
+        const int h0 = half * NC;               // this thread's chains are h0 .. h0 + NC - 1: rows t + 64 h
         int t = sl;
-        for (; t + 64 < T; t += 128) {
-            a0 += qs[(int64_t)t * B + b];
-            a2 += q2[(int64_t)t * B + b];
-            c0 += qs[(int64_t)(t + 64) * B + b];
-            c2 += q2[(int64_t)(t + 64) * B + b];
+        for (; t + 64 * (h0 + NC - 1) + 128 * (NR - 1) < T; t += 128 * NR) {
+            float v0[NC][NR], v2[NC][NR];
+#pragma unroll
+            for (int j = 0; j < NR; j++)
+#pragma unroll
+                for (int i = 0; i < NC; i++) {
+                    v0[i][j] = qs[(int64_t)(t + 64 * (h0 + i) + 128 * j) * B + b];
+                    v2[i][j] = q2[(int64_t)(t + 64 * (h0 + i) + 128 * j) * B + b];
+                }
+#pragma unroll
+            for (int j = 0; j < NR; j++)
+#pragma unroll
+                for (int i = 0; i < NC; i++) {
+                    a0[i] += v0[i][j];
+                    a2[i] += v2[i][j];
+                }
         }
-        if (t < T) {
-            a0 += qs[(int64_t)t * B + b];
-            a2 += q2[(int64_t)t * B + b];
-        }
+#pragma unroll
+        for (int i = 0; i < NC; i++)
+            for (int tt = t + 64 * (h0 + i); tt < T; tt += 128) {
+                a0[i] += qs[(int64_t)tt * B + b];
+                a2[i] += q2[(int64_t)tt * B + b];
+            }
     }
-    r0[sl][bl] = a0 + c0;
-    r2[sl][bl] = a2 + c2;
+#pragma unroll
+    for (int i = 0; i < NC; i++) {
+        r0[half * NC + i][sl][bl] = a0[i];
+        r2[half * NC + i][sl][bl] = a2[i];
+    }
     __syncthreads();
-    if (sl == 0 && b < B) {
+    if (threadIdx.x < PB && b < B) {
         float s0 = 0.0f, s2 = 0.0f;
 #pragma unroll
         for (int k = 0; k < 64; k++) {
-            s0 += r0[k][bl];
-            s2 += r2[k][bl];
+            s0 += r0[0][k][bl] + r0[1][k][bl];
+            s2 += r2[0][k][bl] + r2[1][k][bl];
         }
         bfi[b] = 100.0f * (s2 / (s0 + nz));
     }
 }
 
+// 16-basin blocks (64-byte pieces of a row, both chains on a thread) once they fill the chip on their own; below
+// that 4-basin blocks with a chain per thread: four times the blocks (measured: the comment above; at 12 500 basins
+// x 730 days the 4-basin form took 44 us against 34 us for 16-basin blocks).
+#define BFI_WIDE_BLOCKS 256
 extern "C" int hbvx_bfi(int32_t T, int32_t B, const float *qs, const float *q2, float nearzero,
                         float *bfi, void *stream)
 {
     if (!qs || !q2 || !bfi || T <= 0 || B <= 0) return fail(HBVX_E_NULL, "hbvx_bfi: bad arguments");
-    hipLaunchKernelGGL(k_bfi, dim3((B + 15) / 16), dim3(1024), 0, (hipStream_t)stream, T, B, qs, q2,
-                       nearzero, bfi);
+    if ((B + 15) / 16 >= BFI_WIDE_BLOCKS)
+        hipLaunchKernelGGL((k_bfi<16, 1>), dim3(xcd_grid((B + 15) / 16)), dim3(1024), 0, (hipStream_t)stream, T, B, qs, q2,
+                           nearzero, bfi);
+    else
+        hipLaunchKernelGGL((k_bfi<4, 2>), dim3(xcd_grid((B + 3) / 4)), dim3(512), 0, (hipStream_t)stream, T, B, qs, q2,
+                           nearzero, bfi);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "hbvx_bfi launch");
     return HBVX_OK;
 }
 
-// Tangent of the baseflow index (quotient rule), the block layout and summation order of k_bfi.
+// Tangent of the baseflow index (quotient rule).  Block = 16 basins x 64 time slices; a slice's rows t = sl, sl + 64, ..
+// are summed in ascending order, then the slices in sequence.
 __device__ __forceinline__ void bfi_tan_body(int T, int B, const float *__restrict__ qs,
                                              const float *__restrict__ q2, const float *__restrict__ qsd,
                                              const float *__restrict__ q2d, float nz, float *__restrict__ bfid)

@@ -727,17 +727,24 @@ class HbvPath(torch.autograd.Function):
         if g_routed is not None and cfg.route is not None:
             r = _route_desc(cfg, ptensors, S=n_live)
             gq = _out((4, T, B), dev)
-            if n_live < 4:
+            # the rows without a routed gradient must be zero: the routing adjoint's own launch writes them where the
+            # library has hbvx_route_backward_rows, else a fill of its own before the call
+            in_launch = n_live < 4 and "hbvx_route_backward_rows" not in lib.missing
+            if n_live < 4 and not in_launch:
                 gq[n_live:].zero_()
             rs = cfg.route
             gt = gp[rs.tensor_idx]
             ws_bytes = _cached(cfg, ("route_ws", n_live), lambda: lib.route_workspace_bytes(r))
             ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
             g_routed = g_routed.contiguous()
-            _call(lib, 'hbvx_route_backward', lib.route_backward, r, _ptr(flux), _ptr(uh),
-                  _ptr(g_routed), _ptr(gq), sta_ptr(rs.tensor_idx, rs.a_off) if gt is not None else None,
-                  sta_ptr(rs.tensor_idx, rs.b_off) if gt is not None else None,
-                  _ptr(ws), ws_bytes, stream)
+            g_ab = (sta_ptr(rs.tensor_idx, rs.a_off) if gt is not None else None,
+                    sta_ptr(rs.tensor_idx, rs.b_off) if gt is not None else None)
+            if in_launch:
+                _call(lib, 'hbvx_route_backward', lib.route_backward_rows, r, _ptr(flux), _ptr(uh),
+                      _ptr(g_routed), _ptr(gq), 4, *g_ab, _ptr(ws), ws_bytes, stream)
+            else:
+                _call(lib, 'hbvx_route_backward', lib.route_backward, r, _ptr(flux), _ptr(uh),
+                      _ptr(g_routed), _ptr(gq), *g_ab, _ptr(ws), ws_bytes, stream)
         # Which series carry gradient?  Only the four runoff series (the usual losses: streamflow,
         # with or without routing) -> a [4,T,B] buffer and the adjoint's 4-series kernels; anything
         # else -> the dense [n_flux,T,B] form.

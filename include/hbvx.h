@@ -297,6 +297,8 @@ int hbvx_route_backward(const hbvx_route_desc *r, const float *q, const float *u
                         const float *grad_q_rout, float *grad_q, float *grad_ra,
                         float *grad_rb, void *workspace, uint64_t workspace_bytes,
                         void *stream);
+/* hbvx_route_backward into a grad_q buffer of more rows than series, the rest zeroed in the launch: the optional export
+ * hbvx_route_backward_rows, include/hbvx_route_rows.h. */
 
 /* Gage routing of unit runoff (hbv_2_hourly.py:800-897 `distr_routing` + `_frac_shift1d`): for every
  * (gage, unit) pair with outlet_topo == 1 a normalised gamma unit hydrograph of L = min(T, 72)
