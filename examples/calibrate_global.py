@@ -13,7 +13,7 @@ wide).  Two routes from that start, both per basin:
                                         [--objective sse|nse|kge|kge12] [--transform none|sqrt|log] [--model Hbv|HbvAdj]
                                         [--aux-key AET_hydro|SWE|srflow_no_rout|ssflow_no_rout|gwflow_no_rout |
                                                    SNOWPACK|MELTWATER|SM|SUZ|SLZ (HbvAdj)] [--aux-share 0.5]
-                                        [--aux-period N]
+                                        [--aux-period N] [--fdc-share S]
 
 --model HbvAdj runs the same experiment on the implicit scheme: adj_population_search (hbvx_adj_population_cost: every
 candidate's days solved in registers) in front of calibrate, scored on 'flow_sim', from the module's own start (empty
@@ -32,6 +32,11 @@ of one day's value in eight.  The flow stays daily.
 --model HbvAdj takes --aux-key SNOWPACK, MELTWATER, SM, SUZ or SLZ: the second series is then the ensemble mean of that
 storage at the end of each day (the hidden row's comes from the module's trajectory), and both forms of the aux
 observation go through hbvx_adj_population_period.
+--fdc-share S (Hbv, with --objective nse / kge / kge12, without --aux-key) adds a route: the search on (1 - S) * flow cost
++ S * fdc_freq, the mean distance between the simulated and the observed flow-duration curve at fifteen exceedance
+probabilities (hbvx_population_fdc: the exceedance counts of every candidate from the launch that scores its flow), in
+front of the same Levenberg-Marquardt.  The line then carries the basin-mean fdc_freq at the start and at the end of the
+search with and without the term, beside the SSE / NSE / KGE of both.
 Prints one JSON line: per route the summed cost and the number of basins in which it ended lower, with the cost of
 the start and of the search's pick beside them, and -- whichever objective was searched -- the basin means of SSE, NSE
 and KGE on the raw flow at the start and at the end of every route.  Synthetic forcings (tests/synth.py), a fixed seed.
@@ -72,7 +77,11 @@ def main():
     ap.add_argument("--aux-share", type=float, default=0.5, help="the aux term's share of the searched cost")
     ap.add_argument("--aux-period", type=int, default=None,
                     help="observe the aux series as N-day means of the hidden row instead of every 8th day")
+    ap.add_argument("--fdc-share", type=float, default=0.0,
+                    help="also search on (1 - S) * flow cost + S * fdc_freq, the distance between the flow-duration curves")
     args = ap.parse_args()
+    if args.fdc_share and (args.model != "Hbv" or args.objective == "sse" or args.aux_key or not 0 < args.fdc_share <= 1):
+        ap.error("--fdc-share S in (0, 1] goes with --model Hbv and --objective nse, kge or kge12, without --aux-key")
     if args.aux_period is not None and (not args.aux_key or args.aux_period < 1):
         ap.error("--aux-period N >= 1 goes with --aux-key")
     if args.aux_key and args.objective == "sse":
@@ -165,6 +174,27 @@ def main():
             "mean_scores_search_with_aux_then_calibrate": worth(both_aux),
             "cost_search_with_aux_then_calibrate": float(h_both_aux["cost"][-1].sum()),
             "search_with_aux_history_mean": {k: [float(v) for v in h_aux[k].nanmean(1)] for k in ("cost", "score", "score_aux")},
+        }
+
+    if args.fdc_share:
+        picked_fdc, h_fdc = search(model, x, start, obs, names=names, n_candidates=args.candidates, n_rounds=args.rounds,
+                                   generator=torch.Generator().manual_seed(74), objective=args.objective,
+                                   transform=args.transform, fdc_share=args.fdc_share)
+        both_fdc, h_both_fdc = hydrodl2_amd.calibrate(model, x, picked_fdc, obs, names=names, n_iter=args.lm_iters)
+
+        def fdc_freq(row):
+            cand = row[-1][:, cols].unsqueeze(0).contiguous()
+            st = hydrodl2_amd.population_fdc_stats(model, x, row, cand, obs, names=names)
+            return float(hydrodl2_amd.population_fdc_score(st, "fdc_freq").nanmean())
+
+        joint = {
+            "fdc_share": args.fdc_share,
+            "mean_fdc_freq": {"start": fdc_freq(start), "search_flow_only": fdc_freq(picked), "search_with_fdc": fdc_freq(picked_fdc),
+                              "search_flow_only_then_calibrate": fdc_freq(both), "search_with_fdc_then_calibrate": fdc_freq(both_fdc)},
+            "mean_scores_after_search_with_fdc": worth(picked_fdc),
+            "mean_scores_search_with_fdc_then_calibrate": worth(both_fdc),
+            "cost_search_with_fdc_then_calibrate": float(h_both_fdc["cost"][-1].sum()),
+            "search_with_fdc_history_mean": {k: [float(v) for v in h_fdc[k].nanmean(1)] for k in ("cost", "score", "score_fdc")},
         }
 
     c_start, c_lm = h_lm["cost"][0], h_lm["cost"][-1]

@@ -14,6 +14,7 @@ from hydrodl2_amd.calibrate import calibrate, lm_step, normal_equations
 from hydrodl2_amd.uncertainty import covariance_factor, parameter_covariance, predictive_variance
 from hydrodl2_amd.population import (population_cost, population_joint_stats, population_period_stats, population_score,
                                      population_search, population_stats)
+from hydrodl2_amd.population_fdc import population_fdc_score, population_fdc_stats
 from hydrodl2_amd.adj_population import (adj_population_cost, adj_population_period_stats, adj_population_search,
                                          adj_population_stats)
 
@@ -25,6 +26,6 @@ __all__ = ["__version__", "available_models", "available_modules", "load_model",
            "parameter_jacobian", "lstm_jvp_batch", "hourly_jvp_batch", "adj_jvp_batch", "adj_parameter_jacobian",
            "normal_equations", "lm_step", "calibrate", "parameter_covariance", "covariance_factor", "predictive_variance",
            "population_cost", "population_search", "population_stats", "population_score", "population_joint_stats",
-           "population_period_stats",
+           "population_period_stats", "population_fdc_stats", "population_fdc_score",
            "adj_population_cost", "adj_population_stats", "adj_population_period_stats", "adj_population_search",
            "hourly_population_stats", "hourly_population_columns"]

@@ -290,6 +290,27 @@ GAGE_POP_SIGNATURES = [
 ]
 
 
+POP_FDC_ABI_VERSION = 1     # HBVX_POP_FDC_ABI_VERSION
+POP_FDC_MAX_THR = 32        # HBVX_POP_FDC_MAX_THR
+
+
+class PopFdc(C.Structure):
+    """hbvx_pop_fdc: hbvx_pop_stats for the flow, the K thresholds per basin and the [P,K,B] exceedance counts and volumes
+    of hbvx_population_fdc (include/hbvx_pop_fdc.h)."""
+    _fields_ = [("abi_version", C.c_int32), ("n_thr", C.c_int32), ("flow", PopStats), ("thr", _fp),
+                ("count", C.c_void_p),          # int32_t *: an address like the float pointers, of another type
+                ("volume", _fp)]
+
+
+# The exports of include/hbvx_pop_fdc.h, rows as in SIGNATURES (all optional; in neither SIGNATURES nor POPULATION); the
+# layout index is hbvx_pop_fdc_sizeof's.
+POP_FDC_SIGNATURES = [
+    ("hbvx_pop_fdc_sizeof", False, _u64, [_int], None),
+    ("hbvx_population_fdc", False, _int, [_P(Desc), _P(PopFdc), _vp], (0, PopFdc)),
+]
+POP_FDC_ENTRY = PopEntry(PopFdc, False, None)       # what ops.population_fdc needs to know about hbvx_population_fdc
+
+
 # The export of include/hbvx_route_rows.h, a row as in SIGNATURES (optional, no struct of its own).
 ROUTE_ROWS_SIGNATURES = [
     ("hbvx_route_backward_rows", False, _int, [_P(RouteDesc), _fp, _fp, _fp, _fp, _i32, _fp, _fp, _fp, _u64, _vp], None),
@@ -312,13 +333,15 @@ class Library:
         for name in EXPORTS:
             if not hasattr(d, name):
                 raise HbvxError(f"{path}: missing export {name}")
-        self.missing = [name for name in OPTIONAL_EXPORTS + [row[0] for row in GAGE_POP_SIGNATURES + ROUTE_ROWS_SIGNATURES]
+        self.missing = [name for name in OPTIONAL_EXPORTS +
+                        [row[0] for row in GAGE_POP_SIGNATURES + ROUTE_ROWS_SIGNATURES + POP_FDC_SIGNATURES]
                         if not hasattr(d, name)]
         checked = set()             # (sizeof export, index): several exports share a struct
         # the required rows come first, and each table's sizeof export before the rows that name a layout: it is bound by then
         for name, _, restype, argtypes, layout, sizeof in [row + ("hbvx_sizeof",) for row in SIGNATURES] + \
                 [row + ("hbvx_gage_pop_sizeof",) for row in GAGE_POP_SIGNATURES] + \
-                [row + ("hbvx_sizeof",) for row in ROUTE_ROWS_SIGNATURES]:
+                [row + ("hbvx_sizeof",) for row in ROUTE_ROWS_SIGNATURES] + \
+                [row + ("hbvx_pop_fdc_sizeof",) for row in POP_FDC_SIGNATURES]:
             if name in self.missing:
                 continue
             fn = getattr(d, name)
@@ -571,16 +594,19 @@ class Library:
                     "hbvx_route_backward_rows")
 
 
-def _population_method(entry: str):
+def _population_method(entry: str, struct=None):
+    struct = struct or POPULATION[entry].struct
+
     def call(self, desc, args, stream: int):
         self.require(entry)
         self._check(getattr(self.dll, entry)(None if desc is None else C.byref(desc),
                                              None if args is None else C.byref(args), C.c_void_p(stream)), entry)
     call.__name__ = entry[len("hbvx_"):]
-    call.__doc__ = (f"{entry}; `desc` / `args` (its {POPULATION[entry].struct.__name__}) may be None (the ABI's own "
+    call.__doc__ = (f"{entry}; `desc` / `args` (its {struct.__name__}) may be None (the ABI's own "
                     "refusals are under test).")
     return call
 
 
 for _name in POPULATION:        # Library.population_cost(desc, pop, stream) ... Library.adj_population_period(desc, pq, stream)
     setattr(Library, _name[len("hbvx_"):], _population_method(_name))
+Library.population_fdc = _population_method("hbvx_population_fdc", PopFdc)       # (desc, pf, stream)

@@ -10,7 +10,9 @@
 //                           instead of once per day, and the optional series are [P,K,B] period means.
 // One kernel template, k_pop below, is the day loop of all four; launch_pop.hip has the entry points.  A fifth form of
 // it, the runoff form, is stage 1 of the hourly model's population evaluation (hbvx_hourly_population_runoff,
-// include/hbvx_gage_pop.h; launch_gage_pop.hip): the candidate loop alone, storing each candidate's unit runoff.
+// include/hbvx_gage_pop.h; launch_gage_pop.hip): the candidate loop alone, storing each candidate's unit runoff.  A
+// sixth, the FDC form (hbvx_population_fdc, include/hbvx_pop_fdc.h; launch_pop.hip), is the daily stats form with
+// exceedance counts and volumes above per-basin thresholds: the simulated flow-duration curve sampled at K points.
 //
 // What happens to a basin's ensemble mean after the day step -- the normalised gamma unit hydrograph, the 15-day
 // window, the causal convolution and the residual chain -- is hbvx_popk::Basin below and compiles for the host as
@@ -19,6 +21,7 @@
 // hbvx_popk::AuxStats is the aux term's four chains (tests/hosttest/popjoint_host.cpp).
 // hbvx_popk::PeriodMean is the mean over a period that hbvx_population_period puts between each of the two values and
 // its chains (tests/hosttest/popperiod_host.cpp).
+// hbvx_popk::FdcSlot is one threshold's exceedance count and volume (tests/hosttest/popfdc_host.cpp).
 #pragma once
 
 #include <math.h>
@@ -199,6 +202,31 @@ struct AuxStats {
     }
 };
 
+// One threshold of hbvx_population_fdc for one (candidate, basin).  push() takes the days that enter the flow-duration
+// curve in ascending order, with the raw routed flow y (never its transform):
+//   y > thr:   n = n + 1      vol = vol + y          (one float32 addition, in day order)
+// A day at the threshold is not above it; a NaN flow is above nothing; -0 is not above +0.
+struct FdcSlot {
+    uint32_t n;
+    float vol;
+
+    HBVX_POP_HD void start()
+    {
+        n = 0;
+        vol = 0.0f;
+    }
+
+    HBVX_POP_HD void push(float y, float thr)
+    {
+        if (y > thr) {
+            n += 1;
+            vol = vol + y;
+        }
+    }
+};
+
+constexpr int FDC_MAX_THR = 32;     // HBVX_POP_FDC_MAX_THR
+
 } // namespace hbvx_popk
 
 #if defined(__HIPCC__)
@@ -245,19 +273,43 @@ struct PopPeriodArgs {
     const int *flow_end, *aux_end;      // [KF], [KA]: closing days relative to t_first, ascending
 };
 
+// hbvx_population_fdc (include/hbvx_pop_fdc.h): the daily stats form, and per (candidate, threshold, basin) a count and a
+// volume.
+struct PopFdcArgs {
+    PopStatsArgs s;             // hbvx_population_stats' arguments
+    int n_thr;                  // K, 1..hbvx_popk::FDC_MAX_THR
+    const float *thr;           // [K,B]
+    int32_t *count;             // [P,K,B]
+    float *volume;              // [P,K,B]
+};
+
+// The slots of the FDC form per lane, R = ceil(K / Mp), and the dynamic LDS of a launch: [R][threshold, count,
+// volume][64 lanes] of four bytes each.
+__host__ __device__ __forceinline__ int fdc_slots(int n_thr, int lgMp) { return (n_thr + (1 << lgMp) - 1) >> lgMp; }
+__host__ __device__ __forceinline__ unsigned fdc_lds_bytes(int n_thr, int lgMp) { return (unsigned)fdc_slots(n_thr, lgMp) * 64u * 12u; }
+
 // each struct's view of the ones nested in it
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopArgs &A) { return A; }
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopStatsArgs &A) { return A.a; }
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopJointArgs &A) { return A.s.a; }
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopPeriodArgs &A) { return A.j.s.a; }
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopRunoffArgs &A) { return A.a; }
+__host__ __device__ __forceinline__ const PopArgs &pop_args(const PopFdcArgs &A) { return A.s.a; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopStatsArgs &A) { return A; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopJointArgs &A) { return A.s; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopPeriodArgs &A) { return A.j.s; }
+__host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopFdcArgs &A) { return A.s; }
 __host__ __device__ __forceinline__ const PopJointArgs &joint_args(const PopJointArgs &A) { return A; }
 __host__ __device__ __forceinline__ const PopJointArgs &joint_args(const PopPeriodArgs &A) { return A.j; }
 
 constexpr int T_COST = -1;      // TR of the cost-only instances (the others are hbvx_popk::T_*)
+
+// The FDC form's dynamic LDS (fdc_lds_bytes): only its instances name it.
+__device__ __forceinline__ float *fdc_lds()
+{
+    extern __shared__ float fdc_lds_base[];
+    return fdc_lds_base;
+}
 
 template <int TR> struct PopBasin { using type = hbvx_popk::BasinStats; };
 template <> struct PopBasin<T_COST> { using type = hbvx_popk::Basin; };
@@ -306,6 +358,18 @@ template <> struct PopBasin<T_COST> { using type = hbvx_popk::Basin; };
 //   PopRunoffArgs  (RUNOFF) TR = T_COST; Step<MODEL_HOURLY> only: the candidate loop with none of the window or chains.  The
 //                  hour's ensemble mean times 1/24 is the module's Qs, and the unit's leader stores it to [P,T,B]: the score
 //                  of the hourly model lives at the gages, after a sum over units (hbv_gage_pop.h takes it from there).
+//   PopFdcArgs     (FDC) the daily stats form, and K exceedance counters and volumes per basin (hbvx_popk::FdcSlot).  After
+//                  the butterfly all Mp lanes of a basin hold the same y, so the lanes share the thresholds out: lane jm
+//                  owns k = jm, jm + Mp, ... below K -- padded member lanes too, they hold y as well -- which is R =
+//                  ceil(K / Mp) slots per lane, uniform over the launch.  R is a run-time number, so the slots live in
+//                  dynamic LDS, slot-major [R][thr, n, vol][64 lanes]: a lane touches its own column only (no atomics, no
+//                  barrier, no bank conflict; the three planes of a slot are one address and three immediate offsets).  A
+//                  slot beyond K holds thr = +inf and is never stored.  The thresholds are in LDS beside the sums, not
+//                  re-read from memory: a global load per slot and day would put R more vector loads on a loop that
+//                  issue binds, behind the same address arithmetic the LDS column needs once.  A day enters when it is
+//                  counted and its weight is > 0 (the weight is a mask here); the comparison is on y, not its transform.
+//                  Everything of it is behind `if constexpr (FDC)`: the other instances are untouched
+//                  (profiles/r24_population_fdc.md has the comparison).
 // The flow's operations are the same ones on the same values in every form, and the aux term's in both of its forms:
 // tests/test_population_stats_gpu.py, test_population_joint_gpu.py and test_population_period_gpu.py (daily calendars)
 // hold each form to the bits of the one before it.
@@ -329,6 +393,7 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
     constexpr bool STATS = !RUNOFF && !std::is_same<Args, PopArgs>::value;
     constexpr bool PERIOD = std::is_same<Args, PopPeriodArgs>::value;
     constexpr bool JOINT = PERIOD || std::is_same<Args, PopJointArgs>::value;      // the forms with an aux term
+    constexpr bool FDC = std::is_same<Args, PopFdcArgs>::value;
     static_assert(STATS == (TR != T_COST), "TR = T_COST is the cost form's, and its alone");
     constexpr int NP = NParam<MODEL, BETAET>::value;
     const PopArgs &A = pop_args(Q);
@@ -434,6 +499,20 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
             if (awt) pawobs = awt[L.b];
         }
         pf.acc = pa.acc = 0.0f;
+    }
+
+    // FDC: the lane's column of the slots, R of them; slot r is threshold k = jm + r * Mp, +inf from K on
+    float *slot = nullptr;
+    int R = 0;
+    if constexpr (FDC) {
+        R = fdc_slots(Q.n_thr, lgMp);
+        slot = fdc_lds() + (threadIdx.x & 63);
+        for (int r = 0; r < R; r++) {
+            const int k = L.jm + (r << lgMp);
+            slot[r * 192] = k < Q.n_thr ? Q.thr[(int64_t)k * d.B + L.b] : INFINITY;
+            slot[r * 192 + 64] = __uint_as_float(0u);
+            slot[r * 192 + 128] = 0.0f;
+        }
     }
 
     // one-step-ahead register prefetch of the per-step inputs (k_fwd's); in the daily forms the observations and their
@@ -559,6 +638,18 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
             if constexpr (STATS) y = bs.template push<TR>(q, obs, wobs, counted);
             else y = bs.push(q, obs, wobs, counted);
             if (counted && sim && L.leader) sim[(int64_t)(t - t_first) * d.B] = y;      // y, not its transform
+            if constexpr (FDC) {
+                if (counted && wobs > 0.0f) {
+                    for (int r = 0; r < R; r++) {
+                        hbvx_popk::FdcSlot f;
+                        f.n = __float_as_uint(slot[r * 192 + 64]);
+                        f.vol = slot[r * 192 + 128];
+                        f.push(y, slot[r * 192]);
+                        slot[r * 192 + 64] = __uint_as_float(f.n);
+                        slot[r * 192 + 128] = f.vol;
+                    }
+                }
+            }
             if constexpr (JOINT) {
                 if (counted) {
                     ax.push(v, aobs, awobs);
@@ -568,6 +659,20 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
         }
     }
     if constexpr (RUNOFF) return;
+    if constexpr (FDC) {
+        // every lane of a real basin stores the slots it owns (L.b is clamped: the lanes of basins beyond B store nothing)
+        const bool real = (int)blockIdx.x * (64 >> lgMp) + ((int)(threadIdx.x & 63) >> lgMp) < d.B;
+        if (real) {
+            for (int r = 0; r < R; r++) {
+                const int k = L.jm + (r << lgMp);
+                if (k < Q.n_thr) {
+                    const int64_t at = (c * Q.n_thr + k) * d.B + L.b;
+                    Q.count[at] = (int32_t)__float_as_uint(slot[r * 192 + 64]);
+                    Q.volume[at] = slot[r * 192 + 128];
+                }
+            }
+        }
+    }
     if (L.leader) {
         if constexpr (STATS) {
             const int64_t at = c * d.B + L.b;

@@ -1,7 +1,9 @@
 // launch_pop.hip -- the entry points of the population evaluation: hbvx_population_cost, hbvx_population_stats,
-// hbvx_population_joint and hbvx_population_period (hbv_pop.h), and the implicit scheme's hbvx_adj_population_cost,
+// hbvx_population_joint and hbvx_population_period (hbv_pop.h), the flow-duration call hbvx_population_fdc
+// (include/hbvx_pop_fdc.h; k_pop's FDC form), and the implicit scheme's hbvx_adj_population_cost,
 // hbvx_adj_population_stats and hbvx_adj_population_period (hbv_adj_pop.h).
 #include "hbvx_host.h"
+#include "../../include/hbvx_pop_fdc.h"
 #include "hbv_pop.h"
 #define HBVX_CHUNK_NO_SHARED_KERNELS
 #include "hbv_chunked.h"        // (first: hbv_adj_kernels.h uses its XCD-aware block map)
@@ -166,15 +168,16 @@ int launched(const char *who)
     return hip_fail(e, what);
 }
 
-// The explicit models: k_pop's instance for the descriptor's model, TR (T_COST for PopArgs) and the form Args.
+// The explicit models: k_pop's instance for the descriptor's model, TR (T_COST for PopArgs) and the form Args.  lds: the
+// launch's dynamic LDS in bytes (the FDC form's slots; nothing in the others).
 template <int TR, typename Args>
-int launch_pop(const char *who, const Args &args, void *stream)
+int launch_pop(const char *who, const Args &args, void *stream, unsigned lds = 0)
 {
     const PopArgs &a = pop_args(args);
     const dim3 grid = pop_grid(a);
     with_model(&a.d, [&](auto m, auto be) {
         if constexpr (m != MODEL_HOURLY)
-            hipLaunchKernelGGL((k_pop<m, be, TR, Args>), grid, dim3(64), 0, (hipStream_t)stream, args);
+            hipLaunchKernelGGL((k_pop<m, be, TR, Args>), grid, dim3(64), lds, (hipStream_t)stream, args);
     });
     return launched(who);
 }
@@ -251,6 +254,34 @@ extern "C" int hbvx_population_period(const hbvx_desc *d, const hbvx_pop_period 
     rc = prepare_period(who, d, pq, q, false);
     if (rc) return rc;
     return with_transform(pq->joint.flow.transform, [&](auto tr) { return launch_pop<tr>(who, q, stream); });
+}
+
+static_assert(HBVX_POP_FDC_MAX_THR == hbvx_popk::FDC_MAX_THR, "the header's limit and the kernel's");
+
+extern "C" uint64_t hbvx_pop_fdc_sizeof(int which) { return which == 0 ? sizeof(hbvx_pop_fdc) : 0; }
+
+extern "C" int hbvx_population_fdc(const hbvx_desc *d, const hbvx_pop_fdc *pf, void *stream)
+{
+    const char *who = "hbvx_population_fdc";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!pf) return fail_as(who, HBVX_E_NULL, "pf is NULL");
+    if (pf->abi_version != HBVX_POP_FDC_ABI_VERSION) return fail_as(who, HBVX_E_ABI, "pf abi_version mismatch");
+    PopFdcArgs f;
+    rc = prepare(who, d, &pf->flow.pop, f.s.a);        // (refuses HBVX_MODEL_HBVADJ and HBVX_MODEL_HOURLY)
+    if (rc) return rc;
+    rc = prepare_stats(who, &pf->flow, f.s);
+    if (rc) return rc;
+    if (pf->n_thr < 1 || pf->n_thr > HBVX_POP_FDC_MAX_THR) return fail_as(who, HBVX_E_SHAPE, "n_thr must be in 1..32");
+    if (!pf->thr) return fail_as(who, HBVX_E_NULL, "thr is NULL");
+    if (!pf->count || !pf->volume) return fail_as(who, HBVX_E_NULL, "count / volume is NULL");
+    f.n_thr = pf->n_thr;
+    f.thr = pf->thr;
+    f.count = pf->count;
+    f.volume = pf->volume;
+    // at most 32 slots of 768 bytes: 24 KB, under the 64 KB a launch may ask for without an attribute
+    const unsigned lds = fdc_lds_bytes(f.n_thr, f.s.a.lgMp);
+    return with_transform(pf->flow.transform, [&](auto tr) { return launch_pop<tr>(who, f, stream, lds); });
 }
 
 extern "C" int hbvx_adj_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream)

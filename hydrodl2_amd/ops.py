@@ -1115,7 +1115,29 @@ def population(rec: PathRecord, entry: str, cand_sources: dict, route_cands, flo
                   fields None), the others refuse it.  The entries of the implicit scheme take a record of HbvAdjPath
                   only, and their aux series is one of the five solved storages.
     More than POP_MAX_CAND candidates go in several launches; a candidate's bits do not depend on the split."""
-    info = _abi.POPULATION[entry]
+    return _population(rec, entry, _abi.POPULATION[entry], cand_sources, route_cands, flow, aux, t_first, want_sim)[:2]
+
+
+def _out_i32(shape, device) -> torch.Tensor:
+    """`_out` for int32 counts: under HBVX_DEBUG_POISON the fill is -1, which no count can be."""
+    if _POISON:
+        return torch.full(shape, -1, dtype=torch.int32, device=device)
+    return torch.empty(shape, dtype=torch.int32, device=device)
+
+
+def population_fdc(rec: PathRecord, cand_sources: dict, route_cands, flow: PopTerm, thresholds: torch.Tensor,
+                   t_first: int = 0, want_sim: bool = False):
+    """hbvx_population_fdc (include/hbvx_pop_fdc.h) on one recorded call of the path: `population` on
+    hbvx_population_stats -- the same arguments, the same flow_out bit for bit -- and the simulated flow-duration curve at
+    `thresholds`, [K,B] float32 on the device of the record, K in 1.._abi.POP_FDC_MAX_THR, in the units of the flow.
+    Returns (flow_out, (count [P,K,B] int32, volume [P,K,B] float32)): on how many scored days with a weight > 0 the
+    routed flow was above each threshold, and the sum of the flow over those days."""
+    return _population(rec, "hbvx_population_fdc", _abi.POP_FDC_ENTRY, cand_sources, route_cands, flow, None, t_first,
+                       want_sim, thresholds)[::2]
+
+
+def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first, want_sim, thr=None):
+    """`population` / `population_fdc`: (flow_out, aux_out, fdc_out), fdc_out None without `thr`."""
     what = entry[len("hbvx_"):]
     cost_form, period_form = info.struct is _abi.Pop, info.struct is _abi.PopPeriod
     if not cost_form:
@@ -1201,6 +1223,12 @@ def population(rec: PathRecord, entry: str, cand_sources: dict, route_cands, flo
         _check_tensor(lib, t, name)
         if tuple(t.shape) != (B,) or t.device != dev:
             raise ValueError(f"{name} must be [{B}] on {dev}, got {tuple(t.shape)} on {t.device}")
+    if thr is not None:
+        _check_tensor(lib, thr, "thresholds")
+        if thr.dim() != 2 or int(thr.shape[1]) != B or not 1 <= int(thr.shape[0]) <= _abi.POP_FDC_MAX_THR or thr.device != dev:
+            raise ValueError(f"thresholds must be [K,{B}] on {dev} with K in 1..{_abi.POP_FDC_MAX_THR}, got "
+                             f"{tuple(thr.shape)} on {thr.device}")
+        thr = thr.contiguous()
     tc, wc, shc, epc = (None if t is None else t.contiguous() for t in (flow.target, flow.w, shift, eps))
     atc, awc, ashc = (None if t is None else t.contiguous() for t in (aux or no_aux)[:3])
     stream = _stream_of(lib, x)
@@ -1213,6 +1241,10 @@ def population(rec: PathRecord, entry: str, cand_sources: dict, route_cands, flo
         aux_out = None
         if aux is not None:
             aux_out = tuple(_out((P, B), dev) for _ in range(4)) + ((_out((P, rows_a, B), dev) if want_sim else None),)
+        fdc_out = None
+        if thr is not None:
+            K = int(thr.shape[0])
+            fdc_out = (_out_i32((P, K, B), dev), _out((P, K, B), dev))
         for c0 in range(0, P, POP_MAX_CAND):
             args = info.struct()
             pq, pj, ps, pop = _abi.pop_levels(args)
@@ -1244,8 +1276,11 @@ def population(rec: PathRecord, entry: str, cand_sources: dict, route_cands, flo
                 pq.n_flow_periods, pq.flow_end = rows_f, ends[0].data_ptr()
                 if ends[1] is not None:
                     pq.n_aux_periods, pq.aux_end = rows_a, ends[1].data_ptr()
+            if thr is not None:
+                args.abi_version, args.n_thr, args.thr = _abi.POP_FDC_ABI_VERSION, K, _ptr(thr)
+                args.count, args.volume = fdc_out[0].data_ptr() + 4 * c0 * K * B, _ptr(fdc_out[1], c0 * K * B)
             _call(lib, entry, call, desc, args, stream)
-    return (cost,) + moments + (sim,), aux_out
+    return (cost,) + moments + (sim,), aux_out, fdc_out
 
 
 class PathOut(NamedTuple):

@@ -17,6 +17,9 @@ series -- and `population_search(aux_target=...)` minimises a weighted sum of th
 `population_period_stats` is the joint launch against period MEANS -- 8-day composites, months -- on a calendar per
 series (hbvx_population_period): each series is averaged over its periods inside the kernel, the chains take one step
 per period, and `population_search(periods=..., aux_periods=...)` searches on those scores.
+`population_fdc_stats` (population_fdc.py) is `population_stats` with each candidate's flow-duration curve sampled at
+thresholds of the observations (hbvx_population_fdc: exceedance counts and volumes, [P,K,B], still no series), and
+`population_search(fdc_share=...)` mixes a distance between the curves into its objective.
 
 Hbv, Hbv_1_1p and Hbv_2 only.  HbvAdj has the first three calls and a period call of its own in adj_population.py
 (`adj_population_period_stats`: its second series is one of its five storages).  Hbv_2_hourly, whose scores live at
@@ -582,7 +585,8 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
                       n_candidates: int = 256, n_rounds: int = 1, shrink: float = 0.5, weights=None,
                       generator: Optional[torch.Generator] = None, objective: str = 'sse', transform: str = 'none',
                       eps=None, aux_target=None, aux_key: Optional[str] = None, aux_weights=None,
-                      aux_objective: str = 'nse', aux_share: float = 0.5, periods=None, aux_periods=None):
+                      aux_objective: str = 'nse', aux_share: float = 0.5, periods=None, aux_periods=None,
+                      fdc_share: float = 0.0, fdc_probs=None, fdc_metric: str = 'fdc_freq'):
     """Per-basin shrinking random search over the static row, for a start that `calibrate` can refine.
 
     Round 0 evaluates the current row as candidate 0 and n_candidates - 1 uniform draws in the unit interval per
@@ -614,10 +618,19 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
     periods / aux_periods (as `population_period_stats` takes them; either may be given alone, the other is then daily)
     score period means: target, weights, aux_target and aux_weights then hold one row per period, and every round is one
     `population_period_stats` call, with or without an aux term; cost and history are formed as above.  With both None
-    the function is the one above, bit for bit."""
+    the function is the one above, bit for bit.
+
+    fdc_share > 0 adds a flow-duration term (population_fdc.py): every round is one `population_fdc_stats` call at
+    `fdc_probs` (None: its default probabilities), and the quantity minimised, and what history['cost'] holds, is
+    (1 - fdc_share) * cost_flow + fdc_share * fdc_score, with cost_flow = 1 - score under `objective` and fdc_score
+    `population_fdc_score(stats, fdc_metric)` ('fdc_freq' or 'fdc_vol': zero is perfect), +inf where either is
+    undefined; history['score'] and history['score_fdc'] hold the two.  fdc_share in [0, 1].  It goes with objective
+    'nse', 'kge' or 'kge12' on daily streamflow alone: with objective 'sse' the raw cost has no scale to mix with, and
+    with aux_target or periods / aux_periods it is a ValueError.  With fdc_share == 0 (the default) the function is the
+    one above, bit for bit, and hbvx_population_fdc is not touched."""
     return _search_call(EXPLICIT, "population_search", model, x_dict, parameters, target, names, n_candidates, n_rounds,
                         shrink, weights, generator, objective, transform, eps, aux_target, aux_key, aux_weights,
-                        aux_objective, aux_share, periods, aux_periods)
+                        aux_objective, aux_share, periods, aux_periods, fdc_share, fdc_probs, fdc_metric)
 
 
 def _check_mix(objective, aux_objective, aux_share, what):
@@ -633,11 +646,17 @@ def _check_mix(objective, aux_objective, aux_share, what):
 
 def _search_call(family, what, model, x_dict, parameters, target, names, n_candidates, n_rounds, shrink, weights,
                  generator, objective, transform, eps, aux_target, aux_key, aux_weights, aux_objective, aux_share, periods,
-                 aux_periods):
+                 aux_periods, fdc_share=0.0, fdc_probs=None, fdc_metric='fdc_freq'):
     """`population_search` / `adj_population_search`: the checks, the form every round is scored in ('period' with a
     calendar, or an aux term where there is no joint export) and the loop.  The export is required before the first draw."""
     _check_search(model, n_candidates, n_rounds, shrink, objective, what)
     joint = aux_target is not None or aux_key is not None or aux_weights is not None
+    if not 0.0 <= float(fdc_share) <= 1.0:          # (a NaN fails both comparisons)
+        raise ValueError(f"{what}: fdc_share must lie in [0, 1], got {fdc_share!r}")
+    if float(fdc_share) > 0:
+        return _fdc_search(what, model, x_dict, parameters, target, names, n_candidates, n_rounds, shrink, weights,
+                           generator, objective, transform, eps, joint, periods, aux_periods, float(fdc_share), fdc_probs,
+                           fdc_metric)
     if periods is not None or aux_periods is not None or (joint and not family.has_joint):
         form = 'period'
         if joint:
@@ -663,6 +682,32 @@ def _search_call(family, what, model, x_dict, parameters, target, names, n_candi
 
     return _search(rq.req, x_dict, parameters, evaluate, rq.req.tname != 'p_sta', n_candidates, n_rounds, shrink, generator,
                    joint or objective != 'sse', joint)
+
+
+def _fdc_search(what, model, x_dict, parameters, target, names, n_candidates, n_rounds, shrink, weights, generator,
+                objective, transform, eps, joint, periods, aux_periods, fdc_share, fdc_probs, fdc_metric):
+    """`population_search` with fdc_share > 0: its refusals, and the loop on `population_fdc_stats`' numbers."""
+    from . import population_fdc as pf              # (it imports this module)
+    if joint or periods is not None or aux_periods is not None:
+        raise ValueError(f"{what}: fdc_share > 0 goes with daily streamflow alone, not with aux_target or periods / "
+                         "aux_periods")
+    if objective == 'sse':
+        raise ValueError(f"{what}: fdc_share > 0 with objective 'sse' would add a distance between curves to a squared "
+                         "error: the raw cost has no scale to mix with; use 'nse', 'kge' or 'kge12'")
+    if fdc_metric not in pf.FDC_METRICS:
+        raise ValueError(f"{what}: fdc_metric must be one of {list(pf.FDC_METRICS)}, got {fdc_metric!r}")
+    rq, curve = pf._fdc_request(what, model, x_dict, parameters, None, target, names, weights, transform, eps, fdc_probs,
+                                None)
+
+    def evaluate(cands):
+        st = pf._fdc_run(rq._replace(candidates=cands), curve)
+        score = population_score(st, objective)
+        score_fdc = pf.population_fdc_score(st, fdc_metric)
+        cost_fdc = torch.where(torch.isnan(score_fdc), torch.full_like(score_fdc, float('inf')), score_fdc)
+        return _mixed_cost(_objective_cost(score, objective), cost_fdc, fdc_share), (score, score_fdc)
+
+    return _search(rq.req, x_dict, parameters, evaluate, rq.req.tname != 'p_sta', n_candidates, n_rounds, shrink, generator,
+                   True, 'score_fdc')
 
 
 def _mixed_cost(cost_flow: torch.Tensor, cost_aux: torch.Tensor, aux_share: float) -> torch.Tensor:
@@ -691,7 +736,8 @@ def _search(req, x_dict, parameters, evaluate, raw, n_candidates, n_rounds, shri
             two_scores=False):
     """The search loop of `population_search` and `adj_population_search`: `evaluate(cands)` -> (cost, score or None)
     [P,B] is the front end's route to one round's numbers; raw: the module applies a sigmoid to the row.  two_scores:
-    `evaluate` returns the pair (score, score_aux), kept as history['score'] and history['score_aux']."""
+    `evaluate` returns the pair (score, score_aux), kept as history['score'] and history['score_aux'] -- or under the
+    name two_scores itself where it is one ('score_fdc')."""
     two = req.tname == 'p_sta'
     cur = _static_tensor(two, parameters).detach().clone()
     row = cur if two else cur[-1]           # [B,width] view of the row that moves
@@ -702,7 +748,7 @@ def _search(req, x_dict, parameters, evaluate, raw, n_candidates, n_rounds, shri
 
     best = row[:, cols].to(device=dev, dtype=torch.float32)                     # [B,C], input space
     best_u = torch.sigmoid(best) if raw else best.clone()
-    kept = ['score'] * bool(keep_score) + ['score_aux'] * bool(two_scores)
+    kept = ['score'] * bool(keep_score) + [two_scores if isinstance(two_scores, str) else 'score_aux'] * bool(two_scores)
     hist = {'cost': [], 'best_index': [], 'columns': list(req.cols), **{name: [] for name in kept}}
     for k in range(n_rounds):
         draws = torch.rand((n_candidates - 1, req.B, C), generator=generator, device=gdev).to(dev)
