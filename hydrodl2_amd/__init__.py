@@ -19,6 +19,8 @@ from hydrodl2_amd.adj_population import (adj_population_cost, adj_population_per
                                          adj_population_stats)
 
 from hydrodl2_amd.hourly_population import hourly_population_columns, hourly_population_stats
+from hydrodl2_amd.hourly_events import (flood_events, hourly_event_score, hourly_population_event_stats,
+                                        hourly_routing_search)
 
 __version__ = "0.1.0"
 
@@ -28,4 +30,5 @@ __all__ = ["__version__", "available_models", "available_modules", "load_model",
            "population_cost", "population_search", "population_stats", "population_score", "population_joint_stats",
            "population_period_stats", "population_fdc_stats", "population_fdc_score",
            "adj_population_cost", "adj_population_stats", "adj_population_period_stats", "adj_population_search",
-           "hourly_population_stats", "hourly_population_columns"]
+           "hourly_population_stats", "hourly_population_columns", "flood_events", "hourly_population_event_stats",
+           "hourly_event_score", "hourly_routing_search"]

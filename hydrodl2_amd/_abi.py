@@ -290,6 +290,26 @@ GAGE_POP_SIGNATURES = [
 ]
 
 
+GAGE_EVENTS_ABI_VERSION = 1     # HBVX_GAGE_EVENTS_ABI_VERSION
+
+
+class GageEvents(C.Structure):
+    """hbvx_gage_events: the [P,T,G] hourly gage series, the [E,G] event windows and the [P,E,G] peaks, hours of the peak
+    and volumes of hbvx_gage_population_events (include/hbvx_gage_events.h)."""
+    _fields_ = [("abi_version", C.c_int32), ("n_cand", C.c_int32), ("T", C.c_int32), ("G", C.c_int32),
+                ("n_events", C.c_int32), ("series", _fp),
+                ("start", C.c_void_p), ("end", C.c_void_p),     # const int32_t *: addresses like the float pointers
+                ("peak", _fp), ("peak_hour", C.c_void_p), ("volume", _fp)]
+
+
+# The exports of include/hbvx_gage_events.h, rows as in SIGNATURES (all optional); the layout index is
+# hbvx_gage_events_sizeof's.
+GAGE_EVENTS_SIGNATURES = [
+    ("hbvx_gage_events_sizeof", False, _u64, [_int], None),
+    ("hbvx_gage_population_events", False, _int, [_P(GageEvents), _vp], (0, GageEvents)),
+]
+
+
 POP_FDC_ABI_VERSION = 1     # HBVX_POP_FDC_ABI_VERSION
 POP_FDC_MAX_THR = 32        # HBVX_POP_FDC_MAX_THR
 
@@ -334,14 +354,16 @@ class Library:
             if not hasattr(d, name):
                 raise HbvxError(f"{path}: missing export {name}")
         self.missing = [name for name in OPTIONAL_EXPORTS +
-                        [row[0] for row in GAGE_POP_SIGNATURES + ROUTE_ROWS_SIGNATURES + POP_FDC_SIGNATURES]
+                        [row[0] for row in GAGE_POP_SIGNATURES + ROUTE_ROWS_SIGNATURES + POP_FDC_SIGNATURES +
+                         GAGE_EVENTS_SIGNATURES]
                         if not hasattr(d, name)]
         checked = set()             # (sizeof export, index): several exports share a struct
         # the required rows come first, and each table's sizeof export before the rows that name a layout: it is bound by then
         for name, _, restype, argtypes, layout, sizeof in [row + ("hbvx_sizeof",) for row in SIGNATURES] + \
                 [row + ("hbvx_gage_pop_sizeof",) for row in GAGE_POP_SIGNATURES] + \
                 [row + ("hbvx_sizeof",) for row in ROUTE_ROWS_SIGNATURES] + \
-                [row + ("hbvx_pop_fdc_sizeof",) for row in POP_FDC_SIGNATURES]:
+                [row + ("hbvx_pop_fdc_sizeof",) for row in POP_FDC_SIGNATURES] + \
+                [row + ("hbvx_gage_events_sizeof",) for row in GAGE_EVENTS_SIGNATURES]:
             if name in self.missing:
                 continue
             fn = getattr(d, name)
@@ -564,6 +586,12 @@ class Library:
         self._check(self.dll.hbvx_gage_population_stats(None if r is None else C.byref(r),
                                                         None if gp is None else C.byref(gp), ws, C.c_uint64(ws_bytes),
                                                         C.c_void_p(stream)), "hbvx_gage_population_stats")
+
+    def gage_population_events(self, ev, stream: int):
+        """hbvx_gage_population_events; `ev` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_gage_population_events")
+        self._check(self.dll.hbvx_gage_population_events(None if ev is None else C.byref(ev), C.c_void_p(stream)),
+                    "hbvx_gage_population_events")
 
     def lstm_check(self, r: LstmDesc, ws, stream: int):
         self._check(self.dll.hbvx_lstm_check(C.byref(r), ws, C.c_void_p(stream)), "hbvx_lstm_check")

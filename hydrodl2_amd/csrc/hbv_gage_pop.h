@@ -19,6 +19,10 @@
 //                   the candidates supply the parallelism one gage lacks;
 //   k_gp_score      lanes are gages, blockIdx.y the candidate: one ascending pass over the hours of [P,T,G], a PeriodMean
 //                   and the period cursor of k_pop's period form, BasinStats::score<TR> at each close.
+// A fifth kernel works on the series these leave behind:
+//   k_gp_events     hbvx_gage_population_events (include/hbvx_gage_events.h): per (candidate, event, gage) the peak, its
+//                   hour and the volume inside a window of hours fixed on the observed side.  It sits on the [P,T,G]
+//                   series and not inside k_gp_route, whose workgroups own 1024-hour tiles: an event crosses tiles.
 // The statements of hbv_gage.h are restated, not shared: that header defines its kernels (one translation unit may
 // include it), and its kernels' code is pinned.  A change to either belongs in both; tests/test_hourly_population_gpu.py
 // holds the gage series to hbvx_gage_route_forward's bits.
@@ -30,6 +34,7 @@
 
 #include "hbv_step.h"
 #include "../../include/hbvx_gage_pop.h"
+#include "../../include/hbvx_gage_events.h"
 
 namespace hbvx {
 namespace gagepop {
@@ -115,6 +120,69 @@ __global__ void __launch_bounds__(128) k_gp_uh(const Args A)
     const float w0 = (i0 >= 0 && i0 <= L - 1) ? w[i0] / sum : 0.0f;
     const float w1 = (i1 >= 0 && i1 <= L - 1) ? w[i1] / sum : 0.0f;
     dst[k] = (1.0f - f) * w0 + f * w1;
+}
+
+// hbvx_gage_population_events (include/hbvx_gage_events.h): the peak, its hour and the volume of event blockIdx.z's window
+// at gage (blockIdx.x * 64 + lane) in candidate blockIdx.y's series.  Lanes are gages, so a wave's loads are coalesced
+// ([t*G + g]); the wave walks the hours from the smallest start to the largest end among its lanes, both wave-uniform,
+// EV_HOURS at a time into registers so that the serial pass waits on memory once per batch, and each lane pushes the
+// hours of its OWN window into its EventSlot, in ascending order.  A lane reads hours of its wave's span alone, all
+// within 0 .. T-1 whatever start / end hold; an inactive lane of a partial wave reads gage G-1 and stores nothing.
+// (It stands before k_gp_route so that the code of that kernel, the last of this file's plain functions in the object, is
+// byte for byte what it was, the padding behind it included: tools/compare_code.py.)
+constexpr int EV_HOURS = 8;
+
+struct EventArgs {
+    hbvx_gage_events ev;
+    int c0, e0;             // the first candidate and the first event of this launch (launch_gage_pop.hip splits the call
+                            // so that no launch exceeds a grid dimension or 2^32 threads)
+};
+
+__global__ void __launch_bounds__(64) k_gp_events(const EventArgs A)
+{
+    const hbvx_gage_events &ev = A.ev;
+    const int lane = threadIdx.x, G = ev.G, T = ev.T, E = ev.n_events;
+    const int gl = blockIdx.x * 64 + lane;
+    const bool active = gl < G;
+    const int g = active ? gl : G - 1;
+    const int64_t c = A.c0 + blockIdx.y;
+    const int e = A.e0 + blockIdx.z;
+    const int s = ev.start[(int64_t)e * G + g];
+    int f = ev.end[(int64_t)e * G + g];
+    f = f < T - 1 ? f : T - 1;
+    const bool present = active && s >= 0 && f >= s;
+    // the wave's span: present lanes have 0 <= s <= f <= T - 1
+    int lo = present ? s : T, hi = present ? f : -1;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const int ol = __shfl_xor(lo, m), oh = __shfl_xor(hi, m);
+        lo = ol < lo ? ol : lo;
+        hi = oh > hi ? oh : hi;
+    }
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    hi = __builtin_amdgcn_readfirstlane(hi);
+    const float *ser = ev.series + c * (int64_t)T * G + g;
+    hbvx_popk::EventSlot slot;
+    slot.start();
+    for (int tb = lo; tb <= hi; tb += EV_HOURS) {
+        float v[EV_HOURS];
+#pragma unroll
+        for (int i = 0; i < EV_HOURS; i++) {
+            const int t = tb + i <= hi ? tb + i : hi;       // lo <= t <= hi <= T - 1
+            v[i] = ser[(int64_t)t * G];
+        }
+#pragma unroll
+        for (int i = 0; i < EV_HOURS; i++) {
+            const int t = tb + i;
+            if (present && t >= s && t <= f) slot.push(v[i], t);
+        }
+    }
+    if (active) {
+        const int64_t at = (c * E + e) * (int64_t)G + g;
+        ev.peak[at] = slot.peak;
+        ev.peak_hour[at] = slot.hour;
+        ev.volume[at] = slot.vol;
+    }
 }
 
 // series[c][t][g] for the tile blockIdx.x, the gage blockIdx.y, the candidate blockIdx.z.

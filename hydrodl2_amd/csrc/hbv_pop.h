@@ -22,6 +22,8 @@
 // hbvx_popk::PeriodMean is the mean over a period that hbvx_population_period puts between each of the two values and
 // its chains (tests/hosttest/popperiod_host.cpp).
 // hbvx_popk::FdcSlot is one threshold's exceedance count and volume (tests/hosttest/popfdc_host.cpp).
+// hbvx_popk::EventSlot is one flood event's peak, hour of the peak and volume (hbvx_gage_population_events,
+// include/hbvx_gage_events.h; tests/hosttest/gageevents_host.cpp).
 #pragma once
 
 #include <math.h>
@@ -226,6 +228,33 @@ struct FdcSlot {
 };
 
 constexpr int FDC_MAX_THR = 32;     // HBVX_POP_FDC_MAX_THR
+
+// One event window of hbvx_gage_population_events for one (candidate, gage).  push() takes the hours of the window in
+// ascending order, with the hourly gage flow y and the hour t:
+//   y > peak:  peak = y, hour = t          vol = vol + y   (one float32 addition per hour, in hour order)
+// A plateau keeps its first hour; a NaN flow is above nothing (it leaves peak and hour alone and poisons vol); -0 is not
+// above +0.  A slot that is pushed nothing stays at -inf, -1, +0: the absent event.
+struct EventSlot {
+    float peak;
+    int32_t hour;
+    float vol;
+
+    HBVX_POP_HD void start()
+    {
+        peak = -INFINITY;
+        hour = -1;
+        vol = 0.0f;
+    }
+
+    HBVX_POP_HD void push(float y, int32_t t)
+    {
+        if (y > peak) {
+            peak = y;
+            hour = t;
+        }
+        vol = vol + y;
+    }
+};
 
 } // namespace hbvx_popk
 

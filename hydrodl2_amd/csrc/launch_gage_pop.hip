@@ -1,5 +1,6 @@
 // launch_gage_pop.hip -- the entry points of the hourly model's population evaluation (include/hbvx_gage_pop.h):
-// hbvx_hourly_population_runoff (k_pop's runoff form, hbv_pop.h) and hbvx_gage_population_stats (hbv_gage_pop.h).
+// hbvx_hourly_population_runoff (k_pop's runoff form, hbv_pop.h) and hbvx_gage_population_stats (hbv_gage_pop.h), and of
+// the event statistics on the latter's series (include/hbvx_gage_events.h): hbvx_gage_population_events (k_gp_events).
 #include "hbvx_host.h"
 #include "hbv_gage_pop.h"
 
@@ -56,6 +57,19 @@ int check_gage_pop(const char *who, const hbvx_gage_desc *r, const hbvx_gage_pop
     if (!gp->shift) return fail_as(who, HBVX_E_NULL, "shift is NULL");
     if (gp->transform == HBVX_POP_T_LOG && !gp->eps) return fail_as(who, HBVX_E_NULL, "eps is NULL under HBVX_POP_T_LOG");
     if (!gp->sse || !gp->s1 || !gp->s2 || !gp->s3) return fail_as(who, HBVX_E_NULL, "sse / s1 / s2 / s3 is NULL");
+    return HBVX_OK;
+}
+
+int check_gage_events(const char *who, const hbvx_gage_events *ev)
+{
+    if (!ev) return fail_as(who, HBVX_E_NULL, "ev is NULL");
+    if (ev->abi_version != HBVX_GAGE_EVENTS_ABI_VERSION) return fail_as(who, HBVX_E_ABI, "ev abi_version mismatch");
+    if (ev->n_cand < 1 || ev->n_cand > 65535) return fail_as(who, HBVX_E_SHAPE, "n_cand must be in 1..65535");
+    if (ev->T < 1 || ev->G < 1) return fail_as(who, HBVX_E_SHAPE, "bad T/G");
+    if (ev->n_events < 1 || ev->n_events > ev->T) return fail_as(who, HBVX_E_SHAPE, "n_events must be in 1..T");
+    if (!ev->series) return fail_as(who, HBVX_E_NULL, "series is NULL");
+    if (!ev->start || !ev->end) return fail_as(who, HBVX_E_NULL, "start / end is NULL");
+    if (!ev->peak || !ev->peak_hour || !ev->volume) return fail_as(who, HBVX_E_NULL, "peak / peak_hour / volume is NULL");
     return HBVX_OK;
 }
 
@@ -148,5 +162,33 @@ extern "C" int hbvx_gage_population_stats(const hbvx_gage_desc *r, const hbvx_ga
     case HBVX_POP_T_LOG: hipLaunchKernelGGL(gagepop::k_gp_score<hbvx_popk::T_LOG>, sgrid, dim3(64), 0, st, a); break;
     default: hipLaunchKernelGGL(gagepop::k_gp_score<hbvx_popk::T_NONE>, sgrid, dim3(64), 0, st, a); break;
     }
+    return launched(who);
+}
+
+extern "C" uint64_t hbvx_gage_events_sizeof(int which)
+{
+    return which == 0 ? sizeof(hbvx_gage_events) : 0;
+}
+
+extern "C" int hbvx_gage_population_events(const hbvx_gage_events *ev, void *stream)
+{
+    const char *who = "hbvx_gage_population_events";
+    int rc = check_gage_events(who, ev);
+    if (rc) return rc;
+    gagepop::EventArgs a;
+    a.ev = *ev;
+    // A launch holds at most 65535 candidates and events (grid dimensions) and fewer than 2^32 threads: (candidates x
+    // events) of one launch are bounded by what the gage groups leave of that, and the call is split on both axes.
+    const uint64_t gx = ((uint64_t)ev->G + 63) / 64;
+    const uint64_t budget = 0xFFFFFFFFull / (gx * 64);          // >= 1: G is an int32
+    const int pc = (uint64_t)ev->n_cand < budget ? ev->n_cand : (int)budget;
+    const uint64_t per = budget / (uint64_t)pc;
+    const int ec = per < 65535 ? (int)per : 65535;              // >= 1
+    for (a.c0 = 0; a.c0 < ev->n_cand; a.c0 += pc)
+        for (a.e0 = 0; a.e0 < ev->n_events; a.e0 += ec) {
+            const int np = ev->n_cand - a.c0 < pc ? ev->n_cand - a.c0 : pc;
+            const int ne = ev->n_events - a.e0 < ec ? ev->n_events - a.e0 : ec;
+            hipLaunchKernelGGL(gagepop::k_gp_events, dim3((unsigned)gx, np, ne), dim3(64), 0, (hipStream_t)stream, a);
+        }
     return launched(who);
 }

@@ -12,9 +12,10 @@ ONCE at `parameters`; then, per chunk of candidates,
 
 Candidates come in two families: `candidates`, columns of the static physical parameters per unit, and
 `distr_candidates`, route_a / route_b / route_tau per (gage, unit) pair -- a family that only a search reaches.  The
-generic `population_*` calls keep refusing the model.  Not built: a search on top (a routing-only search is separable per
-gage and is the natural next step), a second observed series, cache_states, the per-unit 72-tap routing, per-gage
-calendars, and everything for Hbv_2_mts.
+generic `population_*` calls keep refusing the model.  hourly_events.py builds on this call: flood-event statistics of
+every candidate at the gages, and the routing-only search (`hourly_routing_search`), which is separable per gage.  Not
+built: a search over the unit parameters (gages share units: there is no per-gage selection), a second observed series,
+cache_states, the per-unit 72-tap routing, per-gage calendars, and everything for Hbv_2_mts.
 """
 from __future__ import annotations
 
@@ -142,6 +143,20 @@ def hourly_population_stats(model, x_dict: dict, parameters, target, candidates:
     cache_states=True, routing=True, use_distr_routing=False, dynamic or unknown names, a wrong shape / dtype / device of
     any tensor, infinite targets, negative or non-finite weights, a calendar `population_period_stats` would refuse,
     max_candidates < 1 (ValueError); a library without the exports (HbvxError naming the missing one)."""
+    return _evaluate(model, x_dict, parameters, target, candidates, distr_candidates, names, weights, periods, transform,
+                     eps, return_series, max_candidates)
+
+
+def _evaluate(model, x_dict, parameters, target, candidates, distr_candidates, names, weights, periods, transform, eps,
+              return_series, max_candidates, hook=None) -> dict:
+    """The body of `hourly_population_stats`, and of the calls that want more of a chunk's hourly gage series than its
+    four sums (hourly_events.py).  `hook`, if given, has
+      check(T, G, dev)   the caller's own refusals, after this call's and before the library is asked or the model runs;
+      exports            the exports it needs beyond EXPORTS;
+      bytes              what it writes per candidate;
+      chunk(series)      called once per chunk of candidates with that chunk's [p,T,G] series, before the next chunk
+                         overwrites the scratch the series came with.
+    Without a hook the series stays in the export's own scratch, and the launches are what they were."""
     _check_model(model)
     x = x_dict['x_phy']
     dev = x.device
@@ -176,8 +191,10 @@ def hourly_population_stats(model, x_dict: dict, parameters, target, candidates:
     _check_rows(gages, x_dict, target, weights, K, f"{K} periods of its calendar" if periods is not None else "hours of the record",
                 WHAT)
     ob = _observations(gages, x_dict, target, weights, transform, eps, WHAT, rows=K)
+    if hook is not None:
+        hook.check(T, G, dev)
     lib = get_library()
-    for name in EXPORTS:
+    for name in EXPORTS + (() if hook is None else tuple(hook.exports)):
         lib.require(name)
 
     with torch.no_grad(), ops.record_paths() as records, ops.record_gage_routes() as routes:
@@ -192,6 +209,8 @@ def hourly_population_stats(model, x_dict: dict, parameters, target, candidates:
     dcands = None if distr_candidates is None else distr_candidates.detach().contiguous()
     per = 4 * ((2 * T * U if cands is not None else 0) + T * G + (n_pair * min(T, _abi.GAGE_MAXLEN) if dcands is not None else 0)
                + (K * G if return_series else 0))
+    if hook is not None:
+        per += 4 * T * G + int(hook.bytes)      # the [p,T,G] series is then an output of its own, beside the scratch
     chunk = max_candidates or _default_chunk(P, per, dev)
     parts = []
     for c0, c1 in direction_chunks(P, chunk):
@@ -200,8 +219,11 @@ def hourly_population_stats(model, x_dict: dict, parameters, target, candidates:
             runoff = ops.hourly_population_runoff(main, {slot: (piece, col) for slot, col in sources.items()}, c1 - c0)
         else:
             runoff = grec.qs            # the primal run's own [T,U] runoff serves every candidate
-        parts.append(ops.gage_population(grec, runoff, None if dcands is None else dcands[c0:c1], term, ends_dev,
-                                         return_series)[:5])
+        got = ops.gage_population(grec, runoff, None if dcands is None else dcands[c0:c1], term, ends_dev, return_series,
+                                  want_gage=hook is not None)
+        parts.append(got[:5])
+        if hook is not None:
+            hook.chunk(got[5])
     got = [None if parts[0][i] is None else (parts[0][i] if len(parts) == 1 else torch.cat([p[i] for p in parts]))
            for i in range(5)]
     out = dict(zip(('sse', 's1', 's2', 's3'), got[:4]))

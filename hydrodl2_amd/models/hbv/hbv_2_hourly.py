@@ -126,6 +126,17 @@ class Hbv_2_hourly(HbvModule):
         return hourly_population_stats(self, x_dict, parameters, target, candidates, distr_candidates, names, weights,
                                        periods, transform, eps, return_series, max_candidates)
 
+    def population_event_stats(self, x_dict: dict[str, torch.Tensor], parameters, target, events, candidates=None,
+                               distr_candidates=None, names=None, weights=None, periods=None, transform: str = 'none',
+                               eps=None, return_series: bool = False, max_candidates: Optional[int] = None,
+                               event_target=None):
+        """`population_stats` plus every candidate's peak, hour of the peak and volume in flood-event windows at the
+        gages: hydrodl2_amd.hourly_population_event_stats(self, ...), see there."""
+        from hydrodl2_amd.hourly_events import hourly_population_event_stats
+        return hourly_population_event_stats(self, x_dict, parameters, target, events, candidates, distr_candidates,
+                                             names, weights, periods, transform, eps, return_series, max_candidates,
+                                             event_target)
+
     def _topology(self, tag, outlet_topo, areas, T, lag, bounds):
         """GageTopology of (outlet_topo, areas), built once per pair of tensor objects + versions: building it
         costs a `nonzero` (a host synchronisation) and a handful of small kernels per call, and cannot be captured

@@ -1665,6 +1665,43 @@ def gage_population(grec: GageRecord, runoff: torch.Tensor, distr_cands: Optiona
     return sums + (sim, gage)
 
 
+def gage_events(series: torch.Tensor, starts: torch.Tensor, ends: torch.Tensor):
+    """The peak, the hour of the peak and the volume of every candidate's hourly gage series inside E event windows per
+    gage (include/hbvx_gage_events.h), through hbvx_gage_population_events on the current stream.
+    series        [P,T,G] float32 contiguous: `gage_population`'s series (want_gage=True).
+    starts, ends  [E,G] int32 contiguous on the series' device: inclusive hours, 0-based; start < 0 or end < start is an
+                  absent slot, end is clamped to T - 1 -- any content is safe.
+    Returns (peak [P,E,G] float32, peak_hour [P,E,G] int32, volume [P,E,G] float32); an absent slot holds -inf, -1, +0."""
+    lib = get_library()
+    lib.require('hbvx_gage_population_events')
+    _check_tensor(lib, series, "series")
+    dev = series.device
+    if series.dim() != 3 or not series.is_contiguous() or min(series.shape) < 1:
+        raise ValueError(f"series must be a contiguous [P,T,G] tensor, got {tuple(series.shape)}")
+    P, T, G = (int(n) for n in series.shape)
+    for name, t in (("starts", starts), ("ends", ends)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32:
+            raise TypeError(f"{name} must be an int32 tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+        if t.dim() != 2 or int(t.shape[1]) != G or not 1 <= int(t.shape[0]) <= T or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous [E,{G}] tensor of 1..{T} events on {dev}, got {tuple(t.shape)} "
+                             f"on {t.device}")
+    if tuple(starts.shape) != tuple(ends.shape):
+        raise ValueError(f"starts is {tuple(starts.shape)}, ends {tuple(ends.shape)}")
+    E = int(starts.shape[0])
+    stream = _stream_of(lib, series)
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        peak, hour, volume = _out((P, E, G), dev), _out_i32((P, E, G), dev), _out((P, E, G), dev)
+        if _POISON:
+            hour.fill_(-2 ** 31)        # (-1, _out_i32's fill, is what an absent slot holds)
+        for c0 in range(0, P, POP_MAX_CAND):
+            ev = _abi.GageEvents(abi_version=_abi.GAGE_EVENTS_ABI_VERSION, n_cand=min(POP_MAX_CAND, P - c0), T=T, G=G,
+                                 n_events=E, series=_ptr(series, c0 * T * G), start=starts.data_ptr(), end=ends.data_ptr(),
+                                 peak=_ptr(peak, c0 * E * G), peak_hour=_ptr(hour, c0 * E * G),
+                                 volume=_ptr(volume, c0 * E * G))
+            _call(lib, 'hbvx_gage_population_events', lib.gage_population_events, ev, stream)
+    return peak, hour, volume
+
+
 @dataclass
 class GageTopology:
     """Index arrays of the (gage, unit) pairs of `outlet_topo == 1` (hbv_2_hourly.py:813-817), in
