@@ -14,6 +14,7 @@ wide).  Two routes from that start, both per basin:
                                         [--aux-key AET_hydro|SWE|srflow_no_rout|ssflow_no_rout|gwflow_no_rout |
                                                    SNOWPACK|MELTWATER|SM|SUZ|SLZ (HbvAdj)] [--aux-share 0.5]
                                         [--aux-period N] [--fdc-share S]
+                                        [--event-share S] [--event-metric peak_error|peak_bias|peak_timing|volume_error]
 
 --model HbvAdj runs the same experiment on the implicit scheme: adj_population_search (hbvx_adj_population_cost: every
 candidate's days solved in registers) in front of calibrate, scored on 'flow_sim', from the module's own start (empty
@@ -37,6 +38,13 @@ observation go through hbvx_adj_population_period.
 probabilities (hbvx_population_fdc: the exceedance counts of every candidate from the launch that scores its flow), in
 front of the same Levenberg-Marquardt.  The line then carries the basin-mean fdc_freq at the start and at the end of the
 search with and without the term, beside the SSE / NSE / KGE of both.
+--event-share S (Hbv, with --objective nse / kge / kge12, without --aux-key or --fdc-share) adds a route: the search on
+(1 - S) * flow cost + S * the --event-metric score (default peak_error) over the ten highest separated floods of the
+observations per basin, windows from three days before the observed peak to seven after (flood_events;
+hbvx_population_events: every candidate's peak, day of the peak and volume in each window from the launch that scores
+its flow), in front of the same Levenberg-Marquardt.  The line then carries the basin means of all four event scores at
+the start and at the end of the search with and without the term, beside the SSE / NSE / KGE of both.  One seed: read a
+difference between the two searches as one draw, not as a ranking.
 Prints one JSON line: per route the summed cost and the number of basins in which it ended lower, with the cost of
 the start and of the search's pick beside them, and -- whichever objective was searched -- the basin means of SSE, NSE
 and KGE on the raw flow at the start and at the end of every route.  Synthetic forcings (tests/synth.py), a fixed seed.
@@ -79,7 +87,14 @@ def main():
                     help="observe the aux series as N-day means of the hidden row instead of every 8th day")
     ap.add_argument("--fdc-share", type=float, default=0.0,
                     help="also search on (1 - S) * flow cost + S * fdc_freq, the distance between the flow-duration curves")
+    ap.add_argument("--event-share", type=float, default=0.0,
+                    help="also search on (1 - S) * flow cost + S * an event score over the observed floods")
+    ap.add_argument("--event-metric", default="peak_error", choices=list(hydrodl2_amd.population_events.EVENT_METRICS))
     args = ap.parse_args()
+    if args.event_share and (args.model != "Hbv" or args.objective == "sse" or args.aux_key or args.fdc_share
+                             or not 0 < args.event_share <= 1):
+        ap.error("--event-share S in (0, 1] goes with --model Hbv and --objective nse, kge or kge12, without --aux-key "
+                 "or --fdc-share")
     if args.fdc_share and (args.model != "Hbv" or args.objective == "sse" or args.aux_key or not 0 < args.fdc_share <= 1):
         ap.error("--fdc-share S in (0, 1] goes with --model Hbv and --objective nse, kge or kge12, without --aux-key")
     if args.aux_period is not None and (not args.aux_key or args.aux_period < 1):
@@ -195,6 +210,34 @@ def main():
             "mean_scores_search_with_fdc_then_calibrate": worth(both_fdc),
             "cost_search_with_fdc_then_calibrate": float(h_both_fdc["cost"][-1].sum()),
             "search_with_fdc_history_mean": {k: [float(v) for v in h_fdc[k].nanmean(1)] for k in ("cost", "score", "score_fdc")},
+        }
+
+    if args.event_share:
+        events = hydrodl2_amd.flood_events(obs, 10, 3, 7)
+        picked_ev, h_ev = search(model, x, start, obs, names=names, n_candidates=args.candidates, n_rounds=args.rounds,
+                                 generator=torch.Generator().manual_seed(74), objective=args.objective,
+                                 transform=args.transform, events=events, event_share=args.event_share,
+                                 event_metric=args.event_metric)
+        both_ev, h_both_ev = hydrodl2_amd.calibrate(model, x, picked_ev, obs, names=names, n_iter=args.lm_iters)
+
+        def event_scores(row):
+            cand = row[-1][:, cols].unsqueeze(0).contiguous()
+            st = hydrodl2_amd.population_event_stats(model, x, row, cand, obs, events, names=names)
+            return {m: float(hydrodl2_amd.population_event_score(st, m).nanmean())
+                    for m in hydrodl2_amd.population_events.EVENT_METRICS}
+
+        joint = {
+            "event_share": args.event_share, "event_metric": args.event_metric,
+            "events_per_basin_mean": float((events[0] >= 0).sum(0).double().mean()),
+            "mean_event_scores": {"start": event_scores(start), "search_flow_only": event_scores(picked),
+                                  "search_with_events": event_scores(picked_ev),
+                                  "search_flow_only_then_calibrate": event_scores(both),
+                                  "search_with_events_then_calibrate": event_scores(both_ev)},
+            "mean_scores_after_search_with_events": worth(picked_ev),
+            "mean_scores_search_with_events_then_calibrate": worth(both_ev),
+            "cost_search_with_events_then_calibrate": float(h_both_ev["cost"][-1].sum()),
+            "search_with_events_history_mean": {k: [float(v) for v in h_ev[k].nanmean(1)]
+                                                for k in ("cost", "score", "score_event")},
         }
 
     c_start, c_lm = h_lm["cost"][0], h_lm["cost"][-1]

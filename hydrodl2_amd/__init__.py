@@ -18,6 +18,7 @@ from hydrodl2_amd.population_fdc import population_fdc_score, population_fdc_sta
 from hydrodl2_amd.adj_population import (adj_population_cost, adj_population_period_stats, adj_population_search,
                                          adj_population_stats)
 
+from hydrodl2_amd.population_events import population_event_score, population_event_stats
 from hydrodl2_amd.hourly_population import hourly_population_columns, hourly_population_stats
 from hydrodl2_amd.hourly_events import (flood_events, hourly_event_score, hourly_population_event_stats,
                                         hourly_routing_search)
@@ -28,7 +29,8 @@ __all__ = ["__version__", "available_models", "available_modules", "load_model",
            "parameter_jacobian", "lstm_jvp_batch", "hourly_jvp_batch", "adj_jvp_batch", "adj_parameter_jacobian",
            "normal_equations", "lm_step", "calibrate", "parameter_covariance", "covariance_factor", "predictive_variance",
            "population_cost", "population_search", "population_stats", "population_score", "population_joint_stats",
-           "population_period_stats", "population_fdc_stats", "population_fdc_score",
+           "population_period_stats", "population_fdc_stats", "population_fdc_score", "population_event_stats",
+           "population_event_score",
            "adj_population_cost", "adj_population_stats", "adj_population_period_stats", "adj_population_search",
            "hourly_population_stats", "hourly_population_columns", "flood_events", "hourly_population_event_stats",
            "hourly_event_score", "hourly_routing_search"]

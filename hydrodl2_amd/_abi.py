@@ -331,6 +331,26 @@ POP_FDC_SIGNATURES = [
 POP_FDC_ENTRY = PopEntry(PopFdc, False, None)       # what ops.population_fdc needs to know about hbvx_population_fdc
 
 
+POP_EVENTS_ABI_VERSION = 1  # HBVX_POP_EVENTS_ABI_VERSION
+
+
+class PopEvents(C.Structure):
+    """hbvx_pop_events: hbvx_pop_stats for the flow, the [E,B] event windows in scored days and the [P,E,B] peaks, days
+    of the peak and volumes of hbvx_population_events (include/hbvx_pop_events.h)."""
+    _fields_ = [("abi_version", C.c_int32), ("n_events", C.c_int32), ("flow", PopStats),
+                ("start", C.c_void_p), ("end", C.c_void_p),     # const int32_t *: addresses like the float pointers
+                ("peak", _fp), ("peak_day", C.c_void_p), ("volume", _fp)]
+
+
+# The exports of include/hbvx_pop_events.h, rows as in SIGNATURES (all optional; in neither SIGNATURES nor POPULATION, as
+# POP_FDC_SIGNATURES); the layout index is hbvx_pop_events_sizeof's.
+POP_EVENTS_SIGNATURES = [
+    ("hbvx_pop_events_sizeof", False, _u64, [_int], None),
+    ("hbvx_population_events", False, _int, [_P(Desc), _P(PopEvents), _vp], (0, PopEvents)),
+]
+POP_EVENTS_ENTRY = PopEntry(PopEvents, False, None)     # what ops.population_events needs to know about the export
+
+
 # The export of include/hbvx_route_rows.h, a row as in SIGNATURES (optional, no struct of its own).
 ROUTE_ROWS_SIGNATURES = [
     ("hbvx_route_backward_rows", False, _int, [_P(RouteDesc), _fp, _fp, _fp, _fp, _i32, _fp, _fp, _fp, _u64, _vp], None),
@@ -355,7 +375,7 @@ class Library:
                 raise HbvxError(f"{path}: missing export {name}")
         self.missing = [name for name in OPTIONAL_EXPORTS +
                         [row[0] for row in GAGE_POP_SIGNATURES + ROUTE_ROWS_SIGNATURES + POP_FDC_SIGNATURES +
-                         GAGE_EVENTS_SIGNATURES]
+                         GAGE_EVENTS_SIGNATURES + POP_EVENTS_SIGNATURES]
                         if not hasattr(d, name)]
         checked = set()             # (sizeof export, index): several exports share a struct
         # the required rows come first, and each table's sizeof export before the rows that name a layout: it is bound by then
@@ -363,7 +383,8 @@ class Library:
                 [row + ("hbvx_gage_pop_sizeof",) for row in GAGE_POP_SIGNATURES] + \
                 [row + ("hbvx_sizeof",) for row in ROUTE_ROWS_SIGNATURES] + \
                 [row + ("hbvx_pop_fdc_sizeof",) for row in POP_FDC_SIGNATURES] + \
-                [row + ("hbvx_gage_events_sizeof",) for row in GAGE_EVENTS_SIGNATURES]:
+                [row + ("hbvx_gage_events_sizeof",) for row in GAGE_EVENTS_SIGNATURES] + \
+                [row + ("hbvx_pop_events_sizeof",) for row in POP_EVENTS_SIGNATURES]:
             if name in self.missing:
                 continue
             fn = getattr(d, name)
@@ -638,3 +659,4 @@ def _population_method(entry: str, struct=None):
 for _name in POPULATION:        # Library.population_cost(desc, pop, stream) ... Library.adj_population_period(desc, pq, stream)
     setattr(Library, _name[len("hbvx_"):], _population_method(_name))
 Library.population_fdc = _population_method("hbvx_population_fdc", PopFdc)       # (desc, pf, stream)
+Library.population_events = _population_method("hbvx_population_events", PopEvents)     # (desc, pe, stream)

@@ -12,7 +12,9 @@
 // it, the runoff form, is stage 1 of the hourly model's population evaluation (hbvx_hourly_population_runoff,
 // include/hbvx_gage_pop.h; launch_gage_pop.hip): the candidate loop alone, storing each candidate's unit runoff.  A
 // sixth, the FDC form (hbvx_population_fdc, include/hbvx_pop_fdc.h; launch_pop.hip), is the daily stats form with
-// exceedance counts and volumes above per-basin thresholds: the simulated flow-duration curve sampled at K points.
+// exceedance counts and volumes above per-basin thresholds: the simulated flow-duration curve sampled at K points.  A
+// seventh, the event form (hbvx_population_events, include/hbvx_pop_events.h; launch_pop.hip), is the daily stats form
+// with the peak, the day of the peak and the volume inside per-basin event windows of scored days.
 //
 // What happens to a basin's ensemble mean after the day step -- the normalised gamma unit hydrograph, the 15-day
 // window, the causal convolution and the residual chain -- is hbvx_popk::Basin below and compiles for the host as
@@ -23,7 +25,8 @@
 // its chains (tests/hosttest/popperiod_host.cpp).
 // hbvx_popk::FdcSlot is one threshold's exceedance count and volume (tests/hosttest/popfdc_host.cpp).
 // hbvx_popk::EventSlot is one flood event's peak, hour of the peak and volume (hbvx_gage_population_events,
-// include/hbvx_gage_events.h; tests/hosttest/gageevents_host.cpp).
+// include/hbvx_gage_events.h; tests/hosttest/gageevents_host.cpp); the event form of k_pop feeds the same slot days.
+// hbvx_popk::EventCursor is that form's walk over a basin's window rows (tests/hosttest/popevents_host.cpp).
 #pragma once
 
 #include <math.h>
@@ -256,6 +259,41 @@ struct EventSlot {
     }
 };
 
+// The walk of hbvx_population_events over one basin's E window rows (include/hbvx_pop_events.h states the rule): rows are
+// offered in order e = 0, 1, ... through admit(); [ws, we] is the live window in scored days, and `we` doubles as the last
+// day any live window took (-1 before the first), so a row is live iff its start is beyond it and its clamped end is not
+// before its start.  Between live windows, and after the last, ws is INT32_MAX: inside() is false on every day.
+//   admit(s, f, T_out):  f = min(f, T_out - 1);  live = s > we && f >= s;  live: ws = s, we = f
+// The caller steps e past every row it offers, live (when the window closes) or absent (at once), so a basin takes E
+// steps whatever the rows hold, and no day outside 0 .. T_out - 1 is ever inside.
+struct EventCursor {
+    int32_t e, ws, we;
+
+    HBVX_POP_HD void start()
+    {
+        e = 0;
+        ws = INT32_MAX;
+        we = -1;
+    }
+
+    HBVX_POP_HD bool admit(int32_t s, int32_t f, int32_t T_out)
+    {
+        f = f < T_out - 1 ? f : T_out - 1;
+        const bool live = s > we && f >= s;
+        if (live) {
+            ws = s;
+            we = f;
+        }
+        return live;
+    }
+
+    HBVX_POP_HD void rest() { ws = INT32_MAX; }         // no live window: between two, and behind the last row
+
+    HBVX_POP_HD bool inside(int32_t rel) const { return rel >= ws && rel <= we; }
+
+    HBVX_POP_HD bool closes(int32_t rel) const { return rel == we; }      // (asked on a day that is inside)
+};
+
 } // namespace hbvx_popk
 
 #if defined(__HIPCC__)
@@ -312,6 +350,22 @@ struct PopFdcArgs {
     float *volume;              // [P,K,B]
 };
 
+// hbvx_population_events (include/hbvx_pop_events.h): the daily stats form, and per (candidate, event, basin) a peak, its
+// day and a volume.
+struct PopEventArgs {
+    PopStatsArgs s;             // hbvx_population_stats' arguments
+    int n_events;               // E, 1..T - t_first
+    const int32_t *start, *end; // [E,B] inclusive scored days
+    float *peak;                // [P,E,B]
+    int32_t *peak_day;          // [P,E,B]
+    float *volume;              // [P,E,B]
+};
+
+// The event form addresses a basin's rows of start / end and of a candidate's [E,B] outputs with a 32-bit element index,
+// e * B + b (the launcher refuses E * B beyond this): a scalar base and a per-lane 32-bit offset.  With 64-bit per-lane
+// addresses the compiler hoists five of them out of the day loop, ten VGPRs, and HBV 1.1p drops to two waves per SIMD.
+constexpr int64_t EVENT_MAX_CELLS = (int64_t)1 << 30;
+
 // The slots of the FDC form per lane, R = ceil(K / Mp), and the dynamic LDS of a launch: [R][threshold, count,
 // volume][64 lanes] of four bytes each.
 __host__ __device__ __forceinline__ int fdc_slots(int n_thr, int lgMp) { return (n_thr + (1 << lgMp) - 1) >> lgMp; }
@@ -324,10 +378,12 @@ __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopJointArgs &
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopPeriodArgs &A) { return A.j.s.a; }
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopRunoffArgs &A) { return A.a; }
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopFdcArgs &A) { return A.s.a; }
+__host__ __device__ __forceinline__ const PopArgs &pop_args(const PopEventArgs &A) { return A.s.a; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopStatsArgs &A) { return A; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopJointArgs &A) { return A.s; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopPeriodArgs &A) { return A.j.s; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopFdcArgs &A) { return A.s; }
+__host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopEventArgs &A) { return A.s; }
 __host__ __device__ __forceinline__ const PopJointArgs &joint_args(const PopJointArgs &A) { return A; }
 __host__ __device__ __forceinline__ const PopJointArgs &joint_args(const PopPeriodArgs &A) { return A.j; }
 
@@ -399,6 +455,18 @@ template <> struct PopBasin<T_COST> { using type = hbvx_popk::Basin; };
 //                  counted and its weight is > 0 (the weight is a mask here); the comparison is on y, not its transform.
 //                  Everything of it is behind `if constexpr (FDC)`: the other instances are untouched
 //                  (profiles/r24_population_fdc.md has the comparison).
+//   PopEventArgs   (EVENTS) the daily stats form, and E event windows per basin (hbvx_popk::EventCursor, EventSlot).  After
+//                  the butterfly every lane of a basin holds the same y, so every lane carries its basin's cursor and slot
+//                  -- six registers: the row, the live window, the peak, its day, the volume -- and the leader stores.
+//                  One slot is live at a time, so unlike the FDC form's K slots it stays in registers: parked in LDS it
+//                  came out one VGPR higher, not lower (the column's address is a register too).  A scored day inside
+//                  the live window pushes the raw y (not its transform, and whatever the day's weight: the window is
+//                  the mask); the day that closes it stores the row, restarts the slot and
+//                  seeks the next live row, storing -inf, -1, +0 for every absent row it passes.  Windows differ per
+//                  basin, so the lanes of different basins diverge there under the execution mask: no atomics, no
+//                  barrier.  The seek reads two int32 per row and runs E steps per lane over the whole launch; no row
+//                  beyond E and no day outside the scored days is touched whatever the rows hold.  Everything of it is
+//                  behind `if constexpr (EVENTS)` (profiles/r26_population_events.md has the comparison).
 // The flow's operations are the same ones on the same values in every form, and the aux term's in both of its forms:
 // tests/test_population_stats_gpu.py, test_population_joint_gpu.py and test_population_period_gpu.py (daily calendars)
 // hold each form to the bits of the one before it.
@@ -423,6 +491,7 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
     constexpr bool PERIOD = std::is_same<Args, PopPeriodArgs>::value;
     constexpr bool JOINT = PERIOD || std::is_same<Args, PopJointArgs>::value;      // the forms with an aux term
     constexpr bool FDC = std::is_same<Args, PopFdcArgs>::value;
+    constexpr bool EVENTS = std::is_same<Args, PopEventArgs>::value;
     static_assert(STATS == (TR != T_COST), "TR = T_COST is the cost form's, and its alone");
     constexpr int NP = NParam<MODEL, BETAET>::value;
     const PopArgs &A = pop_args(Q);
@@ -542,6 +611,38 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
             slot[r * 192 + 64] = __uint_as_float(0u);
             slot[r * 192 + 128] = 0.0f;
         }
+    }
+
+    // EVENTS: the basin's cursor and slot (the same in all of its lanes), six registers.  ev_seek() offers the rows from
+    // ec.e on until one is live, the leader storing the absent ones on the way; the row index only rises, so all seeks of
+    // a lane together take n_events steps.  The element index of a row is 32-bit (EVENT_MAX_CELLS).
+    hbvx_popk::EventCursor ec;
+    hbvx_popk::EventSlot evs;
+    auto ev_store = [&](int e) {
+        if constexpr (EVENTS) {
+            if (L.leader) {
+                const int64_t cat = c * Q.n_events * d.B;       // (uniform: the candidate's [E,B] block)
+                const uint32_t at = (uint32_t)e * (uint32_t)d.B + (uint32_t)L.b;
+                (Q.peak + cat)[at] = evs.peak;
+                (Q.peak_day + cat)[at] = evs.hour;
+                (Q.volume + cat)[at] = evs.vol;
+            }
+        }
+    };
+    auto ev_seek = [&]() {
+        if constexpr (EVENTS) {
+            ec.rest();
+            for (; ec.e < Q.n_events; ec.e++) {
+                const uint32_t row = (uint32_t)ec.e * (uint32_t)d.B + (uint32_t)L.b;
+                if (ec.admit(Q.start[row], Q.end[row], T - t_first)) break;
+                ev_store(ec.e);         // (evs is at its start: the absent event)
+            }
+        }
+    };
+    if constexpr (EVENTS) {
+        ec.start();
+        evs.start();
+        ev_seek();
     }
 
     // one-step-ahead register prefetch of the per-step inputs (k_fwd's); in the daily forms the observations and their
@@ -676,6 +777,18 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
                         f.push(y, slot[r * 192]);
                         slot[r * 192 + 64] = __uint_as_float(f.n);
                         slot[r * 192 + 128] = f.vol;
+                    }
+                }
+            }
+            if constexpr (EVENTS) {
+                const int rel = t - t_first;            // the day among the scored days; negative days are inside nothing
+                if (ec.inside(rel)) {
+                    evs.push(y, rel);
+                    if (ec.closes(rel)) {
+                        ev_store(ec.e);
+                        evs.start();
+                        ec.e++;
+                        ev_seek();
                     }
                 }
             }

@@ -1,9 +1,11 @@
 // launch_pop.hip -- the entry points of the population evaluation: hbvx_population_cost, hbvx_population_stats,
 // hbvx_population_joint and hbvx_population_period (hbv_pop.h), the flow-duration call hbvx_population_fdc
-// (include/hbvx_pop_fdc.h; k_pop's FDC form), and the implicit scheme's hbvx_adj_population_cost,
+// (include/hbvx_pop_fdc.h; k_pop's FDC form), the flood-event call hbvx_population_events (include/hbvx_pop_events.h;
+// k_pop's event form), and the implicit scheme's hbvx_adj_population_cost,
 // hbvx_adj_population_stats and hbvx_adj_population_period (hbv_adj_pop.h).
 #include "hbvx_host.h"
 #include "../../include/hbvx_pop_fdc.h"
+#include "../../include/hbvx_pop_events.h"
 #include "hbv_pop.h"
 #define HBVX_CHUNK_NO_SHARED_KERNELS
 #include "hbv_chunked.h"        // (first: hbv_adj_kernels.h uses its XCD-aware block map)
@@ -282,6 +284,34 @@ extern "C" int hbvx_population_fdc(const hbvx_desc *d, const hbvx_pop_fdc *pf, v
     // at most 32 slots of 768 bytes: 24 KB, under the 64 KB a launch may ask for without an attribute
     const unsigned lds = fdc_lds_bytes(f.n_thr, f.s.a.lgMp);
     return with_transform(pf->flow.transform, [&](auto tr) { return launch_pop<tr>(who, f, stream, lds); });
+}
+
+extern "C" uint64_t hbvx_pop_events_sizeof(int which) { return which == 0 ? sizeof(hbvx_pop_events) : 0; }
+
+extern "C" int hbvx_population_events(const hbvx_desc *d, const hbvx_pop_events *pe, void *stream)
+{
+    const char *who = "hbvx_population_events";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!pe) return fail_as(who, HBVX_E_NULL, "pe is NULL");
+    if (pe->abi_version != HBVX_POP_EVENTS_ABI_VERSION) return fail_as(who, HBVX_E_ABI, "pe abi_version mismatch");
+    PopEventArgs ev;
+    rc = prepare(who, d, &pe->flow.pop, ev.s.a);        // (refuses HBVX_MODEL_HBVADJ and HBVX_MODEL_HOURLY)
+    if (rc) return rc;
+    rc = prepare_stats(who, &pe->flow, ev.s);
+    if (rc) return rc;
+    if (pe->n_events < 1 || pe->n_events > d->T - pe->flow.pop.t_first)
+        return fail_as(who, HBVX_E_SHAPE, "n_events must be in 1..T - t_first");
+    if ((int64_t)pe->n_events * d->B > EVENT_MAX_CELLS) return fail_as(who, HBVX_E_SHAPE, "n_events * B must not exceed 2^30");
+    if (!pe->start || !pe->end) return fail_as(who, HBVX_E_NULL, "start / end is NULL");
+    if (!pe->peak || !pe->peak_day || !pe->volume) return fail_as(who, HBVX_E_NULL, "peak / peak_day / volume is NULL");
+    ev.n_events = pe->n_events;
+    ev.start = pe->start;
+    ev.end = pe->end;
+    ev.peak = pe->peak;
+    ev.peak_day = pe->peak_day;
+    ev.volume = pe->volume;
+    return with_transform(pe->flow.transform, [&](auto tr) { return launch_pop<tr>(who, ev, stream); });
 }
 
 extern "C" int hbvx_adj_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream)

@@ -15,7 +15,10 @@ line by line).  No series leaves the device.
   hourly_routing_search          shrinking random search over parameters[2], selected PER GAGE: every (gage, unit) pair
                                  belongs to one gage, so the gages' searches do not meet.
 
-Not built: events for the daily or implicit families, event detection on the simulated side, a search over unit
+The daily models Hbv, Hbv_1_1p and Hbv_2 have the same statistics per basin in population_events.py, which reuses
+`flood_events`, `_check_events`, `_observed_events` and the score of this file.
+
+Not built: events for the implicit family, event detection on the simulated side, a search over unit
 parameters (gages share units), Hbv_2_mts, gradients of event scores.
 """
 from __future__ import annotations
@@ -220,13 +223,18 @@ def hourly_event_score(stats: dict, metric: str, timing_scale: float = 24.0) -> 
       'volume_error'  |volume - obs_volume| / obs_volume
     NaN where the gage has no valid event, where a valid event's denominator (obs_peak, obs_volume, timing_scale) is not
     positive, and for a candidate with peak_hour == -1 in a valid event (no finite flow in the window)."""
+    return _event_score(stats['events'], 'peak_hour', metric, timing_scale)
+
+
+def _event_score(ev: dict, when: str, metric: str, timing_scale: float) -> torch.Tensor:
+    """`hourly_event_score` on an 'events' dictionary whose time-of-peak keys are `when` and 'obs_' + `when` ('peak_hour';
+    'peak_day' for the daily models' `population_event_score`)."""
     if metric not in EVENT_METRICS:
         raise ValueError(f"metric must be one of {list(EVENT_METRICS)}, got {metric!r}")
-    ev = stats['events']
     dev = ev['peak'].device
     valid = ev['valid'].to(dev)                                                         # [E,G]
     if metric == 'peak_timing':
-        num = (ev['peak_hour'].to(torch.float64) - ev['obs_peak_hour'].to(dev).to(torch.float64)).abs()
+        num = (ev[when].to(torch.float64) - ev['obs_' + when].to(dev).to(torch.float64)).abs()
         den = torch.full(valid.shape, float(timing_scale), dtype=torch.float64, device=dev)
     else:
         key = 'volume' if metric == 'volume_error' else 'peak'
@@ -239,7 +247,7 @@ def hourly_event_score(stats: dict, metric: str, timing_scale: float = 24.0) -> 
     term = torch.where(valid.unsqueeze(0), term, torch.zeros_like(term))               # [P,E,G]
     n = valid.sum(0)                                                                   # [G]
     mean = term.sum(1) / n.clamp_min(1).to(torch.float64)
-    empty = (valid.unsqueeze(0) & (ev['peak_hour'] == -1)).any(1)                       # [P,G]
+    empty = (valid.unsqueeze(0) & (ev[when] == -1)).any(1)                              # [P,G]
     undefined = empty | ((n == 0) | bad_den.any(0)).unsqueeze(0)
     return torch.where(undefined, torch.full_like(mean, float('nan')), mean)
 

@@ -1136,8 +1136,24 @@ def population_fdc(rec: PathRecord, cand_sources: dict, route_cands, flow: PopTe
                        want_sim, thresholds)[::2]
 
 
-def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first, want_sim, thr=None):
-    """`population` / `population_fdc`: (flow_out, aux_out, fdc_out), fdc_out None without `thr`."""
+def population_events(rec: PathRecord, cand_sources: dict, route_cands, flow: PopTerm, starts: torch.Tensor,
+                      ends: torch.Tensor, t_first: int = 0, want_sim: bool = False):
+    """hbvx_population_events (include/hbvx_pop_events.h) on one recorded call of the path: `population` on
+    hbvx_population_stats -- the same arguments, the same flow_out bit for bit -- and the peak, the day of the peak and the
+    volume of every candidate's routed flow inside E event windows per basin.
+    starts, ends  [E,B] int32 contiguous on the device of the record, E in 1..T_out: inclusive SCORED days (day 0 is
+                  t_first), walked in row order by the header's cursor rule -- a row that is not ahead of the basin's
+                  previous live one, start < 0 or end < start is an absent slot, end is clamped to T_out - 1: any content
+                  is safe.
+    Returns (flow_out, (peak [P,E,B] float32, peak_day [P,E,B] int32, volume [P,E,B] float32)); an absent slot holds
+    -inf, -1, +0."""
+    return _population(rec, "hbvx_population_events", _abi.POP_EVENTS_ENTRY, cand_sources, route_cands, flow, None, t_first,
+                       want_sim, None, (starts, ends))[::3]
+
+
+def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first, want_sim, thr=None, events=None):
+    """`population` / `population_fdc` / `population_events`: (flow_out, aux_out, fdc_out, events_out), fdc_out None
+    without `thr`, events_out None without `events`."""
     what = entry[len("hbvx_"):]
     cost_form, period_form = info.struct is _abi.Pop, info.struct is _abi.PopPeriod
     if not cost_form:
@@ -1229,6 +1245,16 @@ def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first,
             raise ValueError(f"thresholds must be [K,{B}] on {dev} with K in 1..{_abi.POP_FDC_MAX_THR}, got "
                              f"{tuple(thr.shape)} on {thr.device}")
         thr = thr.contiguous()
+    if events is not None:
+        for name, t in zip(("starts", "ends"), events):
+            if not torch.is_tensor(t) or t.dtype != torch.int32:
+                raise TypeError(f"{name} must be an int32 tensor, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+            if t.dim() != 2 or int(t.shape[1]) != B or not 1 <= int(t.shape[0]) <= T_out or not t.is_contiguous() \
+                    or t.device != dev:
+                raise ValueError(f"{name} must be a contiguous [E,{B}] tensor of 1..{T_out} events on {dev}, got "
+                                 f"{tuple(t.shape)} on {t.device}")
+        if tuple(events[0].shape) != tuple(events[1].shape):
+            raise ValueError(f"starts is {tuple(events[0].shape)}, ends {tuple(events[1].shape)}")
     tc, wc, shc, epc = (None if t is None else t.contiguous() for t in (flow.target, flow.w, shift, eps))
     atc, awc, ashc = (None if t is None else t.contiguous() for t in (aux or no_aux)[:3])
     stream = _stream_of(lib, x)
@@ -1245,6 +1271,12 @@ def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first,
         if thr is not None:
             K = int(thr.shape[0])
             fdc_out = (_out_i32((P, K, B), dev), _out((P, K, B), dev))
+        ev_out = None
+        if events is not None:
+            E = int(events[0].shape[0])
+            ev_out = (_out((P, E, B), dev), _out_i32((P, E, B), dev), _out((P, E, B), dev))
+            if _POISON:
+                ev_out[1].fill_(-2 ** 31)       # (-1, _out_i32's fill, is what an absent slot holds)
         for c0 in range(0, P, POP_MAX_CAND):
             args = info.struct()
             pq, pj, ps, pop = _abi.pop_levels(args)
@@ -1279,8 +1311,13 @@ def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first,
             if thr is not None:
                 args.abi_version, args.n_thr, args.thr = _abi.POP_FDC_ABI_VERSION, K, _ptr(thr)
                 args.count, args.volume = fdc_out[0].data_ptr() + 4 * c0 * K * B, _ptr(fdc_out[1], c0 * K * B)
+            if events is not None:
+                args.abi_version, args.n_events = _abi.POP_EVENTS_ABI_VERSION, E
+                args.start, args.end = events[0].data_ptr(), events[1].data_ptr()
+                args.peak, args.volume = _ptr(ev_out[0], c0 * E * B), _ptr(ev_out[2], c0 * E * B)
+                args.peak_day = ev_out[1].data_ptr() + 4 * c0 * E * B
             _call(lib, entry, call, desc, args, stream)
-    return (cost,) + moments + (sim,), aux_out, fdc_out
+    return (cost,) + moments + (sim,), aux_out, fdc_out, ev_out
 
 
 class PathOut(NamedTuple):

@@ -20,6 +20,9 @@ per period, and `population_search(periods=..., aux_periods=...)` searches on th
 `population_fdc_stats` (population_fdc.py) is `population_stats` with each candidate's flow-duration curve sampled at
 thresholds of the observations (hbvx_population_fdc: exceedance counts and volumes, [P,K,B], still no series), and
 `population_search(fdc_share=...)` mixes a distance between the curves into its objective.
+`population_event_stats` (population_events.py) is `population_stats` with each candidate's peak, day of the peak and
+volume inside flood-event windows of the observations (hbvx_population_events: [P,E,B], still no series), and
+`population_search(events=..., event_share=...)` mixes an event score into its objective.
 
 Hbv, Hbv_1_1p and Hbv_2 only.  HbvAdj has the first three calls and a period call of its own in adj_population.py
 (`adj_population_period_stats`: its second series is one of its five storages).  Hbv_2_hourly, whose scores live at
@@ -586,7 +589,8 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
                       generator: Optional[torch.Generator] = None, objective: str = 'sse', transform: str = 'none',
                       eps=None, aux_target=None, aux_key: Optional[str] = None, aux_weights=None,
                       aux_objective: str = 'nse', aux_share: float = 0.5, periods=None, aux_periods=None,
-                      fdc_share: float = 0.0, fdc_probs=None, fdc_metric: str = 'fdc_freq'):
+                      fdc_share: float = 0.0, fdc_probs=None, fdc_metric: str = 'fdc_freq', events=None,
+                      event_share: float = 0.0, event_metric: str = 'peak_error', timing_scale: float = 1.0):
     """Per-basin shrinking random search over the static row, for a start that `calibrate` can refine.
 
     Round 0 evaluates the current row as candidate 0 and n_candidates - 1 uniform draws in the unit interval per
@@ -627,10 +631,22 @@ def population_search(model, x_dict: dict, parameters, target, names: Optional[S
     undefined; history['score'] and history['score_fdc'] hold the two.  fdc_share in [0, 1].  It goes with objective
     'nse', 'kge' or 'kge12' on daily streamflow alone: with objective 'sse' the raw cost has no scale to mix with, and
     with aux_target or periods / aux_periods it is a ValueError.  With fdc_share == 0 (the default) the function is the
-    one above, bit for bit, and hbvx_population_fdc is not touched."""
+    one above, bit for bit, and hbvx_population_fdc is not touched.
+
+    event_share > 0 adds a flood-event term (population_events.py): `events` = (starts, ends) as
+    `population_event_stats` takes them (what `flood_events(target, ...)` returns), every round is one
+    `population_event_stats` call, and the quantity minimised, and what history['cost'] holds, is
+    (1 - event_share) * (1 - score) + event_share * event_score, with event_score
+    `population_event_score(stats, event_metric, timing_scale)` ('peak_error', 'peak_bias', 'peak_timing' or
+    'volume_error'), +inf where either is undefined; history['score'] and history['score_event'] hold the two.  The
+    windows are checked and their observed half is formed once, before the first round.  event_share in [0, 1].  It goes
+    with objective 'nse', 'kge' or 'kge12' on daily streamflow alone: with objective 'sse', with aux_target, periods /
+    aux_periods or fdc_share > 0, and without `events`, it is a ValueError.  With event_share == 0 (the default) the
+    function is the one above, bit for bit: `events` is not read and hbvx_population_events is not touched."""
     return _search_call(EXPLICIT, "population_search", model, x_dict, parameters, target, names, n_candidates, n_rounds,
                         shrink, weights, generator, objective, transform, eps, aux_target, aux_key, aux_weights,
-                        aux_objective, aux_share, periods, aux_periods, fdc_share, fdc_probs, fdc_metric)
+                        aux_objective, aux_share, periods, aux_periods, fdc_share, fdc_probs, fdc_metric, events,
+                        event_share, event_metric, timing_scale)
 
 
 def _check_mix(objective, aux_objective, aux_share, what):
@@ -646,13 +662,20 @@ def _check_mix(objective, aux_objective, aux_share, what):
 
 def _search_call(family, what, model, x_dict, parameters, target, names, n_candidates, n_rounds, shrink, weights,
                  generator, objective, transform, eps, aux_target, aux_key, aux_weights, aux_objective, aux_share, periods,
-                 aux_periods, fdc_share=0.0, fdc_probs=None, fdc_metric='fdc_freq'):
+                 aux_periods, fdc_share=0.0, fdc_probs=None, fdc_metric='fdc_freq', events=None, event_share=0.0,
+                 event_metric='peak_error', timing_scale=1.0):
     """`population_search` / `adj_population_search`: the checks, the form every round is scored in ('period' with a
     calendar, or an aux term where there is no joint export) and the loop.  The export is required before the first draw."""
     _check_search(model, n_candidates, n_rounds, shrink, objective, what)
     joint = aux_target is not None or aux_key is not None or aux_weights is not None
     if not 0.0 <= float(fdc_share) <= 1.0:          # (a NaN fails both comparisons)
         raise ValueError(f"{what}: fdc_share must lie in [0, 1], got {fdc_share!r}")
+    if not 0.0 <= float(event_share) <= 1.0:
+        raise ValueError(f"{what}: event_share must lie in [0, 1], got {event_share!r}")
+    if float(event_share) > 0:
+        return _event_search(what, model, x_dict, parameters, target, names, n_candidates, n_rounds, shrink, weights,
+                             generator, objective, transform, eps, joint, periods, aux_periods, float(fdc_share), events,
+                             float(event_share), event_metric, timing_scale)
     if float(fdc_share) > 0:
         return _fdc_search(what, model, x_dict, parameters, target, names, n_candidates, n_rounds, shrink, weights,
                            generator, objective, transform, eps, joint, periods, aux_periods, float(fdc_share), fdc_probs,
@@ -710,6 +733,35 @@ def _fdc_search(what, model, x_dict, parameters, target, names, n_candidates, n_
                    True, 'score_fdc')
 
 
+def _event_search(what, model, x_dict, parameters, target, names, n_candidates, n_rounds, shrink, weights, generator,
+                  objective, transform, eps, joint, periods, aux_periods, fdc_share, events, event_share, event_metric,
+                  timing_scale):
+    """`population_search` with event_share > 0: its refusals, the windows and their observed half once, and the loop on
+    `population_event_stats`' numbers."""
+    from . import population_events as pe           # (it imports this module)
+    if joint or periods is not None or aux_periods is not None or fdc_share > 0:
+        raise ValueError(f"{what}: event_share > 0 goes with daily streamflow alone, not with aux_target, periods / "
+                         "aux_periods or fdc_share > 0")
+    if objective == 'sse':
+        raise ValueError(f"{what}: event_share > 0 with objective 'sse' would add an event score to a squared error: the "
+                         "raw cost has no scale to mix with; use 'nse', 'kge' or 'kge12'")
+    if event_metric not in pe.EVENT_METRICS:
+        raise ValueError(f"{what}: event_metric must be one of {list(pe.EVENT_METRICS)}, got {event_metric!r}")
+    if events is None:
+        raise ValueError(f"{what}: event_share > 0 needs events (see flood_events)")
+    rq, win = pe._event_request(what, model, x_dict, parameters, None, target, events, names, weights, transform, eps)
+
+    def evaluate(cands):
+        st = pe._event_run(rq._replace(candidates=cands), win)
+        score = population_score(st, objective)
+        score_event = pe.population_event_score(st, event_metric, timing_scale)
+        cost_event = torch.where(torch.isnan(score_event), torch.full_like(score_event, float('inf')), score_event)
+        return _mixed_cost(_objective_cost(score, objective), cost_event, event_share), (score, score_event)
+
+    return _search(rq.req, x_dict, parameters, evaluate, rq.req.tname != 'p_sta', n_candidates, n_rounds, shrink, generator,
+                   True, 'score_event')
+
+
 def _mixed_cost(cost_flow: torch.Tensor, cost_aux: torch.Tensor, aux_share: float) -> torch.Tensor:
     """(1 - aux_share) * cost_flow + aux_share * cost_aux, +inf where either is +inf (a share of 0 does not hide a
     series that admits no score: 0 * inf would be NaN)."""
@@ -737,7 +789,7 @@ def _search(req, x_dict, parameters, evaluate, raw, n_candidates, n_rounds, shri
     """The search loop of `population_search` and `adj_population_search`: `evaluate(cands)` -> (cost, score or None)
     [P,B] is the front end's route to one round's numbers; raw: the module applies a sigmoid to the row.  two_scores:
     `evaluate` returns the pair (score, score_aux), kept as history['score'] and history['score_aux'] -- or under the
-    name two_scores itself where it is one ('score_fdc')."""
+    name two_scores itself where it is one ('score_fdc', 'score_event')."""
     two = req.tname == 'p_sta'
     cur = _static_tensor(two, parameters).detach().clone()
     row = cur if two else cur[-1]           # [B,width] view of the row that moves
