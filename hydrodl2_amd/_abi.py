@@ -313,6 +313,30 @@ GAGE_EVENTS_SIGNATURES = [
 POP_FDC_ABI_VERSION = 1     # HBVX_POP_FDC_ABI_VERSION
 POP_FDC_MAX_THR = 32        # HBVX_POP_FDC_MAX_THR
 
+GAGE_FDC_ABI_VERSION = 1    # HBVX_GAGE_FDC_ABI_VERSION
+GAGE_QUANT_MAX_T = 16384    # HBVX_GAGE_QUANT_MAX_T
+
+
+class GageFdc(C.Structure):
+    """hbvx_gage_fdc: the [P,T,G] hourly gage series, the [T,G] mask of the scored hours, and the [K,G] thresholds with
+    their [P,K,G] counts and volumes (hbvx_gage_population_fdc) or the [K,G] ranks with their [P,K,G] quantiles
+    (hbvx_gage_population_quantiles) -- include/hbvx_gage_fdc.h; K <= POP_FDC_MAX_THR."""
+    _fields_ = [("abi_version", C.c_int32), ("n_cand", C.c_int32), ("T", C.c_int32), ("G", C.c_int32),
+                ("n_lev", C.c_int32), ("series", _fp),
+                ("scored", C.c_void_p),         # const uint8_t *: an address like the float pointers, of another type
+                ("thr", _fp), ("count", C.c_void_p), ("volume", _fp),
+                ("rank", C.c_void_p), ("quantile", _fp)]
+
+
+# The exports of include/hbvx_gage_fdc.h, rows as in SIGNATURES (all optional); the layout index is
+# hbvx_gage_fdc_sizeof's.
+GAGE_FDC_SIGNATURES = [
+    ("hbvx_gage_fdc_sizeof", False, _u64, [_int], None),
+    ("hbvx_gage_population_fdc", False, _int, [_P(GageFdc), _vp], (0, GageFdc)),
+    ("hbvx_gage_quantiles_workspace_bytes", False, _u64, [C.c_int32, C.c_int32, C.c_int32], None),
+    ("hbvx_gage_population_quantiles", False, _int, [_P(GageFdc), _fp, _u64, _vp], (0, GageFdc)),
+]
+
 
 class PopFdc(C.Structure):
     """hbvx_pop_fdc: hbvx_pop_stats for the flow, the K thresholds per basin and the [P,K,B] exceedance counts and volumes
@@ -375,7 +399,7 @@ class Library:
                 raise HbvxError(f"{path}: missing export {name}")
         self.missing = [name for name in OPTIONAL_EXPORTS +
                         [row[0] for row in GAGE_POP_SIGNATURES + ROUTE_ROWS_SIGNATURES + POP_FDC_SIGNATURES +
-                         GAGE_EVENTS_SIGNATURES + POP_EVENTS_SIGNATURES]
+                         GAGE_EVENTS_SIGNATURES + POP_EVENTS_SIGNATURES + GAGE_FDC_SIGNATURES]
                         if not hasattr(d, name)]
         checked = set()             # (sizeof export, index): several exports share a struct
         # the required rows come first, and each table's sizeof export before the rows that name a layout: it is bound by then
@@ -384,7 +408,8 @@ class Library:
                 [row + ("hbvx_sizeof",) for row in ROUTE_ROWS_SIGNATURES] + \
                 [row + ("hbvx_pop_fdc_sizeof",) for row in POP_FDC_SIGNATURES] + \
                 [row + ("hbvx_gage_events_sizeof",) for row in GAGE_EVENTS_SIGNATURES] + \
-                [row + ("hbvx_pop_events_sizeof",) for row in POP_EVENTS_SIGNATURES]:
+                [row + ("hbvx_pop_events_sizeof",) for row in POP_EVENTS_SIGNATURES] + \
+                [row + ("hbvx_gage_fdc_sizeof",) for row in GAGE_FDC_SIGNATURES]:
             if name in self.missing:
                 continue
             fn = getattr(d, name)
@@ -613,6 +638,22 @@ class Library:
         self.require("hbvx_gage_population_events")
         self._check(self.dll.hbvx_gage_population_events(None if ev is None else C.byref(ev), C.c_void_p(stream)),
                     "hbvx_gage_population_events")
+
+    def gage_population_fdc(self, gf, stream: int):
+        """hbvx_gage_population_fdc; `gf` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_gage_population_fdc")
+        self._check(self.dll.hbvx_gage_population_fdc(None if gf is None else C.byref(gf), C.c_void_p(stream)),
+                    "hbvx_gage_population_fdc")
+
+    def gage_quantiles_workspace_bytes(self, n_cand: int, T: int, G: int) -> int:
+        self.require("hbvx_gage_quantiles_workspace_bytes")
+        return int(self.dll.hbvx_gage_quantiles_workspace_bytes(n_cand, T, G))
+
+    def gage_population_quantiles(self, gf, ws, ws_bytes: int, stream: int):
+        """hbvx_gage_population_quantiles; `gf` may be None (the ABI's own refusals are under test)."""
+        self.require("hbvx_gage_population_quantiles")
+        self._check(self.dll.hbvx_gage_population_quantiles(None if gf is None else C.byref(gf), ws, C.c_uint64(ws_bytes),
+                                                            C.c_void_p(stream)), "hbvx_gage_population_quantiles")
 
     def lstm_check(self, r: LstmDesc, ws, stream: int):
         self._check(self.dll.hbvx_lstm_check(C.byref(r), ws, C.c_void_p(stream)), "hbvx_lstm_check")

@@ -23,6 +23,12 @@
 //   k_gp_events     hbvx_gage_population_events (include/hbvx_gage_events.h): per (candidate, event, gage) the peak, its
 //                   hour and the volume inside a window of hours fixed on the observed side.  It sits on the [P,T,G]
 //                   series and not inside k_gp_route, whose workgroups own 1024-hour tiles: an event crosses tiles.
+// Three more work on it for the flow-duration curve (include/hbvx_gage_fdc.h):
+//   k_gp_fdc        hbvx_gage_population_fdc: per (candidate, level, gage) the scored hours above a threshold fixed on the
+//                   observed side and the volume above it -- hbvx_pop_fdc.h's slot on the gage series, one ordered pass;
+//   k_gp_keys, k_gp_quant   hbvx_gage_population_quantiles: the candidate's own curve.  The series gage-major as sortable
+//                   keys, then one LDS sort per (candidate, gage) column and the flows at K ranks.  The sort sits on the
+//                   series because k_pop and k_gp_route keep none: a quantile needs all hours of a column at once.
 // The statements of hbv_gage.h are restated, not shared: that header defines its kernels (one translation unit may
 // include it), and its kernels' code is pinned.  A change to either belongs in both; tests/test_hourly_population_gpu.py
 // holds the gage series to hbvx_gage_route_forward's bits.
@@ -35,6 +41,7 @@
 #include "hbv_step.h"
 #include "../../include/hbvx_gage_pop.h"
 #include "../../include/hbvx_gage_events.h"
+#include "../../include/hbvx_gage_fdc.h"
 
 namespace hbvx {
 namespace gagepop {
@@ -182,6 +189,151 @@ __global__ void __launch_bounds__(64) k_gp_events(const EventArgs A)
         ev.peak[at] = slot.peak;
         ev.peak_hour[at] = slot.hour;
         ev.volume[at] = slot.vol;
+    }
+}
+
+// hbvx_gage_population_fdc (include/hbvx_gage_fdc.h): the exceedance count and the volume above FDC_LEVELS thresholds,
+// the block blockIdx.z of the call's K, at gage (blockIdx.x * 64 + lane) in candidate (c0 + blockIdx.y)'s series.  Lanes
+// are gages, so the loads of the flows and of the mask ([t*G + g]) are coalesced; one ascending pass over the hours,
+// FDC_HOURS at a time into registers, and each lane pushes the hours its mask lets in into its FdcSlots (hbv_pop.h).
+// Threshold, count and volume of the block stay in registers: 3 x 8 of them, which leaves the kernel at eight waves per
+// SIMD; all 32 levels would take 96 (tools/kernel_resources.py, profiles/r27_hourly_fdc.md).  A level from K on has a
+// threshold of +inf and is not stored; an inactive lane of a partial wave reads gage G-1 and stores nothing.  (Like
+// k_gp_events it stands before k_gp_route: tools/compare_code.py.)
+constexpr int FDC_HOURS = 8;
+constexpr int FDC_LEVELS = 8;
+
+struct FdcArgs {
+    hbvx_gage_fdc gf;
+    int c0;                 // the first candidate of this launch (launch_gage_pop.hip splits the call so that no launch
+                            // exceeds 2^32 threads)
+};
+
+__global__ void __launch_bounds__(64) k_gp_fdc(const FdcArgs A)
+{
+    const hbvx_gage_fdc &gf = A.gf;
+    const int lane = threadIdx.x, G = gf.G, T = gf.T, K = gf.n_lev;
+    const int gl = blockIdx.x * 64 + lane;
+    const bool active = gl < G;
+    const int g = active ? gl : G - 1;
+    const int64_t c = A.c0 + blockIdx.y;
+    const int k0 = blockIdx.z * FDC_LEVELS;
+    const float *ser = gf.series + c * (int64_t)T * G + g;
+    const uint8_t *msk = gf.scored + g;
+    float thr[FDC_LEVELS];
+    hbvx_popk::FdcSlot slot[FDC_LEVELS];
+#pragma unroll
+    for (int j = 0; j < FDC_LEVELS; j++) {
+        thr[j] = k0 + j < K ? gf.thr[(int64_t)(k0 + j) * G + g] : INFINITY;
+        slot[j].start();
+    }
+    for (int tb = 0; tb < T; tb += FDC_HOURS) {
+        float v[FDC_HOURS];
+        uint8_t m[FDC_HOURS];
+#pragma unroll
+        for (int i = 0; i < FDC_HOURS; i++) {
+            const int t = tb + i < T ? tb + i : T - 1;      // 0 <= t <= T - 1
+            v[i] = ser[(int64_t)t * G];
+            m[i] = msk[(int64_t)t * G];
+        }
+#pragma unroll
+        for (int i = 0; i < FDC_HOURS; i++) {
+            if (tb + i < T && m[i]) {
+#pragma unroll
+                for (int j = 0; j < FDC_LEVELS; j++) slot[j].push(v[i], thr[j]);
+            }
+        }
+    }
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < FDC_LEVELS; j++) {
+            if (k0 + j < K) {
+                const int64_t at = (c * K + (k0 + j)) * (int64_t)G + g;
+                gf.count[at] = (int32_t)slot[j].n;
+                gf.volume[at] = slot[j].vol;
+            }
+        }
+    }
+}
+
+// hbvx_gage_population_quantiles (include/hbvx_gage_fdc.h), in two kernels.
+//   k_gp_keys   keys[c][g][t] = the sortable image (hbvx_popk::quant_key) of series[c][t][g], QUANT_NONE where the hour is
+//               not scored: k_gp_transpose's statements on a 32 x 32 tile (blockIdx.x: gages, blockIdx.y: hours,
+//               blockIdx.z: candidates from c0), with the mask read beside the flows, so that both reads are rows of
+//               [T,G] and the writes are rows of [G,T].  The sort then never sees the mask.
+//   k_gp_quant  one workgroup per (gage g0 + blockIdx.x, candidate c0 + blockIdx.y): the column's T keys come from one
+//               contiguous row into N = the next power of two >= T words of dynamic LDS (sized by the call's T, not by the
+//               cap), QUANT_NONE behind them; a bitonic network sorts them descending, one barrier per step; then thread
+//               k < K reads the key at rank[k][g].  QUANT_NONE is below every flow, so an index < n lands on a flow and
+//               one >= n on QUANT_NONE: NaN.  QUANT_NAN is above every flow, so after the sort word 0 IS the workgroup's
+//               flag "a scored hour is NaN" -- it costs no LDS beside the column, which at the cap is all 64 KB a
+//               launch may ask for without an attribute.
+constexpr int QUANT_THREADS = 256;
+
+struct QuantArgs {
+    hbvx_gage_fdc gf;
+    uint32_t *keys;         // [P,G,T] of this CALL (c0 indexes into it)
+    int c0, g0;             // the first candidate and the first gage of this launch
+    int N;                  // the padded column: a power of two, T <= N < 2 T
+};
+
+__global__ void __launch_bounds__(256) k_gp_keys(const QuantArgs A)
+{
+    __shared__ uint32_t tile[32][33];
+    const int T = A.gf.T, G = A.gf.G;
+    const int g0 = blockIdx.x * 32, t0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int64_t c = A.c0 + blockIdx.z;
+    const float *src = A.gf.series + c * (int64_t)T * G;
+    uint32_t *dst = A.keys + c * (int64_t)T * G;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int t = t0 + ty + 8 * k, g = g0 + tx;
+        uint32_t key = hbvx_popk::QUANT_NONE;
+        if (t < T && g < G && A.gf.scored[(int64_t)t * G + g]) key = hbvx_popk::quant_key(src[(int64_t)t * G + g]);
+        tile[ty + 8 * k][tx] = key;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int g = g0 + ty + 8 * k, t = t0 + tx;
+        if (g < G && t < T) dst[(int64_t)g * T + t] = tile[tx][ty + 8 * k];
+    }
+}
+
+__global__ void __launch_bounds__(QUANT_THREADS) k_gp_quant(const QuantArgs A)
+{
+    extern __shared__ uint32_t quant_col[];         // [N]
+    const hbvx_gage_fdc &gf = A.gf;
+    const int T = gf.T, G = gf.G, K = gf.n_lev, N = A.N, tid = threadIdx.x;
+    const int g = A.g0 + blockIdx.x;
+    const int64_t c = A.c0 + blockIdx.y;
+    const uint32_t *col = A.keys + (c * G + g) * (int64_t)T;
+    for (int i = tid; i < N; i += QUANT_THREADS) quant_col[i] = i < T ? col[i] : hbvx_popk::QUANT_NONE;
+    __syncthreads();
+    // Comparator i of a step with distance j joins lo = (i with a zero bit inserted at j) and lo + j; inside a block of
+    // 2 k words with bit k of lo clear the larger key goes first, with it set the smaller.  In the last stage k = N, so
+    // the bit is clear everywhere: descending.  All indices are < N.
+    for (int k = 2; k <= N; k <<= 1)
+        for (int j = k >> 1; j >= 1; j >>= 1) {
+            for (int i = tid; i < (N >> 1); i += QUANT_THREADS) {
+                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));
+                const int hi = lo + j;
+                const uint32_t a = quant_col[lo], b = quant_col[hi];
+                const bool desc = (lo & k) == 0;
+                if (desc ? a < b : a > b) {
+                    quant_col[lo] = b;
+                    quant_col[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+    if (tid < K) {
+        const int r = gf.rank[(int64_t)tid * G + g];
+        const bool any_nan = quant_col[0] == hbvx_popk::QUANT_NAN;
+        const uint32_t key = (r >= 0 && r < N) ? quant_col[r] : hbvx_popk::QUANT_NONE;
+        const bool none = any_nan || key == hbvx_popk::QUANT_NONE;
+        gf.quantile[(c * K + tid) * (int64_t)G + g] = none ? __builtin_nanf("") : hbvx_popk::quant_value(key);
     }
 }
 

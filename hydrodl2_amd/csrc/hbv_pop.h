@@ -23,7 +23,9 @@
 // hbvx_popk::AuxStats is the aux term's four chains (tests/hosttest/popjoint_host.cpp).
 // hbvx_popk::PeriodMean is the mean over a period that hbvx_population_period puts between each of the two values and
 // its chains (tests/hosttest/popperiod_host.cpp).
-// hbvx_popk::FdcSlot is one threshold's exceedance count and volume (tests/hosttest/popfdc_host.cpp).
+// hbvx_popk::FdcSlot is one threshold's exceedance count and volume (tests/hosttest/popfdc_host.cpp); k_gp_fdc
+// (hbv_gage_pop.h, include/hbvx_gage_fdc.h) feeds the same slot the hours of a gage, and hbvx_popk::quant_key is the
+// sortable image of a flow in that header's quantile call (tests/hosttest/gagefdc_host.cpp has both).
 // hbvx_popk::EventSlot is one flood event's peak, hour of the peak and volume (hbvx_gage_population_events,
 // include/hbvx_gage_events.h; tests/hosttest/gageevents_host.cpp); the event form of k_pop feeds the same slot days.
 // hbvx_popk::EventCursor is that form's walk over a basin's window rows (tests/hosttest/popevents_host.cpp).
@@ -231,6 +233,24 @@ struct FdcSlot {
 };
 
 constexpr int FDC_MAX_THR = 32;     // HBVX_POP_FDC_MAX_THR
+
+// The sortable image of a flow for hbvx_gage_population_quantiles (include/hbvx_gage_fdc.h): an unsigned key whose
+// integer order is float32's total order on the values that are not NaN, -0 below +0 (a set sign bit flips every bit, a
+// clear one sets it), every NaN QUANT_NAN above all of them, and QUANT_NONE, which no flow maps to (-inf is 0x007FFFFF),
+// below all of them: the key of an hour that is not scored and of the padding.  quant_value undoes quant_key bit for bit.
+constexpr uint32_t QUANT_NONE = 0u, QUANT_NAN = 0xFFFFFFFFu;
+
+HBVX_POP_HD uint32_t quant_key(float y)
+{
+    const uint32_t b = __builtin_bit_cast(uint32_t, y);
+    if (y != y) return QUANT_NAN;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+HBVX_POP_HD float quant_value(uint32_t key)
+{
+    return __builtin_bit_cast(float, (key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}
 
 // One event window of hbvx_gage_population_events for one (candidate, gage).  push() takes the hours of the window in
 // ascending order, with the hourly gage flow y and the hour t:

@@ -1,6 +1,8 @@
 // launch_gage_pop.hip -- the entry points of the hourly model's population evaluation (include/hbvx_gage_pop.h):
 // hbvx_hourly_population_runoff (k_pop's runoff form, hbv_pop.h) and hbvx_gage_population_stats (hbv_gage_pop.h), and of
-// the event statistics on the latter's series (include/hbvx_gage_events.h): hbvx_gage_population_events (k_gp_events).
+// the event statistics on the latter's series (include/hbvx_gage_events.h): hbvx_gage_population_events (k_gp_events),
+// and of the flow-duration statistics on it (include/hbvx_gage_fdc.h): hbvx_gage_population_fdc (k_gp_fdc) and
+// hbvx_gage_population_quantiles (k_gp_keys, k_gp_quant).
 #include "hbvx_host.h"
 #include "hbv_gage_pop.h"
 
@@ -71,6 +73,32 @@ int check_gage_events(const char *who, const hbvx_gage_events *ev)
     if (!ev->start || !ev->end) return fail_as(who, HBVX_E_NULL, "start / end is NULL");
     if (!ev->peak || !ev->peak_hour || !ev->volume) return fail_as(who, HBVX_E_NULL, "peak / peak_hour / volume is NULL");
     return HBVX_OK;
+}
+
+static_assert(HBVX_GAGE_FDC_MAX_LEV == hbvx_popk::FDC_MAX_THR && HBVX_GAGE_FDC_MAX_LEV == HBVX_POP_FDC_MAX_THR,
+              "the gage FDC call and the daily one share one limit on the levels");
+static_assert(HBVX_GAGE_FDC_MAX_LEV <= gagepop::QUANT_THREADS, "k_gp_quant gathers one rank per thread");
+static_assert((uint64_t)HBVX_GAGE_QUANT_MAX_T * sizeof(uint32_t) <= 65536, "the padded column must fit 64 KB of LDS");
+
+// What both exports of include/hbvx_gage_fdc.h check of the struct they share.
+int check_gage_fdc(const char *who, const hbvx_gage_fdc *gf)
+{
+    if (!gf) return fail_as(who, HBVX_E_NULL, "gf is NULL");
+    if (gf->abi_version != HBVX_GAGE_FDC_ABI_VERSION) return fail_as(who, HBVX_E_ABI, "gf abi_version mismatch");
+    if (gf->n_cand < 1 || gf->n_cand > 65535) return fail_as(who, HBVX_E_SHAPE, "n_cand must be in 1..65535");
+    if (gf->T < 1 || gf->G < 1) return fail_as(who, HBVX_E_SHAPE, "bad T/G");
+    if (gf->n_lev < 1 || gf->n_lev > HBVX_GAGE_FDC_MAX_LEV) return fail_as(who, HBVX_E_SHAPE, "n_lev must be in 1..32");
+    if (!gf->series) return fail_as(who, HBVX_E_NULL, "series is NULL");
+    if (!gf->scored) return fail_as(who, HBVX_E_NULL, "scored is NULL");
+    return HBVX_OK;
+}
+
+// The candidates of one launch whose grid has `blocks` workgroups of `threads` threads per candidate: as many as keep the
+// launch below 2^32 threads (and a grid dimension); 0 if one candidate alone does not fit.
+int cands_per_launch(uint64_t blocks, uint64_t threads, int n_cand)
+{
+    const uint64_t budget = 0xFFFFFFFFull / (blocks * threads);
+    return budget < (uint64_t)n_cand ? (int)budget : n_cand;
 }
 
 // the workspace's three parts, in floats
@@ -190,5 +218,76 @@ extern "C" int hbvx_gage_population_events(const hbvx_gage_events *ev, void *str
             const int ne = ev->n_events - a.e0 < ec ? ev->n_events - a.e0 : ec;
             hipLaunchKernelGGL(gagepop::k_gp_events, dim3((unsigned)gx, np, ne), dim3(64), 0, (hipStream_t)stream, a);
         }
+    return launched(who);
+}
+
+extern "C" uint64_t hbvx_gage_fdc_sizeof(int which)
+{
+    return which == 0 ? sizeof(hbvx_gage_fdc) : 0;
+}
+
+extern "C" int hbvx_gage_population_fdc(const hbvx_gage_fdc *gf, void *stream)
+{
+    const char *who = "hbvx_gage_population_fdc";
+    int rc = check_gage_fdc(who, gf);
+    if (rc) return rc;
+    if (!gf->thr) return fail_as(who, HBVX_E_NULL, "thr is NULL");
+    if (!gf->count || !gf->volume) return fail_as(who, HBVX_E_NULL, "count / volume is NULL");
+    gagepop::FdcArgs a;
+    a.gf = *gf;
+    // (gage groups x candidates x blocks of levels) workgroups of 64; the call is split on the candidates so that no
+    // launch reaches 2^32 threads.  One candidate alone exceeds that from 2^30 gages on: refused, not split further.
+    const uint64_t gx = ((uint64_t)gf->G + 63) / 64;
+    const unsigned gz = (unsigned)((gf->n_lev + gagepop::FDC_LEVELS - 1) / gagepop::FDC_LEVELS);
+    const int pc = cands_per_launch(gx * gz, 64, gf->n_cand);
+    if (pc < 1) return fail_as(who, HBVX_E_SHAPE, "G too large for one launch per candidate");
+    for (a.c0 = 0; a.c0 < gf->n_cand; a.c0 += pc) {
+        const int np = gf->n_cand - a.c0 < pc ? gf->n_cand - a.c0 : pc;
+        hipLaunchKernelGGL(gagepop::k_gp_fdc, dim3((unsigned)gx, np, gz), dim3(64), 0, (hipStream_t)stream, a);
+    }
+    return launched(who);
+}
+
+extern "C" uint64_t hbvx_gage_quantiles_workspace_bytes(int32_t n_cand, int32_t T, int32_t G)
+{
+    if (n_cand < 1 || n_cand > 65535 || T < 1 || T > HBVX_GAGE_QUANT_MAX_T || G < 1) return 0;
+    return (uint64_t)n_cand * (uint64_t)T * (uint64_t)G * sizeof(uint32_t);
+}
+
+extern "C" int hbvx_gage_population_quantiles(const hbvx_gage_fdc *gf, float *workspace, uint64_t workspace_bytes,
+                                              void *stream)
+{
+    const char *who = "hbvx_gage_population_quantiles";
+    int rc = check_gage_fdc(who, gf);
+    if (rc) return rc;
+    if (!gf->rank) return fail_as(who, HBVX_E_NULL, "rank is NULL");
+    if (!gf->quantile) return fail_as(who, HBVX_E_NULL, "quantile is NULL");
+    if (gf->T > HBVX_GAGE_QUANT_MAX_T) return fail_as(who, HBVX_E_UNSUPPORTED, "more than 16384 hours per column");
+    if (!workspace || workspace_bytes < hbvx_gage_quantiles_workspace_bytes(gf->n_cand, gf->T, gf->G))
+        return fail_as(who, HBVX_E_NULL, "workspace missing or too small");
+    hipStream_t st = (hipStream_t)stream;
+    gagepop::QuantArgs a;
+    a.gf = *gf;
+    a.keys = reinterpret_cast<uint32_t *>(workspace);
+    a.g0 = 0;
+    a.N = 1;
+    while (a.N < gf->T) a.N <<= 1;                                  // <= 16384
+    // the keys: (G / 32) x (T / 32) tiles of 256 threads per candidate.  Both kernels are split on the candidates so
+    // that no launch reaches 2^32 threads; a G x T at which one candidate alone does (2^24 gages at 2^8 hours) is
+    // refused, not split further.
+    const uint64_t kx = ((uint64_t)gf->G + 31) / 32, ky = ((uint64_t)gf->T + 31) / 32;
+    const int kc = cands_per_launch(kx * ky, 256, gf->n_cand);
+    // the sort: G workgroups of QUANT_THREADS per candidate
+    const int qc = cands_per_launch((uint64_t)gf->G, gagepop::QUANT_THREADS, gf->n_cand);
+    if (kc < 1 || qc < 1) return fail_as(who, HBVX_E_SHAPE, "G x T too large for one launch per candidate");
+    for (a.c0 = 0; a.c0 < gf->n_cand; a.c0 += kc) {
+        const int np = gf->n_cand - a.c0 < kc ? gf->n_cand - a.c0 : kc;
+        hipLaunchKernelGGL(gagepop::k_gp_keys, dim3((unsigned)kx, (unsigned)ky, np), dim3(256), 0, st, a);
+    }
+    for (a.c0 = 0; a.c0 < gf->n_cand; a.c0 += qc) {
+        const int np = gf->n_cand - a.c0 < qc ? gf->n_cand - a.c0 : qc;
+        hipLaunchKernelGGL(gagepop::k_gp_quant, dim3((unsigned)gf->G, np), dim3(gagepop::QUANT_THREADS),
+                           (size_t)a.N * sizeof(uint32_t), st, a);
+    }
     return launched(who);
 }

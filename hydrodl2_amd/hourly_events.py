@@ -13,7 +13,8 @@ line by line).  No series leaves the device.
   hourly_population_event_stats  `hourly_population_stats`' dictionary, same bits, plus 'events';
   hourly_event_score             peak error, peak bias, peak timing and volume error per (candidate, gage);
   hourly_routing_search          shrinking random search over parameters[2], selected PER GAGE: every (gage, unit) pair
-                                 belongs to one gage, so the gages' searches do not meet.
+                                 belongs to one gage, so the gages' searches do not meet.  Its objective can also take a
+                                 flow-duration term (hourly_fdc.py).
 
 The daily models Hbv, Hbv_1_1p and Hbv_2 have the same statistics per basin in population_events.py, which reuses
 `flood_events`, `_check_events`, `_observed_events` and the score of this file.
@@ -29,6 +30,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .hourly_fdc import HOURLY_FDC_METRICS, _FdcHook, _fdc_stats, hourly_fdc_score
 from .hourly_population import _evaluate, hourly_population_stats
 from .population import OBJECTIVES, _check_search, _mixed_cost, _objective_cost, population_score
 
@@ -288,7 +290,8 @@ def hourly_routing_search(model, x_dict: dict, parameters, target, n_candidates:
                           shrink: float = 0.5, weights=None, periods=None, transform: str = 'none', eps=None,
                           objective: str = 'kge', events=None, event_target=None, event_share: float = 0.0,
                           event_metric: str = 'peak_timing', timing_scale: float = 24.0,
-                          generator: Optional[torch.Generator] = None, max_candidates: Optional[int] = None):
+                          generator: Optional[torch.Generator] = None, max_candidates: Optional[int] = None,
+                          fdc_share: float = 0.0, fdc_probs=None, fdc_metric: str = 'fdc_freq', fdc_target=None):
     """Per-gage shrinking random search over the distributed routing parameters parameters[2] (unit-interval route_a,
     route_b, route_tau per (gage, unit) pair) of `Hbv_2_hourly`: `population_search`'s search in the unit cube,
     routing-only, so stage 1 never launches and every round is one `hourly_population_stats` call.
@@ -305,14 +308,23 @@ def hourly_routing_search(model, x_dict: dict, parameters, target, n_candidates:
     either is undefined, and every round is one `hourly_population_event_stats` call.  With S == 0 (the default) the
     events are not touched and hbvx_gage_population_events is not required.
 
+    With fdc_share = S > 0 (not together with event_share > 0) the cost is (1 - S) * (1 - score) + S *
+    hourly_fdc_score(stats, fdc_metric), +inf where either is undefined, and every round is one
+    `hourly_population_fdc_stats` call at the probabilities fdc_probs (None: its default fifteen; 'fdc_slope' needs 0.2
+    and 0.7 among them) with fdc_target as that call takes it.  The observed curve is formed once, before the first
+    round, not per round.  With S == 0 (the default) fdc_probs and fdc_target are not touched, the search is the one
+    above bit for bit, and the exports of include/hbvx_gage_fdc.h are not required.
+
     Returns ((p_dyn, p_sta, new p_distr), history): history['cost'] [n_rounds+1,G] float64 (row 0: the start, row k+1:
-    the best after round k), 'score' and with S > 0 'score_event' likewise, 'best_index' [n_rounds,G] (the winning
+    the best after round k), 'score' and with event_share > 0 'score_event', with fdc_share > 0 'score_fdc' likewise, 'best_index' [n_rounds,G] (the winning
     candidate of the round; 0: nothing better was drawn).  The inputs are not modified.  Deterministic for a given
     `generator` (default: torch's global CPU generator).
 
     Refused (ValueError): what `hourly_population_stats` refuses; dy_drop > 0, n_candidates < 2, n_rounds < 1, shrink
     outside (0, 1], an objective other than the three; event_share outside [0, 1] or NaN; event_share > 0 without
-    `events`; an unknown event_metric."""
+    `events`; an unknown event_metric; fdc_share outside [0, 1] or NaN; fdc_share > 0 together with event_share > 0; an
+    unknown fdc_metric; what `hourly_population_fdc_stats` refuses of fdc_probs and fdc_target (a calendar without
+    fdc_target among it)."""
     what = "hourly_routing_search"
     _check_search(model, n_candidates, n_rounds, shrink, objective, what)
     if objective not in SEARCH_OBJECTIVES:
@@ -324,6 +336,15 @@ def hourly_routing_search(model, x_dict: dict, parameters, target, n_candidates:
         raise ValueError(f"{what}: event_metric must be one of {list(EVENT_METRICS)}, got {event_metric!r}")
     if share > 0 and events is None:
         raise ValueError(f"{what}: event_share > 0 needs events (see flood_events)")
+    if not 0.0 <= float(fdc_share) <= 1.0:
+        raise ValueError(f"{what}: fdc_share must lie in [0, 1], got {fdc_share!r}")
+    fshare = float(fdc_share)
+    if fdc_metric not in HOURLY_FDC_METRICS:
+        raise ValueError(f"{what}: fdc_metric must be one of {list(HOURLY_FDC_METRICS)}, got {fdc_metric!r}")
+    if fshare > 0 and share > 0:
+        raise ValueError(f"{what}: fdc_share > 0 together with event_share > 0 (one extra term per search)")
+    if fshare > 0 and periods is not None and fdc_target is None:
+        raise ValueError(f"{what}: with a calendar `target` holds period rows; give the observed HOURLY series as fdc_target")
     p_distr = parameters[2]
     topo = x_dict['outlet_topo']
     pair_gage = (topo == 1).nonzero(as_tuple=False)[:, 0]           # GageTopology's pair order: by gage, then unit
@@ -331,8 +352,17 @@ def hourly_routing_search(model, x_dict: dict, parameters, target, n_candidates:
         raise ValueError(f"{what}: parameters[2] must be [{int(pair_gage.numel())},3] (the pairs of outlet_topo), got "
                          f"{tuple(p_distr.shape) if torch.is_tensor(p_distr) else type(p_distr).__name__}")
     common = dict(weights=weights, periods=periods, transform=transform, eps=eps, max_candidates=max_candidates)
+    # one hook for every round: it forms the observed curve on its first check and keeps it
+    fdc_hook = _FdcHook(x_dict, target, weights, periods, fdc_probs, None, fdc_target, what) if fshare > 0 else None
 
     def evaluate(dcands):
+        if fshare > 0:
+            st = _fdc_stats(fdc_hook, model, x_dict, parameters, target, None, dcands, None, weights, periods, transform,
+                            eps, False, max_candidates)
+            score = population_score(st, objective)
+            score_fdc = hourly_fdc_score(st, fdc_metric)
+            cost_fdc = torch.where(torch.isnan(score_fdc), torch.full_like(score_fdc, float('inf')), score_fdc)
+            return _mixed_cost(_objective_cost(score, objective), cost_fdc, fshare), {'score': score, 'score_fdc': score_fdc}
         if share > 0:
             st = hourly_population_event_stats(model, x_dict, parameters, target, events, distr_candidates=dcands,
                                                event_target=event_target, **common)
@@ -347,5 +377,6 @@ def hourly_routing_search(model, x_dict: dict, parameters, target, n_candidates:
         return _mixed_cost(cost, cost_event, share), {'score': score, 'score_event': score_event}
 
     best, hist = _routing_search(pair_gage, p_distr.to(x_dict['x_phy'].device), evaluate, n_candidates, n_rounds, shrink,
-                                 generator, ('score', 'score_event') if share > 0 else ('score',))
+                                 generator, ('score', 'score_fdc') if fshare > 0 else
+                                 ('score', 'score_event') if share > 0 else ('score',))
     return (parameters[0], parameters[1], best.to(device=p_distr.device, dtype=p_distr.dtype)), hist

@@ -13,7 +13,8 @@ ONCE at `parameters`; then, per chunk of candidates,
 Candidates come in two families: `candidates`, columns of the static physical parameters per unit, and
 `distr_candidates`, route_a / route_b / route_tau per (gage, unit) pair -- a family that only a search reaches.  The
 generic `population_*` calls keep refusing the model.  hourly_events.py builds on this call: flood-event statistics of
-every candidate at the gages, and the routing-only search (`hourly_routing_search`), which is separable per gage.  Not
+every candidate at the gages, and the routing-only search (`hourly_routing_search`), which is separable per gage;
+hourly_fdc.py does too: every candidate's flow-duration curve at the gages, counted and sorted on the device.  Not
 built: a search over the unit parameters (gages share units: there is no per-gage selection), a second observed series,
 cache_states, the per-unit 72-tap routing, per-gage calendars, and everything for Hbv_2_mts.
 """
@@ -150,7 +151,7 @@ def hourly_population_stats(model, x_dict: dict, parameters, target, candidates:
 def _evaluate(model, x_dict, parameters, target, candidates, distr_candidates, names, weights, periods, transform, eps,
               return_series, max_candidates, hook=None) -> dict:
     """The body of `hourly_population_stats`, and of the calls that want more of a chunk's hourly gage series than its
-    four sums (hourly_events.py).  `hook`, if given, has
+    four sums (hourly_events.py, hourly_fdc.py).  `hook`, if given, has
       check(T, G, dev)   the caller's own refusals, after this call's and before the library is asked or the model runs;
       exports            the exports it needs beyond EXPORTS;
       bytes              what it writes per candidate;

@@ -137,6 +137,18 @@ class Hbv_2_hourly(HbvModule):
                                              names, weights, periods, transform, eps, return_series, max_candidates,
                                              event_target)
 
+    def population_fdc_stats(self, x_dict: dict[str, torch.Tensor], parameters, target, candidates=None,
+                             distr_candidates=None, names=None, weights=None, periods=None, transform: str = 'none',
+                             eps=None, return_series: bool = False, max_candidates: Optional[int] = None, probs=None,
+                             thresholds=None, fdc_target=None):
+        """`population_stats` plus every candidate's flow-duration curve at the gages -- counts and volumes above
+        observed thresholds, and with `probs` its own quantiles: hydrodl2_amd.hourly_population_fdc_stats(self, ...), see
+        there."""
+        from hydrodl2_amd.hourly_fdc import hourly_population_fdc_stats
+        return hourly_population_fdc_stats(self, x_dict, parameters, target, candidates, distr_candidates, names, weights,
+                                           periods, transform, eps, return_series, max_candidates, probs, thresholds,
+                                           fdc_target)
+
     def _topology(self, tag, outlet_topo, areas, T, lag, bounds):
         """GageTopology of (outlet_topo, areas), built once per pair of tensor objects + versions: building it
         costs a `nonzero` (a host synchronisation) and a handful of small kernels per call, and cannot be captured

@@ -1739,6 +1739,76 @@ def gage_events(series: torch.Tensor, starts: torch.Tensor, ends: torch.Tensor):
     return peak, hour, volume
 
 
+def _check_gage_levels(series, scored, levels, name, dtype):
+    """What `gage_fdc` and `gage_quantiles` check of their arguments -> (P, T, G, K)."""
+    dev = series.device
+    if series.dim() != 3 or not series.is_contiguous() or min(series.shape) < 1:
+        raise ValueError(f"series must be a contiguous [P,T,G] tensor, got {tuple(series.shape)}")
+    P, T, G = (int(n) for n in series.shape)
+    if not torch.is_tensor(scored) or scored.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"scored must be a bool or uint8 tensor, got {scored.dtype if torch.is_tensor(scored) else type(scored).__name__}")
+    if tuple(scored.shape) != (T, G) or not scored.is_contiguous() or scored.device != dev:
+        raise ValueError(f"scored must be a contiguous [{T},{G}] tensor on {dev}, got {tuple(scored.shape)} on {scored.device}")
+    if not torch.is_tensor(levels) or levels.dtype != dtype:
+        raise TypeError(f"{name} must be a {dtype} tensor, got {levels.dtype if torch.is_tensor(levels) else type(levels).__name__}")
+    if levels.dim() != 2 or int(levels.shape[1]) != G or not 1 <= int(levels.shape[0]) <= _abi.POP_FDC_MAX_THR \
+            or not levels.is_contiguous() or levels.device != dev:
+        raise ValueError(f"{name} must be a contiguous [K,{G}] tensor on {dev} with K in 1..{_abi.POP_FDC_MAX_THR}, got "
+                         f"{tuple(levels.shape)} on {levels.device}")
+    return P, T, G, int(levels.shape[0])
+
+
+def gage_fdc(series: torch.Tensor, scored: torch.Tensor, thresholds: torch.Tensor):
+    """On how many scored hours every candidate's hourly gage series lies above K thresholds per gage, and the volume
+    above them (include/hbvx_gage_fdc.h), through hbvx_gage_population_fdc on the current stream.
+    series      [P,T,G] float32 contiguous: `gage_population`'s series (want_gage=True).
+    scored      [T,G] bool or uint8 contiguous on the series' device: the hours that enter.
+    thresholds  [K,G] float32 contiguous, K in 1.._abi.POP_FDC_MAX_THR, any order.
+    Returns (count [P,K,G] int32, volume [P,K,G] float32: the float32 sum of those flows in hour order)."""
+    lib = get_library()
+    lib.require('hbvx_gage_population_fdc')
+    _check_tensor(lib, series, "series")
+    P, T, G, K = _check_gage_levels(series, scored, thresholds, "thresholds", torch.float32)
+    dev = series.device
+    stream = _stream_of(lib, series)
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        count, volume = _out_i32((P, K, G), dev), _out((P, K, G), dev)
+        for c0 in range(0, P, POP_MAX_CAND):
+            gf = _abi.GageFdc(abi_version=_abi.GAGE_FDC_ABI_VERSION, n_cand=min(POP_MAX_CAND, P - c0), T=T, G=G, n_lev=K,
+                              series=_ptr(series, c0 * T * G), scored=scored.data_ptr(), thr=_ptr(thresholds),
+                              count=count.data_ptr() + 4 * c0 * K * G, volume=_ptr(volume, c0 * K * G))
+            _call(lib, 'hbvx_gage_population_fdc', lib.gage_population_fdc, gf, stream)
+    return count, volume
+
+
+def gage_quantiles(series: torch.Tensor, scored: torch.Tensor, rank: torch.Tensor) -> torch.Tensor:
+    """Every candidate's own flow-duration curve at K ranks per gage: the scored hours of each (candidate, gage) column
+    of the hourly gage series sorted descending on the device, and the flows at the 0-based indices `rank`
+    (include/hbvx_gage_fdc.h), through hbvx_gage_population_quantiles on the current stream.
+    series  [P,T,G] float32 contiguous, T <= _abi.GAGE_QUANT_MAX_T (the library refuses a longer record).
+    scored  [T,G] bool or uint8 contiguous on the series' device.
+    rank    [K,G] int32 contiguous, K in 1.._abi.POP_FDC_MAX_THR.
+    Returns quantile [P,K,G] float32: a value of the series bit for bit; NaN where the rank is outside 0..n-1 (n the gage's
+    scored hours) or a scored hour of the column is NaN.  The workspace, one series' worth, lives for the call."""
+    lib = get_library()
+    lib.require('hbvx_gage_population_quantiles')
+    _check_tensor(lib, series, "series")
+    P, T, G, K = _check_gage_levels(series, scored, rank, "rank", torch.int32)
+    dev = series.device
+    stream = _stream_of(lib, series)
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        quantile = _out((P, K, G), dev)
+        for c0 in range(0, P, POP_MAX_CAND):
+            n = min(POP_MAX_CAND, P - c0)
+            gf = _abi.GageFdc(abi_version=_abi.GAGE_FDC_ABI_VERSION, n_cand=n, T=T, G=G, n_lev=K,
+                              series=_ptr(series, c0 * T * G), scored=scored.data_ptr(), rank=rank.data_ptr(),
+                              quantile=_ptr(quantile, c0 * K * G))
+            ws_bytes = lib.gage_quantiles_workspace_bytes(n, T, G)
+            ws = _out(((max(ws_bytes, 4) + 3) // 4,), dev)      # poisoned with the outputs: the call must not need it cleared
+            _call(lib, 'hbvx_gage_population_quantiles', lib.gage_population_quantiles, gf, _ptr(ws), ws_bytes, stream)
+    return quantile
+
+
 @dataclass
 class GageTopology:
     """Index arrays of the (gage, unit) pairs of `outlet_topo == 1` (hbv_2_hourly.py:813-817), in

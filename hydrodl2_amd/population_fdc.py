@@ -9,8 +9,10 @@ chains bit for bit -- through hbvx_population_fdc (include/hbvx_pop_fdc.h), whic
 volumes and still writes no series; `population_fdc_score` forms two distances between the simulated and the observed
 curve from them, and `population_search(fdc_share=...)` mixes one into its objective.
 
-Hbv, Hbv_1_1p and Hbv_2, daily.  Not built: the implicit scheme and the hourly model; period calendars; simulated
-quantiles (inverting the sampled curve); an FDC term in `calibrate` (a count has no derivative); more than 32 thresholds.
+Hbv, Hbv_1_1p and Hbv_2, daily.  The hourly model has the same counts at its gages, and the simulated quantiles that
+need the series, in hourly_fdc.py, which reuses `_check_levels`, `fdc_thresholds`, `_fdc_observations` and the score's
+body of this file.  Not built: the implicit scheme; period calendars; simulated quantiles here (k_pop keeps no series);
+an FDC term in `calibrate` (a count has no derivative); more than 32 thresholds.
 """
 from __future__ import annotations
 
@@ -170,12 +172,17 @@ def population_fdc_score(stats: dict, metric: str) -> torch.Tensor:
                   is no such k, or where one of the candidate's volumes is not finite."""
     if metric not in FDC_METRICS:
         raise ValueError(f"metric must be one of {list(FDC_METRICS)}, got {metric!r}")
-    f = stats['fdc']
+    return _fdc_score(stats['fdc'], 'n_days', metric)
+
+
+def _fdc_score(f: dict, scored: str, metric: str) -> torch.Tensor:
+    """`population_fdc_score` on an 'fdc' dictionary whose count of scored steps is under the key `scored` ('n_days';
+    'n_hours' for the hourly model's `hourly_fdc_score`); metric is one of FDC_METRICS."""
     count, volume = f['count'], f['volume'].double()
     dev = count.device
     nan = torch.full((count.shape[0], count.shape[2]), float('nan'), dtype=torch.float64, device=dev)
     if metric == 'fdc_freq':
-        n = f['n_days'].to(dev).double()
+        n = f[scored].to(dev).double()
         dist = (count.double() - f['obs_count'].to(dev).double().unsqueeze(0)).abs().mean(1)
         return torch.where(n > 0, dist / n.clamp_min(1.0), nan)
     ov = f['obs_volume'].to(device=dev, dtype=torch.float64).unsqueeze(0)      # [1,K,B]
