@@ -380,6 +380,12 @@ ROUTE_ROWS_SIGNATURES = [
     ("hbvx_route_backward_rows", False, _int, [_P(RouteDesc), _fp, _fp, _fp, _fp, _i32, _fp, _fp, _fp, _u64, _vp], None),
 ]
 
+# The export of include/hbvx_live_rows.h, a row as in SIGNATURES (optional, no struct of its own).
+E_UNSUPPORTED = -3      # HBVX_E_UNSUPPORTED
+LIVE_ROWS_SIGNATURES = [
+    ("hbvx_backward_live", False, _int, [_P(Desc), _P(BwdIO), _i32, _vp], None),
+]
+
 
 class HbvxError(RuntimeError):
     pass
@@ -398,14 +404,14 @@ class Library:
             if not hasattr(d, name):
                 raise HbvxError(f"{path}: missing export {name}")
         self.missing = [name for name in OPTIONAL_EXPORTS +
-                        [row[0] for row in GAGE_POP_SIGNATURES + ROUTE_ROWS_SIGNATURES + POP_FDC_SIGNATURES +
-                         GAGE_EVENTS_SIGNATURES + POP_EVENTS_SIGNATURES + GAGE_FDC_SIGNATURES]
+                        [row[0] for row in GAGE_POP_SIGNATURES + ROUTE_ROWS_SIGNATURES + LIVE_ROWS_SIGNATURES +
+                         POP_FDC_SIGNATURES + GAGE_EVENTS_SIGNATURES + POP_EVENTS_SIGNATURES + GAGE_FDC_SIGNATURES]
                         if not hasattr(d, name)]
         checked = set()             # (sizeof export, index): several exports share a struct
         # the required rows come first, and each table's sizeof export before the rows that name a layout: it is bound by then
         for name, _, restype, argtypes, layout, sizeof in [row + ("hbvx_sizeof",) for row in SIGNATURES] + \
                 [row + ("hbvx_gage_pop_sizeof",) for row in GAGE_POP_SIGNATURES] + \
-                [row + ("hbvx_sizeof",) for row in ROUTE_ROWS_SIGNATURES] + \
+                [row + ("hbvx_sizeof",) for row in ROUTE_ROWS_SIGNATURES + LIVE_ROWS_SIGNATURES] + \
                 [row + ("hbvx_pop_fdc_sizeof",) for row in POP_FDC_SIGNATURES] + \
                 [row + ("hbvx_gage_events_sizeof",) for row in GAGE_EVENTS_SIGNATURES] + \
                 [row + ("hbvx_pop_events_sizeof",) for row in POP_EVENTS_SIGNATURES] + \
@@ -446,6 +452,19 @@ class Library:
     def backward(self, desc: Desc, io: BwdIO, stream: int):
         self._check(self.dll.hbvx_backward(C.byref(desc), C.byref(io), C.c_void_p(stream)),
                     "hbvx_backward")
+
+    def backward_live(self, desc: Desc, io: BwdIO, n_live4: int, stream: int) -> bool:
+        """hbvx_backward with io.grad_flux4 of n_live4 rows (include/hbvx_live_rows.h).  False: the library refused
+        the call before launching anything (HBVX_E_UNSUPPORTED: no kernel that knows about the missing rows takes
+        it) -- clear the dead rows of a [4,T,B] buffer and call `backward`."""
+        self.require("hbvx_backward_live")
+        if not 1 <= n_live4 <= 4:
+            raise ValueError(f"n_live4 must be 1 .. 4, got {n_live4}")
+        rc = self.dll.hbvx_backward_live(C.byref(desc), C.byref(io), n_live4, C.c_void_p(stream))
+        if rc == E_UNSUPPORTED:
+            return False
+        self._check(rc, "hbvx_backward_live")
+        return True
 
     def zero_rest(self, ptr: int, nbytes: int, state_ptr: int, stream: int):
         """Zero what the forward's launch left of FwdOut.zero_ptr (include/hbvx.h)."""

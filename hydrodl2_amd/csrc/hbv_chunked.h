@@ -172,7 +172,10 @@ __device__ __forceinline__ void chunk_pull_dyn(ChunkRaw<NP> &R, const float *lds
 // MU: the call carries learned ensemble weights (d.muwts) -- a template flag of the static and slot-list modes
 // (as a run-time flag it cost those instances 3-12 registers and the delta-MG default its fourth wave per SIMD); the
 // generic mode (DYN == 2) tests the pointer at run time, the "all" mode never has them.
-template <int NP, int DYN, bool GFULL, bool LDSDV = false, bool MU = false>
+// LIVE: rows of grad_flux4 that exist (hbvx_backward_live; the one-pass form with the runoff-only loss).  The rows
+// behind them are never loaded and count as the +0.0f the routing adjoint used to write there: 3 of a day's 12 loads
+// and their prefetch registers at the streamflow loss.  4: all four, where the pointer is given.
+template <int NP, int DYN, bool GFULL, bool LDSDV = false, bool MU = false, int LIVE = 4>
 __device__ __forceinline__ void chunk_issue(const hbvx_desc &d, const hbvx_bwd_io &io,
                                             const LaneId &L, int t, int nf, ChunkRaw<NP> &R,
                                             int nd, const int *dslot)
@@ -200,7 +203,10 @@ __device__ __forceinline__ void chunk_issue(const hbvx_desc &d, const hbvx_bwd_i
     for (int k = 0; k < HBVX_MAX_FLUX; k++) {
         R.gf[k] = 0.0f;
         if (GFULL && k < nf) R.gf[k] = io.grad_flux[k * fs + go];
-        if (k < 4) R.g4[k] = io.grad_flux4 ? io.grad_flux4[k * fs + go] : 0.0f;
+        if (k < 4) {
+            if (LIVE < 4) R.g4[k] = k < LIVE ? io.grad_flux4[k * fs + go] : 0.0f;   // (the host has checked the pointer)
+            else R.g4[k] = io.grad_flux4 ? io.grad_flux4[k * fs + go] : 0.0f;
+        }
     }
     R.mu = 0.0f;
     if (DYN == 1) {
@@ -498,98 +504,28 @@ struct OnepassRows {
     }
 };
 
-// Registers: 156 / 161 VGPRs (three waves per SIMD) with the runoff-only loss, 179 / 187 (two) with GFULL's full adjoint
-// step on the offset.  Forced to 128 (four waves) the compiler spills 19-33 values (runoff-only) and 84-98 (GFULL).
+// Registers: 156 / 163 VGPRs (three waves per SIMD) with the runoff-only loss, 180 / 188 (two) with GFULL's full adjoint
+// step on the offset (as built today; "156 / 161" and "179 / 187" stood here from an earlier state of the step code).
+//  Forced to 128 (four waves) the compiler spills 19-33 values (runoff-only) and 84-98 (GFULL).
 template <bool BETAET, bool GFULL>
 __global__ void __launch_bounds__(64 * ONEPASS_GMAX) __attribute__((amdgpu_waves_per_eu(GFULL ? 2 : 3)))
 k_bwd_chunk_onepass(const ChunkArgs A)
 {
-    extern __shared__ float onepass_slot[];
-    constexpr int MODEL = MODEL_HBV10, DYN = 0;
-    constexpr int NP = ChunkNP<MODEL, BETAET>::value;
-    typedef Step<MODEL, BETAET> S;
-    const int ds_[3] = {0, 0, 0};
-    const hbvx_desc &d = A.d;
-    const hbvx_bwd_io &io = A.io;
-    ChunkBlock blk;
-    if (!chunk_block(d, A.lgMp, A.per_xcd, blk)) return;
-    const LaneId L = lane_id(d, A.lgMp, blk.bx);
-    const int grp = blk.chunk;                                              // the block map deals groups
-    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);    // wave of the workgroup
-    const int nw = min(min(A.group, ONEPASS_GMAX), A.nchunk - grp * A.group);   // waves of this group with a chunk
-    const int chunk = grp * A.group + w;
-    const int t0 = chunk * A.C, t1 = min(d.T, t0 + A.C);
-    const int64_t N = (int64_t)d.B * d.M;
-    const bool raw = d.raw_sigmoid != 0;
-    const float nz = d.nearzero, invM = 1.0f / (float)d.M;
-    float usta[NP], psta[NP];
-    bool use_dyn[NP];
-    chunk_static<NP, DYN>(d, L, raw, usta, psta, use_dyn, 0, ds_);
+    constexpr int LIVE = 4;
+#include "hbv_onepass_body.h"
+}
 
-    float Phi[5][5], phi[5];
-    float G[6][NPARAM_MAX];   // G[k]: Jθ^T sums of the unit vector Phi[k]; G[5]: of the offset (entries never touched fold away)
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        phi[k] = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 5; i++) Phi[k][i] = (i == k) ? 1.0f : 0.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < 6; k++)
-#pragma unroll
-        for (int i = 0; i < NPARAM_MAX; i++) G[k][i] = 0.0f;
-    if (w < nw) {   // (a wave past the record's last chunk has no days: nothing to load)
-    ChunkRaw<NP> Rn;
-    chunk_issue<NP, DYN, GFULL>(d, io, L, t1 - 1, io.n_flux, Rn, 0, ds_);
-    for (int t = t1 - 1; t >= t0; t--) {
-        ChunkRaw<NP> Rc = Rn;
-        if (t > t0) chunk_issue<NP, DYN, GFULL>(d, io, L, t - 1, io.n_flux, Rn, 0, ds_);   // next day's loads in flight
-        ChunkDay<MODEL, BETAET, NP> D;
-        chunk_finish<MODEL, BETAET, NP, DYN, GFULL>(d, Rc, raw, nz, 0.0f, 0.0f, usta, psta, use_dyn, io.n_flux, invM,
-                                                    D, 0, ds_, io.grad_flux4 != nullptr);
-        const typename S::JT c = D.s.jt_coef(D.p, nz);
-        const typename S::JG k = D.s.jg_coef(D.p, nz);
-        S::template jt_gp<0>(c, k, Phi[0], G[0]);
-        S::template jt_gp<0>(c, k, Phi[1], G[1]);
-        S::template jt_gp<1>(c, k, Phi[2], G[2]);
-        S::template jt_gp<2>(c, k, Phi[3], G[3]);
-        S::template jt_gp<2>(c, k, Phi[4], G[4]);
-        if constexpr (!GFULL) {
-            S::template jt_gp<2, true>(c, k, phi, G[5], D.g.gQ0 + D.g.gQ, D.g.gQ1 + D.g.gQ, D.g.gQ2 + D.g.gQ);
-        } else {
-            float gx[3];
-            D.s.bwd(D.p, nz, D.g, phi, G[5], gx);   // its gp output is g0_c
-        }
-    }
-    }
-    OnepassRows<NP> rows{A.phi + ((int64_t)grp * 30) * N + L.n, A.gpart + ((int64_t)grp * onepass_rows(NP)) * N + L.n, N,
-                         L.active};
-    if (A.group == 1) {
-        onepass_put<float, NP>(Phi, phi, G, rows);
-        return;
-    }
-    // Hand-over, latest chunk first: the last wave with a chunk puts its map into the slot, then stage s belongs to wave
-    // s.  nw and s are the same for every wave of the workgroup, so all of them (those without a chunk too) meet at
-    // every barrier.
-    OnepassSlot<NP> slot{onepass_slot + (threadIdx.x & 63)};
-    if (w == nw - 1 && w > 0) onepass_put<float, NP>(Phi, phi, G, slot);
-    // (Written out stage by stage and nested, so that no stage tests nw again behind a barrier: as a loop over s, or as
-    // three tests in a row, the compiler lays branches back across the compositions and the day loop is no longer the
-    // kernel's largest loop.)
-    static_assert(ONEPASS_GMAX == 4, "one stage per wave above wave 0");
-    if (nw > 1) {
-        if (nw > 2) {
-            if (nw > 3) __syncthreads();                                      // stage 3: wave 3 has put its map
-            if (w == 2 && nw > 3) onepass_compose<float, NP, false>(slot, Phi, phi, G, slot);
-            __syncthreads();
-        }
-        if (w == 1 && nw > 2) onepass_compose<float, NP, false>(slot, Phi, phi, G, slot);
-        __syncthreads();
-    }
-    if (w == 0) {
-        if (nw == 1) onepass_put<float, NP>(Phi, phi, G, rows);
-        else onepass_compose<float, NP, true>(slot, Phi, phi, G, rows);
-    }
+// hbvx_backward_live (include/hbvx_live_rows.h): the runoff-only one-pass adjoint when only the leading LIVE of the
+// four rows of grad_flux4 exist -- one, at the streamflow loss.  The day loop issues LIVE loads of that buffer
+// instead of four and holds LIVE prefetch registers twice (Rn / Rc) instead of four; the sums keep the + 0.0f
+// of the rows that are gone, so every bit stays.  Registers: 148 / 159 VGPRs with one row, 156 / 161 with two,
+// 156 / 163 with three (three waves per SIMD, no scratch: tests/test_code_object_live_rows.py)
+template <bool BETAET, int LIVE>
+__global__ void __launch_bounds__(64 * ONEPASS_GMAX) __attribute__((amdgpu_waves_per_eu(3)))
+k_bwd_chunk_onepass_live(const ChunkArgs A)
+{
+    constexpr bool GFULL = false;
+#include "hbv_onepass_body.h"
 }
 
 #ifndef HBVX_CHUNK_NO_SHARED_KERNELS   // non-template kernels: defined in launch_chunked.hip only

@@ -48,9 +48,18 @@ namespace hbvx {
 #define PIPE_KT 8       // days per tile with at most PIPE_FEWDYN dynamic parameters (host and device)
 #endif
 #ifndef PIPE_KT_STATIC
-#define PIPE_KT_STATIC 10  // ... without any: no staged parameter rows in LDS, so longer tiles fit (140-145 KB of the 160) and
-#endif                     // the workgroup's barrier comes every ten days: forward 0.98 -> 0.91 ms at config 2, six rounds each
-                           // (profiles/r04_pipe_helpers_probe.txt; eleven days no longer fit)
+// ... without any: no staged parameter rows in LDS, so longer tiles fit and the workgroup's barrier comes less often:
+// ten days (eight before) took the forward from 0.98 to 0.91 ms at config 2, six rounds each
+// (profiles/r04_pipe_helpers_probe.txt).  Without the two saved-power rows of the soil tile (PipeLds: HBVX_SAVE_POW
+// builds only) eleven days fit, 154 KB of the 160: k_fwd_pipe 0.908 -> 0.858 ms per call at config 2 against this
+// kernel built with ten, two traces each (sd 0.02), the step 2.134 -> 2.082 ms in three alternating rounds
+// (profiles/r28_tile11_live_rows.md)
+#define PIPE_KT_STATIC (HBVX_SAVE_POW ? 10 : 11)
+#endif
+// ... the implicit scheme (HbvAdj) with static parameters stays at ten: its day is an iteration, not straight-line code,
+// and with eleven-day tiles its forward ran 3.22 -> 3.33 ms at 671 x 16 x 7 300 in three rounds out of three
+// (profiles/r28_tile11_live_rows.md).  The two-stage capillary models run eleven like HBV 1.0 (1.25 -> 1.24 ms: no loss)
+#define PIPE_KT_STATIC_ADJ 10
 #define PIPE_KT_MANY 4  // ... with more: the staged parameter rows need the LDS
 #define PIPE_FEWDYN 3   // rows staged one per filler wave
 #define PIPE_MAXDYN 18  // rows staged at most (shared by the three or four filler waves)
@@ -126,22 +135,28 @@ __device__ __forceinline__ void pipe_fill_role(const PipeArgs &A)
     }
 }
 
+// Rows per day of the soil stage's output tile: four fluxes (five with the capillary flux), SM, and -- only in
+// HBVX_SAVE_POW builds, whose drainers store them to aux -- the two saved powers sw0, ef0
+__host__ __device__ constexpr int pipe_soil_rows(bool cap) { return (cap ? 6 : 5) + (SAVE_POW ? 2 : 0); }
+
 // LDS layout in floats for Kt days per tile
 struct PipeLds {
     int xin, ab, bc, oa, ob, oc, pin, total;
-    __host__ __device__ explicit PipeLds(int Kt, int pd = 0, bool cap = false)
+    __host__ __device__ constexpr explicit PipeLds(int Kt, int pd = 0, bool cap = false)
+        : xin(0), ab(0), bc(0), oa(0), ob(0), oc(0), pin(0), total(0)
     {
-        const int obr = cap ? 8 : 7;   // + capillary flux
+        const int obr = pipe_soil_rows(cap);
         xin = 0;                    // [4][Kt][64][4]
         ab = xin + 4 * Kt * 256;    // [2][Kt][2][64]
         bc = ab + 2 * Kt * 128;     // [2][Kt][2][64]
         oa = bc + 2 * Kt * 128;     // [2][Kt][4][64]  SWE, tosoil | SNOWPACK, MELTWATER
-        ob = oa + 2 * Kt * 256;     // [2][Kt][7|8][64]  AET, recharge, excs, evapfactor (, capillary) | SM, sw0, ef0
+        ob = oa + 2 * Kt * 256;     // [2][Kt][obr][64]  AET, recharge, excs, evapfactor (, capillary) | SM (, sw0, ef0)
         oc = ob + 2 * Kt * obr * 64; // [2][Kt][7][64]  Qsim, Q0, Q1, Q2, PERC | SUZ, SLZ
         pin = oc + 2 * Kt * 448;    // [5][Kt][pd][64]  de-scaled dynamic parameters (pd rows per day)
         total = pin + 5 * Kt * pd * 64;
     }
 };
+static_assert(PipeLds(PIPE_KT_STATIC).total * 4 <= 160 * 1024, "a static three-stage tile must fit the 160 KB of a CU");
 
 // Drain work of the helper waves.  A stage's output tile holds NSER series per day: NFS flux series
 // first (global flux index = nibble i of FMAP), then NSER - NFS storage series.  Everything that
@@ -215,8 +230,8 @@ __global__ void __launch_bounds__(1024) k_fwd_pipe(const PipeArgs A)
     constexpr bool ADJ = MODEL == MODEL_HBVADJ;
     constexpr bool PIPE_NO_UNROLL = ADJ;   // a day of the implicit scheme is an iteration, not 70 straight-line instructions
     constexpr bool CAP = MODEL != MODEL_HBV10 && !ADJ;   // two-stage pipeline (see the header comment)
-    constexpr int KT = MANY ? PIPE_KT_MANY : (DYN ? PIPE_KT : PIPE_KT_STATIC);
-    constexpr int OBR = CAP ? 8 : 7, NFB = CAP ? 5 : 4;
+    constexpr int KT = MANY ? PIPE_KT_MANY : (DYN ? PIPE_KT : (ADJ ? PIPE_KT_STATIC_ADJ : PIPE_KT_STATIC));
+    constexpr int OBR = pipe_soil_rows(CAP), NFB = CAP ? 5 : 4;   // OBR: rows of the soil tile, NFB of them fluxes
 #ifdef PIPE_PROBE
     unsigned long long probe_busy = 0, probe_wait = 0, probe_t = __builtin_readcyclecounter();
     struct ProbeFlush {

@@ -9,6 +9,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared
 #include "hbvx_host.h"
 #include "../../include/hbvx_route_rows.h"
+#include "../../include/hbvx_live_rows.h"
 #include "hbv_step.h"
 #include "hbv_lane.h"
 #include "hbv_gage.h"
@@ -927,7 +928,9 @@ static int forward_dispatch(const hbvx_desc *d, const hbvx_fwd_out *out, void *s
     return HBVX_OK;
 }
 
-extern "C" int hbvx_backward(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream)
+// hbvx_backward (n_live = 4) and hbvx_backward_live: n_live = rows of io->grad_flux4 that exist.  Below 4 only the
+// one-pass static adjoint may take the call -- every other family reads four rows -- and a refusal launches nothing
+static int backward_impl(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int n_live)
 {
     int rc = check_desc(d);
     if (rc) return rc;
@@ -937,6 +940,9 @@ extern "C" int hbvx_backward(const hbvx_desc *d, const hbvx_bwd_io *io, void *st
     const int want_nf = (d->model == HBVX_MODEL_HBV10) ? 11 : 12;
     if (io->n_flux != want_nf) return fail(HBVX_E_SHAPE, "n_flux does not match model");
     if (d->T == 0) return HBVX_OK;
+    const bool live = n_live < 4;
+    if (live && (io->traj_layout != HBVX_TRAJ_ROWS || !io->grad_flux4))
+        return fail(HBVX_E_UNSUPPORTED, "live rows: row trajectory and grad_flux4 only");
     if (io->traj_layout != HBVX_TRAJ_ROWS) {
         if (HBVX_TRAJ_KIND(io->traj_layout) == HBVX_TRAJ_CKPT) {
             if (try_bwd_stream_ckpt(d, io, stream, &rc)) return rc;
@@ -947,8 +953,9 @@ extern "C" int hbvx_backward(const hbvx_desc *d, const hbvx_bwd_io *io, void *st
         if (try_bwd_stream(d, io, stream, &rc)) return rc;
         return fail(HBVX_E_UNSUPPORTED, "packed trajectory: no adjoint kernel for this call");
     }
-    if (try_bwd_stream(d, io, stream, &rc)) return rc;
-    if (try_bwd_chunked(d, io, stream, &rc)) return rc;
+    if (try_bwd_stream(d, io, stream, &rc, n_live)) return rc;
+    if (try_bwd_chunked(d, io, stream, &rc, n_live)) return rc;
+    if (live) return fail(HBVX_E_UNSUPPORTED, "live rows: the one-pass static adjoint does not take this call");
     if (try_bwd_tiled(d, io, stream, &rc)) return rc;
     BwdArgs a;
     a.d = *d;
@@ -964,6 +971,18 @@ extern "C" int hbvx_backward(const hbvx_desc *d, const hbvx_bwd_io *io, void *st
     });
     if (e != hipSuccess) return hip_fail(e, "hbvx_backward launch");
     return HBVX_OK;
+}
+
+extern "C" int hbvx_backward(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream)
+{
+    return backward_impl(d, io, stream, 4);
+}
+
+// include/hbvx_live_rows.h
+extern "C" int hbvx_backward_live(const hbvx_desc *d, const hbvx_bwd_io *io, int32_t n_live4, void *stream)
+{
+    if (n_live4 < 1 || n_live4 > 4) return fail(HBVX_E_SHAPE, "n_live4 must be 1 .. 4");
+    return backward_impl(d, io, stream, n_live4);
 }
 
 static int check_route(const hbvx_route_desc *r)

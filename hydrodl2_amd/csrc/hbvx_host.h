@@ -111,7 +111,9 @@ inline void store_gate(const hbvx_bwd_io *io, hipStream_t st)
 {
     if (io->store_gate) (void)hipStreamWaitEvent(st, (hipEvent_t)io->store_gate, 0);
 }
-bool try_bwd_stream(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc);
+// n_live: rows of io->grad_flux4 that exist (hbvx_backward_live, include/hbvx_live_rows.h); below 4 the streaming
+// adjoint, which reads four, refuses the call it would take (*rc = HBVX_E_UNSUPPORTED, nothing launched)
+bool try_bwd_stream(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc, int n_live = 4);
 // HBVX_TRAJ_CKPT with the segment in LDS (hbv_stream2_ckpt.h): whether it takes this problem (then no scratch is
 // wanted: hbvx_ckpt_workspace_bytes returns 0), and the launch
 bool stream_ckpt_applicable(const hbvx_desc *d, int K);
@@ -122,7 +124,8 @@ bool try_bwd_tiled(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int 
 // launch_chunked.hip
 bool chunked_applicable(const hbvx_desc *d);
 int chunk_days();
-bool try_bwd_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc);
+// n_live as for try_bwd_stream: below 4 only the one-pass runoff-only form takes the call, any other is refused
+bool try_bwd_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc, int n_live = 4);
 
 // launch_ckpt.hip
 bool try_bwd_ckpt(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc);

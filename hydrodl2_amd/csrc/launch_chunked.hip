@@ -69,9 +69,12 @@ static int onepass_group() { return std::min(std::max(env_int("HBVX_ONEPASS_GROU
 static std::atomic<int> g_onepass_group{0};
 extern "C" int hbvx_onepass_group(void) { return g_onepass_group.load(); }
 extern "C" int hbvx_onepass_slot_bytes(int n_param) { return onepass_slot_bytes(n_param); }
+// ... and the rows of grad_flux4 its day loop loaded: 4, or what hbvx_backward_live said (k_bwd_chunk_onepass_live)
+static std::atomic<int> g_onepass_live{0};
+extern "C" int hbvx_onepass_live_rows(void) { return g_onepass_live.load(); }
 
 template <int MODEL, bool BETAET, int DYN, bool GFULL>
-static hipError_t launch_chunked_t(const ChunkArgs &a, hipStream_t st, bool onepass)
+static hipError_t launch_chunked_t(const ChunkArgs &a, hipStream_t st, bool onepass, int n_live)
 {
     const hbvx_desc &d = a.d;
     const int bpw = 64 >> a.lgMp;
@@ -86,8 +89,17 @@ static hipError_t launch_chunked_t(const ChunkArgs &a, hipStream_t st, bool onep
             o.group = onepass_group();
             g_onepass_group = o.group;
             const int ngrp = (a.nchunk + o.group - 1) / o.group;
-            hipLaunchKernelGGL((k_bwd_chunk_onepass<BETAET, GFULL>), dim3((unsigned)(8 * a.per_xcd * ngrp)),
-                               dim3(64 * o.group), o.group > 1 ? onepass_slot_bytes(NP) : 0, st, o);
+            const dim3 og((unsigned)(8 * a.per_xcd * ngrp)), ob(64 * o.group);
+            const int olds = o.group > 1 ? onepass_slot_bytes(NP) : 0;
+            // hbvx_backward_live: the instance that loads only the rows of grad_flux4 that exist (runoff-only loss)
+            const int live = GFULL ? 4 : n_live;
+            g_onepass_live = live;
+            if constexpr (!GFULL) {
+                if (live == 1) hipLaunchKernelGGL((k_bwd_chunk_onepass_live<BETAET, 1>), og, ob, olds, st, o);
+                if (live == 2) hipLaunchKernelGGL((k_bwd_chunk_onepass_live<BETAET, 2>), og, ob, olds, st, o);
+                if (live == 3) hipLaunchKernelGGL((k_bwd_chunk_onepass_live<BETAET, 3>), og, ob, olds, st, o);
+            }
+            if (live >= 4) hipLaunchKernelGGL((k_bwd_chunk_onepass<BETAET, GFULL>), og, ob, olds, st, o);
             ChunkArgs s = a;            // scan and fold walk the groups' maps and boundary adjoints
             s.nchunk = ngrp;
             hipLaunchKernelGGL(k_bwd_chunk_scan, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, s);
@@ -167,12 +179,19 @@ static hipError_t launch_chunked_t(const ChunkArgs &a, hipStream_t st, bool onep
 }
 
 template <int DYN, bool GFULL>
-static hipError_t launch_chunked_v(const hbvx_desc *d, const ChunkArgs &a, hipStream_t st, bool onepass = false)
+static hipError_t launch_chunked_v(const hbvx_desc *d, const ChunkArgs &a, hipStream_t st, bool onepass = false,
+                                   int n_live = 4)
 {
-    return with_model(d, [&](auto m, auto be) { return launch_chunked_t<m, be, DYN, GFULL>(a, st, onepass); });
+    return with_model(d, [&](auto m, auto be) { return launch_chunked_t<m, be, DYN, GFULL>(a, st, onepass, n_live); });
 }
 
-static hipError_t launch_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, hipStream_t st)
+// Whether this call runs the one-pass form (HBVX_CHUNK_ONEPASS=0, a test / tool knob: the two-pass form instead)
+static bool onepass_takes(const hbvx_desc *d, const hbvx_bwd_io *io)
+{
+    return onepass_admitted(d) && !d->muwts && !io->grad_x && env_int("HBVX_CHUNK_ONEPASS", 1) != 0;
+}
+
+static hipError_t launch_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, hipStream_t st, int n_live)
 {
     ChunkArgs a;
     a.d = *d;
@@ -203,15 +222,20 @@ static hipError_t launch_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, hipS
                  d->p[i].dyn_t_stride == d->p[0].dyn_t_stride && d->p[i].dyn_b_stride == d->p[0].dyn_b_stride;
     if (alldyn) return gfull ? launch_chunked_v<3, true>(d, a, st) : launch_chunked_v<3, false>(d, a, st);
     if (ndyn > 0) return gfull ? launch_chunked_v<2, true>(d, a, st) : launch_chunked_v<2, false>(d, a, st);
-    // HBVX_CHUNK_ONEPASS=0 (test / tool knob): the two-pass form where the one-pass one would run
-    const bool onepass = onepass_admitted(d) && !d->muwts && !io->grad_x && env_int("HBVX_CHUNK_ONEPASS", 1) != 0;
-    return gfull ? launch_chunked_v<0, true>(d, a, st, onepass) : launch_chunked_v<0, false>(d, a, st, onepass);
+    const bool onepass = onepass_takes(d, io);
+    return gfull ? launch_chunked_v<0, true>(d, a, st, onepass) : launch_chunked_v<0, false>(d, a, st, onepass, n_live);
 }
 
-bool hbvx_host::try_bwd_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc)
+bool hbvx_host::try_bwd_chunked(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc, int n_live)
 {
     if (io->workspace && chunked_applicable(d) && io->workspace_bytes >= hbvx_backward_workspace_bytes(d)) {
-        hipError_t e = launch_chunked(d, io, (hipStream_t)stream);
+        // hbvx_backward_live: fewer than four rows of grad_flux4 -- only the one-pass form with the runoff-only loss
+        // knows (hbv_chunked.h, LIVE); every other kernel of this family reads four rows
+        if (n_live < 4 && !(onepass_takes(d, io) && !io->grad_flux)) {
+            *rc = fail(HBVX_E_UNSUPPORTED, "live rows: the one-pass static adjoint does not take this call");
+            return true;
+        }
+        hipError_t e = launch_chunked(d, io, (hipStream_t)stream, n_live);
         note_dispatch(1, "chunked");
         *rc = e != hipSuccess ? hip_fail(e, "hbvx_backward (chunked) launch") : HBVX_OK;
         return true;

@@ -5,6 +5,12 @@
 using namespace hbvx;
 using namespace hbvx_host;
 
+// Static parameters, PIPE_KT_STATIC days per tile: the three-stage tile (HBV 1.0; the implicit scheme has ten days) takes 157 696 B,
+// the two-stage one with the capillary row 163 328 B -- exactly LDS_BUDGET, 512 B under the CU's 160 KB.  A row or a
+// day more and the launcher below would hand those models to the tiled forward without a word: fail the build instead.
+static_assert(PipeLds(PIPE_KT_STATIC).total * 4 <= LDS_BUDGET && PipeLds(PIPE_KT_STATIC, 0, true).total * 4 <= LDS_BUDGET,
+              "static pipelined tiles must fit LDS_BUDGET with and without the capillary row");
+
 bool hbvx_host::try_fwd_pipe(const hbvx_desc *d, const hbvx_fwd_out *out, void *stream, int *rc)
 {
         // HBV 1.0 / 1.1p / 2.0, at most PIPE_MAXDYN dynamic parameters, flux requested: pipelined
@@ -16,7 +22,7 @@ bool hbvx_host::try_fwd_pipe(const hbvx_desc *d, const hbvx_fwd_out *out, void *
         const bool mu = d->muwts != nullptr && !adj;
         const int nd = count_dyn(d) + (mu ? 1 : 0);
         const bool many = nd > PIPE_FEWDYN;          // 4-day tiles, several staged rows per filler wave
-        const int Kt = many ? PIPE_KT_MANY : (nd > 0 ? PIPE_KT : PIPE_KT_STATIC);
+        const int Kt = many ? PIPE_KT_MANY : (nd > 0 ? PIPE_KT : (adj ? PIPE_KT_STATIC_ADJ : PIPE_KT_STATIC));
         const bool cap = d->model != HBVX_MODEL_HBV10 && !adj;
         const int nfl = adj ? 1 : (cap ? 12 : 11);
         // per-lane and per-tile byte offsets are 32-bit in the pipelined kernel

@@ -58,7 +58,7 @@ void go_bwd2c(bool gfull, int K, const StreamBwdArgs &sa, dim3 grid, hipStream_t
 
 } // namespace
 
-bool hbvx_host::try_bwd_stream(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc)
+bool hbvx_host::try_bwd_stream(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream, int *rc, int n_live)
 {
     // single-pass streaming adjoint, no workspace
     StreamPlan P = plan_stream(d);
@@ -75,6 +75,10 @@ bool hbvx_host::try_bwd_stream(const hbvx_desc *d, const hbvx_bwd_io *io, void *
         }
     } else if (!(ok && !adjoint_pinned_elsewhere() && P.wgs >= stream_min(true))) {
         return false;
+    }
+    if (n_live < 4) {   // hbvx_backward_live: this family reads four rows
+        *rc = fail(HBVX_E_UNSUPPORTED, "live rows: the streaming adjoint takes this call");
+        return true;
     }
     StreamBwdArgs sa;
     sa.d = *d;

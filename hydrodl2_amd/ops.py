@@ -483,6 +483,13 @@ def _cached(cfg: StepConfig, key, fn):
     return v
 
 
+def _live_rows(n_live4: int) -> int:
+    """Rows of a runoff-gradient buffer handed to hbvx_backward_live: the leading 1 .. 4 of [4,T,B]."""
+    if not isinstance(n_live4, int) or not 1 <= n_live4 <= 4:
+        raise ValueError(f"n_live4 must be an integer in 1 .. 4, got {n_live4!r}")
+    return n_live4
+
+
 def _route_desc(cfg: StepConfig, ptensors, S: int = 4) -> _abi.RouteDesc:
     r = _abi.RouteDesc()
     rs = cfg.route
@@ -724,13 +731,26 @@ class HbvPath(torch.autograd.Function):
                     big[-1] += row
 
         gq = None
+        have = [k for k, g in enumerate(g_rows) if g is not None]
+        # rows of gq the adjoint is told exist (hbvx_backward_live, include/hbvx_live_rows.h): below 4 the rows behind
+        # them are neither written nor read.  Asked for only where the one-pass static adjoint can take the call --
+        # Hbv with every parameter static, row trajectory, routed gradient alone -- and not again for a configuration
+        # the library has refused once (a grid the streaming adjoint takes, a knob that pins another family).
+        # gq keeps its four rows either way (an allocation from the cache, not a pass over memory): a refused call
+        # falls back to `gq[live4:].zero_()` and the four-row entry on the SAME buffer, so do not shrink it
+        live4 = 4
         if g_routed is not None and cfg.route is not None:
             r = _route_desc(cfg, ptensors, S=n_live)
             gq = _out((4, T, B), dev)
+            if (n_live < 4 and "hbvx_backward_live" not in lib.missing and not have and muwts is None
+                    and cfg.model == _abi.MODEL_HBV10 and ctx.traj_layout == _abi.TRAJ_ROWS
+                    and not ctx.needs_input_grad[1] and all(ps.dyn_off < 0 for ps in cfg.params)
+                    and not _cached(cfg, "live_rows_refused", list)):
+                live4 = n_live
             # the rows without a routed gradient must be zero: the routing adjoint's own launch writes them where the
             # library has hbvx_route_backward_rows, else a fill of its own before the call
-            in_launch = n_live < 4 and "hbvx_route_backward_rows" not in lib.missing
-            if n_live < 4 and not in_launch:
+            in_launch = live4 == 4 and n_live < 4 and "hbvx_route_backward_rows" not in lib.missing
+            if live4 == 4 and n_live < 4 and not in_launch:
                 gq[n_live:].zero_()
             rs = cfg.route
             gt = gp[rs.tensor_idx]
@@ -748,7 +768,6 @@ class HbvPath(torch.autograd.Function):
         # Which series carry gradient?  Only the four runoff series (the usual losses: streamflow,
         # with or without routing) -> a [4,T,B] buffer and the adjoint's 4-series kernels; anything
         # else -> the dense [n_flux,T,B] form.
-        have = [k for k, g in enumerate(g_rows) if g is not None]
         g_flux = None
         if have and max(have) < 4:
             if gq is None:
@@ -803,7 +822,17 @@ class HbvPath(torch.autograd.Function):
             fill_done = start_fill()           # beside the adjoint kernels, behind the routing adjoint
             if fill_done is not None and start_fill.gated:
                 io.store_gate = fill_done.cuda_event      # the storing kernel waits for the fill; the others do not
-        _call(lib, 'hbvx_backward', lib.backward, desc, io, stream)
+        if live4 < 4:
+            took = []
+            _call(lib, 'hbvx_backward', lambda *a: took.append(lib.backward_live(*a)),
+                  desc, io, _live_rows(live4), stream)
+            if not took[0]:
+                # refused before any launch: the dead rows as zeros after all, and the four-row call from now on
+                _cached(cfg, "live_rows_refused", list).append(True)
+                gq[live4:].zero_()
+                live4 = 4
+        if live4 == 4:
+            _call(lib, 'hbvx_backward', lib.backward, desc, io, stream)
         join()
 
         return (None, gx, None, gmu, None, None, *gp)
