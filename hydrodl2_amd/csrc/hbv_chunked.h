@@ -122,7 +122,8 @@ template <int NP>
 struct ChunkRaw {
     float f[3];      // P, T, PET
     float st[5];     // storages entering the day
-    float sw0, ef0;  // saved pow results (HBVX_SAVE_POW builds only)
+    float sw0, ef0;  // never read (they held the saved powers): the record keeps its size, without them 28 instances of
+                     // k_bwd_chunk_sweep allocate registers anew (profiles/r29_retire_saved_powers.md)
     float gf[HBVX_MAX_FLUX];
     float g4[4];     // the routing adjoint's share of the four runoff gradients (grad_flux4), added by chunk_finish
     float dv[NP];    // raw dynamic-parameter values
@@ -188,13 +189,7 @@ __device__ __forceinline__ void chunk_issue(const hbvx_desc &d, const hbvx_bwd_i
     const int64_t ks = (int64_t)(T + 1) * N;
 #pragma unroll
     for (int k = 0; k < 5; k++) R.st[k] = tp[k * ks];
-    if (SAVE_POW) {
-        const float *ap = io.aux + (int64_t)t * N + L.n;
-        R.sw0 = ap[0];
-        R.ef0 = ap[(int64_t)T * N];
-    } else {
-        R.sw0 = R.ef0 = 0.0f;   // recomputed by chunk_finish (HBVX_SAVE_POW, hbv_step.h)
-    }
+    R.sw0 = R.ef0 = 0.0f;
     const int64_t fs = (int64_t)T * d.B, go = (int64_t)t * d.B + L.b;
     // loads only, no arithmetic on what they return: an add here (gf + g4) made the compiler wait for every load of
     // the day at the spot where they had just been issued -- a full memory round trip per day instead of a prefetch
@@ -288,7 +283,7 @@ __device__ __forceinline__ void chunk_finish(const hbvx_desc &d, const ChunkRaw<
     }
 #pragma unroll
     for (int i = NP; i < NPARAM_MAX; i++) D.p[i] = 0.0f;
-    D.s.template fwd<SAVE_POW>(D.p, nz, ac, elev, R.sw0, R.ef0);
+    D.s.template fwd<false>(D.p, nz, ac, elev, 0.0f, 0.0f);
     D.gq = gf[HBVX_F_QSIM];
     const float wq = ((MU || DYN == 2) && d.muwts) ? R.mu : invM;
     D.g.gQ = D.gq * wq;

@@ -226,14 +226,14 @@ __global__ void __launch_bounds__(64) k_bwd_ckpt(const CkptBwdArgs A)
 // ---------------------------------------------------------------------------------------------
 // Re-materialisation for the block-wise adjoint (launch_ckpt.hip): one wavefront per (64 lanes,
 // K-day segment) of a block of days [t0, t0 + tb) steps forward from its checkpoint and writes the
-// block's trajectory rows [5, tb + 1, N] and powers [2, tb, N] (HBVX_TRAJ_ROWS, local day index) into
-// scratch.  All segments are independent: thousands of waves, no serial chain longer than K days.
+// block's trajectory rows [5, tb + 1, N] (HBVX_TRAJ_ROWS, local day index) into scratch.  All segments are
+// independent: thousands of waves, no serial chain longer than K days.
 // The regular adjoint kernels then run on the block as on a tb-day record.
 // ---------------------------------------------------------------------------------------------
 struct RematArgs {
     hbvx_desc d;          // the FULL problem (T, strides, parameter sources)
     const float *ckpt;    // [ceil(T/K), 5, N]
-    float *traj, *aux;    // scratch rows of the block
+    float *traj;          // scratch rows of the block
     int lgMp, K, t0, tb;
 };
 
@@ -299,10 +299,6 @@ __global__ void __launch_bounds__(64) k_ckpt_remat(const RematArgs A)
         if (L.active) {
 #pragma unroll
             for (int k = 0; k < 5; k++) A.traj[((int64_t)k * (tb + 1) + l) * N + L.n] = st[k];
-            if (SAVE_POW) {
-                A.aux[(int64_t)l * N + L.n] = s.sw0;
-                A.aux[((int64_t)tb + l) * N + L.n] = s.ef0;
-            }
         }
         st[0] = s.SP3; st[1] = s.MW3; st[2] = s.SM4; st[3] = s.SUZ4; st[4] = s.SLZ2;
     }

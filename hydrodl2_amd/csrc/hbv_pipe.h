@@ -14,7 +14,7 @@
 //   helpers (loads and stores share the in-order vmcnt counter, so no wave does both):
 //     filler        forcings of tile it+3 -> registers, tile it+2 registers -> LDS (never waits
 //                   for a load it has just issued)
-//     row drainers  storages / pow results of tiles it-1..it-3 -> trajectory / aux rows
+//     row drainers  storages of tiles it-1..it-3 -> trajectory rows
 //     reducers      ensemble means of tiles it-1..it-3 -> flux series
 //
 // The stepper waves are bound by vector-ALU issue: the soil wave keeps its SIMD's VALU ~90 % busy
@@ -50,11 +50,10 @@ namespace hbvx {
 #ifndef PIPE_KT_STATIC
 // ... without any: no staged parameter rows in LDS, so longer tiles fit and the workgroup's barrier comes less often:
 // ten days (eight before) took the forward from 0.98 to 0.91 ms at config 2, six rounds each
-// (profiles/r04_pipe_helpers_probe.txt).  Without the two saved-power rows of the soil tile (PipeLds: HBVX_SAVE_POW
-// builds only) eleven days fit, 154 KB of the 160: k_fwd_pipe 0.908 -> 0.858 ms per call at config 2 against this
-// kernel built with ten, two traces each (sd 0.02), the step 2.134 -> 2.082 ms in three alternating rounds
-// (profiles/r28_tile11_live_rows.md)
-#define PIPE_KT_STATIC (HBVX_SAVE_POW ? 10 : 11)
+// (profiles/r04_pipe_helpers_probe.txt).  Eleven days fit, 154 KB of the 160: k_fwd_pipe 0.908 -> 0.858 ms per call
+// at config 2 against this kernel built with ten, two traces each (sd 0.02), the step 2.134 -> 2.082 ms in three
+// alternating rounds (profiles/r28_tile11_live_rows.md)
+#define PIPE_KT_STATIC 11
 #endif
 // ... the implicit scheme (HbvAdj) with static parameters stays at ten: its day is an iteration, not straight-line code,
 // and with eleven-day tiles its forward ran 3.22 -> 3.33 ms at 671 x 16 x 7 300 in three rounds out of three
@@ -135,9 +134,8 @@ __device__ __forceinline__ void pipe_fill_role(const PipeArgs &A)
     }
 }
 
-// Rows per day of the soil stage's output tile: four fluxes (five with the capillary flux), SM, and -- only in
-// HBVX_SAVE_POW builds, whose drainers store them to aux -- the two saved powers sw0, ef0
-__host__ __device__ constexpr int pipe_soil_rows(bool cap) { return (cap ? 6 : 5) + (SAVE_POW ? 2 : 0); }
+// Rows per day of the soil stage's output tile: four fluxes (five with the capillary flux) and SM
+__host__ __device__ constexpr int pipe_soil_rows(bool cap) { return cap ? 6 : 5; }
 
 // LDS layout in floats for Kt days per tile
 struct PipeLds {
@@ -150,7 +148,7 @@ struct PipeLds {
         ab = xin + 4 * Kt * 256;    // [2][Kt][2][64]
         bc = ab + 2 * Kt * 128;     // [2][Kt][2][64]
         oa = bc + 2 * Kt * 128;     // [2][Kt][4][64]  SWE, tosoil | SNOWPACK, MELTWATER
-        ob = oa + 2 * Kt * 256;     // [2][Kt][obr][64]  AET, recharge, excs, evapfactor (, capillary) | SM (, sw0, ef0)
+        ob = oa + 2 * Kt * 256;     // [2][Kt][obr][64]  AET, recharge, excs, evapfactor (, capillary) | SM
         oc = ob + 2 * Kt * obr * 64; // [2][Kt][7][64]  Qsim, Q0, Q1, Q2, PERC | SUZ, SLZ
         pin = oc + 2 * Kt * 448;    // [5][Kt][pd][64]  de-scaled dynamic parameters (pd rows per day)
         total = pin + 5 * Kt * pd * 64;
@@ -212,7 +210,7 @@ __device__ __forceinline__ constexpr int pipe_sc_flag(int X)
 #define DY_LOAD(X, ptr) do { pn_##X = (ptr)[ix_##X]; } while (0)
 #define DY_USE(X) do { p[X] = dy_##X ? pn_##X : p[X]; } while (0)
 
-// TRAJ: the forward also saves the storage trajectory (and, in HBVX_SAVE_POW builds, the pow results: traj and aux given).
+// TRAJ: the forward also saves the storage trajectory.
 //   1: through LDS and row-drainer waves (the steppers touch only LDS + VALU);  2: the steppers store it themselves and
 //   every helper that is not a filler reduces (DIRECT below).  Measured (profiles/r04_ab_direct.txt): with 16 members
 //   (4 basins per wave, 5.5 reducer passes per 8-day tile) form 1 is 15 % faster -- a buffer store costs the lone
@@ -226,7 +224,7 @@ __global__ void __launch_bounds__(1024) k_fwd_pipe(const PipeArgs A)
 {
     // ADJ: the implicit scheme (hbv_adj.py) with the staged solve of hbv_adj_step.h -- its blocks snow -> soil
     // moisture -> upper / lower zone feed forward exactly like the explicit HBV 1.0 stages, so the same three
-    // waves run them one tile apart; flux = Q only, no saved powers
+    // waves run them one tile apart; flux = Q only
     constexpr bool ADJ = MODEL == MODEL_HBVADJ;
     constexpr bool PIPE_NO_UNROLL = ADJ;   // a day of the implicit scheme is an iteration, not 70 straight-line instructions
     constexpr bool CAP = MODEL != MODEL_HBV10 && !ADJ;   // two-stage pipeline (see the header comment)
@@ -298,7 +296,7 @@ __global__ void __launch_bounds__(1024) k_fwd_pipe(const PipeArgs A)
     // to reduce.  One descriptor per storage series and tile (base = the row of the tile's
     // first day, range = the tile's rows: only one tile has to fit 32 bits), day offset in the scalar operand, the
     // lane's offset constant, out-of-range lanes dropped by the hardware.
-    constexpr bool DIRECT = TRAJ == 2 && !SAVE_POW;
+    constexpr bool DIRECT = TRAJ == 2;
     const int64_t SRt = (int64_t)(T + 1) * N;
     auto trj_rsrc = [&](int k, int tile) {
         return A.ckptK ? __builtin_amdgcn_make_buffer_rsrc(o.traj, 0, -1, 0x00020000)
@@ -448,7 +446,7 @@ __global__ void __launch_bounds__(1024) k_fwd_pipe(const PipeArgs A)
                     }
                     float *q = ob + tt * OBR * 64;
                     q[0] = s.ET; q[64] = s.rech; q[128] = s.exc; q[192] = s.ef; q[256] = s.cap;
-                    if (TRAJ && !DIRECT) { q[320] = SM; if (SAVE_POW) { q[384] = s.sw0; q[448] = s.ef0; } }
+                    if (TRAJ && !DIRECT) q[320] = SM;
                     float *r = oc + tt * 448;
                     // (the weight is read where it is used: it only scales an OUTPUT, off the day-to-day chain, and a
                     // prefetch register for it pushed three instances of this stage over their 128)
@@ -523,7 +521,7 @@ __global__ void __launch_bounds__(1024) k_fwd_pipe(const PipeArgs A)
                         bc[tt * 128] = s.rech;
                         bc[tt * 128 + 64] = s.exc;
                         q[0] = s.ET; q[64] = s.rech; q[128] = s.exc; q[192] = s.ef;
-                        if (TRAJ) { if (DIRECT) trj_put(rSM, tile, tt, 2, SM); else { q[256] = SM; if (SAVE_POW) { q[320] = s.sw0; q[384] = s.ef0; } } }
+                        if (TRAJ) { if (DIRECT) trj_put(rSM, tile, tt, 2, SM); else q[256] = SM; }
                         SM = s.SM3;
                     }
                 };
@@ -787,7 +785,7 @@ __global__ void __launch_bounds__(1024) k_fwd_pipe(const PipeArgs A)
             PIPE_BARRIER();
             for (int it = 0; it < nIt; it++) PIPE_BARRIER();
         } else if (quad == 3 || (PIPE_Q1 == 2 && quad == 1 && TRAJ && !MANY)) {
-            // row drainers (waves 7, 11, 15): day tt of every stage tile -> 7 rows.  One buffer
+            // row drainers (waves 7, 11, 15): day tt of every stage tile -> 5 rows.  One buffer
             // descriptor per storage series and tile (base = row of the tile's first day, range =
             // the tile's Kt rows: the range check includes the scalar offset), the day inside the
             // tile goes into the scalar offset operand.
@@ -816,12 +814,11 @@ __global__ void __launch_bounds__(1024) k_fwd_pipe(const PipeArgs A)
                 const int64_t dA = (int64_t)max(tA, 0) * Kt * N, dB = (int64_t)max(tB, 0) * Kt * N,
                               dC = (int64_t)max(tC, 0) * Kt * N;
                 const auto rSP = rsrc(o.traj + dA), rMW = rsrc(o.traj + SR + dA);
-                const auto rSM = rsrc(o.traj + 2 * SR + dB), rSW = rsrc((SAVE_POW ? o.aux : o.traj) + dB),
-                           rEF = rsrc((SAVE_POW ? o.aux : o.traj) + (int64_t)T * N + dB);
+                const auto rSM = rsrc(o.traj + 2 * SR + dB);
                 const auto rSUZ = rsrc(o.traj + 3 * SR + dC), rSLZ = rsrc(o.traj + 4 * SR + dC);
                 if (A.ckptK) {
                     // checkpoints: of each stage tile only the days that are multiples of K, into
-                    // rows [(day / K) * 5 + storage]; the powers are not kept
+                    // rows [(day / K) * 5 + storage]
                     const int cK = A.ckptK;
                     const auto rall = __builtin_amdgcn_make_buffer_rsrc(o.traj, 0, -1, 0x00020000);
                     auto putc = [&](int day, int k, float v) {
@@ -844,19 +841,15 @@ __global__ void __launch_bounds__(1024) k_fwd_pipe(const PipeArgs A)
                 }
                 for (int tt = w; tt < Kt; tt += NRD) {
                     const unsigned soff = (unsigned)tt * row_bytes;
-                    float a0, a1, b0v, b1 = 0.0f, b2 = 0.0f, c0, c1;
+                    float a0, a1, b0v, c0, c1;
                     if (tt < ntA) { a0 = bufA[tt * 256 + 128]; a1 = bufA[tt * 256 + 192]; }
                     if (tt < ntB) {
                         const float *rb = bufB + (tt * OBR + NFB) * 64;
                         b0v = rb[0];
-                        if (SAVE_POW) { b1 = rb[64]; b2 = rb[128]; }
                     }
                     if (tt < ntC) { c0 = bufC[tt * 448 + 320]; c1 = bufC[tt * 448 + 384]; }
                     if (tt < ntA) { put(rSP, soff, a0); put(rMW, soff, a1); }
-                    if (tt < ntB) {
-                        put(rSM, soff, b0v);
-                        if (SAVE_POW && !ADJ) { put(rSW, soff, b1); put(rEF, soff, b2); }   // the implicit scheme keeps no powers
-                    }
+                    if (tt < ntB) put(rSM, soff, b0v);
                     if (tt < ntC) { put(rSUZ, soff, c0); put(rSLZ, soff, c1); }
                 }
                 PIPE_BARRIER();

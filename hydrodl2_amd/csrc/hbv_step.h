@@ -305,16 +305,9 @@ HBVX_HD float pow_unit_(float x, float y)
 #endif
 }
 
-// HBVX_SAVE_POW: whether the forward keeps the two pre-clamp powers of a lane-day, (SM/FC)**BETA and the
-// evaporation factor, next to the trajectory (hbvx_fwd_out.aux, 8 of 28 bytes per lane-day) for the adjoint.
-// That paid while a power cost ~16 dependent instructions; with pow_unit_ it is log, multiply, exp, and the adjoint
-// passes run beside a 3.8 GB gradient fill that wants the same HBM.  Default 0: nothing is
-// written to or read from `aux`, the adjoint recomputes both powers with the forward's own instruction sequence
-// -- the same bits, so every clamp predicate matches.  1 restores the saved rows (A/B builds only).
-#ifndef HBVX_SAVE_POW
-#define HBVX_SAVE_POW 0
+#ifdef HBVX_SAVE_POW
+#error "HBVX_SAVE_POW is retired: the adjoint always recomputes the two powers (profiles/r04_ab_savepow.txt)"
 #endif
-constexpr bool SAVE_POW = HBVX_SAVE_POW != 0;
 
 // HBVX_ADJ_FMA: the library is built with -ffp-contract=off because the FORWARD must round after every operator like the
 // reference does (thresholds branch on those roundings, and the adjoint's recomputation of the forward must land on the
@@ -442,7 +435,7 @@ struct Step {
         exc = fmax_(e0, 0.0f);
         SM2 = SM1 - exc;
         lpfc = LP * FC;
-        q = div_q_((CHAIN && !SAVE_POW) ? SM1 : SM2, lpfc);
+        q = div_q_(CHAIN ? SM1 : SM2, lpfc);
         if (BETAET) ef0 = USE_AUX ? aux_ef0 : pow_unit_(q, p[P_BETAET]);
         else ef0 = q;
         ef = fmin_(fmax_(ef0, 0.0f), 1.0f);

@@ -8,8 +8,8 @@
 // instruction, independent work at ~2.9; tools/micro/issue_rate.hip).  Hence:
 //
 //   * packed trajectory (HBVX_TRAJ_PACKED): per lane-day one 16-byte record (SP, MW, SM, SUZ) and one
-//     4-byte SLZ row (HBVX_SAVE_POW builds: plus one 8-byte record of the two saved powers) -- 2 (3) stores
-//     in the forward and 2 (3) loads in the adjoint instead of 5 + 5 (7 + 7), inside the same caller buffer;
+//     4-byte SLZ row -- 2 stores in the forward and 2 loads in the adjoint instead of 5 + 5, inside the same
+//     caller buffer;
 //   * one flux store per day: after the ensemble butterflies every lane of a basin holds every mean;
 //     member lane j keeps series j and the wave writes 12 series x 4 basins with ONE store;
 //   * the three forcings of a basin in one 12-byte load: the channels are a permutation of {0, 1, 2} and
@@ -157,7 +157,7 @@ __device__ __forceinline__ float s2_get(const float *p, int slot)
 #define STREAM2_ST_AUX 0   // cache policy of the forward's trajectory / flux stores (0 default, 2 nt, 17 sc0 sc1)
 #endif
 #ifndef STREAM2_EXP
-#define STREAM2_EXP 0    // dev experiments: 1 no flux store, 4 no trajectory stores, 8 / 16 / 32 no record / SLZ / powers store
+#define STREAM2_EXP 0    // dev experiments: 1 no flux store, 4 no trajectory stores, 8 / 16 no record / SLZ store
 #endif
 
 typedef float s2_f2 __attribute__((ext_vector_type(2)));
@@ -176,10 +176,6 @@ struct S2Buf {
     {
         return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0));
     }
-    static __device__ __forceinline__ s2_f2 ld2(__amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so)
-    {
-        return __builtin_bit_cast(s2_f2, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0));
-    }
     static __device__ __forceinline__ s2_f3 ld3(__amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so)
     {
         return __builtin_bit_cast(s2_f3, __builtin_amdgcn_raw_buffer_load_b96(r, vo, so, 0));
@@ -196,10 +192,6 @@ struct S2Buf {
     static __device__ __forceinline__ void sts(__amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so, float v)
     {
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, vo, so, STREAM2_ST_AUX);
-    }
-    static __device__ __forceinline__ void sts2(__amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so, s2_f2 v)
-    {
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), r, vo, so, STREAM2_ST_AUX);
     }
     static __device__ __forceinline__ void st2(__amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so, s2_f2 v)
     {
@@ -364,7 +356,7 @@ __device__ __forceinline__ float s2_ens_sum16(const float *f, bool b0, bool b1)
 }
 
 // ---------------------------------------------------------------------------------------------
-// forward.  TRJ: 0 nothing kept, 1 trajectory rows [5,T+1,N] + aux [2,T,N], 2 packed, 3 K-day
+// forward.  TRJ: 0 nothing kept, 1 trajectory rows [5,T+1,N], 2 packed, 3 K-day
 // checkpoints [ceil(T/K),5,N] (HBVX_TRAJ_CKPT; K a power of two).
 // XVEC: forcing channels are {0,1,2} and a basin's three values are adjacent (one 12-byte load).
 // ---------------------------------------------------------------------------------------------
@@ -443,19 +435,21 @@ k_fwd_stream2(const StreamArgs A)
     }
     // outputs
     const auto rflux = S2Buf::rsrc(o.flux);
-    const auto rtraj = S2Buf::rsrc(o.traj), raux = S2Buf::rsrc(o.aux ? o.aux : o.traj);
+    const auto rtraj = S2Buf::rsrc(o.traj);
     const float *const slz0 = o.traj + 4 * (int64_t)(T + 1) * N;   // packed layout: the SLZ rows
+    // avo: never read.  It held the offsets of the two saved-power rows; the eight bytes of private array stay because the
+    // compiler's inlining heuristics weigh a kernel's private arrays, and without them all 120 instances of this kernel
+    // come out with another register allocation (profiles/r29_retire_saved_powers.md): a measured change of its own
     unsigned tvo[5], avo[2];
 #pragma unroll
     for (int k = 0; k < 5; k++) tvo[k] = (TRJ == 1 && L.active) ? (unsigned)((k * (int64_t)(T + 1) * N + L.n) * 4) : OOB;
 #pragma unroll
-    for (int k = 0; k < 2; k++) avo[k] = (TRJ == 1 && L.active && o.aux) ? (unsigned)((k * (int64_t)T * N + L.n) * 4) : OOB;
+    for (int k = 0; k < 2; k++) avo[k] = OOB;
     const int ckK = TRJ == 3 ? HBVX_TRAJ_CKPT_DAYS(o.traj_layout) : 1;
     const int cklg = ckK == 16 ? 4 : (ckK == 8 ? 3 : 2);
     const unsigned cvo = (TRJ == 3 && L.active) ? (unsigned)(L.n * 4) : OOB;
     const unsigned pvo4 = (TRJ == 2 && L.active) ? (unsigned)(L.n * 16) : OOB;
     const unsigned pvo1 = (TRJ == 2 && L.active) ? (unsigned)(L.n * 4) : OOB;
-    const unsigned pvo2 = (TRJ == 2 && L.active && o.aux) ? (unsigned)(L.n * 8) : OOB;
     const unsigned row4 = (unsigned)(N * 4);
     const unsigned fT = (unsigned)((int64_t)T * B * 4), fB = (unsigned)(B * 4);
     // flux, Mp = 16 (the usual nmul): s2_ens_sum16 leaves one series per member lane, one ds_bpermute hands the
@@ -517,10 +511,6 @@ k_fwd_stream2(const StreamArgs A)
             const unsigned so = (unsigned)t * row4;
 #pragma unroll
             for (int k = 0; k < 5; k++) S2Buf::st(rtraj, tvo[k], so, st[k]);
-            if (SAVE_POW) {
-                S2Buf::st(raux, avo[0], so, s.sw0);
-                S2Buf::st(raux, avo[1], so, s.ef0);
-            }
         }
         if (TRJ == 3) {
             if ((t & (ckK - 1)) == 0) {   // wave-uniform
@@ -531,13 +521,11 @@ k_fwd_stream2(const StreamArgs A)
         }
         if (TRJ == 2 && !(STREAM2_EXP & 4)) {
             const s2_f4 rec = {st[0], st[1], st[2], st[3]};
-            const s2_f2 pw = {s.sw0, s.ef0};
             // the day's rows through descriptors rebased on them (64-bit scalar arithmetic): one row
             // has to fit a descriptor's 4 GiB, not the trajectory
             const int64_t tN = (int64_t)t * N;
             if (!(STREAM2_EXP & 8)) S2Buf::st4(S2Buf::words(o.traj + tN * 4), pvo4, 0u, rec);
             if (!(STREAM2_EXP & 16)) S2Buf::sts(S2Buf::rsrc(slz0 + tN), pvo1, 0u, st[4]);
-            if (SAVE_POW && !(STREAM2_EXP & 32)) S2Buf::sts2(S2Buf::rsrc(o.aux + tN * 2), pvo2, 0u, pw);
         }
         st[0] = s.SP3; st[1] = s.MW3; st[2] = s.SM4; st[3] = s.SUZ4; st[4] = s.SLZ2;
         const float act = L.active ? 1.0f : 0.0f;
@@ -719,19 +707,19 @@ k_bwd_stream2(const StreamBwdArgs A)
 #endif
     }
 
-    const auto rx = S2Buf::rsrc(d.x), rtraj = S2Buf::rsrc(io.traj), raux = S2Buf::rsrc(SAVE_POW ? io.aux : io.traj);
+    const auto rx = S2Buf::rsrc(d.x), rtraj = S2Buf::rsrc(io.traj);
     const float *const slz0 = io.traj + 4 * (int64_t)(T + 1) * N;   // packed layout: the SLZ rows
     const auto rgf = S2Buf::rsrc(io.grad_flux ? io.grad_flux : io.grad_flux4);
     const auto rg4 = S2Buf::rsrc(io.grad_flux4 ? io.grad_flux4 : io.grad_flux);
     const bool has_gf = io.grad_flux != nullptr, has_g4 = io.grad_flux4 != nullptr;
     const unsigned xvo = (unsigned)(L.b * d.x_b_stride * 4), xts = (unsigned)(d.x_t_stride * 4);
     const int cp = d.ch_prcp, ct = d.ch_tmean, ce = d.ch_pet;
-    unsigned tvo[5], avo[2];
+    unsigned tvo[5], avo[2];   // avo: never read, kept like the forward's (73 instances otherwise allocate registers anew)
 #pragma unroll
     for (int k = 0; k < 5; k++) tvo[k] = (unsigned)((k * (int64_t)(T + 1) * N + L.n) * 4);
 #pragma unroll
-    for (int k = 0; k < 2; k++) avo[k] = (unsigned)((k * (int64_t)T * N + L.n) * 4);
-    const unsigned pvo4 = (unsigned)(L.n * 16), pvo1 = (unsigned)(L.n * 4), pvo2 = (unsigned)(L.n * 8);
+    for (int k = 0; k < 2; k++) avo[k] = 0u;
+    const unsigned pvo4 = (unsigned)(L.n * 16), pvo1 = (unsigned)(L.n * 4);
     const unsigned row4 = (unsigned)(N * 4);
     const unsigned gvo = (unsigned)(L.b * 4);
     const unsigned fT = (unsigned)((int64_t)T * B * 4), fB = (unsigned)(B * 4);
@@ -776,7 +764,7 @@ k_bwd_stream2(const StreamBwdArgs A)
     // the day uses it (GF below) and only if `add4` -- never where the loads are issued: an add there made the compiler
     // wait for all of the day's loads on the spot (hbv_chunked.h::chunk_issue, profiles/r04_ab_chunk_prefetch.txt)
     struct In {
-        float fx[3], st[5], ax[2], gf[NG], g4[4], dv[ND > 0 ? ND : 1];
+        float fx[3], st[5], gf[NG], g4[4], dv[ND > 0 ? ND : 1];
         bool add4;
     };
     auto issue = [&](int t, In &I) {
@@ -795,16 +783,10 @@ k_bwd_stream2(const StreamBwdArgs A)
             const s2_f4 rec = S2Buf::ld4(S2Buf::rsrc(io.traj + tN * 4), pvo4, 0u);
             I.st[0] = rec.x; I.st[1] = rec.y; I.st[2] = rec.z; I.st[3] = rec.w;
             I.st[4] = S2Buf::ld(S2Buf::rsrc(slz0 + tN), pvo1, 0u);
-            if (SAVE_POW) {
-                const s2_f2 pw = S2Buf::ld2(S2Buf::rsrc(io.aux + tN * 2), pvo2, 0u);
-                I.ax[0] = pw.x; I.ax[1] = pw.y;
-            }
         } else {
 #pragma unroll
             for (int k = 0; k < 5; k++) I.st[k] = S2Buf::ld(rtraj, tvo[k], sr);
-            if (SAVE_POW) { I.ax[0] = S2Buf::ld(raux, avo[0], sr); I.ax[1] = S2Buf::ld(raux, avo[1], sr); }
         }
-        if (!SAVE_POW) I.ax[0] = I.ax[1] = 0.0f;
 #pragma unroll
         for (int k = 0; k < NG; k++) {
             I.gf[k] = 0.0f;
@@ -837,7 +819,7 @@ k_bwd_stream2(const StreamBwdArgs A)
             if (SC >= 3) s2_put<NP>(p, dsl[k], pv);
             else p[stream_slot<SC>(k)] = pv;
         }
-        s.template fwd<SAVE_POW>(p, nz, ac, elev, I.ax[0], I.ax[1]);
+        s.template fwd<false>(p, nz, ac, elev, 0.0f, 0.0f);
         FluxGrad g;
         auto GF = [&](int k) -> float {
             if (k >= NG) return 0.0f;
@@ -900,12 +882,12 @@ k_bwd_stream2(const StreamBwdArgs A)
     };
 
     if (D == 1 && STREAM2_LDSPF) {
-        // One day in flight, staged through LDS: rows of 64 lanes x (12 | 16 | 4 | 8 | 4...) bytes.  Per
+        // One day in flight, staged through LDS: rows of 64 lanes x (12 | 16 | 4 | 4...) bytes.  Per
         // day: wait for the DMA, pull the day's inputs into registers, re-arm the DMA for the day
         // before, compute.  Only ONE set of inputs occupies registers, and it dies as the step
         // consumes it.
         __shared__ s2_f4 l_rec[64];
-        __shared__ float l_x[64 * 4], l_st[5][64], l_ax[SAVE_POW ? 2 * 64 : 1], l_gf[NG][64], l_dv[ND > 0 ? ND : 1][64];
+        __shared__ float l_x[64 * 4], l_st[5][64], l_gf[NG][64], l_dv[ND > 0 ? ND : 1][64];
         const int ln = threadIdx.x & 63;
         auto arm = [&](int t) {
             const unsigned tc = (unsigned)max(t, 0);
@@ -921,19 +903,9 @@ k_bwd_stream2(const StreamBwdArgs A)
                 const int64_t tN = (int64_t)tc * N;
                 S2Buf::ld_lds<16>(S2Buf::rsrc(io.traj + tN * 4), l_rec, pvo4, 0u);
                 S2Buf::ld_lds<4>(S2Buf::rsrc(slz0 + tN), l_st[4], pvo1, 0u);
-                if (SAVE_POW) {
-                    // 8-byte LDS-DMA does not exist: the two saved powers travel as two 4-byte rows
-                    const auto rpw = S2Buf::rsrc(io.aux + tN * 2);
-                    S2Buf::ld_lds<4>(rpw, l_ax, pvo2, 0u);
-                    S2Buf::ld_lds<4>(rpw, l_ax + 64, pvo2 + 4u, 0u);
-                }
             } else {
 #pragma unroll
                 for (int k = 0; k < 5; k++) S2Buf::ld_lds<4>(rtraj, l_st[k], tvo[k], sr);
-                if (SAVE_POW) {
-                    S2Buf::ld_lds<4>(raux, l_ax, avo[0], sr);
-                    S2Buf::ld_lds<4>(raux, l_ax + 64, avo[1], sr);
-                }
             }
 #pragma unroll
             for (int k = 0; k < NG; k++) {
@@ -960,7 +932,6 @@ k_bwd_stream2(const StreamBwdArgs A)
 #pragma unroll
                 for (int k = 0; k < 5; k++) I.st[k] = l_st[k][ln];
             }
-            if (SAVE_POW) { I.ax[0] = l_ax[ln]; I.ax[1] = l_ax[64 + ln]; } else { I.ax[0] = I.ax[1] = 0.0f; }
             const unsigned sg = (unsigned)t * fB;
 #pragma unroll
             for (int k = 0; k < NG; k++) {

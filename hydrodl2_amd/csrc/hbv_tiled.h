@@ -28,6 +28,10 @@
 
 namespace hbvx {
 
+// Rows per day of the trajectory tile in LDS.  Rows 0..4 hold the storages; rows 5 and 6 are unused (they held the
+// two saved powers).  Shrinking the tile changes LDS footprint and occupancy: a measured change of its own.
+constexpr int TILE_TRAJ_ROWS = 7;
+
 struct TileGeom {
     int Kt;       // days per tile
     int ND;       // dynamic parameter slots
@@ -35,9 +39,9 @@ struct TileGeom {
     int in_sz;    // floats per input buffer
     int out_sz;   // floats per output buffer
     int off_pin;  // input buffer: physical dynamic parameters [Kt][NDm][64]
-    int off_tin;  // input buffer (adjoint): trajectory+aux [Kt][7][64]
+    int off_tin;  // input buffer (adjoint): trajectory [Kt][TILE_TRAJ_ROWS][64]
     int off_gin;  // input buffer (adjoint): flux gradients [Kt][NF][bpw]
-    int off_tout; // output buffer (forward): trajectory+aux [Kt][7][64]
+    int off_tout; // output buffer (forward): trajectory [Kt][TILE_TRAJ_ROWS][64]
     int off_xout; // output buffer (adjoint): forcing gradients [Kt][3][64]
     int off_mout; // output buffer (adjoint): muwts gradients [Kt][64]
     int lgMp;
@@ -234,7 +238,7 @@ __global__ void __launch_bounds__(512) k_fwd_tiled(const FwdTArgs A)
     const int nT = (T + Kt - 1) / Kt;
     const int64_t N = (int64_t)d.B * d.M;
     const bool raw = d.raw_sigmoid != 0;
-    const bool has_flux = o.flux != nullptr, has_traj = o.traj != nullptr, has_aux = SAVE_POW && o.aux != nullptr;
+    const bool has_flux = o.flux != nullptr, has_traj = o.traj != nullptr;
     const bool has_mu = DYN && d.muwts != nullptr;
 
     unsigned dmask = 0;
@@ -307,7 +311,7 @@ __global__ void __launch_bounds__(512) k_fwd_tiled(const FwdTArgs A)
                     AdjStep<BETAET> s;
                     s.P = fP; s.Tf = fT; s.PET = fE;
                     if (has_traj) {
-                        float *to = out + G.off_tout + tt * 7 * 64 + lane;
+                        float *to = out + G.off_tout + tt * TILE_TRAJ_ROWS * 64 + lane;
 #pragma unroll
                         for (int k = 0; k < 5; k++) to[k * 64] = st[k];
                     }
@@ -328,10 +332,9 @@ __global__ void __launch_bounds__(512) k_fwd_tiled(const FwdTArgs A)
                     s.SP = st[0]; s.MW = st[1]; s.SM = st[2]; s.SUZ = st[3]; s.SLZ = st[4];
                     s.template fwd<false, true>(p, nz, ac, elev, 0.f, 0.f);
                     if (has_traj) {
-                        float *to = out + G.off_tout + tt * 7 * 64 + lane;
+                        float *to = out + G.off_tout + tt * TILE_TRAJ_ROWS * 64 + lane;
 #pragma unroll
                         for (int k = 0; k < 5; k++) to[k * 64] = st[k];
-                        if (has_aux) { to[5 * 64] = s.sw0; to[6 * 64] = s.ef0; }
                     }
                     st[0] = s.SP3; st[1] = s.MW3; st[2] = s.SM4; st[3] = s.SUZ4; st[4] = s.SLZ2;
                     if (has_flux) {
@@ -413,17 +416,15 @@ __global__ void __launch_bounds__(512) k_fwd_tiled(const FwdTArgs A)
             if (has_traj) {
                 for (int tt = w; tt < nt; tt += NH) {
                     const int t = t0 + tt;
-                    const float *to = out + G.off_tout + tt * 7 * 64 + lane;
-                    float v[7];
+                    const float *to = out + G.off_tout + tt * TILE_TRAJ_ROWS * 64 + lane;
+                    // (rows 5 and 6 of v are never read; with v[5] the HBV 2.0 instance with dynamic parameters allocates
+                    // its registers anew, profiles/r29_retire_saved_powers.md)
+                    float v[TILE_TRAJ_ROWS];
 #pragma unroll
-                    for (int k = 0; k < 7; k++) v[k] = (k < 5 || has_aux) ? to[k * 64] : 0.0f;
+                    for (int k = 0; k < TILE_TRAJ_ROWS; k++) v[k] = k < 5 ? to[k * 64] : 0.0f;
                     if (L.active) {
 #pragma unroll
                         for (int k = 0; k < 5; k++) o.traj[((int64_t)k * (T + 1) + t) * N + L.n] = v[k];
-                        if (has_aux) {
-                            o.aux[((int64_t)0 * T + t) * N + L.n] = v[5];
-                            o.aux[((int64_t)1 * T + t) * N + L.n] = v[6];
-                        }
                     }
                 }
             }
@@ -543,9 +544,8 @@ __global__ void __launch_bounds__((bwd_tiled_threads<MODEL, DYN>())) k_bwd_tiled
 #pragma unroll
                 for (int i = 0; i < NP; i++)
                     if ((dmask >> i) & 1) p[i] = pr[dyn_index(dmask, i) * 64];
-                const float *tr = tin + tt * 7 * 64 + lane;
+                const float *tr = tin + tt * TILE_TRAJ_ROWS * 64 + lane;
                 s.SP = tr[0]; s.MW = tr[64]; s.SM = tr[128]; s.SUZ = tr[192]; s.SLZ = tr[256];
-                const float sw0 = SAVE_POW ? tr[320] : 0.0f, ef0 = SAVE_POW ? tr[384] : 0.0f;
                 const float *gr = gin + tt * NG * bpw + L.bl;
                 FluxGrad g;
                 const float gq = gr[HBVX_F_QSIM * bpw];
@@ -562,7 +562,7 @@ __global__ void __launch_bounds__((bwd_tiled_threads<MODEL, DYN>())) k_bwd_tiled
                 g.gtosoil = GFULL ? gr[HBVX_F_TOSOIL * bpw] : 0.0f;
                 g.gPERC = GFULL ? gr[HBVX_F_PERC * bpw] : 0.0f;
                 g.gcap = (GFULL && NF > HBVX_F_CAPILLARY) ? gr[(NF - 1) * bpw] : 0.0f;
-                s.template fwd<SAVE_POW>(p, nz, ac, elev, sw0, ef0);
+                s.template fwd<false>(p, nz, ac, elev, 0.0f, 0.0f);
                 float gp[NPARAM_MAX], gx[3];
 #pragma unroll
                 for (int i = 0; i < NPARAM_MAX; i++) gp[i] = 0.0f;
@@ -632,24 +632,18 @@ __global__ void __launch_bounds__((bwd_tiled_threads<MODEL, DYN>())) k_bwd_tiled
                 const float *xr = xb + (int64_t)t * d.x_t_stride;
                 float4 f;
                 f.x = xr[d.ch_prcp]; f.y = xr[d.ch_tmean]; f.z = xr[d.ch_pet]; f.w = 0.0f;
-                float tv[7];
+                float tv[5];
 #pragma unroll
                 for (int k = 0; k < 5; k++) tv[k] = io.traj[((int64_t)k * (T + 1) + t) * N + L.n];
-                if (SAVE_POW) {
-                    tv[5] = io.aux[((int64_t)0 * T + t) * N + L.n];
-                    tv[6] = io.aux[((int64_t)1 * T + t) * N + L.n];
-                } else {
-                    tv[5] = tv[6] = 0.0f;
-                }
                 float rv[NP];
 #pragma unroll
                 for (int i = 0; i < NP; i++)
                     rv[i] = ((dmask >> i) & 1) ? dynp[i][(int64_t)t * d.p[i].dyn_t_stride] : 0.0f;
                 float muv = has_mu ? mu[(int64_t)t * d.mu_t_stride] : 0.0f;
                 in4[tt * 64 + lane] = f;
-                float *tr = tin + tt * 7 * 64 + lane;
+                float *tr = tin + tt * TILE_TRAJ_ROWS * 64 + lane;
 #pragma unroll
-                for (int k = 0; k < (SAVE_POW ? 7 : 5); k++) tr[k * 64] = tv[k];
+                for (int k = 0; k < 5; k++) tr[k * 64] = tv[k];
                 float *pr = pin + tt * G.NDm * 64 + lane;
 #pragma unroll
                 for (int i = 0; i < NP; i++)

@@ -57,7 +57,7 @@ extern "C" const char *hbvx_last_dispatch(int direction)
 
 extern "C" int hbvx_version(void) { return HBVX_ABI_VERSION; }
 extern "C" const char *hbvx_last_error(void) { return g_err; }
-extern "C" const char *hbvx_backend(void) { return hbvx::SAVE_POW ? "hip:gfx950+savepow" : "hip:gfx950"; }
+extern "C" const char *hbvx_backend(void) { return "hip:gfx950"; }
 extern "C" uint64_t hbvx_sizeof(int which)
 {
     switch (which) {
@@ -175,10 +175,6 @@ __global__ void __launch_bounds__(64) k_fwd(const FwdArgs A)
 #pragma unroll
             for (int k = 0; k < 5; k++) o.traj[((int64_t)k * (T + 1) + t) * N + L.n] = st[k];
         }
-        if (SAVE_POW && o.aux && L.active) {
-            o.aux[((int64_t)0 * T + t) * N + L.n] = s.sw0;
-            o.aux[((int64_t)1 * T + t) * N + L.n] = s.ef0;
-        }
         st[0] = s.SP3; st[1] = s.MW3; st[2] = s.SM4; st[3] = s.SUZ4; st[4] = s.SLZ2;
 
         if (o.flux) {
@@ -277,8 +273,6 @@ __global__ void __launch_bounds__(64) k_bwd(const BwdArgs A)
         s.SM = io.traj[((int64_t)2 * (T + 1) + t) * N + L.n];
         s.SUZ = io.traj[((int64_t)3 * (T + 1) + t) * N + L.n];
         s.SLZ = io.traj[((int64_t)4 * (T + 1) + t) * N + L.n];
-        const float sw0 = SAVE_POW ? io.aux[((int64_t)0 * T + t) * N + L.n] : 0.0f;
-        const float ef0 = SAVE_POW ? io.aux[((int64_t)1 * T + t) * N + L.n] : 0.0f;
         float ud[NP];
 #pragma unroll
         for (int i = 0; i < NP; i++) {
@@ -292,7 +286,7 @@ __global__ void __launch_bounds__(64) k_bwd(const BwdArgs A)
                 }
             }
         }
-        s.template fwd<SAVE_POW>(p, nz, ac, elev, sw0, ef0);
+        s.template fwd<false>(p, nz, ac, elev, 0.0f, 0.0f);
 
         FluxGrad g;
         const int64_t fs = (int64_t)T * d.B;
@@ -936,7 +930,6 @@ static int backward_impl(const hbvx_desc *d, const hbvx_bwd_io *io, void *stream
     if (rc) return rc;
     if (d->model == HBVX_MODEL_HBVADJ) return fail(HBVX_E_UNSUPPORTED, "use hbvx_adj_backward for HBVADJ");
     if (!io || !io->traj) return fail(HBVX_E_NULL, "traj is NULL");
-    if (SAVE_POW && !io->aux && HBVX_TRAJ_KIND(io->traj_layout) != HBVX_TRAJ_CKPT) return fail(HBVX_E_NULL, "aux is NULL");
     const int want_nf = (d->model == HBVX_MODEL_HBV10) ? 11 : 12;
     if (io->n_flux != want_nf) return fail(HBVX_E_SHAPE, "n_flux does not match model");
     if (d->T == 0) return HBVX_OK;

@@ -34,8 +34,6 @@ int lg_members(int M);
 int count_dyn(const hbvx_desc *d);
 bool use_tiled(const hbvx_desc *d);      // false under HBVX_KERNEL=simple
 int check_desc(const hbvx_desc *d);
-// whether this call's aux pointers are consistent with its trajectory: only HBVX_SAVE_POW builds look at aux at all
-inline bool aux_matches_traj(const hbvx_fwd_out *out) { return !hbvx::SAVE_POW || ((out->traj != nullptr) == (out->aux != nullptr)); }
 
 static const int LDS_BUDGET = 160 * 1024 - 512; // gfx950: 160 KiB per CU, one workgroup may take it all
 

@@ -15,9 +15,8 @@ using namespace hbvx_host;
 
 namespace {
 
-// Days per block.  The block's scratch is 5 (Tb + 1) N floats of re-materialised trajectory (20 bytes per lane-day;
-// 28 in HBVX_SAVE_POW builds) plus the inner adjoint's own workspace: 16 GB for 512 days of 1.6 M lanes -- not
-// "lean".  So the block is sized by BYTES: at most HBVX_CKPT_SCRATCH_MB (default 2048) of trajectory scratch, at
+// Days per block.  The block's scratch is 5 (Tb + 1) N floats of re-materialised trajectory (20 bytes per lane-day)
+// plus the inner adjoint's own workspace: 16 GB for 512 days of 1.6 M lanes -- not "lean".  So the block is sized by BYTES: at most HBVX_CKPT_SCRATCH_MB (default 2048) of trajectory scratch, at
 // most HBVX_CKPT_BLOCK (default 512) days, a multiple of K.  Short blocks cost launches (4 kernels per block), so
 // the block is at least 8 K days while the byte budget allows it; when it does not (1.6 M lanes at K = 16: 67
 // days) the budget wins down to a floor of 2 K days -- the bound include/hbvx.h states is kept.
@@ -26,7 +25,7 @@ int block_days(const hbvx_desc *d, int K)
     int tb = env_int("HBVX_CKPT_BLOCK", 512);
     const uint64_t N = (uint64_t)d->B * d->M;
     const uint64_t budget = (uint64_t)env_int("HBVX_CKPT_SCRATCH_MB", 2048) << 20;
-    const uint64_t by_bytes = budget / ((SAVE_POW ? 28 : 20) * (N ? N : 1));
+    const uint64_t by_bytes = budget / (20 * (N ? N : 1));
     if (tb < 8 * K) tb = 8 * K;
     if ((uint64_t)tb > by_bytes) tb = (int)by_bytes;
     if (tb < 2 * K) tb = 2 * K;
@@ -57,7 +56,7 @@ hipError_t copy_window(const float *in, float *out, int S, int tb, int T, int B,
 
 struct Plan {
     int Tb;
-    uint64_t traj, aux, gf, g4, carry, inner, total;   // byte sizes; total = sum, 256-byte aligned parts
+    uint64_t traj, gf, g4, carry, inner, total;   // byte sizes; total = sum, 256-byte aligned parts
 };
 
 uint64_t al(uint64_t v) { return (v + 255) & ~(uint64_t)255; }
@@ -68,14 +67,13 @@ Plan plan(const hbvx_desc *d, int K)
     P.Tb = block_days(d, K);
     const uint64_t N = (uint64_t)d->B * d->M, nf = d->model == HBVX_MODEL_HBV10 ? 11 : 12;
     P.traj = al(5 * (uint64_t)(P.Tb + 1) * N * 4);
-    P.aux = SAVE_POW ? al(2 * (uint64_t)P.Tb * N * 4) : 0;   // the block's saved powers (HBVX_SAVE_POW builds only)
     P.gf = al(nf * (uint64_t)P.Tb * d->B * 4);
     P.g4 = al(4 * (uint64_t)P.Tb * d->B * 4);
     P.carry = al(5 * N * 4);
     hbvx_desc sub = *d;
     sub.T = P.Tb;
     P.inner = al(hbvx_backward_workspace_bytes(&sub));
-    P.total = P.traj + P.aux + P.gf + P.g4 + 2 * P.carry + P.inner;
+    P.total = P.traj + P.gf + P.g4 + 2 * P.carry + P.inner;
     return P;
 }
 
@@ -104,7 +102,6 @@ bool hbvx_host::try_bwd_ckpt(const hbvx_desc *d, const hbvx_bwd_io *io, void *st
     if (io->workspace && io->workspace_bytes >= P.total && env_int("HBVX_CKPT_BLOCKWISE", 1) != 0) {
         char *w = (char *)io->workspace;
         float *s_traj = (float *)w; w += P.traj;
-        float *s_aux = (float *)w; w += P.aux;
         float *s_gf = (float *)w; w += P.gf;
         float *s_g4 = (float *)w; w += P.g4;
         float *carry[2] = {(float *)w, (float *)(w + P.carry)};
@@ -119,7 +116,6 @@ bool hbvx_host::try_bwd_ckpt(const hbvx_desc *d, const hbvx_bwd_io *io, void *st
             ra.d = *d;
             ra.ckpt = io->traj;
             ra.traj = s_traj;
-            ra.aux = s_aux;
             ra.lgMp = lg; ra.K = K; ra.t0 = t0; ra.tb = tb;
             const dim3 grid(W, (unsigned)((tb + K - 1) / K));
             with_model(d, [&](auto m, auto be) { hipLaunchKernelGGL((k_ckpt_remat<m, be>), grid, dim3(64), 0, st, ra); });
@@ -138,7 +134,6 @@ bool hbvx_host::try_bwd_ckpt(const hbvx_desc *d, const hbvx_bwd_io *io, void *st
             sd.state_in = nullptr;
             hbvx_bwd_io si = *io;
             si.traj = s_traj;
-            si.aux = s_aux;
             si.traj_layout = HBVX_TRAJ_ROWS;
             si.grad_flux = io->grad_flux ? s_gf : nullptr;
             si.grad_flux4 = io->grad_flux4 ? s_g4 : nullptr;

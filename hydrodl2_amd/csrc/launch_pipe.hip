@@ -47,13 +47,13 @@ bool hbvx_host::try_fwd_pipe(const hbvx_desc *d, const hbvx_fwd_out *out, void *
                             d->model == HBVX_MODEL_HBV20 || d->model == HBVX_MODEL_HOURLY ||
                             (adj && d->adj_stop == 2 && !many);
         const size_t lds = (size_t)PipeLds(Kt, nd > 0 ? (many ? nd : PIPE_FEWDYN) : 0, cap).total * 4;
-        // HBVX_TRAJ_CKPT: the row drainers keep every K-th day only (no powers)
+        // HBVX_TRAJ_CKPT: the row drainers keep every K-th day only
         const int ckpt_k = (out->traj && HBVX_TRAJ_KIND(out->traj_layout) == HBVX_TRAJ_CKPT)
                                ? HBVX_TRAJ_CKPT_DAYS(out->traj_layout) : 0;
         const bool ckpt_fits = !ckpt_k || ((int64_t)((d->T + ckpt_k - 1) / ckpt_k) * 5 * d->B * d->M * 4 < (int64_t)1 << 32);
         if (ckpt_fits && use_tiled(d) && !(fv && !strcmp(fv, "tiled")) && pmodel && off32 && day_outer &&
             nd <= PIPE_MAXDYN && (int)lds <= LDS_BUDGET && wgs_p < 4096 && !(adj && d->muwts) && (out->flux || adj) && d->T >= 4 * Kt &&
-            (adj ? !ckpt_k : (ckpt_k ? true : aux_matches_traj(out))) &&
+            !(adj && ckpt_k) &&
             (int64_t)d->B * d->M * 4 * Kt < (int64_t)1 << 31 &&
             (int64_t)nfl * d->T * d->B * 4 < (int64_t)1 << 31) {
             PipeArgs pa;
@@ -92,7 +92,7 @@ bool hbvx_host::try_fwd_pipe(const hbvx_desc *d, const hbvx_fwd_out *out, void *
             // who stores the trajectory (hbv_pipe.h, TRAJ): the steppers themselves where the reducers are the busy
             // helpers -- 8 or more basins per wave (ensembles of at most 8 members); HBVX_PIPE_DIRECT=0|1 pins it (tools)
             const int dflag = env_int("HBVX_PIPE_DIRECT", -1);
-            const bool direct = !SAVE_POW && (dflag >= 0 ? dflag != 0 : bpw_p >= 8);
+            const bool direct = dflag >= 0 ? dflag != 0 : bpw_p >= 8;
             hipStream_t st = (hipStream_t)stream;
             // compile-time dynamic sets (hbv_pipe.h, SC): {BETA, BETAET} and {BETA, K0, BETAET}
             unsigned dmask = 0;

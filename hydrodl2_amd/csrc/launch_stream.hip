@@ -54,8 +54,7 @@ bool hbvx_host::try_fwd_stream(const hbvx_desc *d, const hbvx_fwd_out *out, void
         // checkpoints: the offsets of the checkpoint rows must fit 32 bits
         if (!(P.ok && out->flux && P.packed_ok)) return false;
     }
-    // also a trajectory without the saved powers (inference that keeps the state series)
-    bool ok = P.ok && out->flux && (!SAVE_POW || out->traj || !out->aux);
+    bool ok = P.ok && out->flux;
     if (out->traj && !packed && !ckpt) ok = ok && P.rows_ok;
     if (packed) {
         if (!(ok && P.packed_ok)) {

@@ -24,7 +24,7 @@ static bool geom_fwd(const hbvx_desc *d, const hbvx_fwd_out *o, TileGeom &g)
         g.off_pin = Kt * 256;
         g.in_sz = Kt * (256 + g.NDm * 64);
         g.off_tout = Kt * 64 * (o->flux ? NF : 0);
-        g.out_sz = g.off_tout + Kt * 64 * (o->traj ? 7 : 0);
+        g.out_sz = g.off_tout + Kt * 64 * (o->traj ? TILE_TRAJ_ROWS : 0);
         if (g.out_sz == 0) g.out_sz = 4;
         if (2 * (g.in_sz + g.out_sz) * 4 <= LDS_BUDGET) return true;
     }
@@ -45,7 +45,7 @@ static bool geom_bwd(const hbvx_desc *d, const hbvx_bwd_io *io, TileGeom &g)
         g.Kt = Kt;
         g.off_pin = Kt * 256;
         g.off_tin = g.off_pin + Kt * g.NDm * 64;
-        g.off_gin = g.off_tin + Kt * 7 * 64;
+        g.off_gin = g.off_tin + Kt * TILE_TRAJ_ROWS * 64;
         g.in_sz = (g.off_gin + Kt * NF * bpw + 3) & ~3;
         g.off_xout = Kt * 64 * g.ND;
         g.off_mout = g.off_xout + Kt * 64 * (io->grad_x ? 3 : 0);

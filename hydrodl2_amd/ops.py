@@ -585,17 +585,13 @@ def _hbv_forward(ctx, cfg: StepConfig, x, state_in, muwts, ac, elev, ptensors):
     if ckpt:
         # K-day checkpoints [ceil(T/K), 5, N] instead of the trajectory; the adjoint recomputes
         traj = _out(((T + ckpt - 1) // ckpt * 5, B * M), dev)
-        aux = None
         layout = _abi.TRAJ_CKPT | (ckpt << 8)
     else:
         traj = _out((5, T + 1, B * M), dev) if keep else None
-        # the two saved powers per lane-day: only for A/B builds of the library with -DHBVX_SAVE_POW=1
-        # (csrc/hbv_step.h); the default build recomputes them in the adjoint and never touches `aux`
-        aux = _out((2, T, B * M), dev) if (needs_grad and lib.saves_pow) else None
         layout = (_cached(cfg, ("layout", x.stride(0), x.stride(1)), lambda: lib.preferred_traj_layout(desc))
                   if (keep and cfg.want_flux) else _abi.TRAJ_ROWS)
     out.flux, out.state_out = _ptr(flux), _ptr(state_out)
-    out.traj, out.aux = _ptr(traj), _ptr(aux)
+    out.traj = _ptr(traj)      # (out.aux stays NULL: the library neither writes nor reads it)
     out.n_flux, out.traj_layout = cfg.n_flux, layout
     ctx.early_gp = None
     if needs_grad and cfg.want_flux and any(ctx.needs_input_grad[6:]):
@@ -625,7 +621,7 @@ def _hbv_forward(ctx, cfg: StepConfig, x, state_in, muwts, ac, elev, ptensors):
     ctx.has_bfi = bfi is not None
     ctx.set_materialize_grads(False)
     if needs_grad:
-        ctx.save_for_backward(x, state_in, muwts, ac, elev, traj, aux, flux, uh, routed, *ptensors)
+        ctx.save_for_backward(x, state_in, muwts, ac, elev, traj, flux, uh, routed, *ptensors)
     # Under a forward-AD level the final storages carry a tangent (HbvPath.jvp): a state warm-up hands it to the
     # main call.  Otherwise they are a non-differentiable output, as always.
     fwd_ad = _fwAD._current_level >= 0 and not isinstance(ctx, _NoCtx)
@@ -674,7 +670,7 @@ class HbvPath(torch.autograd.Function):
         if g_bfi is not None:
             # the gradient a streamflow loss never asks for: two broadcasts in torch, added to the series' own
             saved_ = ctx.saved_tensors
-            flux_, routed_ = saved_[7], saved_[9]
+            flux_, routed_ = saved_[6], saved_[8]
             src = routed_ if routed_ is not None else flux_
             qs, q2 = src[0], src[3 if routed_ is not None else _abi.F_Q2]
             den = qs.sum(0) + ctx.cfg.nearzero
@@ -700,8 +696,8 @@ class HbvPath(torch.autograd.Function):
         lib = get_library()
         cfg: StepConfig = ctx.cfg
         saved = ctx.saved_tensors
-        x, state_in, muwts, ac, elev, traj, aux, flux, uh = saved[:9]
-        ptensors = saved[10:]
+        x, state_in, muwts, ac, elev, traj, flux, uh = saved[:8]
+        ptensors = saved[9:]
         dev = x.device
         T, B, M = cfg.T, cfg.B, cfg.M
         stream = _stream_of(lib, x)
@@ -780,7 +776,7 @@ class HbvPath(torch.autograd.Function):
                 g_flux[k] = g_rows[k]
 
         io = _abi.BwdIO()
-        io.traj, io.aux = _ptr(traj), _ptr(aux)
+        io.traj = _ptr(traj)
         io.grad_flux, io.grad_flux4 = _ptr(g_flux), _ptr(gq)
         io.n_flux, io.traj_layout = cfg.n_flux, ctx.traj_layout
         gx = gmu = None

@@ -172,9 +172,9 @@ typedef struct hbvx_desc {
  *           width).  N = B*M, lane n = b*M + j.
  * `aux` (ABI <= 8: the two pre-clamp powers of every lane-day, [2,T,N] / records [T,N,2]) is no longer
  * part of the trajectory: since ABI 9 the adjoint recomputes both powers from the saved storages with
- * the forward's own instruction sequence (20 instead of 28 bytes per lane-day), and the library neither
- * writes nor reads the pointer -- pass NULL.  (Development builds with -DHBVX_SAVE_POW=1 restore the
- * old behaviour for A/B measurements; hbvx_backend() then ends in "+savepow".) */
+ * the forward's own instruction sequence (20 instead of 28 bytes per lane-day), and the device library
+ * neither writes nor reads the pointer, in any build: there is no build switch that restores the old
+ * behaviour.  Pass NULL (a checkpoint forward, HBVX_TRAJ_CKPT, refuses anything else). */
 enum hbvx_traj_layout { HBVX_TRAJ_ROWS = 0, HBVX_TRAJ_PACKED = 1, HBVX_TRAJ_CKPT = 2 };
 /* traj_layout = kind | (K << 8).  HBVX_TRAJ_CKPT with K in {4, 8, 16}: `traj` holds only the five
  * storages entering days 0, K, 2K, ... as [ceil(T/K), 5, N] (20/K bytes per lane-day instead of 20);

@@ -1,6 +1,6 @@
 """GPU tier: the pipelined forward (hbv_pipe.h) on eleven-day static tiles, with the soil stage's output tile at five
-rows per day (six with the capillary flux) instead of seven (eight): the two saved-power rows exist only in
-HBVX_SAVE_POW builds.  The arithmetic is Step::fwd_* in day order, so the kernel must equal the tiled family, which
+rows per day (six with the capillary flux) instead of seven (eight): the two saved-power rows are gone, no build
+keeps them.  The arithmetic is Step::fwd_* in day order, so the kernel must equal the tiled family, which
 HBVX_FWD=tiled forces, bit for bit: all fluxes, the final storages and every trajectory row.
 
 Shapes: T = 44 (four whole tiles, the shortest record the pipeline takes), 45 (a one-day tail), 54 (a ten-day tail),
