@@ -21,6 +21,8 @@ from hydrodl2_amd.adj_population import (adj_population_cost, adj_population_per
 from hydrodl2_amd.population_events import population_event_score, population_event_stats
 from hydrodl2_amd.hourly_population import hourly_population_columns, hourly_population_stats
 from hydrodl2_amd.hourly_fdc import hourly_fdc_score, hourly_population_fdc_stats
+from hydrodl2_amd.ensemble import (EnsembleState, ensemble_forecast, ensemble_record, ensemble_step,
+                                   particle_filter)
 from hydrodl2_amd.hourly_events import (flood_events, hourly_event_score, hourly_population_event_stats,
                                         hourly_routing_search)
 
@@ -34,4 +36,5 @@ __all__ = ["__version__", "available_models", "available_modules", "load_model",
            "population_event_score",
            "adj_population_cost", "adj_population_stats", "adj_population_period_stats", "adj_population_search",
            "hourly_population_stats", "hourly_population_columns", "flood_events", "hourly_population_event_stats",
-           "hourly_event_score", "hourly_routing_search", "hourly_population_fdc_stats", "hourly_fdc_score"]
+           "hourly_event_score", "hourly_routing_search", "hourly_population_fdc_stats", "hourly_fdc_score",
+           "EnsembleState", "ensemble_record", "ensemble_step", "particle_filter", "ensemble_forecast"]

@@ -190,9 +190,9 @@ POPULATION = {"hbvx_population_cost": PopEntry(Pop, False, None),
 
 def pop_levels(args):
     """(PopPeriod, PopJoint, PopStats, Pop) as they nest in `args` -- PopPeriod.joint.flow.pop, entered at the type of
-    `args` -- with None for the levels above it.  The inner ones are views of `args`' memory."""
+    `args` (PopFdc / PopEvents .flow and PopEns .s enter at PopStats) -- with None for the levels above it.  The inner ones are views of `args`' memory."""
     levels = {type(args): args}
-    for field in ("joint", "flow", "pop"):
+    for field in ("joint", "flow", "s", "pop"):
         if hasattr(args, field):
             args = getattr(args, field)
             levels[type(args)] = args
@@ -375,6 +375,27 @@ POP_EVENTS_SIGNATURES = [
 POP_EVENTS_ENTRY = PopEntry(PopEvents, False, None)     # what ops.population_events needs to know about the export
 
 
+POP_ENS_HIST = 14           # HBVX_POP_ENS_HIST: the days of routing history a particle carries
+
+
+class PopEns(C.Structure):
+    """hbvx_pop_ens: hbvx_pop_stats over the window t_begin .. t_end-1, and per particle the storages, the routing
+    history, the ancestor and the forcing perturbations of hbvx_population_ensemble (include/hbvx_pop_ens.h)."""
+    _fields_ = [("s", PopStats), ("t_begin", C.c_int32), ("t_end", C.c_int32), ("n_src", C.c_int32),
+                ("src_first", C.c_int32), ("state_in", _fp), ("state_out", _fp), ("hist_in", _fp), ("hist_out", _fp),
+                ("ancestor", C.c_void_p),       # const int32_t *: an address like the float pointers, of another type
+                ("p_mul", _fp), ("t_add", _fp), ("pm_c_stride", C.c_int64), ("pm_t_stride", C.c_int64),
+                ("ta_c_stride", C.c_int64), ("ta_t_stride", C.c_int64)]
+
+
+# The export of include/hbvx_pop_ens.h, a row as in SIGNATURES (optional; in neither SIGNATURES nor POPULATION, as
+# POP_FDC_SIGNATURES); the layout index is hbvx_sizeof's.
+POP_ENS_SIGNATURES = [
+    ("hbvx_population_ensemble", False, _int, [_P(Desc), _P(PopEns), _vp], (14, PopEns)),
+]
+POP_ENS_ENTRY = PopEntry(PopEns, False, None)       # what ops.population_ensemble needs to know about the export
+
+
 # The export of include/hbvx_route_rows.h, a row as in SIGNATURES (optional, no struct of its own).
 ROUTE_ROWS_SIGNATURES = [
     ("hbvx_route_backward_rows", False, _int, [_P(RouteDesc), _fp, _fp, _fp, _fp, _i32, _fp, _fp, _fp, _u64, _vp], None),
@@ -405,13 +426,14 @@ class Library:
                 raise HbvxError(f"{path}: missing export {name}")
         self.missing = [name for name in OPTIONAL_EXPORTS +
                         [row[0] for row in GAGE_POP_SIGNATURES + ROUTE_ROWS_SIGNATURES + LIVE_ROWS_SIGNATURES +
-                         POP_FDC_SIGNATURES + GAGE_EVENTS_SIGNATURES + POP_EVENTS_SIGNATURES + GAGE_FDC_SIGNATURES]
+                         POP_FDC_SIGNATURES + GAGE_EVENTS_SIGNATURES + POP_EVENTS_SIGNATURES + GAGE_FDC_SIGNATURES +
+                         POP_ENS_SIGNATURES]
                         if not hasattr(d, name)]
         checked = set()             # (sizeof export, index): several exports share a struct
         # the required rows come first, and each table's sizeof export before the rows that name a layout: it is bound by then
         for name, _, restype, argtypes, layout, sizeof in [row + ("hbvx_sizeof",) for row in SIGNATURES] + \
                 [row + ("hbvx_gage_pop_sizeof",) for row in GAGE_POP_SIGNATURES] + \
-                [row + ("hbvx_sizeof",) for row in ROUTE_ROWS_SIGNATURES + LIVE_ROWS_SIGNATURES] + \
+                [row + ("hbvx_sizeof",) for row in ROUTE_ROWS_SIGNATURES + LIVE_ROWS_SIGNATURES + POP_ENS_SIGNATURES] + \
                 [row + ("hbvx_pop_fdc_sizeof",) for row in POP_FDC_SIGNATURES] + \
                 [row + ("hbvx_gage_events_sizeof",) for row in GAGE_EVENTS_SIGNATURES] + \
                 [row + ("hbvx_pop_events_sizeof",) for row in POP_EVENTS_SIGNATURES] + \
@@ -718,3 +740,4 @@ for _name in POPULATION:        # Library.population_cost(desc, pop, stream) ...
     setattr(Library, _name[len("hbvx_"):], _population_method(_name))
 Library.population_fdc = _population_method("hbvx_population_fdc", PopFdc)       # (desc, pf, stream)
 Library.population_events = _population_method("hbvx_population_events", PopEvents)     # (desc, pe, stream)
+Library.population_ensemble = _population_method("hbvx_population_ensemble", PopEns)    # (desc, pe, stream)

@@ -14,7 +14,9 @@
 // sixth, the FDC form (hbvx_population_fdc, include/hbvx_pop_fdc.h; launch_pop.hip), is the daily stats form with
 // exceedance counts and volumes above per-basin thresholds: the simulated flow-duration curve sampled at K points.  A
 // seventh, the event form (hbvx_population_events, include/hbvx_pop_events.h; launch_pop.hip), is the daily stats form
-// with the peak, the day of the peak and the volume inside per-basin event windows of scored days.
+// with the peak, the day of the peak and the volume inside per-basin event windows of scored days.  An eighth, the
+// ensemble form (hbvx_population_ensemble, include/hbvx_pop_ens.h; launch_pop.hip), is the daily stats form over a window
+// of the days with storages, routing history and forcing noise per particle, handed back for the next window.
 //
 // What happens to a basin's ensemble mean after the day step -- the normalised gamma unit hydrograph, the 15-day
 // window, the causal convolution and the residual chain -- is hbvx_popk::Basin below and compiles for the host as
@@ -29,6 +31,8 @@
 // hbvx_popk::EventSlot is one flood event's peak, hour of the peak and volume (hbvx_gage_population_events,
 // include/hbvx_gage_events.h; tests/hosttest/gageevents_host.cpp); the event form of k_pop feeds the same slot days.
 // hbvx_popk::EventCursor is that form's walk over a basin's window rows (tests/hosttest/popevents_host.cpp).
+// Basin::load_history / save_history hand the routing window from one call of the ensemble form to the next
+// (tests/hosttest/popens_host.cpp).
 #pragma once
 
 #include <math.h>
@@ -116,6 +120,22 @@ struct Basin {
             cost = __builtin_fmaf(w * r, r, cost);
         }
         return y;
+    }
+
+    // The window across calls (hbvx_population_ensemble, include/hbvx_pop_ens.h): after a push, win[1 + k] is the value
+    // pushed k + 1 pushes ago, so entry k of a history taken at day t is the un-routed value of day t - 1 - k, k = 0..13,
+    // `stride` floats apart.  load_history before the first push of a call (h NULL: zeros, start()'s own) and
+    // save_history after its last hand the 14 values over bit for bit; win[0] is overwritten by the next push.
+    HBVX_POP_HD void load_history(const float *h, int64_t stride)
+    {
+#pragma unroll
+        for (int k = 0; k < UH - 1; k++) win[k + 1] = h ? h[k * stride] : 0.0f;
+    }
+
+    HBVX_POP_HD void save_history(float *h, int64_t stride) const
+    {
+#pragma unroll
+        for (int k = 0; k < UH - 1; k++) h[k * stride] = win[k + 1];
     }
 };
 
@@ -381,6 +401,21 @@ struct PopEventArgs {
     float *volume;              // [P,E,B]
 };
 
+// hbvx_population_ensemble (include/hbvx_pop_ens.h): the daily stats form over days t_begin .. t_end-1, each particle
+// (candidate) with storages, routing history and forcing noise of its own.
+struct PopEnsArgs {
+    PopStatsArgs s;             // hbvx_population_stats' arguments; target / w / sim are window-relative
+    int t_begin, t_end;         // 0 <= t_begin < t_end <= d.T
+    int n_src, src_first;       // particles of state_in / hist_in (>= 1), the identity ancestor's offset
+    const float *state_in;      // [n_src,5,B,M] or NULL (the descriptor's, or 0.001)
+    float *state_out;           // [P,5,B,M]
+    const float *hist_in;       // [n_src,14,B] or NULL (zeros)
+    float *hist_out;            // [P,14,B]; written when the call routes
+    const int32_t *ancestor;    // [P,B] or NULL (src_first + c)
+    const float *p_mul, *t_add; // each NULL (no operation) or [c * c_stride + (t - t_begin) * t_stride + b]
+    int64_t pm_c_stride, pm_t_stride, ta_c_stride, ta_t_stride;
+};
+
 // The event form addresses a basin's rows of start / end and of a candidate's [E,B] outputs with a 32-bit element index,
 // e * B + b (the launcher refuses E * B beyond this): a scalar base and a per-lane 32-bit offset.  With 64-bit per-lane
 // addresses the compiler hoists five of them out of the day loop, ten VGPRs, and HBV 1.1p drops to two waves per SIMD.
@@ -399,6 +434,8 @@ __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopPeriodArgs 
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopRunoffArgs &A) { return A.a; }
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopFdcArgs &A) { return A.s.a; }
 __host__ __device__ __forceinline__ const PopArgs &pop_args(const PopEventArgs &A) { return A.s.a; }
+__host__ __device__ __forceinline__ const PopArgs &pop_args(const PopEnsArgs &A) { return A.s.a; }
+__host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopEnsArgs &A) { return A.s; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopStatsArgs &A) { return A; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopJointArgs &A) { return A.s; }
 __host__ __device__ __forceinline__ const PopStatsArgs &stats_args(const PopPeriodArgs &A) { return A.j.s; }
@@ -487,6 +524,17 @@ template <> struct PopBasin<T_COST> { using type = hbvx_popk::Basin; };
 //                  barrier.  The seek reads two int32 per row and runs E steps per lane over the whole launch; no row
 //                  beyond E and no day outside the scored days is touched whatever the rows hold.  Everything of it is
 //                  behind `if constexpr (EVENTS)` (profiles/r26_population_events.md has the comparison).
+//   PopEnsArgs     (ENS) the daily stats form over the window t_begin .. t_end-1 of the descriptor's days, the candidate a
+//                  PARTICLE.  One int32 load per lane before the day loop names the particle's ancestor (clamped to
+//                  0 .. n_src-1: memory-safe for any content); the five storages and, when the call routes, the 14 values
+//                  of the window's history come from the ancestor's slot (Basin::load_history).  p_mul / t_add join the
+//                  one-day-ahead prefetch like nxo / nxw and are applied between the prefetch and Step::fwd, one multiply
+//                  and one add; a NULL pointer (uniform over the launch) is the absent operation.  Scored days are those
+//                  >= t0 = max(t_begin, t_first), and target / w / sim rows count from t0.  After the last day every
+//                  active lane stores its five storages (k_fwd's state_out convention: the lanes of padded members
+//                  store nothing) and the leader the history (save_history).  The loop bounds, t0 and the prefetch's
+//                  last-row clamp are this form's own variables (ens_tb, ens_te, ens_t0); the other forms keep theirs.
+//                  Everything of it is behind `if constexpr (ENS)` (profiles/r30_population_ensemble.md has the comparison).
 // The flow's operations are the same ones on the same values in every form, and the aux term's in both of its forms:
 // tests/test_population_stats_gpu.py, test_population_joint_gpu.py and test_population_period_gpu.py (daily calendars)
 // hold each form to the bits of the one before it.
@@ -512,6 +560,7 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
     constexpr bool JOINT = PERIOD || std::is_same<Args, PopJointArgs>::value;      // the forms with an aux term
     constexpr bool FDC = std::is_same<Args, PopFdcArgs>::value;
     constexpr bool EVENTS = std::is_same<Args, PopEventArgs>::value;
+    constexpr bool ENS = std::is_same<Args, PopEnsArgs>::value;
     static_assert(STATS == (TR != T_COST), "TR = T_COST is the cost form's, and its alone");
     constexpr int NP = NParam<MODEL, BETAET>::value;
     const PopArgs &A = pop_args(Q);
@@ -548,8 +597,24 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
     for (int i = NP; i < NPARAM_MAX; i++) p[i] = 0.0f;
 
     float st[5];
+    // ENS: the window and its first scored day (uniform), and the slot the particle starts from: one index load per lane,
+    // clamped to the sources that exist
+    int ens_tb = 0, ens_te = 0, ens_t0 = 0;
+    int64_t anc = 0;
+    if constexpr (ENS) {
+        ens_tb = Q.t_begin, ens_te = Q.t_end;
+        ens_t0 = ens_tb > t_first ? ens_tb : t_first;
+        int a = Q.ancestor ? Q.ancestor[c * d.B + L.b] : Q.src_first + (int)c;
+        a = a < 0 ? 0 : a;
+        a = a > Q.n_src - 1 ? Q.n_src - 1 : a;
+        anc = a;
+        const float *sp = Q.state_in ? Q.state_in + anc * 5 * N : d.state_in;
 #pragma unroll
-    for (int k = 0; k < 5; k++) st[k] = d.state_in ? d.state_in[k * N + L.n] : 0.001f;
+        for (int k = 0; k < 5; k++) st[k] = sp ? sp[k * N + L.n] : 0.001f;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 5; k++) st[k] = d.state_in ? d.state_in[k * N + L.n] : 0.001f;
+    }
 
     typename PopBasin<TR>::type bs;
     if constexpr (RUNOFF) ;     // no window, no chains: the runoff form scores nothing
@@ -563,6 +628,7 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
         const float ua = r.raw_sigmoid ? sigmoid_(va) : va;
         const float ub = r.raw_sigmoid ? sigmoid_(vb) : vb;
         hbvx_popk::gamma_taps(descale_(ua, r.a_lo, r.a_hi), descale_(ub, r.b_lo, r.b_hi), r.L, bs.uh);
+        if constexpr (ENS) bs.load_history(Q.hist_in ? Q.hist_in + anc * (hbvx_popk::UH - 1) * d.B + L.b : nullptr, d.B);
     }
 
     bool has_aux = JOINT;       // uniform over the launch
@@ -589,6 +655,7 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
     const float *wt = pp.w ? pp.w + L.b : nullptr;
     float *sim;
     if constexpr (PERIOD) sim = pp.sim ? pp.sim + c * (int64_t)KF * d.B + L.b : nullptr;
+    else if constexpr (ENS) sim = pp.sim && ens_te > ens_t0 ? pp.sim + c * (int64_t)(ens_te - ens_t0) * d.B + L.b : nullptr;
     else sim = pp.sim ? pp.sim + c * (int64_t)(T - t_first) * d.B + L.b : nullptr;
     // the same rows of the aux target and its weights, addressed from the (scalar) bases with the lane's basin added per
     // load: three per-lane pointers less, which is what keeps HBV 1.1p at three waves (DESIGN.md has the table)
@@ -668,7 +735,23 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
     // one-step-ahead register prefetch of the per-step inputs (k_fwd's); in the daily forms the observations and their
     // weights with them
     float nxf[3], nxd[NP], nxo = 0.0f, nxw = 1.0f, nxa = 0.0f, nxaw = 1.0f;
-    {
+    // ENS: the particle's rows of the two perturbations (row 0 is day t_begin), and their prefetched values
+    const float *pmul = nullptr, *tadd = nullptr;
+    float nxpm = 1.0f, nxta = 0.0f;
+    if constexpr (ENS) {
+        pmul = Q.p_mul ? Q.p_mul + c * Q.pm_c_stride + L.b : nullptr;
+        tadd = Q.t_add ? Q.t_add + c * Q.ta_c_stride + L.b : nullptr;
+        const float *xr = xb + (int64_t)ens_tb * d.x_t_stride;
+        nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
+#pragma unroll
+        for (int i = 0; i < NP; i++) nxd[i] = ((dmask >> i) & 1) ? dynp[i][(int64_t)ens_tb * d.p[i].dyn_t_stride] : 0.f;
+        if (ens_tb >= t_first) {
+            nxo = tg[0];
+            if (wt) nxw = wt[0];
+        }
+        if (pmul) nxpm = pmul[0];
+        if (tadd) nxta = tadd[0];
+    } else {
         const float *xr = xb;
         nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
 #pragma unroll
@@ -685,21 +768,31 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
         }
     }
 
-    for (int t = 0; t < T; t++) {
+    // (ENS ? a : b is folded where it stands: each instance names its own bounds)
+    for (int t = ENS ? ens_tb : 0; t < (ENS ? ens_te : T); t++) {
         Step<MODEL, BETAET> s;
         s.P = nxf[0]; s.Tf = nxf[1]; s.PET = nxf[2];
+        const float cpm = nxpm, cta = nxta;     // (ENS: the day's perturbations, applied below, after the prefetch)
         float cur[NP];
 #pragma unroll
         for (int i = 0; i < NP; i++) cur[i] = nxd[i];
         const float obs = nxo, wobs = nxw, aobs = nxa, awobs = nxaw;
         {
-            const int tn = t + 1 < T ? t + 1 : t;
+            const int tn = t + 1 < (ENS ? ens_te : T) ? t + 1 : t;
             const float *xr = xb + (int64_t)tn * d.x_t_stride;
             nxf[0] = xr[d.ch_prcp]; nxf[1] = xr[d.ch_tmean]; nxf[2] = xr[d.ch_pet];
 #pragma unroll
             for (int i = 0; i < NP; i++)
                 if ((dmask >> i) & 1) nxd[i] = dynp[i][(int64_t)tn * d.p[i].dyn_t_stride];
-            if constexpr (!PERIOD && !RUNOFF) {
+            if constexpr (ENS) {
+                if (tn >= ens_t0) {
+                    const int64_t row = (int64_t)(tn - ens_t0) * d.B;
+                    nxo = tg[row];
+                    if (wt) nxw = wt[row];
+                }
+                if (pmul) nxpm = pmul[(int64_t)(tn - ens_tb) * Q.pm_t_stride];
+                if (tadd) nxta = tadd[(int64_t)(tn - ens_tb) * Q.ta_t_stride];
+            } else if constexpr (!PERIOD && !RUNOFF) {
                 if (tn >= t_first) {
                     const int64_t row = (int64_t)(tn - t_first) * d.B;
                     nxo = tg[row];
@@ -718,6 +811,10 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
                 float pv = descale_(v, d.p[i].lo, d.p[i].hi);
                 if (use_dyn[i]) p[i] = pv;
             }
+        if constexpr (ENS) {
+            if (pmul) s.P = s.P * cpm;          // one multiply, one add; a NULL pointer is no operation at all
+            if (tadd) s.Tf = s.Tf + cta;
+        }
         s.SP = st[0]; s.MW = st[1]; s.SM = st[2]; s.SUZ = st[3]; s.SLZ = st[4];
         s.template fwd<false, true>(p, nz, ac, elev, 0.f, 0.f);
         st[0] = s.SP3; st[1] = s.MW3; st[2] = s.SM4; st[3] = s.SUZ4; st[4] = s.SLZ2;
@@ -787,7 +884,9 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
             float y;
             if constexpr (STATS) y = bs.template push<TR>(q, obs, wobs, counted);
             else y = bs.push(q, obs, wobs, counted);
-            if (counted && sim && L.leader) sim[(int64_t)(t - t_first) * d.B] = y;      // y, not its transform
+            if constexpr (ENS) {
+                if (counted && sim && L.leader) sim[(int64_t)(t - ens_t0) * d.B] = y;
+            } else if (counted && sim && L.leader) sim[(int64_t)(t - t_first) * d.B] = y;      // y, not its transform
             if constexpr (FDC) {
                 if (counted && wobs > 0.0f) {
                     for (int r = 0; r < R; r++) {
@@ -821,6 +920,16 @@ __global__ void __launch_bounds__(64) k_pop(const Args Q)
         }
     }
     if constexpr (RUNOFF) return;
+    if constexpr (ENS) {
+        // the storages after day t_end - 1, as k_fwd stores state_out: the lanes of real (basin, member) pairs; and the
+        // window's history, the same in every lane of a basin, from its leader
+        if (L.active) {
+            float *so = Q.state_out + c * 5 * N;
+#pragma unroll
+            for (int k = 0; k < 5; k++) so[k * N + L.n] = st[k];
+        }
+        if (A.has_route && L.leader) bs.save_history(Q.hist_out + c * (hbvx_popk::UH - 1) * d.B + L.b, d.B);
+    }
     if constexpr (FDC) {
         // every lane of a real basin stores the slots it owns (L.b is clamped: the lanes of basins beyond B store nothing)
         const bool real = (int)blockIdx.x * (64 >> lgMp) + ((int)(threadIdx.x & 63) >> lgMp) < d.B;

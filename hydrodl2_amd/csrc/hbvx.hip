@@ -10,6 +10,7 @@
 #include "hbvx_host.h"
 #include "../../include/hbvx_route_rows.h"
 #include "../../include/hbvx_live_rows.h"
+#include "../../include/hbvx_pop_ens.h"
 #include "hbv_step.h"
 #include "hbv_lane.h"
 #include "hbv_gage.h"
@@ -75,6 +76,7 @@ extern "C" uint64_t hbvx_sizeof(int which)
     case 11: return sizeof(hbvx_pop_stats);
     case 12: return sizeof(hbvx_pop_joint);
     case 13: return sizeof(hbvx_pop_period);
+    case 14: return sizeof(hbvx_pop_ens);
     default: return 0;
     }
 }

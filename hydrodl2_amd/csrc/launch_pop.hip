@@ -1,11 +1,13 @@
 // launch_pop.hip -- the entry points of the population evaluation: hbvx_population_cost, hbvx_population_stats,
 // hbvx_population_joint and hbvx_population_period (hbv_pop.h), the flow-duration call hbvx_population_fdc
 // (include/hbvx_pop_fdc.h; k_pop's FDC form), the flood-event call hbvx_population_events (include/hbvx_pop_events.h;
-// k_pop's event form), and the implicit scheme's hbvx_adj_population_cost,
+// k_pop's event form), the ensemble call hbvx_population_ensemble (include/hbvx_pop_ens.h; k_pop's ensemble form), and the
+// implicit scheme's hbvx_adj_population_cost,
 // hbvx_adj_population_stats and hbvx_adj_population_period (hbv_adj_pop.h).
 #include "hbvx_host.h"
 #include "../../include/hbvx_pop_fdc.h"
 #include "../../include/hbvx_pop_events.h"
+#include "../../include/hbvx_pop_ens.h"
 #include "hbv_pop.h"
 #define HBVX_CHUNK_NO_SHARED_KERNELS
 #include "hbv_chunked.h"        // (first: hbv_adj_kernels.h uses its XCD-aware block map)
@@ -25,7 +27,8 @@ int fail_as(const char *who, int code, const char *msg)
 
 // The argument checks all entry points share, and the kernel's arguments; `who` names the entry point in the messages.
 // adj: the implicit scheme's entry points -- the model test, and what check_adj (launch_adj.hip) asks of the Newton policy.
-int prepare(const char *who, const hbvx_desc *d, const hbvx_pop *pop, PopArgs &a, bool adj = false)
+// need_target: false where the call scores no day (a window of the ensemble form before t_first) and reads no target.
+int prepare(const char *who, const hbvx_desc *d, const hbvx_pop *pop, PopArgs &a, bool adj = false, bool need_target = true)
 {
     if (adj) {
         if (d->model != HBVX_MODEL_HBVADJ) return fail_as(who, HBVX_E_UNSUPPORTED, "the implicit scheme (HBVADJ) only");
@@ -38,7 +41,7 @@ int prepare(const char *who, const hbvx_desc *d, const hbvx_pop *pop, PopArgs &a
         if (d->muwts) return fail_as(who, HBVX_E_UNSUPPORTED, "muwts must be NULL (the implicit scheme has no ensemble weights)");
     } else if (d->model != HBVX_MODEL_HBV10 && d->model != HBVX_MODEL_HBV11P && d->model != HBVX_MODEL_HBV20)
         return fail_as(who, HBVX_E_UNSUPPORTED, "HBV 1.0 / 1.1p / 2.0 only");
-    if (!pop->target) return fail_as(who, HBVX_E_NULL, "target is NULL");
+    if (!pop->target && need_target) return fail_as(who, HBVX_E_NULL, "target is NULL");
     if (!pop->cost) return fail_as(who, HBVX_E_NULL, "cost is NULL");
     if (pop->n_cand < 1 || pop->n_cand > 65535) return fail_as(who, HBVX_E_SHAPE, "n_cand must be in 1..65535");
     if (pop->t_first < 0 || pop->t_first >= d->T) return fail_as(who, HBVX_E_SHAPE, "t_first outside the call's days");
@@ -312,6 +315,59 @@ extern "C" int hbvx_population_events(const hbvx_desc *d, const hbvx_pop_events 
     ev.peak_day = pe->peak_day;
     ev.volume = pe->volume;
     return with_transform(pe->flow.transform, [&](auto tr) { return launch_pop<tr>(who, ev, stream); });
+}
+
+static_assert(HBVX_POP_ENS_HIST == hbvx_popk::UH - 1, "the header's history length and the kernel's");
+
+// whether [a, a + na) and [b, b + nb) floats share an address (NULL shares nothing)
+static bool ranges_overlap(const float *a, int64_t na, const float *b, int64_t nb)
+{
+    if (!a || !b) return false;
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + 4 * (uintptr_t)na, b0 = (uintptr_t)b, b1 = b0 + 4 * (uintptr_t)nb;
+    return a0 < b1 && b0 < a1;
+}
+
+extern "C" int hbvx_population_ensemble(const hbvx_desc *d, const hbvx_pop_ens *pe, void *stream)
+{
+    const char *who = "hbvx_population_ensemble";
+    int rc = check_desc(d);
+    if (rc) return rc;
+    if (!pe) return fail_as(who, HBVX_E_NULL, "pe is NULL");
+    if (pe->t_begin < 0 || pe->t_begin >= pe->t_end || pe->t_end > d->T)
+        return fail_as(who, HBVX_E_SHAPE, "the window must satisfy 0 <= t_begin < t_end <= T");
+    const hbvx_pop *pop = &pe->s.pop;
+    PopEnsArgs e;
+    // a window that ends at or before t_first scores no day: no row of target / w / sim exists, the chains are +0
+    rc = prepare(who, d, pop, e.s.a, false, pop->t_first < pe->t_end);     // (refuses HBVX_MODEL_HBVADJ and HBVX_MODEL_HOURLY)
+    if (rc) return rc;
+    rc = prepare_stats(who, &pe->s, e.s);
+    if (rc) return rc;
+    const int n_src = pe->n_src ? pe->n_src : pop->n_cand;
+    if (n_src < 1 || pe->src_first < 0 || (!pe->ancestor && (int64_t)pe->src_first + pop->n_cand > n_src))
+        return fail_as(who, HBVX_E_SHAPE, "n_src / src_first leave an identity ancestor outside 0..n_src-1");
+    if (!pe->state_out) return fail_as(who, HBVX_E_NULL, "state_out is NULL");
+    if (e.s.a.has_route && !pe->hist_out) return fail_as(who, HBVX_E_NULL, "hist_out is NULL in a call that routes");
+    const int64_t N5 = 5 * (int64_t)d->B * d->M, H = (int64_t)HBVX_POP_ENS_HIST * d->B;
+    if (ranges_overlap(pe->state_out, pop->n_cand * N5, pe->state_in, n_src * N5))
+        return fail_as(who, HBVX_E_SHAPE, "state_out overlaps state_in");
+    if (e.s.a.has_route && ranges_overlap(pe->hist_out, pop->n_cand * H, pe->hist_in, n_src * H))
+        return fail_as(who, HBVX_E_SHAPE, "hist_out overlaps hist_in");
+    e.t_begin = pe->t_begin;
+    e.t_end = pe->t_end;
+    e.n_src = n_src;
+    e.src_first = pe->src_first;
+    e.state_in = pe->state_in;
+    e.state_out = pe->state_out;
+    e.hist_in = pe->hist_in;
+    e.hist_out = pe->hist_out;
+    e.ancestor = pe->ancestor;
+    e.p_mul = pe->p_mul;
+    e.t_add = pe->t_add;
+    e.pm_c_stride = pe->pm_c_stride;
+    e.pm_t_stride = pe->pm_t_stride;
+    e.ta_c_stride = pe->ta_c_stride;
+    e.ta_t_stride = pe->ta_t_stride;
+    return with_transform(pe->s.transform, [&](auto tr) { return launch_pop<tr>(who, e, stream); });
 }
 
 extern "C" int hbvx_adj_population_cost(const hbvx_desc *d, const hbvx_pop *pop, void *stream)

@@ -1158,7 +1158,7 @@ def population_fdc(rec: PathRecord, cand_sources: dict, route_cands, flow: PopTe
     Returns (flow_out, (count [P,K,B] int32, volume [P,K,B] float32)): on how many scored days with a weight > 0 the
     routed flow was above each threshold, and the sum of the flow over those days."""
     return _population(rec, "hbvx_population_fdc", _abi.POP_FDC_ENTRY, cand_sources, route_cands, flow, None, t_first,
-                       want_sim, thresholds)[::2]
+                       want_sim, thresholds)[:3:2]
 
 
 def population_events(rec: PathRecord, cand_sources: dict, route_cands, flow: PopTerm, starts: torch.Tensor,
@@ -1176,9 +1176,81 @@ def population_events(rec: PathRecord, cand_sources: dict, route_cands, flow: Po
                        want_sim, None, (starts, ends))[::3]
 
 
-def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first, want_sim, thr=None, events=None):
-    """`population` / `population_fdc` / `population_events`: (flow_out, aux_out, fdc_out, events_out), fdc_out None
-    without `thr`, events_out None without `events`."""
+class EnsTerm(NamedTuple):
+    """What `population_ensemble` adds to a stats call: the window, the particle count and the per-particle inputs."""
+    P: int
+    t_begin: int
+    t_end: int
+    state_in: Optional[torch.Tensor] = None
+    hist_in: Optional[torch.Tensor] = None
+    ancestor: Optional[torch.Tensor] = None
+    p_mul: Optional[torch.Tensor] = None
+    t_add: Optional[torch.Tensor] = None
+
+
+def population_ensemble(rec: PathRecord, cand_sources: dict, route_cands, flow: PopTerm, ens: EnsTerm, t_first: int = 0,
+                        want_sim: bool = False):
+    """hbvx_population_ensemble (include/hbvx_pop_ens.h) on one recorded call of the path: `population` on
+    hbvx_population_stats over the days ens.t_begin .. ens.t_end-1 of the record, every candidate a PARTICLE with
+    storages, routing history and forcing noise of its own.  All tensors float32 (ancestor int32), contiguous, on the
+    device of the record:
+    ens.P         the particles; the candidate columns are optional here (none: every particle has the record's values),
+                  and a candidate tensor must hold ens.P sets.
+    flow          target / w are WINDOW-RELATIVE, [rows,B] with rows = t_end - max(t_begin, t_first) the scored days of the
+                  window; rows == 0 is valid (target may be None) and gives +0 chains.
+    state_in      [Ps,5,B,M] or None (the record's start state); hist_in [Ps,14,B] or None (zeros): Ps = P, or with
+                  `ancestor` any count >= 1.
+    ancestor      [P,B] int32 or None (the identity): the source particle c of basin b starts from.  Values outside
+                  0..Ps-1 are clamped by the kernel; validity is the caller's.
+    p_mul, t_add  None (no operation), [P,B] (a constant per particle) or [P,t_end-t_begin,B].
+    Returns (flow_out, (state_out [P,5,B,M], hist_out [P,14,B] or None when the record does not route)); the series of
+    flow_out is [P,rows,B].  More than POP_MAX_CAND particles go in several launches; a particle's bits do not depend on
+    the split."""
+    return _population(rec, "hbvx_population_ensemble", _abi.POP_ENS_ENTRY, cand_sources, route_cands, flow, None, t_first,
+                       want_sim, ens=ens)[::4]
+
+
+def _check_ens(lib, ens, cfg, t_first, dev):
+    """population_ensemble's own checks -> (rows, Ps, W): the scored days and the days of the window, the sources."""
+    T, B, M = cfg.T, cfg.B, cfg.M
+    if not all(isinstance(v, int) and not isinstance(v, bool) for v in (ens.P, ens.t_begin, ens.t_end)):
+        raise TypeError("n_particles, t_begin and t_end must be integers")
+    if ens.P < 1:
+        raise ValueError(f"population_ensemble needs at least one particle, got {ens.P}")
+    if not 0 <= ens.t_begin < ens.t_end <= T:
+        raise ValueError(f"the window must satisfy 0 <= t_begin < t_end <= {T}, got {ens.t_begin} .. {ens.t_end}")
+    W = ens.t_end - ens.t_begin
+    Ps = ens.P
+    if ens.ancestor is not None:        # the sources may then be any number: the leading size of what is given
+        for t in (ens.hist_in, ens.state_in):
+            if t is not None and t.dim() >= 1:
+                Ps = int(t.shape[0])
+    for name, t, tail in (("state_in", ens.state_in, (5, B, M)), ("hist_in", ens.hist_in, (_abi.POP_ENS_HIST, B))):
+        if t is None:
+            continue
+        _check_tensor(lib, t, name)
+        if tuple(t.shape) != (Ps,) + tail or Ps < 1 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous {[Ps] + list(tail)} tensor on {dev}, got {tuple(t.shape)} on "
+                             f"{t.device}")
+    if ens.ancestor is not None:
+        a = ens.ancestor
+        if not torch.is_tensor(a) or a.dtype != torch.int32:
+            raise TypeError(f"ancestor must be an int32 tensor, got {a.dtype if torch.is_tensor(a) else type(a).__name__}")
+        if tuple(a.shape) != (ens.P, B) or not a.is_contiguous() or a.device != dev:
+            raise ValueError(f"ancestor must be a contiguous [{ens.P},{B}] tensor on {dev}, got {tuple(a.shape)} on {a.device}")
+    for name, t in (("p_mul", ens.p_mul), ("t_add", ens.t_add)):
+        if t is None:
+            continue
+        _check_tensor(lib, t, name)
+        if tuple(t.shape) not in ((ens.P, B), (ens.P, W, B)) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous [{ens.P},{B}] or [{ens.P},{W},{B}] tensor on {dev}, got "
+                             f"{tuple(t.shape)} on {t.device}")
+    return max(0, ens.t_end - max(ens.t_begin, t_first)), Ps, W
+
+
+def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first, want_sim, thr=None, events=None, ens=None):
+    """`population` / `population_fdc` / `population_events` / `population_ensemble`: (flow_out, aux_out, fdc_out,
+    events_out, ens_out), fdc_out None without `thr`, events_out None without `events`, ens_out None without `ens`."""
     what = entry[len("hbvx_"):]
     cost_form, period_form = info.struct is _abi.Pop, info.struct is _abi.PopPeriod
     if not cost_form:
@@ -1219,15 +1291,22 @@ def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first,
     if not 0 <= t_first < T:
         raise ValueError(f"t_first must be in 0..{T - 1}, got {t_first}")
     named = list(cand_sources.values()) + [s for s in (route_cands or ()) if s is not None]
-    if not named:
+    if not named and ens is None:
         raise ValueError(f"{what} needs at least one candidate column")
-    cands = named[0][0]
-    _check_tensor(lib, cands, "candidates")
-    if cands.dim() != 3 or int(cands.shape[1]) != B or not cands.is_contiguous() or cands.device != dev:
-        raise ValueError(f"candidates must be a contiguous [P,{B},C] tensor on {dev}, got {tuple(cands.shape)} on {cands.device}")
-    P, Cn = int(cands.shape[0]), int(cands.shape[2])
-    if P < 1:
-        raise ValueError(f"{what} needs at least one candidate")
+    if ens is not None:
+        rows_e, Ps, W = _check_ens(lib, ens, cfg, t_first, dev)
+    if named:
+        cands = named[0][0]
+        _check_tensor(lib, cands, "candidates")
+        if cands.dim() != 3 or int(cands.shape[1]) != B or not cands.is_contiguous() or cands.device != dev:
+            raise ValueError(f"candidates must be a contiguous [P,{B},C] tensor on {dev}, got {tuple(cands.shape)} on {cands.device}")
+        P, Cn = int(cands.shape[0]), int(cands.shape[2])
+        if P < 1:
+            raise ValueError(f"{what} needs at least one candidate")
+        if ens is not None and P != ens.P:
+            raise ValueError(f"{what}: the candidates hold {P} sets for {ens.P} particles")
+    else:
+        cands, P, Cn = None, ens.P, 0       # (the ensemble form: every particle has the record's static values)
     for t, col in named:
         if t is not cands:
             raise ValueError("all candidate columns must lie in one compact tensor")
@@ -1238,6 +1317,10 @@ def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first,
         if s is not None and not 0 <= s[1] < Cn:
             raise ValueError(f"routing candidate column {s[1]} outside the {Cn} columns")
     rows_f = rows_a = T_out         # rows of the flow's and the aux term's targets, weights and series
+    if ens is not None:
+        rows_f = rows_e             # the scored days of the window
+        if rows_f > 0 and flow.target is None:
+            raise ValueError(f"{what}: the window has {rows_f} scored days and no target")
     ends = [None, None]
     if period_form:
         for i, (name, e) in enumerate((("flow_end", flow.ends), ("aux_end", None if aux is None else aux.ends))):
@@ -1302,6 +1385,9 @@ def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first,
             ev_out = (_out((P, E, B), dev), _out_i32((P, E, B), dev), _out((P, E, B), dev))
             if _POISON:
                 ev_out[1].fill_(-2 ** 31)       # (-1, _out_i32's fill, is what an absent slot holds)
+        ens_out = None
+        if ens is not None:
+            ens_out = (_out((P, 5, B, M), dev), _out((P, _abi.POP_ENS_HIST, B), dev) if route is not None else None)
         for c0 in range(0, P, POP_MAX_CAND):
             args = info.struct()
             pq, pj, ps, pop = _abi.pop_levels(args)
@@ -1341,8 +1427,21 @@ def _population(rec, entry, info, cand_sources, route_cands, flow, aux, t_first,
                 args.start, args.end = events[0].data_ptr(), events[1].data_ptr()
                 args.peak, args.volume = _ptr(ev_out[0], c0 * E * B), _ptr(ev_out[2], c0 * E * B)
                 args.peak_day = ev_out[1].data_ptr() + 4 * c0 * E * B
+            if ens is not None:
+                args.t_begin, args.t_end, args.n_src, args.src_first = ens.t_begin, ens.t_end, Ps, c0
+                args.state_in, args.hist_in = _ptr(ens.state_in), _ptr(ens.hist_in)
+                args.state_out, args.hist_out = _ptr(ens_out[0], c0 * 5 * B * M), _ptr(ens_out[1], c0 * _abi.POP_ENS_HIST * B)
+                if ens.ancestor is not None:
+                    args.ancestor = ens.ancestor.data_ptr() + 4 * c0 * B
+                for t, name in ((ens.p_mul, "pm"), (ens.t_add, "ta")):
+                    if t is not None:
+                        per_day = t.dim() == 3
+                        cs = W * B if per_day else B
+                        setattr(args, "p_mul" if name == "pm" else "t_add", _ptr(t, c0 * cs))
+                        setattr(args, name + "_c_stride", cs)
+                        setattr(args, name + "_t_stride", B if per_day else 0)
             _call(lib, entry, call, desc, args, stream)
-    return (cost,) + moments + (sim,), aux_out, fdc_out, ev_out
+    return (cost,) + moments + (sim,), aux_out, fdc_out, ev_out, ens_out
 
 
 class PathOut(NamedTuple):

@@ -254,7 +254,7 @@ const char *hbvx_backend(void);         /* "hip:gfx950" or "cpu-oracle" */
 uint64_t hbvx_sizeof(int which);        /* 0 desc, 1 fwd_out, 2 bwd_io, 3 route_desc,
                                            4 param_src, 5 param_grad, 6 gage_desc, 7 tan_io, 8 tan_batch,
                                            9 gram_desc, 10 pop, 11 pop_stats, 12 pop_joint,
-                                           13 pop_period: layout check */
+                                           13 pop_period, 14 pop_ens (hbvx_pop_ens.h): layout check */
 /* Diagnostic: the kernel family that took the process's last hbvx_forward (direction 0) / hbvx_backward (1) call --
  * "pipe", "stream2", "stream", "tiled", "simple", "chunked", "ckpt-block:<family>", "ckpt-lds"; "oracle" in the CPU
  * restatement.  The parity tests assert that the family they mean to pin against the reference is the one that ran. */
