@@ -36,9 +36,9 @@ import synth  # noqa: E402
 SPIN = 30       # days left out of the comparison: the filter starts as dry as the open loop
 
 
-def twin_experiment(basins=8, days=150, nmul=4, particles=64, window=1, seed=5, prcp_sigma=0.4, state_sigma=0.5,
-                    horizon=30, device="cuda:0"):
-    """The experiment above -> a dictionary of plain numbers and lists."""
+def twin_setup(basins=8, days=150, nmul=4, device="cuda:0"):
+    """The truth, the observations and the open loop above (fixed seeds) -> a dictionary; examples/assimilate_enkf.py
+    runs its filter on the same set-up."""
     T, B, M = days, basins, nmul
     cfg = {"nmul": M, "routing": True, "dynamic_params": {"Hbv": []}, "warm_up": 0}
     load = hydrodl2_amd.load_model("hbv", "Hbv")
@@ -55,9 +55,19 @@ def twin_experiment(basins=8, days=150, nmul=4, particles=64, window=1, seed=5, 
     obs = truth + sigma * torch.randn(truth.shape, generator=g).to(device)
     x_open = x.clone()
     x_open[..., 0] = x_open[..., 0] * 0.7
-    xd = {"x_phy": x_open}
     with torch.no_grad():
-        open_loop = model(xd, params)["streamflow"][..., 0].clone()
+        open_loop = model({"x_phy": x_open}, params)["streamflow"][..., 0].clone()
+    return {"model": model, "x_open": x_open, "params": params, "truth": truth, "obs": obs, "sigma": sigma,
+            "open_loop": open_loop}
+
+
+def twin_experiment(basins=8, days=150, nmul=4, particles=64, window=1, seed=5, prcp_sigma=0.4, state_sigma=0.5,
+                    horizon=30, device="cuda:0"):
+    """The experiment above -> a dictionary of plain numbers and lists."""
+    T, B, M = days, basins, nmul
+    su = twin_setup(basins, days, nmul, device)
+    model, x_open, params, truth, obs, sigma, open_loop = (su[k] for k in ("model", "x_open", "params", "truth", "obs",
+                                                                           "sigma", "open_loop"))
 
     def run(T_run):
         gen = torch.Generator().manual_seed(seed)

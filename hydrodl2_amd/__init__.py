@@ -23,6 +23,7 @@ from hydrodl2_amd.hourly_population import hourly_population_columns, hourly_pop
 from hydrodl2_amd.hourly_fdc import hourly_fdc_score, hourly_population_fdc_stats
 from hydrodl2_amd.ensemble import (EnsembleState, ensemble_forecast, ensemble_record, ensemble_step,
                                    particle_filter)
+from hydrodl2_amd.enkf import enkf_filter, enkf_update
 from hydrodl2_amd.hourly_events import (flood_events, hourly_event_score, hourly_population_event_stats,
                                         hourly_routing_search)
 
@@ -37,4 +38,5 @@ __all__ = ["__version__", "available_models", "available_modules", "load_model",
            "adj_population_cost", "adj_population_stats", "adj_population_period_stats", "adj_population_search",
            "hourly_population_stats", "hourly_population_columns", "flood_events", "hourly_population_event_stats",
            "hourly_event_score", "hourly_routing_search", "hourly_population_fdc_stats", "hourly_fdc_score",
-           "EnsembleState", "ensemble_record", "ensemble_step", "particle_filter", "ensemble_forecast"]
+           "EnsembleState", "ensemble_record", "ensemble_step", "particle_filter", "ensemble_forecast",
+           "enkf_update", "enkf_filter"]

@@ -396,6 +396,32 @@ POP_ENS_SIGNATURES = [
 POP_ENS_ENTRY = PopEntry(PopEns, False, None)       # what ops.population_ensemble needs to know about the export
 
 
+ENKF_MAX_ARRAYS = 4         # HBVX_ENKF_MAX_ARRAYS
+ENKF_METHODS = {"perturbed": 0, "sqrt": 1}      # HBVX_ENKF_PERTURBED, HBVX_ENKF_SQRT
+
+
+class EnkfArray(C.Structure):
+    """hbvx_enkf_array: one array of particle values, [P,n] in and out, element e of basin (e / M) % B, floored at lo."""
+    _fields_ = [("in_", _fp), ("out", _fp), ("n", C.c_int64), ("M", C.c_int32), ("lo", C.c_float)]
+
+
+class Enkf(C.Structure):
+    """hbvx_enkf: the analysis step of hbvx_enkf_update (include/hbvx_enkf.h)."""
+    _fields_ = [("P", C.c_int32), ("B", C.c_int32), ("method", C.c_int32), ("n_arrays", C.c_int32),
+                ("inflation", C.c_double), ("y", _fp), ("y_stride", C.c_int64), ("obs", _fp), ("obs_var", _fp),
+                ("active", _fp), ("eps", _fp),
+                ("status", C.c_void_p), ("stats", C.c_void_p),      # int32_t * / double *: addresses of another type
+                ("a", EnkfArray * ENKF_MAX_ARRAYS)]
+
+
+# The exports of include/hbvx_enkf.h, rows as in SIGNATURES (optional; a table of its own, as POP_EVENTS_SIGNATURES); the
+# layout index is hbvx_enkf_sizeof's.
+ENKF_SIGNATURES = [
+    ("hbvx_enkf_sizeof", False, _u64, [_int], None),
+    ("hbvx_enkf_update", False, _int, [_P(Enkf), _vp], (0, Enkf)),
+]
+
+
 # The export of include/hbvx_route_rows.h, a row as in SIGNATURES (optional, no struct of its own).
 ROUTE_ROWS_SIGNATURES = [
     ("hbvx_route_backward_rows", False, _int, [_P(RouteDesc), _fp, _fp, _fp, _fp, _i32, _fp, _fp, _fp, _u64, _vp], None),
@@ -427,13 +453,14 @@ class Library:
         self.missing = [name for name in OPTIONAL_EXPORTS +
                         [row[0] for row in GAGE_POP_SIGNATURES + ROUTE_ROWS_SIGNATURES + LIVE_ROWS_SIGNATURES +
                          POP_FDC_SIGNATURES + GAGE_EVENTS_SIGNATURES + POP_EVENTS_SIGNATURES + GAGE_FDC_SIGNATURES +
-                         POP_ENS_SIGNATURES]
+                         POP_ENS_SIGNATURES + ENKF_SIGNATURES]
                         if not hasattr(d, name)]
         checked = set()             # (sizeof export, index): several exports share a struct
         # the required rows come first, and each table's sizeof export before the rows that name a layout: it is bound by then
         for name, _, restype, argtypes, layout, sizeof in [row + ("hbvx_sizeof",) for row in SIGNATURES] + \
                 [row + ("hbvx_gage_pop_sizeof",) for row in GAGE_POP_SIGNATURES] + \
                 [row + ("hbvx_sizeof",) for row in ROUTE_ROWS_SIGNATURES + LIVE_ROWS_SIGNATURES + POP_ENS_SIGNATURES] + \
+                [row + ("hbvx_enkf_sizeof",) for row in ENKF_SIGNATURES] + \
                 [row + ("hbvx_pop_fdc_sizeof",) for row in POP_FDC_SIGNATURES] + \
                 [row + ("hbvx_gage_events_sizeof",) for row in GAGE_EVENTS_SIGNATURES] + \
                 [row + ("hbvx_pop_events_sizeof",) for row in POP_EVENTS_SIGNATURES] + \
@@ -713,6 +740,12 @@ class Library:
         self._check(self.dll.hbvx_route_backward(C.byref(r), q, uh, gqr, gq, gra, grb, ws,
                                                  C.c_uint64(ws_bytes), C.c_void_p(stream)),
                     "hbvx_route_backward")
+
+    def enkf_update(self, e, stream: int) -> int:
+        """hbvx_enkf_update; `e` may be None (the ABI's own refusals are under test).  Raises HbvxError with the
+        library's text on a negative return code."""
+        self.require("hbvx_enkf_update")
+        self._check(self.dll.hbvx_enkf_update(None if e is None else C.byref(e), C.c_void_p(stream)), "hbvx_enkf_update")
 
     def route_backward_rows(self, r: RouteDesc, q: int, uh: int, gqr: int, gq: int, gq_rows: int, gra, grb,
                             ws, ws_bytes: int, stream: int):

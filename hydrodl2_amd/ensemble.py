@@ -16,9 +16,10 @@ window; on it,
                        is an `ancestor` index the next launch reads, nothing is gathered on the host between windows;
   `ensemble_forecast`  runs particles over a future record without observations and forms weighted quantiles.
 
-Hbv, Hbv_1_1p and Hbv_2, daily.  Not built: EnKF-style linear updates; noise on PET, the dynamic parameters
-or muwts; an aux series or period calendars; the implicit, hourly and multi-timescale models; quantiles across particles
-inside the kernel; graph=True capture.
+Hbv, Hbv_1_1p and Hbv_2, daily.  Updates that MOVE the states by a gain instead of choosing among them -- the ensemble
+Kalman filter on the same launches and the same `EnsembleState` -- are hydrodl2_amd/enkf.py (`enkf_update`,
+`enkf_filter`).  Not built (DESIGN.md): noise on PET, the dynamic parameters or muwts; an aux series or period calendars;
+the implicit, hourly and multi-timescale models; quantiles across particles inside the kernel; graph=True capture.
 """
 from __future__ import annotations
 

@@ -1863,6 +1863,86 @@ def gage_events(series: torch.Tensor, starts: torch.Tensor, ends: torch.Tensor):
     return peak, hour, volume
 
 
+class EnkfArray(NamedTuple):
+    """One array of `enkf_update`: `values` [P,...] float32 contiguous whose trailing sizes are [...,B,M] (M the trailing
+    size, 1 for a [P,k,B] array: pass M=1), floored at `lo` (-inf: no floor); `out` None (a new tensor) or a tensor of the
+    same shape -- `values` itself is an update in place."""
+    values: torch.Tensor
+    M: int = 1
+    lo: float = float("-inf")
+    out: Optional[torch.Tensor] = None
+
+
+def enkf_update(y: torch.Tensor, obs: torch.Tensor, obs_var: torch.Tensor, arrays: Sequence[EnkfArray], method: int,
+                inflation: float = 1.0, eps: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None):
+    """hbvx_enkf_update (include/hbvx_enkf.h) on the current stream: the ensemble Kalman analysis of 1 .. 4 arrays of
+    particle values against one observation per basin.  All float32 on one device:
+    y          [P,B] the predicted observation; the basins contiguous, any particle stride >= B (a row of a series).
+    obs        [B], NaN where missing; obs_var [B] its error variance (a value <= 0 is status 2, not an error).
+    arrays     `EnkfArray`s; an array's elements per particle must be a multiple of B * M.
+    method     _abi.ENKF_METHODS: 0 perturbed observations (eps [P,B] contiguous required), 1 square root (eps ignored).
+    active     [B] bool / uint8 or None (every basin).
+    Returns (outs, status [B] int32, stats [3,B] float64: ybar, the variance of y, the mean innovation)."""
+    lib = get_library()
+    lib.require('hbvx_enkf_update')
+    _check_tensor(lib, y, "y")
+    dev = y.device
+    if y.dim() != 2 or int(y.shape[0]) < 2 or int(y.shape[1]) < 1 or y.stride(1) != 1 or y.stride(0) < int(y.shape[1]):
+        raise ValueError(f"y must be [P,B] with P >= 2, contiguous basins and a particle stride >= B, got {tuple(y.shape)} "
+                         f"with strides {tuple(y.stride())}")
+    P, B = int(y.shape[0]), int(y.shape[1])
+    if method not in _abi.ENKF_METHODS.values():
+        raise ValueError(f"method must be one of {_abi.ENKF_METHODS}, got {method!r}")
+    if not (float(inflation) > 0.0 and float(inflation) != float("inf")):
+        raise ValueError(f"inflation must be finite and > 0, got {inflation!r}")
+    for name, t, shape in (("obs", obs, (B,)), ("obs_var", obs_var, (B,)), ("eps", eps, (P, B))):
+        if name == "eps" and method != 0:
+            continue
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} must be a float32 tensor, got {type(t).__name__}")
+        _check_tensor(lib, t, name)
+        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous {list(shape)} tensor on {dev}, got {tuple(t.shape)} on {t.device}")
+    if active is not None:
+        if not torch.is_tensor(active) or active.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"active must be a bool or uint8 tensor, got "
+                            f"{active.dtype if torch.is_tensor(active) else type(active).__name__}")
+        if tuple(active.shape) != (B,) or not active.is_contiguous() or active.device != dev:
+            raise ValueError(f"active must be a contiguous [{B}] tensor on {dev}, got {tuple(active.shape)} on {active.device}")
+    arrays = list(arrays)
+    if not 1 <= len(arrays) <= _abi.ENKF_MAX_ARRAYS:
+        raise ValueError(f"enkf_update takes 1 .. {_abi.ENKF_MAX_ARRAYS} arrays, got {len(arrays)}")
+    for i, a in enumerate(arrays):
+        for name, t in ((f"arrays[{i}].values", a.values), (f"arrays[{i}].out", a.out)):
+            if t is None and name.endswith("out"):
+                continue
+            if not torch.is_tensor(t):
+                raise TypeError(f"{name} must be a float32 tensor, got {type(t).__name__}")
+            _check_tensor(lib, t, name)
+            if t.dim() < 2 or int(t.shape[0]) != P or not t.is_contiguous() or t.device != dev or \
+                    tuple(t.shape) != tuple(a.values.shape):
+                raise ValueError(f"{name} must be a contiguous [{P},...] tensor on {dev}, got {tuple(t.shape)} on {t.device}")
+        n = a.values.numel() // P
+        if isinstance(a.M, bool) or not isinstance(a.M, int) or a.M < 1 or n < 1 or n % (B * a.M):
+            raise ValueError(f"arrays[{i}]: {n} elements per particle are not a positive multiple of B * M = {B} * {a.M!r}")
+        if a.lo != a.lo:
+            raise ValueError(f"arrays[{i}].lo is NaN")
+    stream = _stream_of(lib, y)
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+        outs = [_out(tuple(a.values.shape), dev) if a.out is None else a.out for a in arrays]
+        status = _out_i32((B,), dev)
+        stats = torch.full((3, B), float("nan"), dtype=torch.float64, device=dev) if _POISON else \
+            torch.empty((3, B), dtype=torch.float64, device=dev)
+        e = _abi.Enkf(P=P, B=B, method=method, n_arrays=len(arrays), inflation=float(inflation), y=_ptr(y),
+                      y_stride=y.stride(0), obs=_ptr(obs), obs_var=_ptr(obs_var),
+                      active=None if active is None else active.data_ptr(), eps=None if method != 0 else _ptr(eps),
+                      status=status.data_ptr(), stats=stats.data_ptr())
+        for i, (a, o) in enumerate(zip(arrays, outs)):
+            e.a[i] = _abi.EnkfArray(in_=_ptr(a.values), out=_ptr(o), n=a.values.numel() // P, M=a.M, lo=a.lo)
+        _call(lib, 'hbvx_enkf_update', lib.enkf_update, e, stream)
+    return outs, status, stats
+
+
 def _check_gage_levels(series, scored, levels, name, dtype):
     """What `gage_fdc` and `gage_quantiles` check of their arguments -> (P, T, G, K)."""
     dev = series.device
